@@ -12,12 +12,16 @@ Metric (BASELINE.json): images/sec at 513x513 of the full training step --
 ResNet-101 DeepLab-v2 forward/backward in fp32 (the reference trains in fp32),
 per-image spherical k-means, prototypes, the three contrastive losses + softmax
 head, SGD step -- on the "VOC12 scribble, ResNet-101, batch 16 per GPU" config,
-synthetic 21-class batches, weak scaling.  Also reported: k-means iterations/sec
-on the 513x513x(256+2) roofline configuration, the HBM roofline fraction of the
-fused k-means pass kernel and the CPU oracle timed on this node's host cores.
-Prints ONE JSON line on rank 0.
+synthetic 21-class batches, weak scaling.  Prints ONE JSON line on rank 0.
 
-How the roofline kernel is timed: HIP events on the launch stream around ONE library call that issues 60
+A plain run sets up, warms up, times the --steps steps and prints the line.  With --full it then also measures
+k-means iterations/sec on the 513x513x(256+2) roofline configuration, the HBM roofline fraction of the fused
+k-means pass kernel, the backbone's matrix-core convolution against the f16 peak, the CPU oracle timed on this
+node's host cores and, on N > 1 ranks, the collective budget of one step.  --dump-outputs DIR writes what the last
+timed step returned (its losses, accuracy and learning rate) and a fixed, seeded sample of the parameters that step
+updated as DIR/<name>.npy (float64 / float32): with the same arguments the inputs are the same on every run.
+
+How the roofline kernel is timed (--full): HIP events on the launch stream around ONE library call that issues 60
 back-to-back launches of the fused pass kernel (`roofline.us_per_launch`: the mean launch period, what a rocprofv3
 kernel trace of this command lists for the kernel plus the kernel boundary); beside it the workgroups' own
 s_memrealtime stamps over all fused launches of five whole k-means calls (`us_per_launch_device_stamps`), the shader
@@ -50,7 +54,7 @@ MFMA_F16_PEAK_TFLOPS = 2500.0   # dense f16/bf16 MFMA peak (MI355X_MICROARCH.md)
 PMC_TRAFFIC_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'profiles', 'kmeans_pass_pmc_traffic.json')
 
 
-# rocprofv3 --kernel-trace --stats of exactly the driver's command (`python bench.py --gpus 1 --steps 20 --warmup 5`),
+# rocprofv3 --kernel-trace --stats of the driver's command with --full (`python bench.py --gpus 1 --steps 20 --warmup 5 --full`),
 # committed per round by tools/run_round_checks.sh + tools/refresh_profiles.py: the average duration of the roofline
 # kernel over ALL its launches of that process (clock ramps, launches inside whole k-means calls, profiler overhead
 # included) is the figure a reader recomputes from profiles/ -- `roofline.frac` never exceeds it
@@ -84,15 +88,20 @@ def parse():
   ap.add_argument('--gpus', type=int, default=1)
   ap.add_argument('--steps', type=int, default=8)
   ap.add_argument('--warmup', type=int, default=3)
+  ap.add_argument('--full', action='store_true',
+                  help='after the timed steps also measure what the headline does not need: k-means and backbone '
+                       'rooflines, the CPU baseline, the collective budget of a multi-rank step')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write what the last timed step computed as DIR/<name>.npy')
   ap.add_argument('--batch', type=int, default=None, help='images per GPU (default: 16; stress: 2)')
   ap.add_argument('--crop', type=int, default=None, help='default: 513; stress: 1025')
-  ap.add_argument('--no-cpu-baseline', action='store_true')
+  ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
   ap.add_argument('--dist-backend', default='nccl', choices=['nccl', 'gloo'],
                   help="collective backend ('nccl' = RCCL over xGMI; 'gloo' only exists so that a test can run "
                        "two ranks on ONE device, which RCCL refuses)")
   ap.add_argument('--share-gpus', action='store_true',
                   help='testing only: allow more ranks than devices (rank r uses device r %% device_count)')
-  ap.add_argument('--no-kmeans', action='store_true')
+  ap.add_argument('--no-kmeans', action='store_true', help='--full without the k-means and backbone rooflines')
   ap.add_argument('--dense-tags', action='store_true',
                   help='synthetic batch of rounds 1-4: every region draws from all classes (image tag sets nearly '
                        'always intersect: the co-occurrence term is identically zero); default: 1-3 object classes '
@@ -417,6 +426,26 @@ WORKLOADS = {
 }
 
 
+DUMP_PARAM_SAMPLE = 1 << 21     # embedding-network parameters --dump-outputs writes (of 47 M: 8 MB instead of 189)
+
+
+def dump_outputs(out_dir, last, trainer):
+  """--dump-outputs: what the last timed step computed -- the scalars Trainer.step returned (float64) and the
+  parameters its SGD update wrote (float32, in the logical order of model.parameters(), whatever the memory
+  format): the prediction head's whole, the embedding network's at DUMP_PARAM_SAMPLE fixed, seeded positions."""
+  import numpy as np
+  os.makedirs(out_dir, exist_ok=True)
+  for k, v in last.items():
+    v = v.detach().double().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64)
+    np.save(os.path.join(out_dir, k + '.npy'), v)
+  for name, model in (('embedding_params', trainer.embedding_model), ('prediction_params', trainer.prediction_model)):
+    flat = torch.cat([p.detach().reshape(-1) for p in model.parameters() if p.requires_grad]).float()
+    if flat.numel() > DUMP_PARAM_SAMPLE:
+      pick = torch.randint(flat.numel(), (DUMP_PARAM_SAMPLE,), generator=torch.Generator().manual_seed(235))
+      flat = flat[pick.sort().values.to(flat.device)]
+    np.save(os.path.join(out_dir, name + '.npy'), flat.cpu().numpy())
+
+
 def _flush_c_stdio():
   try:
     import ctypes
@@ -450,6 +479,8 @@ def main():
   args = parse()
   if args.gpus < 1:
     raise SystemExit('bench.py: --gpus must be >= 1')
+  if args.steps < 1 or args.warmup < 0:
+    raise SystemExit('bench.py: --steps must be >= 1 and --warmup >= 0')
   if not torch.cuda.is_available():
     raise SystemExit('bench.py needs an MI355X (no CPU fallback for the HIP path)')
   ndev = torch.cuda.device_count()
@@ -547,7 +578,7 @@ def main():
   # the collective budget of one step (counted on an untimed extra step) and what ONE small collective costs on
   # this node: a multi-GPU line then explains itself (DESIGN 7 has the table of what each latency does to 8 GPUs)
   coll = None
-  if dist.is_initialized() and (world > 1 or forced):
+  if args.full and dist.is_initialized() and (world > 1 or forced):
     from spml_amd import parallel
     with parallel.count_collectives(timed=device.type == 'cuda') as cc:
       e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -591,10 +622,12 @@ def main():
     dist.all_gather_into_tensor(every, elapsed)
     per_rank = every.tolist()
   elapsed = max(per_rank)                   # the slowest rank's clock prices the job
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, last, trainer)
 
   km = None
   km_total = 0.0
-  if not args.no_kmeans:
+  if args.full and not args.no_kmeans:
     km = kmeans_stress_roofline(device) if args.recipe == 'stress' else kmeans_roofline(device)
     tot = torch.tensor([km['iters_per_s']], device=device, dtype=torch.float64)
     if world > 1:
@@ -652,7 +685,7 @@ def main():
       res['roofline'] = km['roofline']
       if args.recipe in ('voc', 'tag') and args.channels_last and not args.no_mc_conv:
         res['roofline_backbone'] = conv_roofline(device)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
       res['cpu_baseline'] = cpu_baseline(km, quick_kmeans_iters=2 if args.recipe == 'stress' else None)
     line = json.dumps(res)
   else:

@@ -39,7 +39,10 @@ def use_tuned_miopen_db(force=False):
       import shutil
       import tempfile
       private = tempfile.mkdtemp(prefix='spml_miopen_db_')
-      shutil.copytree(db, private, dirs_exist_ok=True)
+      # contents only: the permission bits of a read-only checkout would make the copy read-only too
+      shutil.copytree(db, private, dirs_exist_ok=True, copy_function=shutil.copyfile)
+      for d, _, _ in os.walk(private):
+        os.chmod(d, 0o700)
       atexit.register(shutil.rmtree, private, True)
       db = private
     except Exception:                    # no writable temp dir: fall back to the shipped copy

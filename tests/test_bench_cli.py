@@ -39,7 +39,7 @@ def test_bench_rejects_nonsense_gpu_counts():
 def test_bench_gpus_2_starts_two_ranks_itself():
   """Two ranks on this box's one GPU (gloo: RCCL refuses two ranks per device): the self-launch, DDP +
   SyncBatchNorm + prototype exchange, the max-over-ranks clock and the line's bookkeeping."""
-  r = _run(['--gpus', '2', '--steps', '2', '--warmup', '1', '--no-kmeans', '--no-cpu-baseline', '--batch', '4',
+  r = _run(['--gpus', '2', '--steps', '2', '--warmup', '1', '--full', '--no-kmeans', '--no-cpu-baseline', '--batch', '4',
             '--share-gpus', '--dist-backend', 'gloo'])
   assert r.returncode == 0, r.stderr[-4000:]
   lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -96,6 +96,34 @@ def test_roofline_reads_the_committed_rocprof_average(tmp_path, monkeypatch):
   assert bench.rocprof_mean_us('kmeans_pass16<3, 8, 1, true>') == (None, 0)
   monkeypatch.setattr(bench, 'ROCPROF_STATS_FILE', str(tmp_path / 'missing.csv'))
   assert bench.rocprof_mean_us('kmeans_pass64<3, 8, 1, true>') == (None, 0)
+
+
+def test_dump_outputs_writes_the_step_results_and_a_fixed_parameter_sample(tmp_path, monkeypatch):
+  """--dump-outputs: the scalars of the last step as float64, the trainable parameters as float32 in logical order
+  (a channels-last copy of the model writes the same file), the embedding network's at fixed seeded positions."""
+  import numpy as np
+  bench = _load_bench()
+  monkeypatch.setattr(bench, 'DUMP_PARAM_SAMPLE', 50)
+  torch.manual_seed(0)
+
+  class Trainer:
+    embedding_model = torch.nn.Sequential(torch.nn.Conv2d(3, 8, 3), torch.nn.Conv2d(8, 8, 1))
+    prediction_model = torch.nn.Conv2d(8, 2, 1)
+  Trainer.embedding_model[0].weight.requires_grad_(False)          # frozen: not written
+  last = {'loss': torch.tensor(1.5), 'accuracy': torch.tensor(0.25), 'lr': 3e-3}
+  bench.dump_outputs(str(tmp_path / 'a'), last, Trainer)
+  Trainer.embedding_model = Trainer.embedding_model.to(memory_format=torch.channels_last)
+  bench.dump_outputs(str(tmp_path / 'b'), last, Trainer)
+  a = {f[:-4]: np.load(str(tmp_path / 'a' / f)) for f in os.listdir(str(tmp_path / 'a'))}
+  assert sorted(a) == ['accuracy', 'embedding_params', 'loss', 'lr', 'prediction_params']
+  assert a['loss'].dtype == np.float64 and a['loss'] == 1.5 and a['lr'] == 3e-3 and a['accuracy'] == 0.25
+  flat = torch.cat([p.detach().reshape(-1) for p in Trainer.embedding_model.parameters() if p.requires_grad])
+  assert a['embedding_params'].dtype == np.float32 and a['embedding_params'].shape == (50,) and flat.numel() == 80
+  assert np.isin(a['embedding_params'], flat.numpy()).all()
+  assert np.array_equal(a['prediction_params'], torch.cat([p.detach().reshape(-1) for p in
+                                                           Trainer.prediction_model.parameters()]).numpy())
+  for k, v in a.items():
+    assert np.array_equal(np.load(str(tmp_path / 'b' / (k + '.npy'))), v), k
 
 
 def test_collective_counter_counts_and_restores():

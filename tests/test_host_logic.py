@@ -1,7 +1,6 @@
 """Host-side logic that needs no GPU: config, LR schedules, optimizer, label
 algebra, checkpoint name mapping, parameter groups, synthetic data."""
 import os
-import sys
 import warnings
 
 import numpy as np
@@ -157,6 +156,34 @@ def test_install_as_spml_alias():
   assert t.lr_poly is gt.lr_poly
 
 
+def test_private_miopen_db_is_writable_from_a_read_only_checkout(tmp_path, monkeypatch):
+  """MIOpen opens the user db and the kernel cache for writing (a read-only one fails the first convolution:
+  "attempt to write a readonly database"): the per-process copy must be writable when the shipped files are not."""
+  import shutil
+  import stat
+  shipped = str(tmp_path / 'pkg' / 'miopen_db')
+  shutil.copytree(os.path.join(os.path.dirname(os.path.abspath(spml_amd.__file__)), 'miopen_db'), shipped)
+  for d, _, fs in os.walk(shipped):
+    for f in fs:
+      os.chmod(os.path.join(d, f), 0o444)
+    os.chmod(d, 0o555)
+  monkeypatch.setattr(spml_amd, '_HERE', str(tmp_path / 'pkg'))
+  monkeypatch.delenv('MIOPEN_USER_DB_PATH', raising=False)
+  monkeypatch.delenv('MIOPEN_CUSTOM_CACHE_DIR', raising=False)
+  try:
+    assert spml_amd.use_tuned_miopen_db()
+    private = os.environ['MIOPEN_USER_DB_PATH']
+    assert private != shipped and os.environ['MIOPEN_CUSTOM_CACHE_DIR'] == os.path.join(private, 'cache')
+    dirs = [d for d, _, _ in os.walk(private)]
+    files = [os.path.join(d, f) for d, _, fs in os.walk(private) for f in fs]
+    assert any(f.endswith('.ukdb') for f in files) and any(f.endswith('.ufdb.txt') for f in files)
+    for p in dirs + files:
+      assert os.stat(p).st_mode & stat.S_IWUSR, p
+  finally:
+    for d, _, _ in os.walk(shipped):
+      os.chmod(d, 0o755)
+
+
 def test_synthetic_batch_contract():
   d, t = synth.make_batch(2, 65, seed=3)
   assert d['image'].shape == (2, 3, 65, 65) and d['image'].dtype == torch.float32
@@ -190,34 +217,31 @@ def test_synthetic_batch_with_per_image_palettes():
   assert torch.equal(t['semantic_label'], t2['semantic_label']) and torch.equal(d['image'], d2['image'])
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/spml'), reason='reference tree not mounted')
+def _state_dict_names(model):
+  return ['%s:%s' % (k, 'x'.join(str(s) for s in v.shape)) for k, v in model.state_dict().items()]
+
+
+def _fp64(model):
+  """The fixtures' reference outputs are fp64: fp32 CPU convolutions differ by ~1e-5 between CPU models."""
+  import copy
+  return copy.deepcopy(model).double()
+
+
 def test_embedding_network_matches_reference_modules():
-  """Same weights -> same embedding map as the reference's ResnetDeeplab (CPU)."""
-  sys.dont_write_bytecode = True
-  mods = {k: v for k, v in sys.modules.items() if k == 'spml' or k.startswith('spml.')}
-  for k in mods:
-    del sys.modules[k]
-  sys.path.insert(0, '/root/reference')
-  try:
-    from spml.models.embeddings.resnet_deeplab import ResnetDeeplab as RefNet
-    cfg = voc12_scribble_config(batch_size=1, embedding_dim=16)
-    torch.manual_seed(1)
-    ref = RefNet([1, 1, 1, 1], [1, 2, 1, 1], [1, 1, 2, 4], cfg).eval()
-  finally:
-    sys.path.remove('/root/reference')
-    for k in [k for k in sys.modules if k == 'spml' or k.startswith('spml.')]:
-      del sys.modules[k]
-    sys.modules.update(mods)
+  """Same weights -> same embedding map as the reference's ResnetDeeplab (CPU): m1_resnet_deeplab.npz holds the
+  reference's state-dict names and shapes and its outputs with the weights of tools_synth.reinit_parameters
+  (tools/gen_golden.py; the embedding in fp64)."""
+  from tools_synth import reinit_parameters
   from spml_amd.models.embeddings.resnet_deeplab import ResnetDeeplab
-  mine = ResnetDeeplab([1, 1, 1, 1], [1, 2, 1, 1], [1, 1, 2, 4], cfg).eval()
-  assert list(mine.state_dict().keys()) == list(ref.state_dict().keys())
-  torch.nn.Module.load_state_dict(mine, ref.state_dict())
-  x = {'image': torch.randn(1, 3, 65, 65)}
+  g = load_golden('m1_resnet_deeplab')
+  cfg = voc12_scribble_config(batch_size=1, embedding_dim=16)
+  mine = reinit_parameters(ResnetDeeplab([1, 1, 1, 1], [1, 2, 1, 1], [1, 1, 2, 4], cfg), 41).eval()
+  assert _state_dict_names(mine) == g.state_dict
   with torch.no_grad():
-    a = ref.generate_embeddings(x)
-    b = mine.generate_embeddings(x)
-  torch.testing.assert_close(b['embedding'], a['embedding'], rtol=1e-5, atol=1e-6)
-  torch.testing.assert_close(b['local_feature'], a['local_feature'], rtol=0, atol=0)
+    b = mine.generate_embeddings({'image': g.image})
+    b64 = _fp64(mine).generate_embeddings({'image': g.image.double()})
+  torch.testing.assert_close(b64['embedding'], g.embedding64, rtol=1e-5, atol=1e-6)
+  torch.testing.assert_close(b['local_feature'], g.local_feature, rtol=0, atol=0)
   assert b['embedding'].shape[-2:] == (18, 18)
 
 
@@ -256,69 +280,40 @@ def test_sliding_window_ends_follow_the_reference_arithmetic():
   assert list(inference.sliding_window_ends(1025, 513, 342)) == [513, 769, 1025]
 
 
-def _with_reference_modules(fn):
-  """Run fn() with /root/reference's `spml` importable, then restore sys.modules."""
-  sys.dont_write_bytecode = True
-  mods = {k: v for k, v in sys.modules.items() if k == 'spml' or k.startswith('spml.')}
-  for k in mods:
-    del sys.modules[k]
-  sys.path.insert(0, '/root/reference')
-  try:
-    return fn()
-  finally:
-    sys.path.remove('/root/reference')
-    for k in [k for k in sys.modules if k == 'spml' or k.startswith('spml.')]:
-      del sys.modules[k]
-    sys.modules.update(mods)
-
-
-@pytest.mark.skipif(not os.path.isdir('/root/reference/spml'), reason='reference tree not mounted')
 def test_pspnet_and_softmax_classifier_match_reference_modules():
   """N4: same weights -> same outputs as the reference's ResnetPspnet (head,
-  parameter names, LR groups) and SoftmaxClassifier (logits, loss, accuracy), on CPU."""
-  cfg = voc12_scribble_config(batch_size=1, embedding_dim=16)
-
-  def build():
-    from spml.models.embeddings.resnet_pspnet import ResnetPspnet as RefNet
-    from spml.models.predictions.softmax_classifier import SoftmaxClassifier as RefCls
-    torch.manual_seed(2)
-    return RefNet([1, 1, 1, 1], [1, 2, 1, 1], [1, 1, 2, 4], cfg).eval(), RefCls(cfg)
-  ref, ref_cls = _with_reference_modules(build)
+  parameter names, LR groups) and SoftmaxClassifier (logits, loss, accuracy), on CPU:
+  m2_pspnet_softmax_classifier.npz (tools/gen_golden.py, weights of tools_synth.reinit_parameters)."""
+  from tools_synth import reinit_parameters
   from spml_amd.models.embeddings.resnet_pspnet import ResnetPspnet
   from spml_amd.models.predictions.softmax_classifier import SoftmaxClassifier
-  mine = ResnetPspnet([1, 1, 1, 1], [1, 2, 1, 1], [1, 1, 2, 4], cfg).eval()
-  assert list(mine.state_dict().keys()) == list(ref.state_dict().keys())
-  torch.nn.Module.load_state_dict(mine, ref.state_dict())
-  x = {'image': torch.randn(1, 3, 65, 65)}
+  g = load_golden('m2_pspnet_softmax_classifier')
+  cfg = voc12_scribble_config(batch_size=1, embedding_dim=16)
+  mine = reinit_parameters(ResnetPspnet([1, 1, 1, 1], [1, 2, 1, 1], [1, 1, 2, 4], cfg), 42).eval()
+  assert _state_dict_names(mine) == g.state_dict
   with torch.no_grad():
-    a, b = ref.generate_embeddings(x, resize_as_input=True), mine.generate_embeddings(x, resize_as_input=True)
-  torch.testing.assert_close(b['embedding'], a['embedding'], rtol=1e-5, atol=1e-6)
-  torch.testing.assert_close(b['local_feature'], a['local_feature'], rtol=0, atol=0)
+    b = mine.generate_embeddings({'image': g.image}, resize_as_input=True)
+    b64 = _fp64(mine).generate_embeddings({'image': g.image.double()}, resize_as_input=True)
+  torch.testing.assert_close(b64['embedding'], g.embedding64, rtol=1e-5, atol=1e-6)
+  torch.testing.assert_close(b['local_feature'], g.local_feature, rtol=0, atol=0)
   names = {id(p): n for n, p in mine.named_parameters()}
-  ref_names = {id(p): n for n, p in ref.named_parameters()}
-  for g_mine, g_ref in zip(mine.get_params_lr(), ref.get_params_lr()):
-    assert g_mine['lr'] == g_ref['lr'] and g_mine.get('weight_decay') == g_ref.get('weight_decay')
-    assert [names[id(p)] for p in g_mine['params']] == [ref_names[id(p)] for p in g_ref['params']]
-  assert mine.name_mapping('layer3.0.conv1.weight') == ref.name_mapping('layer3.0.conv1.weight')
+  assert ['%r|%r|%s' % (grp['lr'], grp.get('weight_decay'), ','.join(names[id(p)] for p in grp['params']))
+          for grp in mine.get_params_lr()] == g.lr_groups
+  assert [mine.name_mapping('layer3.0.conv1.weight')] == g.name_mapping
   assert mine.name_mapping('module.pspp.1.bias', resume=True) == 'pspp.1.bias'
 
-  cls = SoftmaxClassifier(cfg)
-  assert list(cls.state_dict().keys()) == list(ref_cls.state_dict().keys())
-  cls.load_state_dict(ref_cls.state_dict())
-  cls.eval(); ref_cls.eval()
-  emb = torch.randn(2, 16, 17, 17)
-  lab = torch.randint(0, 23, (2, 33, 33))
-  lab[0, :5] = 255
-  a = ref_cls({'embedding': emb}, {'semantic_label': lab.clone()})
-  b = cls({'embedding': emb}, {'semantic_label': lab.clone()})
-  torch.testing.assert_close(b['semantic_logit'], a['semantic_logit'], rtol=1e-6, atol=1e-6)
-  torch.testing.assert_close(b['sem_ann_loss'], a['sem_ann_loss'], rtol=1e-6, atol=1e-6)
-  torch.testing.assert_close(b['accuracy'], a['accuracy'], rtol=0, atol=0)
-  assert torch.equal(b['semantic_prediction'], a['semantic_prediction'])
+  cls = reinit_parameters(SoftmaxClassifier(cfg), 43)
+  assert _state_dict_names(cls) == g.cls_state_dict
+  cls.eval()
+  emb, lab = g.cls_embedding, g.cls_label
+  b = _fp64(cls)({'embedding': emb.double()}, {'semantic_label': lab.clone()})
+  torch.testing.assert_close(b['semantic_logit'], g.semantic_logit64, rtol=1e-6, atol=1e-6)
+  torch.testing.assert_close(b['sem_ann_loss'], torch.tensor(g.sem_ann_loss64, dtype=torch.float64), rtol=1e-6, atol=1e-6)
+  torch.testing.assert_close(b['accuracy'], torch.tensor(g.accuracy64, dtype=b['accuracy'].dtype), rtol=0, atol=0)
+  assert torch.equal(b['semantic_prediction'], g.semantic_prediction)
   nolab = cls({'embedding': emb})
   assert nolab['sem_ann_loss'] is None and nolab['semantic_prediction'].shape == (2, 17, 17)
-  for g_mine, g_ref in zip(cls.get_params_lr(), ref_cls.get_params_lr()):
-    assert g_mine['lr'] == g_ref['lr'] and len(g_mine['params']) == len(g_ref['params'])
+  assert [[grp['lr'], len(grp['params'])] for grp in cls.get_params_lr()] == g.cls_lr_groups.tolist()
 
 
 def test_build_models_knows_the_pspnet_backbones():

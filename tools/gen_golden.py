@@ -866,6 +866,50 @@ def main():
        poly=np.array([g_train.lr_poly(3e-3, int(i), 30000, 100) for i in its]),
        step=np.array([g_train.lr_step(3e-3, int(i), [20000, 25000], 100) for i in its]))
 
+  # ======================= M1 / M2: the reference's model classes ============
+  # ResnetDeeplab, ResnetPspnet and SoftmaxClassifier of the reference with the weights of
+  # tests/tools_synth.reinit_parameters (the tests give this repository's classes the same ones):
+  # state-dict names and shapes, LR groups, checkpoint name mapping and the outputs of seeded
+  # inputs on CPU -- in fp64 (`*64`: fp32 convolutions differ by ~1e-5 between CPU models and
+  # thread counts), the location features of the fp32 forward.
+  import copy
+  import spml.models.embeddings.resnet_pspnet as e_psp
+  import spml.models.predictions.softmax_classifier as p_cls
+  from spml_amd.train import voc12_scribble_config
+  cfg_m = voc12_scribble_config(batch_size=1, embedding_dim=16)
+
+  def sd_names(model):
+    return np.array(['%s:%s' % (k, 'x'.join(str(s) for s in v.shape)) for k, v in model.state_dict().items()])
+
+  gen = torch.Generator().manual_seed(41)
+  m_net = reinit_parameters(e_dl.ResnetDeeplab([1, 1, 1, 1], [1, 2, 1, 1], [1, 1, 2, 4], cfg_m), 41).eval()
+  m_img = torch.randn(1, 3, 65, 65, generator=gen)
+  with torch.no_grad():
+    m_out = m_net.generate_embeddings({'image': m_img})
+    m_out64 = copy.deepcopy(m_net).double().generate_embeddings({'image': m_img.double()})
+  save(out, 'm1_resnet_deeplab', state_dict=sd_names(m_net), image=m_img,
+       embedding64=m_out64['embedding'], local_feature=m_out['local_feature'])
+
+  p_net = reinit_parameters(e_psp.ResnetPspnet([1, 1, 1, 1], [1, 2, 1, 1], [1, 1, 2, 4], cfg_m), 42).eval()
+  p_cls_m = reinit_parameters(p_cls.SoftmaxClassifier(cfg_m), 43).eval()
+  p_img = torch.randn(1, 3, 65, 65, generator=gen)
+  with torch.no_grad():
+    p_out = p_net.generate_embeddings({'image': p_img}, resize_as_input=True)
+    p_out64 = copy.deepcopy(p_net).double().generate_embeddings({'image': p_img.double()}, resize_as_input=True)
+  names = {id(p): n for n, p in p_net.named_parameters()}
+  groups = np.array(['%r|%r|%s' % (g['lr'], g.get('weight_decay'), ','.join(names[id(p)] for p in g['params']))
+                     for g in p_net.get_params_lr()])
+  c_emb = torch.randn(2, 16, 17, 17, generator=gen)
+  c_lab = torch.randint(0, 23, (2, 33, 33), generator=gen)
+  c_lab[0, :5] = 255
+  c_out = copy.deepcopy(p_cls_m).double()({'embedding': c_emb.double()}, {'semantic_label': c_lab.clone()})
+  save(out, 'm2_pspnet_softmax_classifier', state_dict=sd_names(p_net), image=p_img,
+       embedding64=p_out64['embedding'], local_feature=p_out['local_feature'],
+       lr_groups=groups, name_mapping=np.array([p_net.name_mapping('layer3.0.conv1.weight')]),
+       cls_state_dict=sd_names(p_cls_m), cls_embedding=c_emb, cls_label=c_lab,
+       semantic_logit64=c_out['semantic_logit'].detach(), sem_ann_loss64=c_out['sem_ann_loss'].detach(),
+       accuracy64=c_out['accuracy'], semantic_prediction=c_out['semantic_prediction'],
+       cls_lr_groups=np.array([[g['lr'], len(g['params'])] for g in p_cls_m.get_params_lr()], dtype=np.float64))
 
 if __name__ == '__main__':
   main()

@@ -75,11 +75,11 @@ tab = subprocess.run(['python', os.path.join(R, 'tools', 'summarize_trace.py'),
                      capture_output=True, text=True).stdout
 open(os.path.join(P, 'r06_train_step_steady_state.md'), 'w').write('''# Round 6 -- steady-state kernel time per training step (1x MI355X)
 
-Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --steps 3 --warmup 2 --no-cpu-baseline`
+Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --steps 3 --warmup 2 --full --no-cpu-baseline`
 (batch 16, 513x513, ResNet-101 DeepLab-v2, fp32 in / out, channels-last; stride-1 bottleneck units of res3 / res4 / res5
 and the ASPP head (forward as one 1x1 convolution with 36 x 64 columns + `conv_tap_gather`, data gradient as one 36-tap
 launch, weight gradients as one launch of `conv_wgrad<256, 256, 4, true, true>` on tiles of four taps x 64 channels) on
-the matrix-core convolutions of `csrc/conv.hip` with fused batch norm, the rest (stem, res2, the stride-2 unit) on MIOpen with the tuned find-db of `spml_amd/miopen_db`).  Default `python bench.py` of the same build without
+the matrix-core convolutions of `csrc/conv.hip` with fused batch norm, the rest (stem, res2, the stride-2 unit) on MIOpen with the tuned find-db of `spml_amd/miopen_db`).  Default `python bench.py --full` of the same build without
 the profiler: %.1f images/s, %.1f ms/step (`r06_bench_default.json`); `python bench.py --no-mc-conv` (library
 convolutions everywhere): %.1f images/s, %.1f ms.  Aggregated with `tools/summarize_trace.py` over the last 3 timed
 steps (the whole-run `--stats` file is `r06_bench_kernel_stats.csv`); `tools/run_round_checks.sh` +

@@ -9,12 +9,12 @@ mkdir -p $OUT
 for p in tools/hw_probes/global_atomics.hip; do [ -x ${p%.hip}.bin ] || hipcc --offload-arch=gfx950 -O3 -Wno-unused-value -Wno-inline-asm -mllvm -amdgpu-mfma-vgpr-form $p -o ${p%.hip}.bin; done
 python -m pytest tests -m gpu -q -rf 2>&1 | tail -6 | tee $OUT/pytest_gpu.txt
 python __graft_entry__.py --smoke 2>&1 | tail -1
-python bench.py 2>$OUT/bench_default.err | tail -1 > $OUT/bench_default.json; cat $OUT/bench_default.json
+python bench.py --full 2>$OUT/bench_default.err | tail -1 > $OUT/bench_default.json; cat $OUT/bench_default.json
 R=$PWD
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof_step -o step -- python $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline 2>&1 | grep -v "^[WE]2" | tail -1
+rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof_step -o step -- python $R/bench.py --steps 3 --warmup 2 --full --no-cpu-baseline 2>&1 | grep -v "^[WE]2" | tail -1
 # exactly the driver's command: its kernel stats are profiles/r06_bench_driver_cmd_kernel_stats.csv
-rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof_driver -o drv -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>&1 | grep -v "^[WE]2" | tail -1 > $R/$OUT/bench_driver_cmd_under_rocprof.json; cut -c1-300 $R/$OUT/bench_driver_cmd_under_rocprof.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof_driver -o drv -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline 2>&1 | grep -v "^[WE]2" | tail -1 > $R/$OUT/bench_driver_cmd_under_rocprof.json; cut -c1-300 $R/$OUT/bench_driver_cmd_under_rocprof.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof_km -o km -- python $R/tools/bench_kmeans.py --reps 5 2>&1 | grep path | tail -1
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof_km5 -o km5 -- python $R/tools/bench_kmeans.py --side 258 --d 514 --k 32 --reps 5 2>&1 | grep path | tail -1
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof_km144 -o km144 -- python $R/tools/bench_kmeans.py --k 12 --reps 5 2>&1 | grep path | tail -1
@@ -25,7 +25,7 @@ for cfg in "--side 513 --d 258 --k 6 --imgs 1" "--side 130 --d 66 --k 6 --imgs 1
 python tools/bench_nll.py > $OUT/bench_nll.txt 2>&1; cat $OUT/bench_nll.txt
 python tools/bench_nll.py 66564 3000 9000 --d 514 > $OUT/bench_nll_d514.txt 2>&1; cat $OUT/bench_nll_d514.txt
 python tools/bench_k1.py > $OUT/bench_k1.txt 2>&1; cat $OUT/bench_k1.txt
-for r in tag stress; do python bench.py --recipe $r --steps 6 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_$r.json; cut -c1-400 $OUT/bench_$r.json; done
+for r in tag stress; do python bench.py --recipe $r --steps 6 --warmup 3 --full --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_$r.json; cut -c1-400 $OUT/bench_$r.json; done
 python bench.py --recipe densepose --batch 8 --crop 769 --steps 3 --warmup 2 --no-cpu-baseline --no-kmeans 2>/dev/null | tail -1 > $OUT/bench_densepose.json; cut -c1-300 $OUT/bench_densepose.json
 python tools/bench_inference.py 2>&1 | tail -1 > $OUT/bench_inference_n2.json; cat $OUT/bench_inference_n2.json
 python tools/bench_inference.py --walk 64 64 2>&1 | tail -1 > $OUT/bench_inference_n3.json; cat $OUT/bench_inference_n3.json

@@ -2,7 +2,7 @@
 """Steady-state per-step kernel table from a rocprofv3 kernel trace of bench.py.
 
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o step -- \
-      python bench.py --steps 3 --warmup 2 --no-cpu-baseline
+      python bench.py --steps 3 --warmup 2 --full --no-cpu-baseline
   python tools/summarize_trace.py DIR/step_kernel_trace.csv --steps 3 > profiles/rNN_....md
 
 The whole-run --stats file is dominated by MIOpen's first-iteration solver search,
@@ -23,7 +23,7 @@ def main():
                        "(own channels-last kernel; the framework's max_pool_forward_nhwc / _nchw on other paths)")
   ap.add_argument('--top', type=int, default=45)
   ap.add_argument('--tail-marker', default='kmeans_pass16<3, 8',
-                  help='first kernel of what bench.py runs after the timed steps')
+                  help='first kernel of what bench.py --full runs after the timed steps')
   args = ap.parse_args()
 
   rows = []
