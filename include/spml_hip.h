@@ -43,8 +43,9 @@ const char* spml_status_string(int status);
 /* ABI version: bumped on any signature change. */
 /* Bumped whenever an entry point changes its arguments or a flag its meaning; spml_amd/_ffi.py refuses a library
  * whose version differs from the header it was written against.  2: round 4 (count_dev in the batch-norm backward,
- * spml_bn_finalize_ranks_f32); 3: round 5 (SPML_KMEANS_NO_PASS64 / _TWO_KERNEL_FINALIZE / _NO_V4K, paths "mfma_f16x2_v4p", "mfma_f16x2_v4k"). */
-#define SPML_ABI_VERSION 4
+ * spml_bn_finalize_ranks_f32); 3: round 5 (SPML_KMEANS_NO_PASS64 / _TWO_KERNEL_FINALIZE / _NO_V4K, paths "mfma_f16x2_v4p", "mfma_f16x2_v4k");
+ * 5: the softmax-inference entry points (spml_unit_hl8_from_nchw_f32 .. spml_iou_counts_i64). */
+#define SPML_ABI_VERSION 5
 int spml_abi_version(void);
 
 /* ------------------------------------------------------------------------
@@ -734,6 +735,50 @@ int spml_upsample_ce_fwd_f32(const float* logits, const int64_t* labels, int N, 
 int spml_upsample_ce_bwd_f32(const float* logits, const int64_t* labels, const float* lse,
                              int N, int C, int h, int w, int H, int W, int64_t ignore_index,
                              const float* scale, float* d_logits, void* stream);
+
+/* ---- full-resolution softmax inference: classifier head on a sliding-window crop, label map, IoU counts ----
+ * Replaces, per crop, pyscripts/inference/inference_softmax.py:126-137 with
+ * spml/models/predictions/softmax_classifier.py:52-55 in eval mode (x / |x|, 3x3 convolution C -> 2C, batch norm,
+ * ReLU, dropout = identity, 1x1 convolution 2C -> num_classes, `outputs[..., sh:eh, sw:ew] += crop_out`: the logits
+ * of overlapping windows are SUMMED, there are no counts), then :140-148 (arg-max, crop to the un-padded size) and
+ * pyscripts/benchmark/benchmark_by_mIoU.py:25-53 (iou_stats).  The 3x3 convolution + batch norm + ReLU between the
+ * first two calls is spml_conv_hl8_affine_f32 with the batch norm folded into weight and bias by the caller. */
+
+/* x fp32 [n][C][h][w] (NCHW) -> hl8 [n*h*w][C] of x / |x|_2 over the channels (softmax_classifier.py:52-54), one
+ * pass.  The scale of the split is the one of a bound of 1.0f (S = 2^13): pass a device float 1.0f as `a_bound` of
+ * the convolution.  C % 16 == 0, C <= 512.  The reference divides without an epsilon, so a zero-norm pixel is NaN
+ * there; here it is outside the contract and written as a row of zeros (non-finite inputs give non-finite halves;
+ * nothing faults). */
+int spml_unit_hl8_from_nchw_f32(const float* x, int n, int C, int h, int w, void* out,
+                                void* stream);
+
+/* 1 when spml_class_head_accumulate_f32 takes (Ch hidden channels, ncls classes): Ch % 32 == 0, ncls <= 64 and the
+ * weights plus one pixel tile fit the LDS. */
+int spml_class_head_supported(int Ch, int ncls);
+
+/* canvas[c][sh + y][sw + x] += sum_k hidden[y*w + x][k] * weight[c][k] + bias[c]   (softmax_classifier.py:26-30,55
+ * and inference_softmax.py:137), in place.  hidden fp32 [h*w][Ch] (channels-last: `out` of the affine convolution of
+ * ONE crop), weight [ncls][Ch], bias [ncls], canvas fp32 [ncls][Hp][Wp] (`semantic_logit`, N = 1).  fp32-input
+ * matrix cores: exact fp32 products, fp32 accumulation.  Plain loads and stores on the canvas: the windows of one
+ * image overlap, so their launches must be ordered (one stream). */
+int spml_class_head_accumulate_f32(const float* hidden, int Ch, int h, int w,
+                                   const float* weight, const float* bias, int ncls,
+                                   float* canvas, int Hp, int Wp, int sh, int sw,
+                                   void* stream);
+
+/* out int64 [h][w] = arg-max over the classes of the top-left h x w region of canvas [ncls][Hp][Wp]
+ * (inference_softmax.py:142-148).  Ties: the lowest class index; NaN (outside the contract) counts as the
+ * largest value and the first one wins -- both as torch.argmax. */
+int spml_argmax_channels_i64(const float* canvas, int ncls, int Hp, int Wp, int h, int w,
+                             int64_t* out, void* stream);
+
+/* counts int64 [3][ncls] += (TP+FN, TP+FP, TP) of pred / target (int64 [n]) over the pixels with
+ * 0 <= target < ncls (benchmark_by_mIoU.py:25-53); accumulated INTO counts, so a caller loops over images and zeroes
+ * it once.  TP+FP bins pred at those pixels: a prediction outside [0, ncls) falls into no bin (numpy's histogram
+ * closes its last bin on the right, so the reference counts pred == ncls as class ncls - 1; an arg-max over ncls
+ * planes never gives that value).  Integer atomics: bit-reproducible in either mode.  ncls <= 4096. */
+int spml_iou_counts_i64(const int64_t* pred, const int64_t* target, int64_t n, int ncls,
+                        int64_t* counts, void* stream);
 
 #ifdef __cplusplus
 }

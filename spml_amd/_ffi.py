@@ -123,6 +123,12 @@ _SIGNATURES = {
     'spml_maxpool3x3s2_nhwc_f32': (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     'spml_window_accumulate_f32': (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int,
                                            _P]),
+    'spml_unit_hl8_from_nchw_f32': (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
+    'spml_class_head_supported': (c_int, [c_int, c_int]),
+    'spml_class_head_accumulate_f32': (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, _P, c_int, c_int, c_int, c_int,
+                                               _P]),
+    'spml_argmax_channels_i64': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    'spml_iou_counts_i64': (c_int, [_P, _P, c_int64, c_int, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -132,7 +138,7 @@ class SpmlHipError(RuntimeError):
   pass
 
 
-ABI_VERSION = 4            # = SPML_ABI_VERSION of include/spml_hip.h (tests/test_cabi_exports.py compares the two)
+ABI_VERSION = 5            # = SPML_ABI_VERSION of include/spml_hip.h (tests/test_cabi_exports.py compares the two)
 
 
 def lib():
@@ -539,6 +545,56 @@ def window_accumulate(patch, acc, counts, sh, sw):
   check(lib().spml_window_accumulate_f32(
       ptr(patch, torch.float32), c, h, w, ptr(acc, torch.float32), ptr(counts, torch.float32),
       big_h, big_w, int(sh), int(sw), stream_ptr()), 'spml_window_accumulate_f32')
+
+
+# ---------------------------------------------------------------------------
+# full-resolution softmax inference (csrc/softmax_head.hip)
+def unit_hl8_from_nchw(x):
+  """x fp32 [n, C, h, w] (NCHW, contiguous) -> Hl8 [n*h*w, C] of x / |x| over the channels; its bound is a device
+  1.0 (a unit row: the scale is fixed, no abs-max pass)."""
+  n, c, h, w = x.shape
+  out = torch.empty((n * h * w * c * 4,), dtype=torch.uint8, device=x.device)
+  check(lib().spml_unit_hl8_from_nchw_f32(ptr(x, torch.float32), n, c, h, w, ptr(out), stream_ptr()),
+        'spml_unit_hl8_from_nchw_f32')
+  return Hl8(out, torch.ones((1,), dtype=torch.float32, device=x.device), n * h * w, c)
+
+
+def class_head_supported(ch, ncls):
+  return bool(lib().spml_class_head_supported(int(ch), int(ncls)))
+
+
+def class_head_accumulate(hidden, weight, bias, canvas, sh, sw, h, w):
+  """canvas[:, sh:sh+h, sw:sw+w] += hidden @ weight.T + bias (in place).  hidden: fp32, h*w*Ch values stored
+  channels-last (any shape); weight [ncls, Ch]; canvas [ncls, Hp, Wp]."""
+  ncls, ch = weight.shape
+  if hidden.numel() != h * w * ch or canvas.dim() != 3 or canvas.shape[0] != ncls or bias.numel() != ncls:
+    raise SpmlHipError('class_head_accumulate: shape mismatch')
+  check(lib().spml_class_head_accumulate_f32(
+      _ptr_any(hidden), ch, int(h), int(w), ptr(weight, torch.float32), ptr(bias, torch.float32), ncls,
+      ptr(canvas, torch.float32), canvas.shape[1], canvas.shape[2], int(sh), int(sw), stream_ptr()),
+        'spml_class_head_accumulate_f32')
+
+
+def argmax_channels(canvas, h, w):
+  """canvas fp32 [ncls, Hp, Wp] -> int64 [h, w]: arg-max over the classes of the top-left region."""
+  ncls, hp, wp = canvas.shape
+  out = torch.empty((h, w), dtype=torch.int64, device=canvas.device)
+  check(lib().spml_argmax_channels_i64(ptr(canvas, torch.float32), ncls, hp, wp, int(h), int(w), ptr(out),
+                                       stream_ptr()), 'spml_argmax_channels_i64')
+  return out
+
+
+def iou_counts(pred, target, ncls, counts=None):
+  """counts int64 [3, ncls] += (TP+FN, TP+FP, TP) of two int64 label maps (a fresh zero tensor when None)."""
+  if pred.numel() != target.numel():
+    raise SpmlHipError('iou_counts: pred and target differ in size')
+  if counts is None:
+    counts = torch.zeros((3, ncls), dtype=torch.int64, device=pred.device)
+  elif tuple(counts.shape) != (3, ncls):
+    raise SpmlHipError('iou_counts: counts must be [3, num_classes]')
+  check(lib().spml_iou_counts_i64(ptr(pred, torch.int64), ptr(target, torch.int64), pred.numel(), int(ncls),
+                                  ptr(counts, torch.int64), stream_ptr()), 'spml_iou_counts_i64')
+  return counts
 
 
 def affinity_transition(emb, scale=5.0, power=20):

@@ -109,6 +109,41 @@ def predict_full_resolution(embedding_model, prediction_model, image, valid_hw, 
           'semantic_score': outputs['semantic_score'], 'cluster_index': embeddings['cluster_index']}
 
 
+def predict_softmax_full_resolution(embedding_model, prediction_model, image, valid_hw, crop_size, stride):
+  """One image of the softmax label inference (`pyscripts/inference/inference_softmax.py:105-148`): sliding
+  windows over the padded `image` `[1,3,Hp,Wp]` (:105-123), per crop the embedding at input resolution and the
+  classifier head (:126-128), the crops' logits SUMMED into the canvas (:130-137: no counts, unlike the embedding
+  route), arg-max (:142) cropped to the top-left `valid_hw` region (:148).  The crops of a group go through the
+  backbone together; each crop's logits are added in the reference's window order, so the fp32 sum order of a pixel is
+  the reference's.  Returns `semantic_logit` `[1,ncls,Hp,Wp]`, `semantic_prediction` `[h,w]` (int64) and `head_path`,
+  the name of the path `SoftmaxClassifier.accumulate_logits` took."""
+  if image.dim() != 4 or image.shape[0] != 1:
+    raise ValueError('predict_softmax_full_resolution expects one image [1,3,H,W]')
+  h, w = valid_hw
+  pad_h, pad_w = image.shape[-2:]
+  crop_h, crop_w = crop_size
+  ends_h = sliding_window_ends(pad_h, crop_h, stride[0])
+  ends_w = sliding_window_ends(pad_w, crop_w, stride[1])
+  windows = [(int(eh) - crop_h, int(ew) - crop_w) for eh in ends_h for ew in ends_w]
+  first = next(embedding_model.parameters(), None)
+  nhwc = first is not None and first.is_cuda and first.dim() == 4 and \
+      first.is_contiguous(memory_format=torch.channels_last) and not first.is_contiguous()
+  canvas = torch.zeros((1, prediction_model.num_classes, pad_h, pad_w), dtype=torch.float32, device=image.device)
+  prediction_model.prepare_inference()          # once per image: validates the folded operands (one host read)
+  group, path = 8, None
+  with torch.no_grad():
+    for g0 in range(0, len(windows), group):
+      part = windows[g0:g0 + group]
+      crops = torch.cat([image[:, :, sh:sh + crop_h, sw:sw + crop_w] for sh, sw in part], 0)
+      if nhwc:
+        crops = crops.contiguous(memory_format=torch.channels_last)
+      embs = embedding_model.generate_embeddings({'image': crops}, resize_as_input=True)['embedding']
+      for i, (sh, sw) in enumerate(part):
+        path = prediction_model.accumulate_logits(embs[i:i + 1], canvas, sh, sw)
+    prediction = _ffi.argmax_channels(canvas[0], h, w)
+  return {'semantic_logit': canvas, 'semantic_prediction': prediction, 'head_path': path}
+
+
 def save_image_memory(path, prototypes, prototype_labels):
   """`np.save` of `{'prototype', 'prototype_label'}` (prototype.py:207-211)."""
   segsort_others.save_memory_bank(path, prototypes, prototype_labels)

@@ -800,6 +800,80 @@ def main():
     e_dl2.segsort_common.segment_by_kmeans = orig_sbk2
   save(out, 'n5_inference', **n5_store)
 
+  # ======================= N6: full-resolution softmax inference + IoU counts ==============
+  # pyscripts/inference/inference_softmax.py:105-148: window ends, per crop `embedding_model(crop,
+  # resize_as_input=True)` and the reference's own SoftmaxClassifier in eval mode, the crops' outputs SUMMED into the
+  # padded canvas (no counts), arg-max, crop to the un-padded size.  Same exec-the-lines arrangement as N2 / N5: the
+  # seeded 5x5 conv as the embedding model (called as a function here), seeded head weights, non-trivial running
+  # statistics.  `margin` = top-1 minus top-2 of the reference canvas per valid pixel: the tests compare labels where
+  # it is at least 2e-4 * max|logit|, and fewer than 1 % of the valid pixels may fall below (asserted here).
+  import spml.models.predictions.softmax_classifier as p_cls6
+  sm_py = os.path.join(args.ref, 'pyscripts', 'inference', 'inference_softmax.py')
+  src_n6 = ref_lines(sm_py, 105, 148)
+  assert 'patch_ind_h' in src_n6 and 'torch.argmax(semantic_logits, 1)' in src_n6 and 'counts' not in src_n6
+
+  class CallableStub(StubEmbedder):
+    def __call__(self, datas, targets=None, resize_as_input=False):
+      return self.generate_embeddings(datas, targets, resize_as_input=resize_as_input)
+
+  n6_store = {}
+  for ci, (c, ncls, pad, valid, crop, stride) in enumerate([
+      (32, 5, (70, 90), (60, 83), (48, 48), (32, 32)),
+      (64, 21, (50, 50), (41, 50), (50, 50), (33, 33))]):
+    gen = torch.Generator().manual_seed(1600 + ci)
+    torch.manual_seed(1600 + ci)
+    conv = torch.nn.Conv2d(3, c, 5, padding=2)
+    base = torch.randn(1, 3, pad[0] // 8 + 2, pad[1] // 8 + 2, generator=gen)
+    image = torch.nn.functional.interpolate(base, size=pad, mode='bilinear', align_corners=False)
+    image = image + 0.05 * torch.randn(1, 3, pad[0], pad[1], generator=gen)
+    cfg6 = AttrDict(dataset=AttrDict(semantic_ignore_index=255, num_classes=ncls),
+                    network=AttrDict(embedding_dim=c),
+                    test=AttrDict(stride=list(stride), crop_size=list(crop)))
+    head = p_cls6.SoftmaxClassifier(cfg6)
+    with torch.no_grad():
+      bn = head.semantic_classifier[1]
+      bn.weight.copy_(0.5 + torch.rand(2 * c, generator=gen))
+      bn.bias.copy_(0.1 * torch.randn(2 * c, generator=gen))
+      bn.running_mean.copy_(0.05 * torch.randn(2 * c, generator=gen))
+      bn.running_var.copy_(0.02 + 0.05 * torch.rand(2 * c, generator=gen))
+      head.semantic_classifier[4].bias.copy_(0.1 * torch.randn(ncls, generator=gen))
+    head.eval()
+    env = {'config': cfg6, 'pad_image_h': pad[0], 'pad_image_w': pad[1], 'resize_image_h': valid[0],
+           'resize_image_w': valid[1], 'image_batch': {'image': image},
+           'embedding_model': CallableStub(conv, [1, 1]), 'prediction_model': head, 'math': math, 'np': np,
+           'torch': torch}
+    exec(compile(src_n6, sm_py + ':105-148', 'exec'), env)
+    logit = env['semantic_logits']
+    pred = env['semantic_pred']
+    assert tuple(logit.shape) == (1, ncls, pad[0], pad[1]) and pred.shape == tuple(valid) and pred.dtype == np.uint8
+    top2 = logit[0, :, :valid[0], :valid[1]].topk(2, dim=0).values
+    margin = top2[0] - top2[1]
+    low = (margin < 2e-4 * logit.abs().max()).float().mean().item()
+    assert low < 0.01, 'case %d: %.4f of the valid pixels have a low margin -- pick another seed' % (ci, low)
+    t = 'c%d_' % ci
+    n6_store.update({
+        t + 'image': image, t + 'conv_w': conv.weight, t + 'conv_b': conv.bias,
+        t + 'cfg': np.array([c, ncls, pad[0], pad[1], valid[0], valid[1], crop[0], crop[1], stride[0], stride[1]]),
+        t + 'semantic_logit': logit, t + 'semantic_pred': pred, t + 'margin': margin,
+        t + 'state_names': np.array(list(head.state_dict().keys()))})
+    n6_store.update({t + 'sd_' + k: v for k, v in head.state_dict().items()})
+  # IoU counts: pyscripts/benchmark/benchmark_by_mIoU.py:25-53 (pure numpy; the module imports PIL at its top, so the
+  # function's lines are exec'd).  Targets of 255 and a prediction >= num_classes at a valid pixel are included.
+  iou_py = os.path.join(args.ref, 'pyscripts', 'benchmark', 'benchmark_by_mIoU.py')
+  iou_env = {'np': np}
+  exec(compile(ref_lines(iou_py, 25, 53), iou_py + ':25-53', 'exec'), iou_env)
+  rs = np.random.RandomState(1650)
+  iou_ncls = 7
+  iou_target = rs.randint(0, iou_ncls, size=(37, 53)).astype(np.uint8)
+  iou_pred = np.where(rs.rand(37, 53) < 0.6, iou_target, rs.randint(0, iou_ncls, size=(37, 53))).astype(np.uint8)
+  iou_target[rs.rand(37, 53) < 0.1] = 255
+  iou_target[0, 0], iou_pred[0, 0] = 3, iou_ncls + 2          # a prediction outside every bin at a valid pixel
+  iou_target[0, 1], iou_pred[0, 1] = 255, iou_ncls + 2        # ... and at an ignored one
+  tp_fn, tp_fp, tp = iou_env['iou_stats'](iou_pred, iou_target, num_classes=iou_ncls)
+  n6_store.update({'iou_pred': iou_pred, 'iou_target': iou_target, 'iou_num_classes': np.array(iou_ncls),
+                   'iou_counts': np.stack([tp_fn, tp_fp, tp]).astype(np.int64)})
+  save(out, 'n6_softmax_inference', **n6_store)
+
   # ======================= H2: two steps of the stage-2 classifier training ===============
   # pyscripts/train/train_classifier.py:139-169, the loop body exec'd as it stands on ONE device:
   # the reference's ResnetDeeplab in eval mode under no_grad, its SoftmaxClassifier (dropout
