@@ -44,8 +44,9 @@ const char* spml_status_string(int status);
 /* Bumped whenever an entry point changes its arguments or a flag its meaning; spml_amd/_ffi.py refuses a library
  * whose version differs from the header it was written against.  2: round 4 (count_dev in the batch-norm backward,
  * spml_bn_finalize_ranks_f32); 3: round 5 (SPML_KMEANS_NO_PASS64 / _TWO_KERNEL_FINALIZE / _NO_V4K, paths "mfma_f16x2_v4p", "mfma_f16x2_v4k");
- * 5: the softmax-inference entry points (spml_unit_hl8_from_nchw_f32 .. spml_iou_counts_i64). */
-#define SPML_ABI_VERSION 5
+ * 5: the softmax-inference entry points (spml_unit_hl8_from_nchw_f32 .. spml_iou_counts_i64);
+ * 6: the pseudo-label entry points (spml_resample_unit_f32 .. spml_upsample_argmax_i64). */
+#define SPML_ABI_VERSION 6
 int spml_abi_version(void);
 
 /* ------------------------------------------------------------------------
@@ -779,6 +780,52 @@ int spml_argmax_channels_i64(const float* canvas, int ncls, int Hp, int Wp, int 
  * planes never gives that value).  Integer atomics: bit-reproducible in either mode.  ncls <= 4096. */
 int spml_iou_counts_i64(const int64_t* pred, const int64_t* target, int64_t n, int ncls,
                         int64_t* counts, void* stream);
+
+/* ------------------------------------------------------------------------
+ * N7  pseudo-label generation from the softmax head (csrc/pseudo_label.hip)
+ * replaces: pyscripts/inference/pseudo_softmaxrw_crf.py:130-136, 141-157, 173-176 and pseudo_softmax.py:129-135,
+ *           140-160, 176-179 -- everything of the two scripts around the affinity (spml_affinity_transition_f32 above)
+ *           and the walk's GEMMs.  No entry point below uses floating-point atomics: results are bit-reproducible and
+ *           the same with and without the deterministic mode.
+ * Resampling is bilinear with half-pixel centres (`F.interpolate(mode='bilinear')`, align_corners = False, no
+ * anti-aliasing) as ATen computes it: scale = in / out in fp32, src = max(scale * (dst + 0.5) - 0.5, 0), i0 = floor(src),
+ * i1 = min(i0 + 1, in - 1), lambda = src - i0.  A view's source is the top-left rh x rw region of a padded Hp x Wp
+ * plane (in = rh, rw); with `flip` the source column of x is rw - 1 - x (the reference crops, flips back, then
+ * interpolates).  Tensors of the network are read through element strides (stride_c, stride_y, stride_x > 0), so NCHW
+ * and channels-last storage are both read as they are, with the same result bit for bit.
+ * ------------------------------------------------------------------------ */
+#define SPML_COMBINE_PROB_MEAN 0   /* softmax per view, mean of the probabilities (pseudo_softmaxrw_crf.py:143-147) */
+#define SPML_COMBINE_LOGIT_MEAN 1  /* mean of the logits, then one softmax (pseudo_softmax.py:144-150) */
+
+/* out[b][c][p] = r[c][p] / |r[:, p]|_2, r = view `emb` [C][Hp][Wp] cropped, un-flipped and resampled to oh x ow
+ * (pseudo_softmaxrw_crf.py:130-136; plain division, no epsilon).  out: fp32 [B][C][oh*ow], the layout
+ * spml_affinity_transition_f32 reads; this call writes slice b.  C <= 256. */
+int spml_resample_unit_f32(const float* emb, int C, int Hp, int Wp, int64_t stride_c, int64_t stride_y,
+                           int64_t stride_x, int rh, int rw, int flip, int oh, int ow, float* out, int B, int b,
+                           void* stream);
+
+/* acc[c][p] += softmax over c of r[c][p] (SPML_COMBINE_PROB_MEAN, pseudo_softmaxrw_crf.py:131-144) or r[c][p] itself
+ * (SPML_COMBINE_LOGIT_MEAN, pseudo_softmax.py:130-144), r = view `logit` [ncls][Hp][Wp] cropped, un-flipped and
+ * resampled.  acc: fp32 [ncls][oh*ow], zeroed by the caller before the first view; plain loads and stores, so the
+ * views of one image are added in call order on one stream (a pixel's fp32 sum has the reference's order).
+ * ncls <= 256. */
+int spml_resample_classes_accumulate_f32(const float* logit, int ncls, int Hp, int Wp, int64_t stride_c,
+                                         int64_t stride_y, int64_t stride_x, int rh, int rw, int flip, int oh,
+                                         int ow, int combine, float* acc, void* stream);
+
+/* cam [ncls][n] from the sum `acc` [ncls][n] of B views: acc / B; with SPML_COMBINE_LOGIT_MEAN the softmax over the
+ * classes (pseudo_softmax.py:149-150); every class divided by its maximum over the n pixels; classes with tags[c] == 0
+ * set to 0; class 0 set to `threshold` where has_threshold != 0 (pseudo_softmaxrw_crf.py:146-157; the reference's
+ * TH = None is has_threshold = 0).  tags: one byte per class.  One launch (prob_mean) or two (logit_mean).  cam may not
+ * alias acc.  ncls <= 256. */
+int spml_cam_finalize_f32(const float* acc, int ncls, int64_t n, int B, int combine, const unsigned char* tags,
+                          int has_threshold, float threshold, float* cam, void* stream);
+
+/* out int64 [h][w] = arg-max over the classes of cam [ncls][oh][ow] resampled to h x w, in one kernel: the
+ * ncls x h x w tensor of pseudo_softmaxrw_crf.py:173-176 (`cv2.resize(..., INTER_LINEAR)` + `np.argmax`, the same
+ * half-pixel mapping) is never written.  Ties: the lowest class; NaN as torch.argmax (the rules of
+ * spml_argmax_channels_i64). */
+int spml_upsample_argmax_i64(const float* cam, int ncls, int oh, int ow, int h, int w, int64_t* out, void* stream);
 
 #ifdef __cplusplus
 }

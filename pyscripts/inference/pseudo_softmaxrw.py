@@ -1,0 +1,26 @@
+#!/usr/bin/env python3
+"""Generate pseudo labels by the softmax classifier and a random walk over the pixel affinity, with the reference's
+command line and config surface (`pyscripts/inference/pseudo_softmaxrw_crf.py` of twke18/SPML; the scribble / point /
+box recipes run it between stage 1 and stage 2):
+
+  python3 pyscripts/inference/pseudo_softmaxrw.py --snapshot_dir S --cfg_path C.yaml --save_dir OUT --data_list L
+
+Flip pair at scale 1, softmax per view and mean of the probabilities, WALK_STEPS = 6 squarings of the transition
+matrix (:29, :109-112, :143-147).  Writes the labels of :176 (before the denseCRF refinement, which is outside this
+repository) as `semantic_gray/<name>.npy`; see spml_amd/pseudo_labels_cli.py."""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+
+SCALES, COMBINE, WALK_STEPS = (1,), 'prob_mean', 6
+
+
+def main(argv=None):
+  from spml_amd.pseudo_labels_cli import run
+  run('Generate pseudo labels by softmax classifier and random walk.', SCALES, COMBINE, WALK_STEPS, argv)
+
+
+if __name__ == '__main__':
+  main()

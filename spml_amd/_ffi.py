@@ -129,6 +129,12 @@ _SIGNATURES = {
                                                _P]),
     'spml_argmax_channels_i64': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     'spml_iou_counts_i64': (c_int, [_P, _P, c_int64, c_int, _P, _P]),
+    'spml_resample_unit_f32': (c_int, [_P, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int,
+                                       c_int, _P, c_int, c_int, _P]),
+    'spml_resample_classes_accumulate_f32': (c_int, [_P, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int, c_int,
+                                                     c_int, c_int, c_int, c_int, _P, _P]),
+    'spml_cam_finalize_f32': (c_int, [_P, c_int, c_int64, c_int, c_int, _P, c_int, c_float, _P, _P]),
+    'spml_upsample_argmax_i64': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -138,7 +144,7 @@ class SpmlHipError(RuntimeError):
   pass
 
 
-ABI_VERSION = 5            # = SPML_ABI_VERSION of include/spml_hip.h (tests/test_cabi_exports.py compares the two)
+ABI_VERSION = 6            # = SPML_ABI_VERSION of include/spml_hip.h (tests/test_cabi_exports.py compares the two)
 
 
 def lib():
@@ -595,6 +601,85 @@ def iou_counts(pred, target, ncls, counts=None):
   check(lib().spml_iou_counts_i64(ptr(pred, torch.int64), ptr(target, torch.int64), pred.numel(), int(ncls),
                                   ptr(counts, torch.int64), stream_ptr()), 'spml_iou_counts_i64')
   return counts
+
+
+# ---------------------------------------------------------------------------
+# pseudo-label generation (csrc/pseudo_label.hip)
+COMBINE_MODES = {'prob_mean': 0, 'logit_mean': 1}      # SPML_COMBINE_* of include/spml_hip.h
+
+
+def _combine(combine):
+  if combine not in COMBINE_MODES:
+    raise SpmlHipError("combine must be 'prob_mean' or 'logit_mean' (got %r)" % (combine,))
+  return COMBINE_MODES[combine]
+
+
+def _view_args(x, crop_hw, out_hw, what):
+  """(C, Hp, Wp, strides..., rh, rw, oh, ow) of a network output [C, Hp, Wp] read through its strides."""
+  if x.dim() != 3:
+    raise SpmlHipError('%s: expected a [C, Hp, Wp] tensor' % what)
+  c, hp, wp = x.shape
+  (rh, rw), (oh, ow) = crop_hw, out_hw
+  if not (0 < rh <= hp and 0 < rw <= wp and oh > 0 and ow > 0):
+    raise SpmlHipError('%s: crop %r / output %r do not fit a %d x %d plane' % (what, crop_hw, out_hw, hp, wp))
+  sc, sy, sx = x.stride()
+  return c, hp, wp, sc, sy, sx, int(rh), int(rw), int(oh), int(ow)
+
+
+def resample_unit(emb, crop_hw, flip, out_hw, out, b):
+  """out[b] = unit-norm columns of `emb` [C, Hp, Wp] (fp32, any positive strides: NCHW or channels-last, no copy)
+  cropped to its top-left `crop_hw`, flipped back when `flip`, bilinearly resampled to `out_hw`.  out: fp32
+  [B, C, oh*ow] (contiguous), the operand of `affinity_transition`."""
+  c, hp, wp, sc, sy, sx, rh, rw, oh, ow = _view_args(emb, crop_hw, out_hw, 'resample_unit')
+  if out.dim() != 3 or out.shape[1] != c or out.shape[2] != oh * ow or not 0 <= b < out.shape[0]:
+    raise SpmlHipError('resample_unit: out must be [B, %d, %d] with b < B' % (c, oh * ow))
+  check(lib().spml_resample_unit_f32(_ptr_any(emb), c, hp, wp, sc, sy, sx, rh, rw, int(bool(flip)), oh, ow,
+                                     ptr(out, torch.float32), out.shape[0], int(b), stream_ptr()),
+        'spml_resample_unit_f32')
+  return out
+
+
+def resample_classes_accumulate(logit, crop_hw, flip, out_hw, acc, combine='prob_mean'):
+  """acc += the view `logit` [ncls, Hp, Wp] (fp32, any positive strides) cropped, un-flipped, resampled to `out_hw` and
+  -- with combine='prob_mean' -- soft-maxed over the classes; 'logit_mean' adds the resampled logits.  acc: fp32
+  [ncls, oh*ow] (or [ncls, oh, ow]), contiguous, updated in place."""
+  ncls, hp, wp, sc, sy, sx, rh, rw, oh, ow = _view_args(logit, crop_hw, out_hw, 'resample_classes_accumulate')
+  if acc.shape[0] != ncls or acc.numel() != ncls * oh * ow:
+    raise SpmlHipError('resample_classes_accumulate: acc must hold [%d, %d] values' % (ncls, oh * ow))
+  check(lib().spml_resample_classes_accumulate_f32(_ptr_any(logit), ncls, hp, wp, sc, sy, sx, rh, rw, int(bool(flip)),
+                                                   oh, ow, _combine(combine), ptr(acc, torch.float32), stream_ptr()),
+        'spml_resample_classes_accumulate_f32')
+  return acc
+
+
+def cam_finalize(acc, num_views, label_tags, combine='prob_mean', background_threshold=None):
+  """Summed views `acc` [ncls, ...] -> class activation maps of the same shape: mean over the views, softmax over the
+  classes for 'logit_mean', every class divided by its maximum, untagged classes 0, class 0 = `background_threshold`
+  when given.  label_tags: bool (or uint8) [ncls] on the device."""
+  ncls = acc.shape[0]
+  if label_tags.numel() != ncls or label_tags.dtype not in (torch.bool, torch.uint8):
+    raise SpmlHipError('cam_finalize: label_tags must be a bool [%d] tensor' % ncls)
+  if int(num_views) < 1:
+    raise SpmlHipError('cam_finalize: no views')
+  cam = torch.empty_like(acc)
+  tags = label_tags.view(torch.uint8) if label_tags.dtype == torch.bool else label_tags
+  check(lib().spml_cam_finalize_f32(ptr(acc, torch.float32), ncls, acc.numel() // ncls, int(num_views),
+                                    _combine(combine), ptr(tags, torch.uint8), int(background_threshold is not None),
+                                    float(background_threshold or 0.0), ptr(cam), stream_ptr()),
+        'spml_cam_finalize_f32')
+  return cam
+
+
+def upsample_argmax(cam, h, w):
+  """cam fp32 [ncls, oh, ow] -> int64 [h, w]: arg-max over the classes of the bilinearly up-sampled maps (which are
+  never materialised)."""
+  if cam.dim() != 3:
+    raise SpmlHipError('upsample_argmax: expected [ncls, oh, ow]')
+  ncls, oh, ow = cam.shape
+  out = torch.empty((int(h), int(w)), dtype=torch.int64, device=cam.device)
+  check(lib().spml_upsample_argmax_i64(ptr(cam, torch.float32), ncls, oh, ow, int(h), int(w), ptr(out), stream_ptr()),
+        'spml_upsample_argmax_i64')
+  return out
 
 
 def affinity_transition(emb, scale=5.0, power=20):

@@ -149,6 +149,14 @@ def save_image_memory(path, prototypes, prototype_labels):
   segsort_others.save_memory_bank(path, prototypes, prototype_labels)
 
 
+def _walk(trans, cam, walk_steps):
+  """`trans <- trans . trans` `walk_steps` times, then `cam . trans` (pseudo_camrw_crf.py:159-164 =
+  pseudo_softmaxrw_crf.py:165-170): fp32 library GEMMs (rocBLAS through torch.matmul)."""
+  for _ in range(walk_steps):
+    trans = torch.matmul(trans, trans)
+  return torch.matmul(cam.reshape(cam.shape[0], -1).float(), trans).view(cam.shape)
+
+
 def affinity_random_walk(embs_list, cam, walk_steps=6, scale=5.0, power=20):
   """Random walk of class activation maps `[K,h,w]` over the pixel affinity of one image
   (pseudo_camrw_crf.py:143-164).  `embs_list`: one `[1,C,h,w]` embedding
@@ -162,6 +170,108 @@ def affinity_random_walk(embs_list, cam, walk_steps=6, scale=5.0, power=20):
       views.append(embs.reshape(embs.shape[1], -1))
     emb = torch.stack(views, 0).float().contiguous()          # [B,C,n]
     trans = _ffi.affinity_transition(emb, scale, power)
-    for _ in range(walk_steps):
-      trans = torch.matmul(trans, trans)
-    return torch.matmul(cam.reshape(cam.shape[0], -1).float(), trans).view(cam.shape)
+    return _walk(trans, cam, walk_steps)
+
+
+def label_tags_from_map(label, num_classes):
+  """The classes below `num_classes` that occur in a label map -> bool `[num_classes]` on the label's device
+  (pseudo_softmaxrw_crf.py:102-106)."""
+  label = torch.as_tensor(label)
+  present = torch.unique(label.reshape(-1).long())
+  tags = torch.zeros((num_classes,), dtype=torch.bool, device=label.device)
+  tags[present[(present >= 0) & (present < num_classes)]] = True
+  return tags
+
+
+def flip_scale_views(image, scales, is_flip, crop_size):
+  """The views of one image `[1,3,h,w]` in the reference's order (`create_image_pyramid` of
+  spml/utils/general/others.py + `resize_with_pad`, pseudo_softmaxrw_crf.py:109-125): per scale the flipped view first
+  (when `is_flip`), then the plain one; each resized bilinearly to `round(h * scale) x round(w * scale)` and
+  zero-padded at the bottom / right to at least `crop_size`.  -> list of `(image [1,3,Hp,Wp], (rh, rw), is_flip)`,
+  the `views` of `pseudo_labels_softmax`.  A host-side stand-in for the loader (cv2 there): not parity-pinned."""
+  if image.dim() != 4 or image.shape[0] != 1:
+    raise ValueError('flip_scale_views expects one image [1,3,H,W]')
+  h, w = image.shape[-2:]
+  views = []
+  for scale in scales:
+    if scale == 1:
+      scaled = image
+    else:
+      size = (max(int(round(h * scale)), 1), max(int(round(w * scale)), 1))
+      scaled = torch.nn.functional.interpolate(image, size=size, mode='bilinear', align_corners=False)
+    rh, rw = scaled.shape[-2:]
+    pad_h, pad_w = max(rh, int(crop_size[0])), max(rw, int(crop_size[1]))
+    for flip in ((True, False) if is_flip else (False,)):
+      view = torch.zeros((1, image.shape[1], pad_h, pad_w), dtype=image.dtype, device=image.device)
+      view[:, :, :rh, :rw] = torch.flip(scaled, dims=[3]) if flip else scaled
+      views.append((view, (rh, rw), flip))
+  return views
+
+
+def pseudo_labels_softmax(embedding_model, prediction_model, views, image_hw, label_tags, combine='prob_mean',
+                          walk_steps=6, background_threshold=None, scale=5.0, power=20, return_transition=False):
+  """One image of the pseudo-label generation (`pyscripts/inference/pseudo_softmaxrw_crf.py:116-176` with
+  combine='prob_mean', walk_steps=6; `pseudo_softmax.py:115-179` with combine='logit_mean', walk_steps=0), before
+  the denseCRF.  `views`: list of `(image [1,3,Hp,Wp], (rh, rw), is_flip)` (`flip_scale_views`); `image_hw`: the
+  un-padded image; `label_tags`: bool `[ncls]` device tensor (`label_tags_from_map`).
+
+  Per view the whole padded image goes through `generate_embeddings(..., resize_as_input=True)` and the classifier
+  head (:127-128; consecutive views of one padded size -- a flip pair -- share the backbone call, the head runs through
+  `accumulate_logits` into a zero canvas), then `spml_resample_unit_f32` (crop, un-flip, 1/8 bilinear, unit columns,
+  read through the embedding's strides: no NCHW copy of a channels-last map) and
+  `spml_resample_classes_accumulate_f32` (the same for the logits, soft-maxed and summed in view order).  After the
+  last view: `spml_affinity_transition_f32`, `spml_cam_finalize_f32`, the walk's GEMMs, `spml_upsample_argmax_i64`.
+  Returns `cam`, `cam_rw` `[ncls, h//8, w//8]`, `semantic_prediction` `[h,w]` int64, `head_path`, and `transition`
+  `[n,n]` (before the squarings) only with `return_transition`."""
+  if combine not in _ffi.COMBINE_MODES:
+    raise ValueError("combine must be 'prob_mean' or 'logit_mean'")
+  if not views:
+    raise ValueError('pseudo_labels_softmax needs at least one view')
+  if not label_tags.is_cuda:
+    raise _ffi.SpmlHipError('the HIP path needs GPU tensors (label_tags on %s); there is no CPU fallback'
+                            % label_tags.device)
+  for image, _, _ in views:
+    if image.dim() != 4 or image.shape[0] != 1:
+      raise ValueError('pseudo_labels_softmax expects views of one image [1,3,Hp,Wp]')
+    if not image.is_cuda:
+      raise _ffi.SpmlHipError('the HIP path needs GPU tensors (a view on %s); there is no CPU fallback' % image.device)
+  h, w = image_hw
+  out_hw = (h // 8, w // 8)
+  if out_hw[0] < 1 or out_hw[1] < 1:
+    raise ValueError('pseudo_labels_softmax: the image is smaller than 8 x 8')
+  n = out_hw[0] * out_hw[1]
+  device = views[0][0].device
+  ncls = prediction_model.num_classes
+  first = next(embedding_model.parameters(), None)
+  nhwc = first is not None and first.is_cuda and first.dim() == 4 and \
+      first.is_contiguous(memory_format=torch.channels_last) and not first.is_contiguous()
+  prediction_model.prepare_inference()          # once per image, as in predict_softmax_full_resolution
+  groups = []                                   # consecutive views of one padded size
+  for view in views:
+    if groups and groups[-1][0][0].shape == view[0].shape:
+      groups[-1].append(view)
+    else:
+      groups.append([view])
+  units, acc, path, b = None, torch.zeros((ncls, n), dtype=torch.float32, device=device), None, 0
+  with torch.no_grad():
+    for part in groups:
+      images = torch.cat([v[0] for v in part], 0) if len(part) > 1 else part[0][0]
+      if nhwc:
+        images = images.contiguous(memory_format=torch.channels_last)
+      embs = embedding_model.generate_embeddings({'image': images}, resize_as_input=True)['embedding'].float()
+      canvas = torch.empty((1, ncls) + tuple(embs.shape[-2:]), dtype=torch.float32, device=device)
+      if units is None:
+        units = torch.empty((len(views), embs.shape[1], n), dtype=torch.float32, device=device)
+      for i, (_, crop_hw, flip) in enumerate(part):
+        path = prediction_model.accumulate_logits(embs[i:i + 1], canvas.zero_(), 0, 0)
+        _ffi.resample_unit(embs[i], crop_hw, flip, out_hw, units, b)
+        _ffi.resample_classes_accumulate(canvas[0], crop_hw, flip, out_hw, acc, combine)
+        b += 1
+    trans = _ffi.affinity_transition(units, scale, power)
+    cam = _ffi.cam_finalize(acc, len(views), label_tags, combine, background_threshold).view(ncls, *out_hw)
+    cam_rw = _walk(trans, cam, walk_steps)
+    prediction = _ffi.upsample_argmax(cam_rw, h, w)
+  out = {'cam': cam, 'cam_rw': cam_rw, 'semantic_prediction': prediction, 'head_path': path}
+  if return_transition:
+    out['transition'] = trans
+  return out
