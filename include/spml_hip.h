@@ -45,8 +45,9 @@ const char* spml_status_string(int status);
  * whose version differs from the header it was written against.  2: round 4 (count_dev in the batch-norm backward,
  * spml_bn_finalize_ranks_f32); 3: round 5 (SPML_KMEANS_NO_PASS64 / _TWO_KERNEL_FINALIZE / _NO_V4K, paths "mfma_f16x2_v4p", "mfma_f16x2_v4k");
  * 5: the softmax-inference entry points (spml_unit_hl8_from_nchw_f32 .. spml_iou_counts_i64);
- * 6: the pseudo-label entry points (spml_resample_unit_f32 .. spml_upsample_argmax_i64). */
-#define SPML_ABI_VERSION 6
+ * 6: the pseudo-label entry points (spml_resample_unit_f32 .. spml_upsample_argmax_i64);
+ * 7: the multi-scale inference entry point (spml_view_probs_accumulate_f32). */
+#define SPML_ABI_VERSION 7
 int spml_abi_version(void);
 
 /* ------------------------------------------------------------------------
@@ -826,6 +827,30 @@ int spml_cam_finalize_f32(const float* acc, int ncls, int64_t n, int B, int comb
  * half-pixel mapping) is never written.  Ties: the lowest class; NaN as torch.argmax (the rules of
  * spml_argmax_channels_i64). */
 int spml_upsample_argmax_i64(const float* cam, int ncls, int oh, int ow, int h, int w, int64_t* out, void* stream);
+
+/* ------------------------------------------------------------------------
+ * N8  multi-scale + flip softmax inference: the per-view tail (csrc/msc_inference.hip)
+ * replaces: pyscripts/inference/inference_softmax_msc.py:135-143 per view and the sum of :146-147 (divide the summed
+ *           window logits by the overlap counts, crop, `F.interpolate(mode='bilinear')` to the image, softmax over the
+ *           classes, flip back through host numpy, concatenate and sum: six passes over an ncls x H x W tensor).
+ * ------------------------------------------------------------------------ */
+
+/* acc[c][y][x] += softmax over c of r[c][y][xd], xd = flip ? w - 1 - x : x, where r is `canvas / counts` cropped to its
+ * top-left rh x rw region and resampled bilinearly to h x w (the rule above spml_resample_unit_f32, in = rh, rw -- never
+ * Hp, Wp: values outside the region are not read).  Unlike the N7 entries the view is interpolated as it is and the RESULT
+ * is flipped (:141-142), which differs from flipping the source in the last bit.
+ * canvas: fp32 [ncls][Hp][Wp], the window logits of ONE view, summed (spml_class_head_accumulate_f32).  cnt_y [Hp],
+ * cnt_x [Wp]: the numbers of windows that cover a row / a column; the reference's counts[y][x] (:134) is
+ * cnt_y[y] * cnt_x[x] exactly, the windows being a Cartesian product.  Each of the four taps is divided by its own count
+ * product (a true fp32 division, before the interpolation, as :135), then combined as
+ * h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11); softmax = subtract the maximum, exp, sum, divide.
+ * acc: fp32 [ncls][h][w], zeroed by the caller before the first view; plain loads and stores, so the views of one image
+ * are added in call order on one stream (a pixel's fp32 sum has the order of :147).  No atomics, no workspace: results
+ * are bit-reproducible and the same with and without the deterministic mode.  acc may not alias canvas
+ * (SPML_ERR_INVALID_ARG, as for rh > Hp, rw > Wp or a size below 1); ncls <= 64, else SPML_ERR_UNSUPPORTED. */
+int spml_view_probs_accumulate_f32(const float* canvas, int ncls, int Hp, int Wp, const float* cnt_y,
+                                   const float* cnt_x, int rh, int rw, int flip, int h, int w, float* acc,
+                                   void* stream);
 
 #ifdef __cplusplus
 }

@@ -135,6 +135,8 @@ _SIGNATURES = {
                                                      c_int, c_int, c_int, c_int, _P, _P]),
     'spml_cam_finalize_f32': (c_int, [_P, c_int, c_int64, c_int, c_int, _P, c_int, c_float, _P, _P]),
     'spml_upsample_argmax_i64': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    'spml_view_probs_accumulate_f32': (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P,
+                                               _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -144,7 +146,7 @@ class SpmlHipError(RuntimeError):
   pass
 
 
-ABI_VERSION = 6            # = SPML_ABI_VERSION of include/spml_hip.h (tests/test_cabi_exports.py compares the two)
+ABI_VERSION = 7            # = SPML_ABI_VERSION of include/spml_hip.h (tests/test_cabi_exports.py compares the two)
 
 
 def lib():
@@ -680,6 +682,28 @@ def upsample_argmax(cam, h, w):
   check(lib().spml_upsample_argmax_i64(ptr(cam, torch.float32), ncls, oh, ow, int(h), int(w), ptr(out), stream_ptr()),
         'spml_upsample_argmax_i64')
   return out
+
+
+# ---------------------------------------------------------------------------
+# multi-scale + flip softmax inference (csrc/msc_inference.hip)
+def view_probs_accumulate(canvas, cnt_y, cnt_x, crop_hw, flip, acc):
+  """acc += softmax over the classes of one view: `canvas` [ncls, Hp, Wp] (the summed window logits) divided by the
+  overlap counts `cnt_y[:, None] * cnt_x[None, :]`, cropped to its top-left `crop_hw`, bilinearly resampled to the
+  `[h, w]` of `acc` [ncls, h, w] and -- when `flip` -- mirrored AFTER the softmax (inference_softmax_msc.py:135-147).
+  All four tensors fp32, contiguous, on the GPU; acc is updated in place and returned."""
+  if canvas.dim() != 3 or acc.dim() != 3 or acc.shape[0] != canvas.shape[0]:
+    raise SpmlHipError('view_probs_accumulate: canvas must be [ncls, Hp, Wp] and acc [ncls, h, w]')
+  ncls, hp, wp = canvas.shape
+  rh, rw = int(crop_hw[0]), int(crop_hw[1])
+  if not (0 < rh <= hp and 0 < rw <= wp):
+    raise SpmlHipError('view_probs_accumulate: crop %r does not fit a %d x %d plane' % (tuple(crop_hw), hp, wp))
+  if tuple(cnt_y.shape) != (hp,) or tuple(cnt_x.shape) != (wp,):
+    raise SpmlHipError('view_probs_accumulate: cnt_y must be [%d] and cnt_x [%d]' % (hp, wp))
+  check(lib().spml_view_probs_accumulate_f32(
+      ptr(canvas, torch.float32), ncls, hp, wp, ptr(cnt_y, torch.float32), ptr(cnt_x, torch.float32), rh, rw,
+      int(bool(flip)), acc.shape[1], acc.shape[2], ptr(acc, torch.float32), stream_ptr()),
+        'spml_view_probs_accumulate_f32')
+  return acc
 
 
 def affinity_transition(emb, scale=5.0, power=20):

@@ -19,6 +19,7 @@
 // Bilinear weights as ATen forms them (align_corners = False, no anti-aliasing): scale = in / out in fp32,
 // src = max(scale * (dst + 0.5) - 0.5, 0), i0 = floor(src), i1 = min(i0 + 1, in - 1), l1 = src - i0, l0 = 1 - l1,
 // value = h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11).
+#include "bilinear.hpp"
 #include "common.hpp"
 
 namespace spml {
@@ -27,22 +28,6 @@ namespace {
 constexpr int kSlices = 16;            // lanes per pixel in the view kernels
 constexpr int kViewPix = 16;           // pixels per 256-thread workgroup there
 constexpr int kOwn = 4;                // channels of one 64-channel chunk a lane owns (slice, +16, +32, +48)
-
-struct Tap {
-  int i0, i1;
-  float l0, l1;
-};
-
-__device__ __forceinline__ Tap make_tap(int dst, float scale, int in) {
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  Tap t;
-  t.i0 = min((int)src, in - 1);        // (src >= 0: the conversion is the floor)
-  t.i1 = min(t.i0 + 1, in - 1);
-  t.l1 = src - (float)t.i0;
-  t.l0 = 1.0f - t.l1;
-  return t;
-}
 
 // the four element offsets of output pixel p of an oh x ow map over the top-left rh x rw region of a plane with
 // strides (sy, sx); with `flip` logical column x is stored at rw - 1 - x

@@ -109,6 +109,46 @@ def predict_full_resolution(embedding_model, prediction_model, image, valid_hw, 
           'semantic_score': outputs['semantic_score'], 'cluster_index': embeddings['cluster_index']}
 
 
+def window_counts(pad_size, crop_size, stride):
+  """How many sliding windows cover each position of one axis -> float32 `[pad_size]`.  The windows of an image are the
+  Cartesian product of the two axes' windows, so the reference's `counts[y][x]` (inference_softmax_msc.py:120-134) is
+  `window_counts(pad_h, ...)[y] * window_counts(pad_w, ...)[x]` exactly (small integers)."""
+  counts = np.zeros((int(pad_size),), dtype=np.float32)
+  for end in sliding_window_ends(pad_size, crop_size, stride):
+    counts[int(end) - crop_size:int(end)] += 1
+  return counts
+
+
+def _is_channels_last(embedding_model):
+  first = next(embedding_model.parameters(), None)
+  return first is not None and first.is_cuda and first.dim() == 4 and \
+      first.is_contiguous(memory_format=torch.channels_last) and not first.is_contiguous()
+
+
+def _accumulate_window_logits(embedding_model, prediction_model, images, canvases, crop_size, stride):
+  """The sliding-window loop of inference_softmax.py:105-137 (= inference_softmax_msc.py:107-134 without the counts) over
+  `images`, padded images `[1,3,Hp,Wp]` of ONE size: the crops of all of them -- image after image, each in the
+  reference's window order -- go through the backbone in groups of 8, and each crop's logits are added into the canvas
+  `[1,ncls,Hp,Wp]` of its own image, so the fp32 sum order of a pixel is the reference's.  Returns the name of the path
+  `SoftmaxClassifier.accumulate_logits` took."""
+  pad_h, pad_w = images[0].shape[-2:]
+  crop_h, crop_w = crop_size
+  ends_h = sliding_window_ends(pad_h, crop_h, stride[0])
+  ends_w = sliding_window_ends(pad_w, crop_w, stride[1])
+  windows = [(k, int(eh) - crop_h, int(ew) - crop_w) for k in range(len(images)) for eh in ends_h for ew in ends_w]
+  nhwc = _is_channels_last(embedding_model)
+  group, path = 8, None
+  for g0 in range(0, len(windows), group):
+    part = windows[g0:g0 + group]
+    crops = torch.cat([images[k][:, :, sh:sh + crop_h, sw:sw + crop_w] for k, sh, sw in part], 0)
+    if nhwc:
+      crops = crops.contiguous(memory_format=torch.channels_last)
+    embs = embedding_model.generate_embeddings({'image': crops}, resize_as_input=True)['embedding']
+    for i, (k, sh, sw) in enumerate(part):
+      path = prediction_model.accumulate_logits(embs[i:i + 1], canvases[k], sh, sw)
+  return path
+
+
 def predict_softmax_full_resolution(embedding_model, prediction_model, image, valid_hw, crop_size, stride):
   """One image of the softmax label inference (`pyscripts/inference/inference_softmax.py:105-148`): sliding
   windows over the padded `image` `[1,3,Hp,Wp]` (:105-123), per crop the embedding at input resolution and the
@@ -121,27 +161,78 @@ def predict_softmax_full_resolution(embedding_model, prediction_model, image, va
     raise ValueError('predict_softmax_full_resolution expects one image [1,3,H,W]')
   h, w = valid_hw
   pad_h, pad_w = image.shape[-2:]
-  crop_h, crop_w = crop_size
-  ends_h = sliding_window_ends(pad_h, crop_h, stride[0])
-  ends_w = sliding_window_ends(pad_w, crop_w, stride[1])
-  windows = [(int(eh) - crop_h, int(ew) - crop_w) for eh in ends_h for ew in ends_w]
-  first = next(embedding_model.parameters(), None)
-  nhwc = first is not None and first.is_cuda and first.dim() == 4 and \
-      first.is_contiguous(memory_format=torch.channels_last) and not first.is_contiguous()
   canvas = torch.zeros((1, prediction_model.num_classes, pad_h, pad_w), dtype=torch.float32, device=image.device)
   prediction_model.prepare_inference()          # once per image: validates the folded operands (one host read)
-  group, path = 8, None
   with torch.no_grad():
-    for g0 in range(0, len(windows), group):
-      part = windows[g0:g0 + group]
-      crops = torch.cat([image[:, :, sh:sh + crop_h, sw:sw + crop_w] for sh, sw in part], 0)
-      if nhwc:
-        crops = crops.contiguous(memory_format=torch.channels_last)
-      embs = embedding_model.generate_embeddings({'image': crops}, resize_as_input=True)['embedding']
-      for i, (sh, sw) in enumerate(part):
-        path = prediction_model.accumulate_logits(embs[i:i + 1], canvas, sh, sw)
+    path = _accumulate_window_logits(embedding_model, prediction_model, [image], [canvas], crop_size, stride)
     prediction = _ffi.argmax_channels(canvas[0], h, w)
   return {'semantic_logit': canvas, 'semantic_prediction': prediction, 'head_path': path}
+
+
+HIP_VIEW_PROBS_PATH = 'hip_view_probs'
+FRAMEWORK_VIEW_PROBS_PATH = 'framework_view_probs'
+MAX_VIEW_PROBS_CLASSES = 64            # spml_view_probs_accumulate_f32 keeps every class of a pixel in registers
+
+
+def framework_view_probs_accumulate(canvas, cnt_y, cnt_x, crop_hw, flip, acc):
+  """The tail of one view as the reference's own ops on the tensors' device (inference_softmax_msc.py:135-143, 147):
+  what `_ffi.view_probs_accumulate` computes in one kernel.  The path of `predict_softmax_multiscale` above 64 classes
+  and the yardstick of tools/bench_softmax_msc.py."""
+  rh, rw = crop_hw
+  logit = canvas.unsqueeze(0) / (cnt_y.view(-1, 1) * cnt_x.view(1, -1))
+  logit = logit[..., :rh, :rw]
+  logit = torch.nn.functional.interpolate(logit, size=tuple(acc.shape[-2:]), mode='bilinear')
+  prob = torch.softmax(logit, dim=1)[0]
+  acc += torch.flip(prob, dims=[2]) if flip else prob
+  return acc
+
+
+def predict_softmax_multiscale(embedding_model, prediction_model, views, image_hw, crop_size, stride):
+  """One image of the multi-scale + flip softmax label inference (`pyscripts/inference/inference_softmax_msc.py:95-149`).
+  `views`: list of `(image [1,3,Hp,Wp], (rh, rw), is_flip)` (`flip_scale_views`: per scale the flipped view first, as
+  `create_image_pyramid`); `image_hw`: the un-padded image.
+
+  Per view the sliding windows run exactly as in `predict_softmax_full_resolution` (:107-134; consecutive views of one
+  padded size -- a flip pair, or several scales that all pad up to the crop size -- send their crops through the backbone
+  together, each view's windows are added into that view's canvas in the reference's order), then ONE kernel, `spml_view_probs_accumulate_f32`, divides by the overlap
+  counts, crops, interpolates to the image, soft-maxes, un-flips and adds into the `[ncls,h,w]` sum (:135-143, :146-147;
+  views in call order: the fp32 sum order of a pixel is the reference's).  After the last view
+  `spml_argmax_channels_i64` gives the labels (:149).  Above 64 classes the tail of a view runs as the reference's torch
+  ops on the device instead (`framework_view_probs_accumulate`); `combine_path` names which of the two ran, as
+  `head_path` does for the classifier head.  Returns `semantic_prob` `[ncls,h,w]` (the sum over the views, :147),
+  `semantic_prediction` `[h,w]` int64, `head_path` and `combine_path`."""
+  if not views:
+    raise ValueError('predict_softmax_multiscale needs at least one view')
+  for image, _, _ in views:
+    if image.dim() != 4 or image.shape[0] != 1:
+      raise ValueError('predict_softmax_multiscale expects views of one image [1,3,Hp,Wp]')
+    if not image.is_cuda:
+      raise _ffi.SpmlHipError('the HIP path needs GPU tensors (a view on %s); there is no CPU fallback' % image.device)
+  h, w = image_hw
+  device = views[0][0].device
+  ncls = prediction_model.num_classes
+  combine_path = HIP_VIEW_PROBS_PATH if ncls <= MAX_VIEW_PROBS_CLASSES else FRAMEWORK_VIEW_PROBS_PATH
+  combine = _ffi.view_probs_accumulate if combine_path == HIP_VIEW_PROBS_PATH else framework_view_probs_accumulate
+  prediction_model.prepare_inference()          # once per image, as in predict_softmax_full_resolution
+  groups = []                                   # consecutive views of one padded size
+  for view in views:
+    if groups and groups[-1][0][0].shape == view[0].shape:
+      groups[-1].append(view)
+    else:
+      groups.append([view])
+  acc, path = torch.zeros((ncls, h, w), dtype=torch.float32, device=device), None
+  with torch.no_grad():
+    for part in groups:
+      pad_h, pad_w = part[0][0].shape[-2:]
+      cnt_y = torch.from_numpy(window_counts(pad_h, crop_size[0], stride[0])).to(device)
+      cnt_x = torch.from_numpy(window_counts(pad_w, crop_size[1], stride[1])).to(device)
+      canvases = [torch.zeros((1, ncls, pad_h, pad_w), dtype=torch.float32, device=device) for _ in part]
+      path = _accumulate_window_logits(embedding_model, prediction_model, [v[0] for v in part], canvases, crop_size,
+                                       stride)
+      for canvas, (_, crop_hw, flip) in zip(canvases, part):
+        combine(canvas[0], cnt_y, cnt_x, crop_hw, flip, acc)
+    prediction = _ffi.argmax_channels(acc, h, w)
+  return {'semantic_prob': acc, 'semantic_prediction': prediction, 'head_path': path, 'combine_path': combine_path}
 
 
 def save_image_memory(path, prototypes, prototype_labels):

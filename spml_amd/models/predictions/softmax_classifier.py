@@ -113,12 +113,20 @@ class SoftmaxClassifier(nn.Module):
     self._inference_cache = None
     return super()._load_from_state_dict(*args, **kwargs)
 
+  @staticmethod
+  def _padded_hidden(c):
+    """Hidden channels of the HIP head: 2C rounded up to the 64 output channels a tile of the matrix-core convolution
+    covers.  The added channels have zero weights and a zero bias (ReLU(0) = 0) and zero columns in the 1x1 head: they
+    add exact zeros, so C = 16 or 48 (2C % 64 = 32) run on the kernels too."""
+    return (2 * c + 63) // 64 * 64
+
   def head_path_name(self, embedding):
     """Which path `accumulate_logits` takes for this embedding: the HIP head, or -- where the shape is outside what
-    the kernels cover (C % 16, 2C % 64, num_classes > 64, C > 512) -- the framework ops."""
+    the kernels cover (C % 16, num_classes > 64, C > 512) -- the framework ops."""
     c = embedding.shape[-3]
-    ok = (c % 16 == 0 and c <= 512 and _ffi.conv_hl8_supported(c, 2 * c, 9) and
-          _ffi.class_head_supported(2 * c, self.num_classes))
+    hidden = self._padded_hidden(c)
+    ok = (c % 16 == 0 and c <= 512 and _ffi.conv_hl8_supported(c, hidden, 9) and
+          _ffi.class_head_supported(hidden, self.num_classes))
     return HIP_HEAD_PATH if ok else FRAMEWORK_HEAD_PATH
 
   def prepare_inference(self):
@@ -131,10 +139,15 @@ class SoftmaxClassifier(nn.Module):
     if self._inference_cache is None or self._inference_cache['key'] != key:
       head = self.semantic_classifier
       w, bias = fold_conv_bn(head[0].weight.float(), head[1])
+      cls_weight = head[4].weight.detach().float().reshape(self.num_classes, -1)
+      pad = self._padded_hidden(w.shape[1]) - w.shape[0]
+      if pad:                                                   # (zero hidden channels: `_padded_hidden`)
+        w = torch.cat([w, w.new_zeros((pad,) + tuple(w.shape[1:]))], 0)
+        bias = torch.cat([bias.float(), bias.new_zeros((pad,), dtype=torch.float32)], 0)
+        cls_weight = torch.cat([cls_weight, cls_weight.new_zeros((self.num_classes, pad))], 1)
       wf, _ = _ffi.hl8_weight(w)
       self._inference_cache = {
-          'key': key, 'weight': wf, 'bias': bias.float().contiguous(),
-          'cls_weight': head[4].weight.detach().float().reshape(self.num_classes, -1).contiguous(),
+          'key': key, 'weight': wf, 'bias': bias.float().contiguous(), 'cls_weight': cls_weight.contiguous(),
           'cls_bias': head[4].bias.detach().float().contiguous()}
     return self._inference_cache
 

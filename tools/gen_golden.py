@@ -183,6 +183,125 @@ def gen_n7(ref, out):
   save(out, 'n7_pseudo_labels', **store)
 
 
+def gen_n8(ref, out):
+  """N8: multi-scale + flip softmax inference.  pyscripts/inference/inference_softmax_msc.py:107-143 exec'd per view and
+  :146-149 once, from the reference's own lines on seeded CPU inputs (`.cuda()` / `.to("cuda:0")` stripped).
+  `transforms.resize_with_pad` (:99-102) needs cv2 to import: the views are zero-padded here, before the exec'd lines.
+  The stub network is the N6 arrangement: a seeded 5x5 convolution as the embedding model and the reference's own
+  SoftmaxClassifier with seeded non-trivial running statistics; the last 1x1's weight is multiplied by 6 so that the maps
+  are confident (with the default initialisation every probability is near 1 / ncls and the labels say nothing).
+  Stored: per scale the un-flipped scaled image (flip and zero-padding are exact: the tests rebuild the views), the conv
+  and head state, the view list, the summed probabilities and `semantic_pred` of the reference, its top-1 minus top-2
+  margin and `max_abs_logit`, the largest |crop logit| the wrapped prediction model saw."""
+  import linecache
+  import math
+  import textwrap
+  import spml.models.predictions.softmax_classifier as p_cls
+  F = torch.nn.functional
+
+  def ref_lines(path, first, last):
+    txt = ''.join(linecache.getline(path, i) for i in range(first, last + 1))
+    assert txt.strip(), path
+    return textwrap.dedent(txt).replace('.cuda()', '').replace('.to("cuda:0")', '')
+
+  msc_py = os.path.join(ref, 'pyscripts', 'inference', 'inference_softmax_msc.py')
+  src_view, src_once = ref_lines(msc_py, 107, 143), ref_lines(msc_py, 146, 149)
+  assert 'semantic_logit /= counts' in src_view and 'F.softmax(semantic_logit, dim=1)' in src_view
+  assert 'semantic_logit[..., ::-1]' in src_view and 'cuda' not in src_view
+  assert 'np.sum(semantic_logits, axis=0)' in src_once and 'np.argmax(semantic_logits, axis=0)' in src_once
+
+  class StubEmbedder:
+    def __init__(self, conv):
+      self.conv = conv
+
+    def __call__(self, datas, targets=None, resize_as_input=False):
+      assert resize_as_input
+      return {'embedding': self.conv(datas['image'])}
+
+  class RecordingHead:
+    def __init__(self, head):
+      self.head, self.max_abs_logit = head, 0.0
+
+    def __call__(self, datas):
+      outputs = self.head(datas)
+      self.max_abs_logit = max(self.max_abs_logit, outputs['semantic_logit'].abs().max().item())
+      return outputs
+
+  store = {}
+  # (seed, C, classes, image, crop, stride, scales).  Seeds are changed until the two assertions at the end hold.
+  cases = [(1800, 16, 5, (44, 60), (32, 32), (20, 20), (0.5, 1, 1.5)),
+           (1810, 32, 21, (41, 50), (50, 50), (33, 33), (0.75, 1, 1.25))]
+  for ci, (seed, c, ncls, image_hw, crop, stride, scales) in enumerate(cases):
+    gen = torch.Generator().manual_seed(seed)
+    torch.manual_seed(seed)
+    image_h, image_w = image_hw
+    conv = torch.nn.Conv2d(3, c, 5, padding=2)
+    base = torch.randn(1, 3, image_h // 8 + 2, image_w // 8 + 2, generator=gen)
+    image = F.interpolate(base, size=image_hw, mode='bilinear', align_corners=False)
+    image = image + 0.05 * torch.randn(1, 3, image_h, image_w, generator=gen)
+    cfg = AttrDict(dataset=AttrDict(semantic_ignore_index=255, num_classes=ncls),
+                   network=AttrDict(embedding_dim=c),
+                   test=AttrDict(stride=list(stride), crop_size=list(crop)))
+    head = p_cls.SoftmaxClassifier(cfg)
+    with torch.no_grad():
+      bn = head.semantic_classifier[1]
+      bn.weight.copy_(0.5 + torch.rand(2 * c, generator=gen))
+      bn.bias.copy_(0.1 * torch.randn(2 * c, generator=gen))
+      bn.running_mean.copy_(0.05 * torch.randn(2 * c, generator=gen))
+      bn.running_var.copy_(0.02 + 0.05 * torch.rand(2 * c, generator=gen))
+      head.semantic_classifier[4].weight.mul_(6.0)
+      head.semantic_classifier[4].bias.copy_(0.1 * torch.randn(ncls, generator=gen))
+    head.eval()
+    recorder = RecordingHead(head)
+    t = 'c%d_' % ci
+    views, semantic_logits = [], []
+    for si, scale in enumerate(scales):
+      size = (max(int(round(image_h * scale)), 1), max(int(round(image_w * scale)), 1))
+      scaled = image if scale == 1 else F.interpolate(image, size=size, mode='bilinear', align_corners=False)
+      store[t + 'scaled%d' % si] = scaled
+      rh, rw = scaled.shape[-2:]
+      pad_h, pad_w = max(rh, crop[0]), max(rw, crop[1])
+      for flip in (True, False):                              # create_image_pyramid: the flipped view first
+        view = torch.zeros(1, 3, pad_h, pad_w)
+        view[:, :, :rh, :rw] = torch.flip(scaled, dims=[3]) if flip else scaled
+        views.append([si, pad_h, pad_w, rh, rw, int(flip)])
+        env = {'config': cfg, 'math': math, 'np': np, 'torch': torch, 'F': F, 'image_batch': {'image': view},
+               'pad_image_h': pad_h, 'pad_image_w': pad_w, 'resize_image_h': rh, 'resize_image_w': rw,
+               'image_h': image_h, 'image_w': image_w, 'data_info': {'is_flip': flip},
+               'embedding_model': StubEmbedder(conv), 'prediction_model': recorder,
+               'semantic_logits': semantic_logits}
+        with torch.no_grad():
+          exec(compile(src_view, msc_py + ':107-143', 'exec'), env)
+        assert semantic_logits[-1].shape == (1, ncls, image_h, image_w) and semantic_logits[-1].dtype == np.float32
+        assert tuple(env['counts'].shape) == (1, 1, pad_h, pad_w)
+    env = {'np': np, 'semantic_logits': semantic_logits}
+    exec(compile(src_once, msc_py + ':146-149', 'exec'), env)
+    prob, pred = env['semantic_logits'], env['semantic_pred']
+    assert prob.shape == (ncls, image_h, image_w) and prob.dtype == np.float32
+    assert pred.shape == image_hw and pred.dtype == np.uint8
+    top2 = torch.from_numpy(prob).topk(2, dim=0).values
+    margin = top2[0] - top2[1]
+    # B: the project's logit bound is 1e-4 * max|logit| per view, a softmax moves a probability by at most half of the
+    # logit error, the errors of the views add up; a label can flip only where the margin is below 2 B
+    bound = 0.5 * len(views) * 1e-4 * recorder.max_abs_logit
+    low = (margin < 2 * bound).float().mean().item()
+    winners = np.unique(pred).size
+    print('n8 case %d: %d views, max|logit| %.3f, B %.3e, low margin %.2f %%, %d classes win, max prob sum %.3f'
+          % (ci, len(views), recorder.max_abs_logit, bound, 100 * low, winners, prob.max()))
+    assert low < 0.01, 'case %d: %.4f of the pixels have a low margin -- pick another seed' % (ci, low)
+    assert winners >= 3, 'case %d: only %d classes win -- pick another seed' % (ci, winners)
+    store.update({
+        t + 'conv_w': conv.weight, t + 'conv_b': conv.bias,
+        t + 'cfg': np.array([c, ncls, image_h, image_w, crop[0], crop[1], stride[0], stride[1]]),
+        t + 'views': np.array(views), t + 'semantic_prob': prob, t + 'semantic_pred': pred, t + 'margin': margin,
+        t + 'max_abs_logit': np.array(recorder.max_abs_logit, dtype=np.float64),
+        t + 'state_names': np.array(list(head.state_dict().keys()))})
+    store.update({t + 'sd_' + k: v for k, v in head.state_dict().items()})
+  save(out, 'n8_softmax_msc', **store)
+  size = os.path.getsize(os.path.join(out, 'n8_softmax_msc.npz'))
+  assert size < 600 * 1024, 'n8_softmax_msc.npz is %d bytes' % size
+
+
 class AttrDict(dict):
   __getattr__ = dict.__getitem__
 
@@ -201,8 +320,11 @@ def main():
 
   sys.path.insert(0, args.ref)
   torch.set_num_threads(1)       # bit-stable fp32 sums
-  if ONLY == {'n7_pseudo_labels'}:      # (needs none of the imports and shims below)
-    gen_n7(args.ref, out)
+  if ONLY is not None and ONLY <= {'n7_pseudo_labels', 'n8_softmax_msc'}:      # (need none of the imports and shims below)
+    if 'n7_pseudo_labels' in ONLY:
+      gen_n7(args.ref, out)
+    if 'n8_softmax_msc' in ONLY:
+      gen_n8(args.ref, out)
     return
 
   import spml.utils.general.common as g_common
@@ -996,6 +1118,10 @@ def main():
   # ======================= N7: pseudo labels from the softmax head + affinity random walk ==
   if ONLY is None or 'n7_pseudo_labels' in ONLY:
     gen_n7(args.ref, out)
+
+  # ======================= N8: multi-scale + flip softmax inference =========================
+  if ONLY is None or 'n8_softmax_msc' in ONLY:
+    gen_n8(args.ref, out)
 
   # ======================= H2: two steps of the stage-2 classifier training ===============
   # pyscripts/train/train_classifier.py:139-169, the loop body exec'd as it stands on ONE device:
