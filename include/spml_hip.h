@@ -46,8 +46,9 @@ const char* spml_status_string(int status);
  * spml_bn_finalize_ranks_f32); 3: round 5 (SPML_KMEANS_NO_PASS64 / _TWO_KERNEL_FINALIZE / _NO_V4K, paths "mfma_f16x2_v4p", "mfma_f16x2_v4k");
  * 5: the softmax-inference entry points (spml_unit_hl8_from_nchw_f32 .. spml_iou_counts_i64);
  * 6: the pseudo-label entry points (spml_resample_unit_f32 .. spml_upsample_argmax_i64);
- * 7: the multi-scale inference entry point (spml_view_probs_accumulate_f32). */
-#define SPML_ABI_VERSION 7
+ * 7: the multi-scale inference entry point (spml_view_probs_accumulate_f32);
+ * 8: spml_upsample_ce_bwd_path_name. */
+#define SPML_ABI_VERSION 8
 int spml_abi_version(void);
 
 /* ------------------------------------------------------------------------
@@ -324,7 +325,10 @@ int spml_kmeans_run_profiled_f32(const float* x, int64_t P, int D,
  * replaces: segsort/common.py:11-41 (calculate_prototypes_from_labels) as
  *           used at models/utils.py:113-116 and segsort.py:236-237.
  *   x [P,D], ids [P] int64 in [0,M)  ->  protos [M,D]; sums [M,D] is scratch
- *   that also feeds the backward (it holds the un-normalised sums).
+ *   that also feeds the backward (it holds the un-normalised sums).  D <= 1088.
+ *   An id outside [0,M) -- negative, >= M, or beyond 32 bits: all 64 bits are
+ *   compared -- marks a pixel that belongs to no segment: it adds nothing to
+ *   any prototype and its dx row is 0 (with `accumulate`: left as it was).
  * backward: dx[p] = J(ids[p]) where J = d_sums = (dP - P<P,dP>)/|s|
  *           (or dP/eps where |s| < eps).  `accumulate` != 0 adds into dx.
  * ------------------------------------------------------------------------ */
@@ -397,10 +401,13 @@ int spml_segsort_nll_bwd_f32(const float* emb, const int64_t* own,
  * replaces: segsort/eval.py:32-35 (mm + full argsort + [:, :k]) and
  *           models/utils.py:198-214 (mm + where(mask) + topk).
  *   q [Q,D], protos [M,D]  ->  idx [Q,k] int64 (descending affinity, ties ->
- *   lowest index), val [Q,k] fp32.  k <= 32.
+ *   lowest index), val [Q,k] fp32.  k <= 32, D <= 528.
+ *   k > M: the first M entries of a row are all M candidates in that order,
+ *   the remaining k - M entries are idx == 0 and val == -inf.
  *   Optional mask predicate (B3): candidate m is allowed for query i iff
  *   q_group[i] == pr_group[m] && pr_valid[m] != 0; disallowed candidates rank
- *   after every allowed one with value `masked_value`.  Pass NULLs for none.
+ *   after every allowed one with value `masked_value` (a finite value below
+ *   every affinity), among themselves by ascending index.  Pass NULLs for none.
  * ------------------------------------------------------------------------ */
 size_t spml_topk_workspace_bytes(int64_t Q, int64_t M, int D, int k);
 
@@ -728,6 +735,11 @@ int spml_conv_hl8_affine_f32(const void* a, const float* a_bound, const void* b,
  *        result[2] = their mean (NaN without counted pixels, like the framework loss);
  *   bwd: d_logits [N][h][w][C] = scale[0] * d(sum of the pixel losses) / d logits, scale a device
  *        scalar (d_loss / result[1] for the mean).  Gather formulation: deterministic, no atomics.
+ *        Two kernels, chosen by shape (spml_upsample_ce_bwd_path_name, a pure host function with the launch's own
+ *        expression): "tiled" -- a workgroup per 8 x 8 low-resolution pixels with the softmax rows of the output
+ *        rectangle it feeds in LDS -- while that layout needs at most 72 KiB and N <= 65535; "gather" -- one thread
+ *        per low-resolution pixel, no LDS -- otherwise (up-sampling ratios above ~4.4 at 21 classes, ~3.8 at 64);
+ *        "unsupported" for arguments the backward refuses.
  * Interpolation arithmetic as ATen's upsample_bilinear2d (align_corners = False). */
 int spml_upsample_ce_supported(int C);
 size_t spml_upsample_ce_workspace_bytes(int N, int H, int W);
@@ -737,6 +749,7 @@ int spml_upsample_ce_fwd_f32(const float* logits, const int64_t* labels, int N, 
 int spml_upsample_ce_bwd_f32(const float* logits, const int64_t* labels, const float* lse,
                              int N, int C, int h, int w, int H, int W, int64_t ignore_index,
                              const float* scale, float* d_logits, void* stream);
+const char* spml_upsample_ce_bwd_path_name(int N, int C, int h, int w, int H, int W);
 
 /* ---- full-resolution softmax inference: classifier head on a sliding-window crop, label map, IoU counts ----
  * Replaces, per crop, pyscripts/inference/inference_softmax.py:126-137 with

@@ -114,6 +114,7 @@ _SIGNATURES = {
     'spml_upsample_ce_fwd_f32': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, _P, _P, _P,
                                          c_size_t, _P]),
     'spml_upsample_ce_bwd_f32': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, _P, _P, _P]),
+    'spml_upsample_ce_bwd_path_name': (c_char_p, [c_int, c_int, c_int, c_int, c_int, c_int]),
     'spml_bn_stats_f32': (c_int, [_P, c_int64, c_int, _P, _P, _P, c_size_t, _P]),
     'spml_bn_act_apply_f32': (c_int, [_P, _P, c_int64, c_int, _P, _P, _P, _P, c_int, _P, _P]),
     'spml_bn_act_bwd_reduce_f32': (c_int, [_P, _P, _P, c_int64, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
@@ -146,7 +147,7 @@ class SpmlHipError(RuntimeError):
   pass
 
 
-ABI_VERSION = 7            # = SPML_ABI_VERSION of include/spml_hip.h (tests/test_cabi_exports.py compares the two)
+ABI_VERSION = 8            # = SPML_ABI_VERSION of include/spml_hip.h (tests/test_cabi_exports.py compares the two)
 
 
 def lib():
@@ -493,13 +494,18 @@ def segment_sum_normalize(x, ids, m):
   return protos, sums
 
 
-def segment_sum_normalize_bwd(d_protos, sums, ids, p):
+def segment_sum_normalize_bwd(d_protos, sums, ids, p, accumulate=0, dx=None):
+  """-> dx [p, D].  accumulate != 0: the gradient is ADDED into the given `dx` (which the call returns)."""
   m, d = sums.shape
   scratch = torch.empty_like(sums)
-  dx = torch.empty((p, d), dtype=torch.float32, device=sums.device)
+  if accumulate:
+    if dx is None or tuple(dx.shape) != (p, d):
+      raise SpmlHipError('accumulate needs a dx of shape (%d, %d) to add into' % (p, d))
+  else:
+    dx = torch.empty((p, d), dtype=torch.float32, device=sums.device)
   check(lib().spml_segment_sum_normalize_bwd_f32(
       ptr(d_protos, torch.float32), ptr(sums, torch.float32), ptr(ids, torch.int64), p, d, m,
-      ptr(scratch), ptr(dx), 0, stream_ptr()), 'spml_segment_sum_normalize_bwd_f32')
+      ptr(scratch), ptr(dx, torch.float32), 1 if accumulate else 0, stream_ptr()), 'spml_segment_sum_normalize_bwd_f32')
   return dx
 
 
@@ -1234,6 +1240,12 @@ def conv_hl8_affine(a, b, bias, n_img, h, w, taps, dilation=1, addend=None, relu
 # softmax head: cross-entropy of bilinearly up-sampled logits
 def upsample_ce_supported(c):
   return bool(lib().spml_upsample_ce_supported(int(c)))
+
+
+def upsample_ce_bwd_path_name(n, c, h, w, hh, ww):
+  """Kernel the backward launches for [n, c, h, w] logits and [n, hh, ww] labels: 'tiled' or 'gather' (a pure host
+  function of the library, the launch's own expression)."""
+  return lib().spml_upsample_ce_bwd_path_name(int(n), int(c), int(h), int(w), int(hh), int(ww)).decode()
 
 
 def upsample_ce_fwd(logits_nhwc, labels, ignore_index):

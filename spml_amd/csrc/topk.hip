@@ -97,12 +97,17 @@ __global__ __launch_bounds__(64 * WAVES) void topk_kernel(TopkArgs a) {
       }
       const bool cand = ok && (z > tv[KMAX - 1]);
       if (__any(cand)) {                       // wave-uniform early out
-        // insert (z,row) keeping the list sorted (desc value; earlier rows first on ties)
+        // insert (z,row) keeping the list sorted (desc value; earlier rows first on ties): the candidate goes
+        // in front of the first strictly smaller entry, and from there on EVERY entry moves down one place -- a
+        // comparison of the displaced entry with its successor would stop at an equal one, which dropped the
+        // displaced (lowest-index) entry of a run of ties or put it behind the run
         float cv = cand ? z : -INFINITY;
         int ci = cand ? row : 0x7fffffff;
+        bool placed = false;
 #pragma unroll
         for (int i = 0; i < KMAX; ++i) {
-          const bool sw = cv > tv[i];
+          const bool sw = placed || cv > tv[i];
+          placed = sw;
           const float ov = tv[i];
           const int oi = ti[i];
           tv[i] = sw ? cv : ov;

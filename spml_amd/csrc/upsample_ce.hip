@@ -295,6 +295,16 @@ inline int uce_rect(int in, int out) {
 
 inline int64_t uce_blocks(int N, int H, int W) { return ((int64_t)N * H * W + 255) / 256; }
 
+// The backward's choice of kernel, in one place (spml_upsample_ce_bwd_f32 launches by it, spml_upsample_ce_bwd_path_name
+// reports it): the tiled kernel while its LDS layout leaves room for two workgroups per CU and the image count fits
+// gridDim.z; else the un-tiled gather kernel.
+inline bool uce_bwd_tiled_fits(int N, int C, int h, int w, int H, int W, UceTile& cap, size_t& lds) {
+  cap = UceTile{uce_rect(h, H), uce_rect(w, W)};
+  lds = ((size_t)(kUceT + 2) * (kUceT + 2) * C + (size_t)kUceT * (cap.roy + cap.rox) + 4 * kUceT +
+         (size_t)cap.roy * cap.rox * kUceCH) * 4 + 16;
+  return lds <= 72 * 1024 && N <= 65535;
+}
+
 }  // namespace
 }  // namespace spml
 
@@ -327,6 +337,13 @@ extern "C" int spml_upsample_ce_fwd_f32(const float* logits, const int64_t* labe
   return launch_status();
 }
 
+extern "C" const char* spml_upsample_ce_bwd_path_name(int N, int C, int h, int w, int H, int W) {
+  if (N <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0 || !spml_upsample_ce_supported(C)) return "unsupported";
+  UceTile cap;
+  size_t lds;
+  return uce_bwd_tiled_fits(N, C, h, w, H, W, cap, lds) ? "tiled" : "gather";
+}
+
 extern "C" int spml_upsample_ce_bwd_f32(const float* logits, const int64_t* labels, const float* lse, int N,
                                         int C, int h, int w, int H, int W, int64_t ignore_index,
                                         const float* scale, float* d_logits, void* stream) {
@@ -338,17 +355,14 @@ extern "C" int spml_upsample_ce_bwd_f32(const float* logits, const int64_t* labe
   a.N = N; a.C = C; a.h = h; a.w = w; a.H = H; a.W = W; a.ignore_index = ignore_index;
   a.rh = (float)h / (float)H; a.rw = (float)w / (float)W;
   hipStream_t s = (hipStream_t)stream;
-  {
-    UceTile cap{uce_rect(h, H), uce_rect(w, W)};
-    const size_t lds = ((size_t)(kUceT + 2) * (kUceT + 2) * C + (size_t)kUceT * (cap.roy + cap.rox) + 4 * kUceT +
-                        (size_t)cap.roy * cap.rox * kUceCH) * 4 + 16;
-    if (lds <= 72 * 1024 && N <= 65535) {             // two workgroups per CU; else: the un-tiled kernel
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(uce_bwd_tiled), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds);
-      hipLaunchKernelGGL(uce_bwd_tiled, dim3((w + kUceT - 1) / kUceT, (h + kUceT - 1) / kUceT, N), dim3(256), lds, s,
-                         a, cap);
-      return launch_status();
-    }
+  UceTile cap;
+  size_t lds;
+  if (uce_bwd_tiled_fits(N, C, h, w, H, W, cap, lds)) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(uce_bwd_tiled), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds);
+    hipLaunchKernelGGL(uce_bwd_tiled, dim3((w + kUceT - 1) / kUceT, (h + kUceT - 1) / kUceT, N), dim3(256), lds, s,
+                       a, cap);
+    return launch_status();
   }
   const unsigned blocks = (unsigned)(((int64_t)N * h * w + 255) / 256);
   if (C <= 24) hipLaunchKernelGGL(uce_bwd<24>, dim3(blocks), dim3(256), 0, s, a);

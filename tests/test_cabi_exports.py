@@ -187,3 +187,27 @@ def test_profiling_builds_are_stamped_and_refused(monkeypatch):
   monkeypatch.delenv('SPML_CONV_EXP')
   monkeypatch.delenv('SPML_P64_EXP')
   assert _ffi.lib().spml_build_experiment() == 0
+
+
+def test_upsample_ce_backward_route_of_every_tested_shape(lib_path):
+  """spml_upsample_ce_bwd_path_name (a host function: the expression the launch itself uses): the cases of
+  tests/test_kernel_branches_gpu.py take the un-tiled gather kernel, those of tests/test_upsample_ce_gpu.py the tiled
+  one -- the coverage claim of the two files, checkable without a GPU -- and so do the recipe-sized shapes DESIGN.md
+  names."""
+  from spml_amd import _ffi
+  from test_kernel_branches_gpu import UCE_GATHER_CASES, UCE_TILED_NEIGHBOUR
+  from test_upsample_ce_gpu import TILED_CASES
+  for must in [(2, 21, 9, 9, 65, 65), (1, 24, 9, 7, 60, 50), (2, 32, 9, 7, 60, 50), (1, 33, 6, 5, 47, 41),
+               (1, 64, 4, 4, 40, 40), (1, 64, 17, 17, 65, 65), (1, 21, 5, 6, 41, 47)]:
+    assert must in [c[:6] for c in UCE_GATHER_CASES]
+  assert len(TILED_CASES) == 8 and UCE_TILED_NEIGHBOUR in TILED_CASES
+  for case in UCE_GATHER_CASES:
+    assert _ffi.upsample_ce_bwd_path_name(*case[:6]) == 'gather', case
+  for case in TILED_CASES:
+    assert _ffi.upsample_ce_bwd_path_name(*case[:6]) == 'tiled', case
+  for case in [(16, 21, 65, 65, 513, 513), (16, 64, 17, 17, 65, 65), (16, 64, 33, 33, 129, 129), (16, 21, 20, 20, 97, 97)]:
+    assert _ffi.upsample_ce_bwd_path_name(*case) == 'gather', case
+  assert _ffi.upsample_ce_bwd_path_name(16, 21, 130, 130, 513, 513) == 'tiled'      # the training recipe's own shape
+  assert _ffi.upsample_ce_bwd_path_name(65536, 21, 33, 29, 129, 113) == 'gather'    # more images than gridDim.z takes
+  assert _ffi.upsample_ce_bwd_path_name(1, 65, 9, 9, 65, 65) == 'unsupported'
+  assert {len(_ffi.upsample_ce_bwd_path_name(1, c, 9, 9, 65, 65)) for c in (1, 24, 25, 32, 33, 64)} == {6}

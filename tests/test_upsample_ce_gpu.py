@@ -33,11 +33,16 @@ def _reference(logits, labels, dtype):
   return loss.detach(), x.grad
 
 
-@pytest.mark.parametrize('n,c,h,w,hh,ww,ign,cl', [
+# (N, C, h, w, H, W, share of ignored pixels, channels-last input); all of them take the tiled backward
+# (tests/test_cabi_exports.py asks the library; the gather kernel's shapes are in tests/test_kernel_branches_gpu.py)
+TILED_CASES = [
     (2, 21, 33, 29, 129, 113, 0.2, True), (1, 5, 7, 9, 7, 9, 0.0, True), (3, 40, 17, 17, 65, 66, 0.5, False),
     (2, 21, 130, 130, 513, 513, 0.1, True), (1, 64, 9, 8, 20, 31, 0.3, True), (2, 3, 12, 12, 5, 7, 0.1, True),
-    (1, 24, 1, 1, 9, 9, 0.0, True), (1, 25, 6, 1, 11, 1, 0.0, True)])
-def test_loss_and_gradient_match_the_framework_ops(n, c, h, w, hh, ww, ign, cl):
+    (1, 24, 1, 1, 9, 9, 0.0, True), (1, 25, 6, 1, 11, 1, 0.0, True)]
+
+
+def check_loss_and_gradient(n, c, h, w, hh, ww, ign, cl):
+  """Loss and gradient against the fp64 evaluation of the framework ops; returns the figures it asserted on."""
   logits, labels = _case(n, c, h, w, hh, ww, ign, seed=n * 100 + c, channels_last=cl)
   assert ops.upsample_cross_entropy_available(logits, labels)
   x = logits.clone().requires_grad_(True)
@@ -46,6 +51,7 @@ def test_loss_and_gradient_match_the_framework_ops(n, c, h, w, hh, ww, ign, cl):
   l64, g64 = _reference(logits, labels, torch.float64)
   l32, g32 = _reference(logits, labels, torch.float32)
   e_own, e_lib = abs(float(loss.detach()) - float(l64)), abs(float(l32) - float(l64))
+  figures = {'loss_err': e_own, 'loss_lib_err': e_lib, 'loss_bound': max(_LIB * 4.0 * e_lib, 2e-6 * abs(float(l64)))}
   assert e_own <= max(_LIB * 4.0 * e_lib, 2e-6 * abs(float(l64))), (e_own, e_lib)
   g64 = g64 * 1.7
   ref = g64.abs().max().item()
@@ -56,8 +62,16 @@ def test_loss_and_gradient_match_the_framework_ops(n, c, h, w, hh, ww, ign, cl):
   # 526 k for both -- so the floor is 2e-6 x max(1, sqrt(pixels) / 64) = 2.2 - 2.5 x those values; SPML_TEST_STRICT_FLOOR=1
   # checks it without the library term)
   floor = 2e-6 * max(1.0, (n * hh * ww) ** 0.5 / 64.0)
+  figures.update(grad_err=e_own, grad_lib_err=e_lib, grad_bound=max(_LIB * 4.0 * e_lib, floor))
+  print('upsample ce %s: %s' % ((n, c, h, w, hh, ww), ', '.join('%s %.3e' % kv for kv in figures.items())))
   assert e_own <= max(_LIB * 4.0 * e_lib, floor), (e_own, e_lib, floor)
   assert x.grad.shape == logits.shape
+  return figures
+
+
+@pytest.mark.parametrize('n,c,h,w,hh,ww,ign,cl', TILED_CASES)
+def test_loss_and_gradient_match_the_framework_ops(n, c, h, w, hh, ww, ign, cl):
+  check_loss_and_gradient(n, c, h, w, hh, ww, ign, cl)
 
 
 def test_every_pixel_ignored_gives_nan_like_the_framework_loss():
