@@ -865,6 +865,32 @@ int spml_view_probs_accumulate_f32(const float* canvas, int ncls, int Hp, int Wp
                                    const float* cnt_x, int rh, int rw, int flip, int h, int w, float* acc,
                                    void* stream);
 
+/* ------------------------------------------------------------------------
+ * N9  multi-scale + flip kNN inference: the per-view tail (csrc/knn_msc.hip)
+ * replaces: pyscripts/inference/inference_msc.py:223-234 per view and the sum of :237-239 (one-hot of the retrieved
+ *           labels `topk[clu]` [rh * rw, k] over the classes, mean over k, host copy, `cv2.resize(..., INTER_LINEAR)` to
+ *           the image, un-flip, stack + mean over the views -- here without the final division by the view count).
+ *
+ *   acc[c][y][x] += bilinear_{(rh, rw) -> (h, w)}( votes[clu[.]][c] )  evaluated at xd = flip ? w - 1 - x : x, stored at x
+ *   votes[s][c]   = #{ j < k : topk[s][j] == c } / k
+ *
+ * clu: int64 [rh][rw] (contiguous), the dense segment id of every pixel of the view, 0 <= id < m (an id outside that
+ * range is outside the contract and is clamped into it: nothing is read out of bounds).  topk: int64 [m][k], the labels
+ * retrieved per SEGMENT (Segsort.segment_predictions); a label outside [0, ncls) adds to no class, so that row of votes
+ * sums to less than 1 (the reference's one_hot would fail on it).  The count is an exact small integer, divided once by
+ * (float)k: what `one_hot(...).float().mean(1)` gives.  Bilinear taps as ATen forms them (align_corners = False, the
+ * half-pixel mapping of cv2's INTER_LINEAR) with in = rh / rw, combined as
+ * h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11).
+ * acc: fp32 [ncls][h][w], zeroed by the caller before the first view; plain loads and stores, so the views of one image
+ * are added in call order on one stream (a pixel's fp32 sum has the order of :237-239).  ws: 16-byte aligned, at least
+ * spml_view_votes_workspace_bytes(m, ncls) bytes (the votes table; that call returns 0 outside the limits), else
+ * SPML_ERR_WORKSPACE.  No atomics: results are bit-reproducible and the same with and without the deterministic mode.
+ * acc may alias neither clu, topk nor ws, and ws neither input (SPML_ERR_INVALID_ARG, as for a null pointer or a size
+ * below 1); ncls <= 64 and m <= 4096, else SPML_ERR_UNSUPPORTED. */
+size_t spml_view_votes_workspace_bytes(int m, int ncls);
+int spml_view_votes_accumulate_f32(const int64_t* clu, int rh, int rw, const int64_t* topk, int m, int k, int ncls,
+                                   int flip, int h, int w, float* acc, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,9 @@ _SIGNATURES = {
     'spml_upsample_argmax_i64': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     'spml_view_probs_accumulate_f32': (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P,
                                                _P]),
+    'spml_view_votes_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'spml_view_votes_accumulate_f32': (c_int, [_P, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P,
+                                               c_size_t, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -709,6 +712,36 @@ def view_probs_accumulate(canvas, cnt_y, cnt_x, crop_hw, flip, acc):
       ptr(canvas, torch.float32), ncls, hp, wp, ptr(cnt_y, torch.float32), ptr(cnt_x, torch.float32), rh, rw,
       int(bool(flip)), acc.shape[1], acc.shape[2], ptr(acc, torch.float32), stream_ptr()),
         'spml_view_probs_accumulate_f32')
+  return acc
+
+
+# ---------------------------------------------------------------------------
+# multi-scale + flip kNN inference (csrc/knn_msc.hip)
+MAX_VIEW_VOTES_CLASSES = 64            # the limits of spml_view_votes_accumulate_f32 (include/spml_hip.h)
+MAX_VIEW_VOTES_SEGMENTS = 4096
+
+
+def view_votes_accumulate(clu, crop_hw, topk, ncls, flip, acc):
+  """acc += the class votes of one view: `clu` int64 `[rh * rw]` (or `[rh, rw]`), the dense segment id of every pixel of
+  the un-padded view; `topk` int64 `[m, k]`, the labels retrieved per segment; votes[s][c] = the share of `topk[s]` equal
+  to c, gathered by `clu`, bilinearly resampled from `crop_hw` to the `[h, w]` of `acc` `[ncls, h, w]` (fp32) and -- when
+  `flip` -- mirrored afterwards (inference_msc.py:223-234, the sum of :237-239).  All tensors contiguous, on the GPU; acc
+  is updated in place and returned."""
+  rh, rw = int(crop_hw[0]), int(crop_hw[1])
+  if rh < 1 or rw < 1 or clu.numel() != rh * rw:
+    raise SpmlHipError('view_votes_accumulate: clu must hold %d x %d segment ids' % (rh, rw))
+  if topk.dim() != 2 or acc.dim() != 3 or acc.shape[0] != int(ncls):
+    raise SpmlHipError('view_votes_accumulate: topk must be [m, k] and acc [%d, h, w]' % int(ncls))
+  m, k = topk.shape
+  nbytes = lib().spml_view_votes_workspace_bytes(int(m), int(ncls))
+  if nbytes == 0:
+    raise SpmlHipError('view_votes_accumulate: %d segments x %d classes are outside the kernel (at most %d x %d)'
+                       % (m, ncls, MAX_VIEW_VOTES_SEGMENTS, MAX_VIEW_VOTES_CLASSES))
+  ws = workspace(nbytes, acc.device)
+  check(lib().spml_view_votes_accumulate_f32(
+      ptr(clu, torch.int64), rh, rw, ptr(topk, torch.int64), int(m), int(k), int(ncls), int(bool(flip)),
+      acc.shape[1], acc.shape[2], ptr(acc, torch.float32), ptr(ws), ws.numel(), stream_ptr()),
+        'spml_view_votes_accumulate_f32')
   return acc
 
 

@@ -11,6 +11,7 @@ import math
 import numpy as np
 import torch
 
+import spml_amd.utils.general.common as common_utils
 import spml_amd.utils.segsort.common as segsort_common
 import spml_amd.utils.segsort.others as segsort_others
 from spml_amd import _ffi
@@ -233,6 +234,76 @@ def predict_softmax_multiscale(embedding_model, prediction_model, views, image_h
         combine(canvas[0], cnt_y, cnt_x, crop_hw, flip, acc)
     prediction = _ffi.argmax_channels(acc, h, w)
   return {'semantic_prob': acc, 'semantic_prediction': prediction, 'head_path': path, 'combine_path': combine_path}
+
+
+HIP_VIEW_VOTES_PATH = 'hip_view_votes'
+FRAMEWORK_VIEW_VOTES_PATH = 'framework_view_votes'
+
+
+def framework_view_votes_accumulate(clu, crop_hw, topk, ncls, flip, acc):
+  """The tail of one view as the reference's own ops on the tensors' device (inference_msc.py:223-234, the sum of
+  :237-239): gather the retrieved labels per pixel, one-hot over the classes, mean over the k retrievals, bilinear resize
+  to the image (the half-pixel mapping of `cv2.resize(..., INTER_LINEAR)`), un-flip, add.  What
+  `_ffi.view_votes_accumulate` computes in two small kernels; the path of `predict_knn_multiscale` outside the kernel's
+  limits and the yardstick of tools/bench_knn_msc.py.  As in the reference, a label outside `[0, ncls)` is an error."""
+  rh, rw = crop_hw
+  score = topk[clu.reshape(-1)]                                                          # [rh * rw, k]
+  votes = torch.mean(common_utils.one_hot(score, int(ncls)).float(), dim=1)              # :223-225
+  votes = votes.view(rh, rw, -1).permute(2, 0, 1).unsqueeze(0)
+  votes = torch.nn.functional.interpolate(votes, size=tuple(acc.shape[-2:]), mode='bilinear', align_corners=False)[0]
+  acc += torch.flip(votes, dims=[2]) if flip else votes
+  return acc
+
+
+def predict_knn_multiscale(embedding_model, prediction_model, views, image_hw, crop_size, stride, memory_prototypes,
+                           memory_prototype_labels, num_classes):
+  """One image of the multi-scale + flip kNN label inference (`pyscripts/inference/inference_msc.py:129-242`), the form
+  the recipes report their numbers through.  `views`: list of `(image [1,3,Hp,Wp], (rh, rw), is_flip)`
+  (`flip_scale_views`: per scale the flipped view first); `image_hw`: the un-padded image.
+
+  Per view: `embed_full_resolution` (:157-204), the embedding cropped to the un-padded `[:rh, :rw]` BEFORE clustering
+  (:208-214 -- unlike `predict_full_resolution` the k-means grid is laid over the un-padded view), `generate_clusters`
+  with all-zero fake labels, `Segsort.segment_predictions` against the memory bank (:218-222: `[m, 20]` labels per
+  segment and one segment id per pixel), then `spml_view_votes_accumulate_f32`: the vote table per segment, gathered by
+  the id map, resized to the image, un-flipped and added into the `[ncls,h,w]` sum (:223-234; views in call order: the
+  fp32 sum order of a pixel is the reference's).  After the last view the sum is divided by the number of views (:239)
+  and `spml_argmax_channels_i64` gives the labels (:242; ties go to the lowest class, as `np.argmax`).  Where
+  `num_classes` or a view's segment count is outside the kernel's limits, that view's tail runs as the reference's torch
+  ops on the device (`framework_view_votes_accumulate`) and `combine_path` names it.  Returns `semantic_prob`
+  `[ncls,h,w]`, `semantic_prediction` `[h,w]` int64 and `combine_path`; and, per view, what the tail was fed:
+  `cluster_index` (list of `[rh * rw]` dense segment ids) and `segment_topk` (list of `[m, 20]`)."""
+  if not views:
+    raise ValueError('predict_knn_multiscale needs at least one view')
+  for image, _, _ in views:
+    if image.dim() != 4 or image.shape[0] != 1:
+      raise ValueError('predict_knn_multiscale expects views of one image [1,3,Hp,Wp]')
+    if not image.is_cuda:
+      raise _ffi.SpmlHipError('the HIP path needs GPU tensors (a view on %s); there is no CPU fallback' % image.device)
+  h, w = image_hw
+  device = views[0][0].device
+  ncls = int(num_classes)
+  memory = {'semantic_memory_prototype': memory_prototypes, 'semantic_memory_prototype_label': memory_prototype_labels}
+  acc = torch.zeros((ncls, h, w), dtype=torch.float32, device=device)
+  combine_path, cluster_index, segment_topk = HIP_VIEW_VOTES_PATH, [], []
+  with torch.no_grad():
+    for image, (rh, rw), flip in views:
+      embs = embed_full_resolution(embedding_model, image, crop_size, stride)[..., :rh, :rw].contiguous()
+      fake = torch.zeros((1, rh, rw), dtype=torch.long, device=device)
+      out = embedding_model.generate_clusters(embs, fake, fake)
+      topk, clu = prediction_model.segment_predictions(out, memory)
+      if topk is None:
+        raise ValueError('predict_knn_multiscale needs a memory bank and a clustering')
+      cluster_index.append(clu)
+      segment_topk.append(topk)
+      if ncls <= _ffi.MAX_VIEW_VOTES_CLASSES and topk.shape[0] <= _ffi.MAX_VIEW_VOTES_SEGMENTS:
+        _ffi.view_votes_accumulate(clu, (rh, rw), topk.contiguous(), ncls, flip, acc)
+      else:
+        framework_view_votes_accumulate(clu, (rh, rw), topk, ncls, flip, acc)
+        combine_path = FRAMEWORK_VIEW_VOTES_PATH
+    acc /= len(views)
+    prediction = _ffi.argmax_channels(acc, h, w)
+  return {'semantic_prob': acc, 'semantic_prediction': prediction, 'combine_path': combine_path,
+          'cluster_index': cluster_index, 'segment_topk': segment_topk}
 
 
 def save_image_memory(path, prototypes, prototype_labels):

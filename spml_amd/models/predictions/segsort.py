@@ -85,9 +85,11 @@ class Segsort(nn.Module):
     raise KeyError('Unsupported loss types: {:s}'.format(loss_types))
 
   # ------------------------------------------------------------------ predict
-  def predictions(self, datas, targets={}):
-    """k-NN retrieval of segment prototypes against a prototype memory
-    (segsort.py:68-125)."""
+  def segment_predictions(self, datas, targets={}):
+    """The two values `predictions` forms before its final gather (segsort.py:68-123): the labels retrieved per
+    SEGMENT, `topk` `[m, k]` int64, and every pixel's dense segment index `clu` `[N]` int64 (`topk[clu]` is the
+    `semantic_score` of `predictions`).  What the multi-scale kNN inference needs: m <= 144 rows instead of one per
+    pixel."""
     memory = targets.get('semantic_memory_prototype', None)
     memory_labels = targets.get('semantic_memory_prototype_label', None)
     emb = datas.get('cluster_embedding', None)
@@ -99,6 +101,14 @@ class Segsort(nn.Module):
     protos = segsort_common.calculate_prototypes_from_labels(emb, clu, m)
     dummy = torch.zeros(m, dtype=torch.long, device=protos.device)
     _, topk = segsort_eval.top_k_ranking(protos, dummy, memory, memory_labels, 20)
+    return topk, clu
+
+  def predictions(self, datas, targets={}):
+    """k-NN retrieval of segment prototypes against a prototype memory
+    (segsort.py:68-125)."""
+    topk, clu = self.segment_predictions(datas, targets)
+    if topk is None:
+      return None, None
     pred = segsort_eval.majority_label_from_topk(topk)
     return pred[clu], topk[clu]
 

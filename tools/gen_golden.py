@@ -302,6 +302,167 @@ def gen_n8(ref, out):
   assert size < 600 * 1024, 'n8_softmax_msc.npz is %d bytes' % size
 
 
+def gen_n9(ref, out):
+  """N9: multi-scale + flip kNN inference.  pyscripts/inference/inference_msc.py:157-226 exec'd per view (window ends,
+  per-crop normalise + overlap average, crop to the un-padded view, k-means, Segsort.predictions against a memory bank,
+  one-hot + mean over the 20 retrievals) and :237-242 once, from the reference's own lines on seeded CPU inputs.  The
+  arrangement of N5 and N8: a seeded 5x5 convolution as `generate_embeddings`, the reference's own `generate_clusters`
+  (on the CPU-shimmed segment_by_kmeans) and `Segsort`, a bank of perturbed image embeddings with random labels.
+  cv2 is not installed: as in `gen_n7` the yardstick of :230-231 (`cv2.resize(..., INTER_LINEAR)`) is CPU
+  `F.interpolate(..., mode='bilinear', align_corners=False)`, the same half-pixel mapping; the flip of :232-233 is
+  applied to its result.  Stored per view: `cluster_index` (int16, dense), the labels retrieved per SEGMENT (uint8
+  `[m, 20]`, recovered from `semantic_score`: all pixels of a segment are asserted to agree) and the view's vote map;
+  once: `semantic_prob`, `semantic_pred` and the top-1 minus top-2 `margin`.  Labels are compared where the margin is at
+  least 2e-4 * max|semantic_prob| (the N7 rule); at most 1 % of the pixels may fall below (asserted here)."""
+  import linecache
+  import math
+  import textwrap
+  import spml.models.embeddings.resnet_deeplab as e_dl
+  import spml.models.predictions.segsort as p_segsort
+  import spml.utils.general.common as g_common
+  import spml.utils.segsort.common as s_common
+  F = torch.nn.functional
+
+  def ref_lines(path, first, last):
+    txt = ''.join(linecache.getline(path, i) for i in range(first, last + 1))
+    assert txt.strip(), path
+    return textwrap.dedent(txt).replace('.cuda()', '').replace('.to("cuda:0")', '')
+
+  msc_py = os.path.join(ref, 'pyscripts', 'inference', 'inference_msc.py')
+  src_view, src_once = ref_lines(msc_py, 157, 226), ref_lines(msc_py, 237, 242)
+  assert 'patch_ind_h' in src_view and '[..., :resize_image_h, :resize_image_w]' in src_view and 'cuda' not in src_view
+  assert 'with_prediction=True' in src_view and 'torch.mean(semantic_topk, dim=1)' in src_view
+  assert src_view.rstrip().endswith('semantic_topk.view(resize_image_h, resize_image_w, -1)')
+  assert 'np.mean(semantic_topks, axis=0)' in src_once and 'np.argmax(semantic_prob, axis=0)' in src_once
+  resize_src = ref_lines(msc_py, 230, 233)
+  assert 'cv2.INTER_LINEAR' in resize_src and 'semantic_topk[:, ::-1]' in resize_src
+
+  # the CPU shim of main(): spml/utils/segsort/common.py:376 reads `tensor.device.index`, None on the CPU
+  src = inspect.getsource(s_common.segment_by_kmeans)
+  assert 'cur_cluster_indices.device.index' in src
+  ns = dict(s_common.__dict__)
+  exec(compile(src.replace('cur_cluster_indices.device.index', '(cur_cluster_indices.device.index or 0)'),
+               '<segment_by_kmeans+cpu-shim>', 'exec'), ns)
+
+  class StubEmbedder:
+    label_divisor = 2048
+    semantic_ignore_index = 255
+    kmeans_iterations = 10
+
+    def __init__(self, conv, clusters):
+      self.conv, self.kmeans_num_clusters = conv, clusters
+
+    def generate_embeddings(self, datas, targets=None, resize_as_input=False):
+      assert resize_as_input
+      return {'embedding': self.conv(datas['image']), 'local_feature': None}
+
+    generate_clusters = e_dl.ResnetDeeplab.generate_clusters
+
+  store = {}
+  # (seed, C, classes, image, crop, stride, scales, k-means grid, bank size).  (a) one scale, a flip pair, no padding;
+  # (b) two scales, odd image width: 0.75 up-samples to the image from a padded view (45 x 58 in 48 x 58, two windows
+  # along x), 1.25 down-samples to it (75 x 96: 2 x 3 windows).  The banks hold 400 / 500 entries so that the 20
+  # retrievals of a segment are its neighbourhood (with 80 entries they were a quarter of the bank and every vote map
+  # diffuse).  Seeds: 1900 meets the cap for (a) (0.45 % of the pixels under the margin); for (b) 1910 sits on the cap
+  # (1.00 %) and is rejected, 1911 has 0.09 % (1912-1914: 0.15 %, 0.39 %, 0.17 %; 1915: 2.25 %).
+  cases = [(1900, 16, 5, (44, 60), (44, 60), (30, 30), (1,), (4, 4), 400),
+           (1911, 32, 7, (60, 77), (48, 48), (32, 32), (0.75, 1.25), (5, 4), 500)]
+  orig = e_dl.segsort_common.segment_by_kmeans
+  e_dl.segsort_common.segment_by_kmeans = ns['segment_by_kmeans']
+  try:
+    for ci, (seed, c, ncls, image_hw, crop, stride, scales, grid, n_bank) in enumerate(cases):
+      gen = torch.Generator().manual_seed(seed)
+      torch.manual_seed(seed)
+      image_h, image_w = image_hw
+      conv = torch.nn.Conv2d(3, c, 5, padding=2)
+      base = torch.randn(1, 3, image_h // 8 + 2, image_w // 8 + 2, generator=gen)
+      image = F.interpolate(base, size=image_hw, mode='bilinear', align_corners=False)
+      image = image + 0.05 * torch.randn(1, 3, image_h, image_w, generator=gen)
+      cfg = AttrDict(
+          train=AttrDict(sem_ann_loss_types='none', sem_occ_loss_types='none', img_sim_loss_types='none',
+                         feat_aff_loss_types='none', sem_ann_concentration=0.0, sem_occ_concentration=0.0,
+                         img_sim_concentration=0.0, feat_aff_concentration=0.0, sem_ann_loss_weight=0.0,
+                         sem_occ_loss_weight=0.0, img_sim_loss_weight=0.0, feat_aff_loss_weight=0.0),
+          dataset=AttrDict(semantic_ignore_index=255, num_classes=ncls),
+          network=AttrDict(label_divisor=2048),
+          test=AttrDict(stride=list(stride), crop_size=list(crop)))
+      predictor = p_segsort.Segsort(cfg)
+      # a memory bank that looks like the image's own segments (N5): normalised embeddings of random pixels, perturbed
+      with torch.no_grad():
+        full = g_common.normalize_embedding(conv(image).permute(0, 2, 3, 1).reshape(-1, c))
+      pick = torch.randint(0, full.shape[0], (n_bank,), generator=gen)
+      bank = g_common.normalize_embedding(full[pick] + 0.1 * torch.randn(n_bank, c, generator=gen))
+      # random labels, drawn per cell of a coarse grid over the image; an entry takes the label of its source pixel's
+      # cell.  (Votes are multiples of 1/20: with labels drawn per ENTRY the top two classes of a segment tie so often
+      # that 14 % of the pixels of case (a) had a zero margin -- whole segments, not a matter of seeds.)
+      bank_lab = blocky_labels(gen, 1, image_h, image_w, 4, 0, ncls)[0].reshape(-1)[pick]
+      t = 'c%d_' % ci
+      views, semantic_topks = [], []
+      for si, scale in enumerate(scales):
+        size = (max(int(round(image_h * scale)), 1), max(int(round(image_w * scale)), 1))
+        scaled = image if scale == 1 else F.interpolate(image, size=size, mode='bilinear', align_corners=False)
+        store[t + 'scaled%d' % si] = scaled
+        rh, rw = scaled.shape[-2:]
+        pad_h, pad_w = max(rh, crop[0]), max(rw, crop[1])
+        for flip in (True, False):                            # create_image_pyramid: the flipped view first
+          view = torch.zeros(1, 3, pad_h, pad_w)
+          view[:, :, :rh, :rw] = torch.flip(scaled, dims=[3]) if flip else scaled
+          fake = torch.full((1, pad_h, pad_w), 255, dtype=torch.long)
+          fake[:, :rh, :rw] = 0                               # :140-151
+          env = {'config': cfg, 'math': math, 'np': np, 'torch': torch, 'image_batch': {'image': view},
+                 'pad_image_h': pad_h, 'pad_image_w': pad_w, 'resize_image_h': rh, 'resize_image_w': rw,
+                 'embedding_model': StubEmbedder(conv, list(grid)), 'prediction_model': predictor,
+                 'common_utils': g_common, 'fake_label_batch': {'semantic_label': fake, 'instance_label': fake.clone()},
+                 'semantic_memory_prototypes': bank, 'semantic_memory_prototype_labels': bank_lab}
+          with torch.no_grad():
+            exec(compile(src_view, msc_py + ':157-226', 'exec'), env)
+          votes = env['semantic_topk']
+          assert tuple(votes.shape) == (rh, rw, ncls) and votes.dtype == torch.float32
+          # :228-233 with F.interpolate in the place of cv2.resize
+          resized = F.interpolate(votes.permute(2, 0, 1).unsqueeze(0), size=image_hw, mode='bilinear',
+                                  align_corners=False)[0].permute(1, 2, 0).numpy().astype(np.float32)
+          if flip:
+            resized = resized[:, ::-1]
+          semantic_topks.append(resized)
+          # dense segment ids and the labels retrieved per segment, from the per-pixel outputs
+          score = env['outputs']['semantic_score']
+          _, clu = torch.unique(env['embeddings']['cluster_index'], return_inverse=True)
+          m = int(clu.max()) + 1
+          assert tuple(score.shape) == (rh * rw, 20) and clu.shape[0] == rh * rw
+          first = torch.full((m,), rh * rw, dtype=torch.long).scatter_reduce(0, clu, torch.arange(rh * rw), 'amin')
+          topk = score[first]
+          assert torch.equal(topk[clu], score), 'the pixels of a segment disagree on their retrieved labels'
+          assert m <= 32767 and int(topk.max()) < ncls
+          vi = len(views)
+          views.append([si, pad_h, pad_w, rh, rw, int(flip), m])
+          store[t + 'cluster_index%d' % vi] = clu.to(torch.int16)
+          store[t + 'topk%d' % vi] = topk.to(torch.uint8)
+          store[t + 'votes%d' % vi] = np.ascontiguousarray(resized.transpose(2, 0, 1))
+      env = {'np': np, 'semantic_topks': semantic_topks}
+      exec(compile(src_once, msc_py + ':237-242', 'exec'), env)
+      prob, pred = env['semantic_prob'], env['semantic_pred']
+      assert prob.shape == (ncls, image_h, image_w) and prob.dtype == np.float32
+      assert pred.shape == image_hw and pred.dtype == np.uint8
+      top2 = torch.from_numpy(np.ascontiguousarray(prob)).topk(2, dim=0).values
+      margin = top2[0] - top2[1]
+      low = (margin < 2e-4 * float(np.abs(prob).max())).float().mean().item()
+      winners = np.unique(pred).size
+      print('n9 case %d (seed %d): %d views, segments %s, low margin %.2f %%, %d classes win, max prob %.3f'
+            % (ci, seed, len(views), [v[6] for v in views], 100 * low, winners, prob.max()))
+      assert low <= 0.01, 'case %d: %.4f of the pixels have a low margin -- pick another seed' % (ci, low)
+      assert winners >= 3, 'case %d: only %d classes win -- pick another seed' % (ci, winners)
+      store.update({
+          t + 'conv_w': conv.weight, t + 'conv_b': conv.bias, t + 'bank': bank, t + 'bank_lab': bank_lab,
+          t + 'cfg': np.array([c, ncls, image_h, image_w, crop[0], crop[1], stride[0], stride[1], grid[0], grid[1]]),
+          t + 'views': np.array(views), t + 'semantic_prob': np.ascontiguousarray(prob), t + 'semantic_pred': pred,
+          t + 'margin': margin})
+  finally:
+    e_dl.segsort_common.segment_by_kmeans = orig
+  save(out, 'n9_knn_msc', **store)
+  size = os.path.getsize(os.path.join(out, 'n9_knn_msc.npz'))
+  assert size < 600 * 1024, 'n9_knn_msc.npz is %d bytes' % size
+
+
 class AttrDict(dict):
   __getattr__ = dict.__getitem__
 
@@ -320,11 +481,13 @@ def main():
 
   sys.path.insert(0, args.ref)
   torch.set_num_threads(1)       # bit-stable fp32 sums
-  if ONLY is not None and ONLY <= {'n7_pseudo_labels', 'n8_softmax_msc'}:      # (need none of the imports and shims below)
+  if ONLY is not None and ONLY <= {'n7_pseudo_labels', 'n8_softmax_msc', 'n9_knn_msc'}:      # (need none of the imports and shims below)
     if 'n7_pseudo_labels' in ONLY:
       gen_n7(args.ref, out)
     if 'n8_softmax_msc' in ONLY:
       gen_n8(args.ref, out)
+    if 'n9_knn_msc' in ONLY:
+      gen_n9(args.ref, out)
     return
 
   import spml.utils.general.common as g_common
@@ -1122,6 +1285,10 @@ def main():
   # ======================= N8: multi-scale + flip softmax inference =========================
   if ONLY is None or 'n8_softmax_msc' in ONLY:
     gen_n8(args.ref, out)
+
+  # ======================= N9: multi-scale + flip kNN inference ==============================
+  if ONLY is None or 'n9_knn_msc' in ONLY:
+    gen_n9(args.ref, out)
 
   # ======================= H2: two steps of the stage-2 classifier training ===============
   # pyscripts/train/train_classifier.py:139-169, the loop body exec'd as it stands on ONE device:
