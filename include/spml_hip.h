@@ -47,7 +47,8 @@ const char* spml_status_string(int status);
  * 5: the softmax-inference entry points (spml_unit_hl8_from_nchw_f32 .. spml_iou_counts_i64);
  * 6: the pseudo-label entry points (spml_resample_unit_f32 .. spml_upsample_argmax_i64);
  * 7: the multi-scale inference entry point (spml_view_probs_accumulate_f32);
- * 8: spml_upsample_ce_bwd_path_name. */
+ * 8: spml_upsample_ce_bwd_path_name (entry points added since leave every earlier signature and flag as it was and
+ *    keep the version: spml_view_votes_*, spml_segsort_nll_batched_*). */
 #define SPML_ABI_VERSION 8
 int spml_abi_version(void);
 
@@ -395,6 +396,43 @@ int spml_segsort_nll_bwd_f32(const float* emb, const int64_t* own,
                              const float* stats, const float* d_nll,
                              float* d_emb, float* d_protos, int64_t m_grad,
                              void* ws, size_t ws_bytes, void* stream);
+
+/* A9/A10 over N independent problems in one call
+ * replaces: the per-image loop of the image-similarity term, spml/models/predictions/segsort.py:221-241 (one
+ *           SegSortLoss per image over that image's pixels and prototypes), which reached the GPU as N times the
+ *           launches of spml_segsort_nll_fwd_f32 / _bwd_f32 on grids far smaller than the chip.
+ *
+ *   Problem i owns the pixel rows [p_off[i], p_off[i+1]) of emb / own / px_code / nll / stats / d_nll / d_emb and
+ *   the prototype rows [m_off[i], m_off[i+1]) of protos / pr_code / d_protos.  p_off, m_off: HOST arrays of
+ *   n_problems + 1 non-decreasing offsets, p_off[0] = m_off[0] = 0.  own is ABSOLUTE: an index into the
+ *   concatenated prototypes (the library subtracts m_off[i]).  D, kappa and mode are shared.
+ *   One launch per kernel for every 32 problems (the problem is the grid's z coordinate); every problem runs the
+ *   arithmetic of the single-problem call on its rows -- nll, stats and d_emb are bit-identical to N such calls,
+ *   d_protos up to the order of its fp32 atomics (bit-identical in deterministic mode).  All prototypes receive a
+ *   gradient; d_protos is ADDED into (zero it first).
+ *   Covered: 64 < D <= 80 with SPML_NLL_CODE32 (LABEL or TAGSET, with or without PLAIN);
+ *   spml_segsort_nll_batched_supported returns 0 for anything else and the calls SPML_ERR_UNSUPPORTED.
+ *   A problem without pixels does nothing; n_problems = 0 or no pixel at all: SPML_OK.  Pixels without prototypes
+ *   (P_i > 0, M_i <= 0): SPML_ERR_INVALID_ARG.  Workspace: query AFTER switching the deterministic mode. */
+int spml_segsort_nll_batched_supported(int D, int mode);
+
+size_t spml_segsort_nll_batched_workspace_bytes(int n_problems, const int64_t* p_off,
+                                                const int64_t* m_off, int D);
+
+int spml_segsort_nll_batched_fwd_f32(const float* emb, const int64_t* own,
+                                     const int64_t* px_code, const int64_t* p_off,
+                                     const float* protos, const int64_t* pr_code,
+                                     const int64_t* m_off, int n_problems, int D,
+                                     float kappa, int mode, float* nll, float* stats,
+                                     void* ws, size_t ws_bytes, void* stream);
+
+int spml_segsort_nll_batched_bwd_f32(const float* emb, const int64_t* own,
+                                     const int64_t* px_code, const int64_t* p_off,
+                                     const float* protos, const int64_t* pr_code,
+                                     const int64_t* m_off, int n_problems, int D,
+                                     float kappa, int mode, const float* stats,
+                                     const float* d_nll, float* d_emb, float* d_protos,
+                                     void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * A11/B3  top-k retrieval by cosine affinity

@@ -62,6 +62,12 @@ _SIGNATURES = {
                                          _P, _P, _P, c_size_t, _P]),
     'spml_segsort_nll_bwd_f32': (c_int, [_P, _P, _P, c_int64, _P, _P, c_int64, c_int, c_float, c_int,
                                          _P, _P, _P, _P, c_int64, _P, c_size_t, _P]),
+    'spml_segsort_nll_batched_supported': (c_int, [c_int, c_int]),
+    'spml_segsort_nll_batched_workspace_bytes': (c_size_t, [c_int, _P, _P, c_int]),
+    'spml_segsort_nll_batched_fwd_f32': (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_int,
+                                                 _P, _P, _P, c_size_t, _P]),
+    'spml_segsort_nll_batched_bwd_f32': (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_int,
+                                                 _P, _P, _P, _P, _P, c_size_t, _P]),
     'spml_topk_workspace_bytes': (c_size_t, [c_int64, c_int64, c_int, c_int]),
     'spml_topk_affinity_f32': (c_int, [_P, c_int64, _P, c_int64, c_int, c_int, _P, _P, _P, c_float,
                                        _P, _P, _P, c_size_t, _P]),
@@ -536,6 +542,62 @@ def segsort_nll_bwd(emb, own, px_code, protos, pr_code, kappa, mode, stats, d_nl
       ptr(protos, torch.float32), ptr(pr_code, torch.int64), m, d, float(kappa), int(mode),
       ptr(stats, torch.float32), ptr(d_nll, torch.float32), ptr(d_emb), ptr(d_protos),
       int(m_grad), ptr(ws), ws.numel(), stream_ptr()), 'spml_segsort_nll_bwd_f32')
+  return d_emb, d_protos
+
+
+def segsort_nll_batched_supported(d, mode):
+  """True when the batched NLL entry points take this embedding width and mode (include/spml_hip.h)."""
+  return bool(lib().spml_segsort_nll_batched_supported(int(d), int(mode)))
+
+
+def _host_offsets(sizes):
+  """Host prefix array [n + 1] of a list of sizes (the library reads it during the call only)."""
+  off = (c_int64 * (len(sizes) + 1))()
+  for i, v in enumerate(sizes):
+    off[i + 1] = off[i] + int(v)
+  return off
+
+
+def _nll_batched_workspace(p_off, m_off, n, d, device):
+  nbytes = lib().spml_segsort_nll_batched_workspace_bytes(n, p_off, m_off, d)
+  if nbytes == 0 and n > 0:
+    raise SpmlHipError('spml_segsort_nll_batched_workspace_bytes refused the sizes (D = %d)' % d)
+  return workspace(nbytes, device)
+
+
+def segsort_nll_batched_fwd(emb, own_abs, px_code, p_sizes, protos, pr_code, m_sizes, kappa, mode):
+  """N problems in one call: problem i owns p_sizes[i] consecutive pixel rows and m_sizes[i] consecutive
+  prototype rows; own_abs indexes the concatenated prototypes."""
+  p, d = emb.shape
+  n = len(p_sizes)
+  p_off, m_off = _host_offsets(p_sizes), _host_offsets(m_sizes)
+  if len(m_sizes) != n or p_off[n] != p or m_off[n] != protos.shape[0]:
+    raise SpmlHipError('the problem sizes do not add up to the rows given')
+  nll = torch.empty((p,), dtype=torch.float32, device=emb.device)
+  stats = torch.empty((p, 4), dtype=torch.float32, device=emb.device)
+  ws = _nll_batched_workspace(p_off, m_off, n, d, emb.device)
+  check(lib().spml_segsort_nll_batched_fwd_f32(
+      ptr(emb, torch.float32), ptr(own_abs, torch.int64), ptr(px_code, torch.int64), p_off,
+      ptr(protos, torch.float32), ptr(pr_code, torch.int64), m_off, n, d, float(kappa), int(mode),
+      ptr(nll), ptr(stats), ptr(ws), ws.numel(), stream_ptr()), 'spml_segsort_nll_batched_fwd_f32')
+  return nll, stats
+
+
+def segsort_nll_batched_bwd(emb, own_abs, px_code, p_sizes, protos, pr_code, m_sizes, kappa, mode, stats, d_nll):
+  p, d = emb.shape
+  n = len(p_sizes)
+  p_off, m_off = _host_offsets(p_sizes), _host_offsets(m_sizes)
+  if len(m_sizes) != n or p_off[n] != p or m_off[n] != protos.shape[0] or \
+      stats.shape[0] != p or d_nll.shape[0] != p:
+    raise SpmlHipError('the problem sizes do not add up to the rows given')
+  d_emb = torch.empty_like(emb)
+  d_protos = torch.zeros_like(protos)
+  ws = _nll_batched_workspace(p_off, m_off, n, d, emb.device)
+  check(lib().spml_segsort_nll_batched_bwd_f32(
+      ptr(emb, torch.float32), ptr(own_abs, torch.int64), ptr(px_code, torch.int64), p_off,
+      ptr(protos, torch.float32), ptr(pr_code, torch.int64), m_off, n, d, float(kappa), int(mode),
+      ptr(stats, torch.float32), ptr(d_nll, torch.float32), ptr(d_emb), ptr(d_protos),
+      ptr(ws), ws.numel(), stream_ptr()), 'spml_segsort_nll_batched_bwd_f32')
   return d_emb, d_protos
 
 

@@ -40,9 +40,9 @@ namespace {
 // contraction go into ONE accumulator (nll_fwd2); the caller scales the two operands by 2^3 / 2^-3 so
 // that residuals of O(1) elements stay normal f16 numbers and the rest lose at most 2^-25 absolute.
 template <bool RAW>
-__global__ __launch_bounds__(256) void prep_std(const float* __restrict__ x, int64_t R, int D,
-                                                int KS, float scale, _Float16* __restrict__ oh,
-                                                _Float16* __restrict__ ol) {
+__device__ __forceinline__ void prep_std_body(const float* __restrict__ x, int64_t R, int D,
+                                              int KS, float scale, _Float16* __restrict__ oh,
+                                              _Float16* __restrict__ ol) {
   const int64_t f = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);   // fragment block id
   const int64_t nfrag = ((R + 31) / 32) * KS;
   if (f >= nfrag) return;
@@ -68,13 +68,19 @@ __global__ __launch_bounds__(256) void prep_std(const float* __restrict__ x, int
   *reinterpret_cast<half8*>(oh + ((size_t)f * 64 + lane) * 8) = h;
   *reinterpret_cast<half8*>(ol + ((size_t)f * 64 + lane) * 8) = l;
 }
+template <bool RAW>
+__global__ __launch_bounds__(256) void prep_std(const float* __restrict__ x, int64_t R, int D,
+                                                int KS, float scale, _Float16* __restrict__ oh,
+                                                _Float16* __restrict__ ol) {
+  prep_std_body<RAW>(x, R, D, KS, scale, oh, ol);
+}
 
 template <bool RAW>
-__global__ __launch_bounds__(256) void prep_T(const float* __restrict__ x, int64_t R, int D,
-                                              int DT, const float* __restrict__ rowscale,
-                                              const float* __restrict__ gscale, float scale,
-                                              _Float16* __restrict__ oh,
-                                              _Float16* __restrict__ ol) {
+__device__ __forceinline__ void prep_T_body(const float* __restrict__ x, int64_t R, int D,
+                                            int DT, const float* __restrict__ rowscale,
+                                            const float* __restrict__ gscale, float scale,
+                                            _Float16* __restrict__ oh,
+                                            _Float16* __restrict__ ol) {
   const int64_t f = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int64_t nfrag = ((R + 31) / 32) * DT * 2;
   if (f >= nfrag) return;
@@ -107,10 +113,18 @@ __global__ __launch_bounds__(256) void prep_T(const float* __restrict__ x, int64
   *reinterpret_cast<half8*>(oh + ((size_t)f * 64 + lane) * 8) = h;
   *reinterpret_cast<half8*>(ol + ((size_t)f * 64 + lane) * 8) = l;
 }
+template <bool RAW>
+__global__ __launch_bounds__(256) void prep_T(const float* __restrict__ x, int64_t R, int D,
+                                              int DT, const float* __restrict__ rowscale,
+                                              const float* __restrict__ gscale, float scale,
+                                              _Float16* __restrict__ oh,
+                                              _Float16* __restrict__ ol) {
+  prep_T_body<RAW>(x, R, D, DT, rowscale, gscale, scale, oh, ol);
+}
 
 // gscale[0] = power of two >= max |g|  (so that g/gscale is in [-1,1]); 1 if all zero
-__global__ __launch_bounds__(1024) void max_abs_pow2(const float* __restrict__ g, int64_t n,
-                                                     float* __restrict__ out) {
+__device__ __forceinline__ void max_abs_pow2_body(const float* __restrict__ g, int64_t n,
+                                                  float* __restrict__ out) {
   __shared__ float red[16];
   float m = 0.f;
   for (int64_t i = threadIdx.x; i < n; i += 1024) m = fmaxf(m, fabsf(g[i]));
@@ -128,6 +142,10 @@ __global__ __launch_bounds__(1024) void max_abs_pow2(const float* __restrict__ g
     }
     out[0] = p;
   }
+}
+__global__ __launch_bounds__(1024) void max_abs_pow2(const float* __restrict__ g, int64_t n,
+                                                     float* __restrict__ out) {
+  max_abs_pow2_body(g, n, out);
 }
 
 // z tile (rows = A rows, cols = B cols) for KS k-steps; A fragments from LDS
@@ -299,7 +317,7 @@ __global__ __launch_bounds__(256) void nll_fwd(NllArgs a) {
 //     nll_finalize (deterministic).
 // Two workgroups per CU (12 KB of row codes + 2 x MTB x 2 KS KB of ring each, <= 256 VGPRs).
 template <int KS, int MTB, bool TAG>
-__global__ __launch_bounds__(256, 2) void nll_fwd2(NllArgs a) {
+__device__ __forceinline__ void nll_fwd2_body(const NllArgs& a) {
   constexpr int TILE = 2 * KS * 1024;            // hi blocks, lo blocks of one prototype tile
   constexpr int SLOT = MTB * TILE;
   constexpr int CODES = kFwd2TilesPerChunk * 32 * 4;   // the chunk's row codes (low words), resident
@@ -345,7 +363,7 @@ __global__ __launch_bounds__(256, 2) void nll_fwd2(NllArgs a) {
     }
     const int64_t p = min(32 * pt + j, a.n.P - 1);
     pcode[nb] = (int)a.px_code[p];
-    own[nb] = (int)a.own[p] - (int)(32 * mt_lo);         // relative to this chunk's first prototype
+    own[nb] = (int)(a.own[p] - a.own_base) - (int)(32 * mt_lo);   // relative to this chunk's first prototype
     s_same[nb] = 0.f; s_all[nb] = 0.f; s_own[nb] = 0.f;
   }
 
@@ -531,11 +549,15 @@ __global__ __launch_bounds__(256, 2) void nll_fwd2(NllArgs a) {
     }
   }
 }
+template <int KS, int MTB, bool TAG>
+__global__ __launch_bounds__(256, 2) void nll_fwd2(NllArgs a) {
+  nll_fwd2_body<KS, MTB, TAG>(a);
+}
 
 // per pixel: chunk partials (same, all, own) summed in chunk order -> nll, stats (loss.py:61-80)
-__global__ __launch_bounds__(256) void nll_finalize(const float* __restrict__ partial, int chunks,
-                                                    int64_t P, int64_t P_pad, int plain,
-                                                    float* __restrict__ nll, float* __restrict__ stats) {
+__device__ __forceinline__ void nll_finalize_body(const float* __restrict__ partial, int chunks,
+                                                  int64_t P, int64_t P_pad, int plain,
+                                                  float* __restrict__ nll, float* __restrict__ stats) {
   const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (p >= P) return;
   float same = 0.f, all = 0.f, osim = 0.f;
@@ -553,6 +575,11 @@ __global__ __launch_bounds__(256) void nll_finalize(const float* __restrict__ pa
   const float4v st = {num, den, osim, fb ? 1.f : 0.f};
   *reinterpret_cast<float4v*>(stats + (size_t)p * 4) = st;
 }
+__global__ __launch_bounds__(256) void nll_finalize(const float* __restrict__ partial, int chunks,
+                                                    int64_t P, int64_t P_pad, int plain,
+                                                    float* __restrict__ nll, float* __restrict__ stats) {
+  nll_finalize_body(partial, chunks, P, P_pad, plain, nll, stats);
+}
 
 // ---------------------------------------------------------------------------
 // backward.  With  s = exp(kappa z),  nll = -log(num) + log(den):
@@ -565,10 +592,12 @@ __global__ __launch_bounds__(256) void nll_finalize(const float* __restrict__ pa
 // fragments by the prep kernel, scaled by a power of two so that they stay in
 // f16 range).
 // ---------------------------------------------------------------------------
+// own_base: first prototype of the problem among the ones `own` counts (batched calls; else 0)
 template <bool TAG>
-__global__ void coef_kernel(const float* __restrict__ stats, const int64_t* __restrict__ own,
-                            const int64_t* __restrict__ px_code, const int64_t* __restrict__ pr_code, int64_t M,
-                            int64_t P, int64_t P_pad, PixelCoef* __restrict__ out) {
+__device__ __forceinline__ void coef_body(const float* __restrict__ stats, const int64_t* __restrict__ own,
+                                          const int64_t* __restrict__ px_code, const int64_t* __restrict__ pr_code,
+                                          int64_t M, int64_t P, int64_t P_pad, int64_t own_base,
+                                          PixelCoef* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= P_pad) return;
   PixelCoef c{0.f, 0.f, -1, 0.f};
@@ -577,12 +606,18 @@ __global__ void coef_kernel(const float* __restrict__ stats, const int64_t* __re
     const float inv_num = 1.0f / st[0], inv_den = 1.0f / st[1];
     c.wa = st[3] != 0.f ? 0.f : inv_den - inv_num;
     c.wb = inv_den;
-    c.own = (int)own[i];
-    const int64_t m = own[i];
+    const int64_t m = own[i] - own_base;
+    c.own = (int)m;
     const bool own_same = m >= 0 && m < M && code_match<TAG, int64_t>(px_code[i], pr_code[m]);
     c.tscale = nll_t_scale(st[0], st[1], st[2], st[3] != 0.f, own_same);
   }
   out[i] = c;
+}
+template <bool TAG>
+__global__ void coef_kernel(const float* __restrict__ stats, const int64_t* __restrict__ own,
+                            const int64_t* __restrict__ px_code, const int64_t* __restrict__ pr_code, int64_t M,
+                            int64_t P, int64_t P_pad, PixelCoef* __restrict__ out) {
+  coef_body<TAG>(stats, own, px_code, pr_code, M, P, P_pad, 0, out);
 }
 
 // kappa g_p (2^14 / tscale_p): row scale of the transposed pixel fragments of nll_dp3.hip (T carries tscale_p)
@@ -718,7 +753,7 @@ __device__ __forceinline__ void tcache_load(const float* base, int64_t tile, int
 // LDS ring.  dE^T[d][pixel] += PrT[d][m] * T[m][pixel].
 // TM: 0 = compute T, 1 = compute and keep it in the cache, 2 = read it from the cache (no similarity GEMM)
 template <int KS, int DT, bool TAG, bool C32, int TM = 0>
-__global__ __launch_bounds__(256) void nll_bwd_de(NllArgs a) {
+__device__ __forceinline__ void nll_bwd_de_body(const NllArgs& a) {
   using CodeT = code_t<C32>;
   constexpr int kStd = TM == 2 ? 0 : 2 * KS + 1; // std hi/lo + codes (not needed when T comes from the cache)
   constexpr int NBLK = kStd + 4 * DT;            // ... + T-layout [DT][2][hi|lo]
@@ -827,6 +862,10 @@ __global__ __launch_bounds__(256) void nll_bwd_de(NllArgs a) {
         if (d < a.n.D) a.d_emb[(size_t)pp * a.n.D + d] = gk * dacc[dt][r];
       }
   }
+}
+template <int KS, int DT, bool TAG, bool C32, int TM = 0>
+__global__ __launch_bounds__(256) void nll_bwd_de(NllArgs a) {
+  nll_bwd_de_body<KS, DT, TAG, C32, TM>(a);
 }
 
 // ------------------------------- backward: dE, v2 ---------------------------
@@ -1060,7 +1099,7 @@ __global__ __launch_bounds__(256) void nll_de_finalize(const float* __restrict__
 // the LDS ring.  dPr^T[d][proto] += ET[d][p] * T'[p][proto]; every wave owns its
 // accumulators, which leave with one fp32 atomic per element per chunk.
 template <int KS, int DT, bool TAG, bool C32, int TM = 0>
-__global__ __launch_bounds__(256) void nll_bwd_dp(NllArgs a) {
+__device__ __forceinline__ void nll_bwd_dp_body(const NllArgs& a) {
   using CodeT = code_t<C32>;
   constexpr int kStd = TM == 2 ? 0 : 2 * KS + 2; // std hi/lo, coef, codes (not needed when T comes from the cache)
   constexpr int NBLK = kStd + 4 * DT;            // ... + T-layout blocks
@@ -1180,10 +1219,17 @@ __global__ __launch_bounds__(256) void nll_bwd_dp(NllArgs a) {
       }
   }
 }
+template <int KS, int DT, bool TAG, bool C32, int TM = 0>
+__global__ __launch_bounds__(256) void nll_bwd_dp(NllArgs a) {
+  nll_bwd_dp_body<KS, DT, TAG, C32, TM>(a);
+}
 
-__global__ void pad_codes_kernel(const int64_t* in, int64_t n, int64_t n_pad, int64_t* out) {
+__device__ __forceinline__ void pad_codes_body(const int64_t* in, int64_t n, int64_t n_pad, int64_t* out) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n_pad) out[i] = i < n ? in[i] : 0;
+}
+__global__ void pad_codes_kernel(const int64_t* in, int64_t n, int64_t n_pad, int64_t* out) {
+  pad_codes_body(in, n, n_pad, out);
 }
 
 __global__ void rowscale_kernel(const float* g, float kappa, int64_t n, float* out) {
@@ -1209,9 +1255,18 @@ inline int64_t tcache_strip_tiles(const NllDims& n) {
   return tiles < n.PT ? tiles : n.PT;
 }
 
-inline int64_t fwd2_chunks(const NllDims& n) { return (n.MT + kFwd2TilesPerChunk - 1) / kFwd2TilesPerChunk; }
+__host__ __device__ inline int64_t fwd2_chunks(const NllDims& n) { return (n.MT + kFwd2TilesPerChunk - 1) / kFwd2TilesPerChunk; }
 // grid rows of the v2 backward kernels: chunk c is taken by row c mod rows (a function of M alone)
 inline int bwd2_rows(const NllDims& n) { return (int)std::min<int64_t>(fwd2_chunks(n), 8); }
+
+// nll_bwd_dp: pixel chunks per group of 4 prototype tiles, so that the grid has a few thousand workgroups
+__host__ __device__ inline int64_t dp_chunks(int64_t mgroups, int64_t PT) {
+  int64_t chunks = mgroups > 0 ? (2048 + mgroups - 1) / mgroups : 1;
+  if (chunks > (PT + 7) / 8) chunks = (PT + 7) / 8;
+  if (chunks < 1) chunks = 1;
+  if (chunks > 65535) chunks = 65535;
+  return chunks;
+}
 
 NllWs nll_ws(const NllDims& n) {
   NllWs w{};
@@ -1257,12 +1312,16 @@ NllWs nll_ws(const NllDims& n) {
 }
 
 // fixed-point sums -> d_protos (+=), and the sums back to zero
-__global__ void nll_dpr_from_fix(long long* __restrict__ acc, int64_t n, const float* __restrict__ gscale,
-                                 float* __restrict__ d_protos) {
+__device__ __forceinline__ void nll_dpr_from_fix_body(long long* __restrict__ acc, int64_t n,
+                                                      const float* __restrict__ gscale, float* __restrict__ d_protos) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const long long q = acc[i];
   if (q != 0) d_protos[i] += (float)((double)q * kDetFixInv) * gscale[0];
+}
+__global__ void nll_dpr_from_fix(long long* __restrict__ acc, int64_t n, const float* __restrict__ gscale,
+                                 float* __restrict__ d_protos) {
+  nll_dpr_from_fix_body(acc, n, gscale, d_protos);
 }
 
 int ks_bucket(int ks) {
@@ -1306,6 +1365,313 @@ void launch_prep_T_raw(const float* x, int64_t R, int D, int DT, const float* ro
   const int64_t nfrag = ((R + 31) / 32) * DT * 2;
   hipLaunchKernelGGL(prep_T<true>, dim3((unsigned)((nfrag + 3) / 4)), dim3(256), 0, s, x, R, D, DT,
                      rowscale, gscale, scale, h, l);
+}
+
+
+// ------------------------------- batched calls ------------------------------
+// N independent problems of one shape class (same D, kappa, mode, kernel instantiation) in one launch per kernel:
+// blockIdx.z names the problem, blockIdx.x / .y are the coordinates of the problem's own grid (the launch is sized
+// for the largest problem; workgroups beyond a problem's grid leave at once).  Every kernel body is the
+// single-problem one, run on the problem's NllArgs: no sum changes its terms or their order.
+// The arrays are the problems' arrays one after the other: pixels / prototypes by rows, everything that is tiled by
+// padded 32-row tiles (pt_off / mt_off), the forward's chunk partials by part_off (units of 4 floats).
+constexpr int kNllBatchMax = 32;       // problems per descriptor (a kernel argument: < 4 KB)
+struct NllBatch {
+  NllArgs a;                           // what the problems share; pointers = start of the concatenated arrays
+  int count, first;                    // problems of this launch, index of the first one in the call
+  int64_t p_off[kNllBatchMax + 1], m_off[kNllBatchMax + 1];     // rows
+  int64_t pt_off[kNllBatchMax + 1], mt_off[kNllBatchMax + 1];   // padded tiles
+  int64_t part_off[kNllBatchMax + 1];
+  const float* emb;                    // [sum P][D]
+  const float* protos;                 // [sum M][D]
+  float* rowscale;                     // [sum P]
+};
+static_assert(sizeof(NllBatch) <= 2048, "a kernel argument");
+
+// NllArgs of problem z; false: the problem has no pixels (nothing to do)
+__device__ __forceinline__ bool batch_problem(const NllBatch& b, int z, NllArgs& a) {
+  const int64_t p0 = b.p_off[z], m0 = b.m_off[z], pt0 = b.pt_off[z], mt0 = b.mt_off[z];
+  const int64_t P = b.p_off[z + 1] - p0;
+  if (P <= 0) return false;
+  a = b.a;
+  a.n.P = P;
+  a.n.M = b.m_off[z + 1] - m0;
+  a.n.PT = b.pt_off[z + 1] - pt0;
+  a.n.MT = b.mt_off[z + 1] - mt0;
+  const size_t ks = (size_t)a.n.KS * 512, dt = (size_t)a.n.DT * 1024, D = (size_t)a.n.D;
+  a.eh += pt0 * ks; a.el += pt0 * ks; a.ph += mt0 * ks; a.pl += mt0 * ks;
+  a.pth += mt0 * dt; a.ptl += mt0 * dt; a.eth += pt0 * dt; a.etl += pt0 * dt;
+  a.own += p0; a.own_base = m0;
+  a.px_code += p0; a.pr_code += m0;
+  a.pr_code_pad += mt0 * 32; a.px_code_pad += pt0 * 32; a.coef += pt0 * 32;
+  a.mt_grad = a.n.MT;
+  a.nll += p0; a.stats += p0 * 4; a.d_nll += p0;
+  a.gscale += b.first + z;
+  a.d_emb += p0 * D; a.d_protos += m0 * D;
+  if (a.d_protos64) a.d_protos64 += m0 * D;
+  a.chunks = (int)dp_chunks((a.n.MT + 3) / 4, a.n.PT);
+  a.spt0 = 0; a.spt1 = a.n.PT;
+  a.partial += b.part_off[z] * 4;
+  return true;
+}
+
+template <int KS, int MTB, bool TAG>
+__global__ __launch_bounds__(256, 2) void nll_fwd2_batched(NllBatch b) {
+  NllArgs a;
+  if (!batch_problem(b, blockIdx.z, a)) return;
+  if (blockIdx.x >= (a.n.PT + 7) / 8 || blockIdx.y >= fwd2_chunks(a.n)) return;
+  nll_fwd2_body<KS, MTB, TAG>(a);
+}
+template <int KS, int DT, bool TAG>
+__global__ __launch_bounds__(256) void nll_bwd_de_batched(NllBatch b) {
+  NllArgs a;
+  if (!batch_problem(b, blockIdx.z, a)) return;
+  if (blockIdx.x >= (a.n.PT + 3) / 4) return;
+  nll_bwd_de_body<KS, DT, TAG, false, 0>(a);
+}
+template <int KS, int DT, bool TAG>
+__global__ __launch_bounds__(256) void nll_bwd_dp_batched(NllBatch b) {
+  NllArgs a;
+  if (!batch_problem(b, blockIdx.z, a)) return;
+  if (blockIdx.x >= (a.mt_grad + 3) / 4 || (int)blockIdx.y >= a.chunks) return;
+  nll_bwd_dp_body<KS, DT, TAG, false, 0>(a);
+}
+// px: the pixels' codes, else the prototypes'
+__global__ void pad_codes_batched(NllBatch b, int px) {
+  NllArgs a;
+  if (!batch_problem(b, blockIdx.z, a)) return;
+  if (px) pad_codes_body(a.px_code, a.n.P, a.n.PT * 32, const_cast<int64_t*>(a.px_code_pad));
+  else pad_codes_body(a.pr_code, a.n.M, a.n.MT * 32, const_cast<int64_t*>(a.pr_code_pad));
+}
+// px: the pixels' rows (b.emb) into eh / el, else the prototypes' (b.protos) into ph / pl
+template <bool RAW>
+__global__ __launch_bounds__(256) void prep_std_batched(NllBatch b, int px, float scale) {
+  NllArgs a;
+  if (!batch_problem(b, blockIdx.z, a)) return;
+  if (px)
+    prep_std_body<RAW>(b.emb + (size_t)b.p_off[blockIdx.z] * a.n.D, a.n.P, a.n.D, a.n.KS, scale,
+                       const_cast<_Float16*>(a.eh), const_cast<_Float16*>(a.el));
+  else
+    prep_std_body<RAW>(b.protos + (size_t)b.m_off[blockIdx.z] * a.n.D, a.n.M, a.n.D, a.n.KS, scale,
+                       const_cast<_Float16*>(a.ph), const_cast<_Float16*>(a.pl));
+}
+// px: the pixels' rows x rowscale / gscale into eth / etl, else the prototypes' into pth / ptl
+__global__ __launch_bounds__(256) void prep_T_batched(NllBatch b, int px) {
+  NllArgs a;
+  if (!batch_problem(b, blockIdx.z, a)) return;
+  if (px)
+    prep_T_body<false>(b.emb + (size_t)b.p_off[blockIdx.z] * a.n.D, a.n.P, a.n.D, a.n.DT,
+                       b.rowscale + b.p_off[blockIdx.z], a.gscale, 1.0f, const_cast<_Float16*>(a.eth),
+                       const_cast<_Float16*>(a.etl));
+  else
+    prep_T_body<false>(b.protos + (size_t)b.m_off[blockIdx.z] * a.n.D, a.n.M, a.n.D, a.n.DT, nullptr, nullptr,
+                       1.0f, const_cast<_Float16*>(a.pth), const_cast<_Float16*>(a.ptl));
+}
+__global__ __launch_bounds__(256) void nll_finalize_batched(NllBatch b) {
+  NllArgs a;
+  if (!batch_problem(b, blockIdx.z, a)) return;
+  nll_finalize_body(a.partial, (int)fwd2_chunks(a.n), a.n.P, a.n.PT * 32, (a.mode & SPML_NLL_PLAIN) ? 1 : 0, a.nll,
+                    a.stats);
+}
+__global__ __launch_bounds__(1024) void max_abs_pow2_batched(NllBatch b) {
+  NllArgs a;
+  if (!batch_problem(b, blockIdx.z, a)) return;
+  max_abs_pow2_body(a.d_nll, a.n.P, const_cast<float*>(a.gscale));
+}
+template <bool TAG>
+__global__ void coef_batched(NllBatch b) {
+  NllArgs a;
+  if (!batch_problem(b, blockIdx.z, a)) return;
+  coef_body<TAG>(a.stats, a.own, a.px_code, a.pr_code, a.n.M, a.n.P, a.n.PT * 32, a.own_base,
+                 const_cast<PixelCoef*>(a.coef));
+}
+__global__ void nll_dpr_from_fix_batched(NllBatch b) {
+  NllArgs a;
+  if (!batch_problem(b, blockIdx.z, a)) return;
+  nll_dpr_from_fix_body(a.d_protos64, a.n.M * a.n.D, a.gscale, a.d_protos);
+}
+
+// workspace of a batched call (offsets from its start): the arrays of nll_ws, each the problems' arrays in a row
+struct NllBatchWs {
+  size_t eh, el, ph, pl, pth, ptl, eth, etl, gscale, rowscale, codes, pxcodes, coef, partial, dp64, total;
+};
+// totals of a batched call, from the host-side offsets; false: an offset list the entry points refuse
+struct NllBatchTotals {
+  int64_t P, M, PT, MT, part;          // rows, padded tiles, chunk partials (units of 16 B)
+};
+bool batch_totals(int n_problems, const int64_t* p_off, const int64_t* m_off, int D, NllBatchTotals& t) {
+  t = NllBatchTotals{0, 0, 0, 0, 0};
+  if (n_problems < 0 || D <= 0 || (n_problems > 0 && (!p_off || !m_off))) return false;
+  if (n_problems == 0) return true;
+  if (p_off[0] != 0 || m_off[0] != 0) return false;
+  for (int i = 0; i < n_problems; ++i) {
+    const int64_t P = p_off[i + 1] - p_off[i], M = m_off[i + 1] - m_off[i];
+    if (P < 0 || M < 0 || (P > 0 && M <= 0)) return false;
+    // (own prototype ids and tile-relative rows are 32-bit in the kernels, as in the single-problem call)
+    if (P > (int64_t)1 << 30 || M > (int64_t)1 << 30) return false;
+    const NllDims n = nll_dims(P, M, D);
+    t.PT += n.PT;
+    t.MT += n.MT;
+    t.part += fwd2_chunks(n) * n.PT * 32;
+  }
+  t.P = p_off[n_problems];
+  t.M = m_off[n_problems];
+  return true;
+}
+NllBatchWs nll_batch_ws(const NllBatchTotals& t, int n_problems, int D, int KS, int DT) {
+  NllBatchWs w{};
+  size_t o = 0;
+  const size_t e_std = (size_t)t.PT * KS * 1024, p_std = (size_t)t.MT * KS * 1024;
+  const size_t e_t = (size_t)t.PT * DT * 2048, p_t = (size_t)t.MT * DT * 2048;
+  w.eh = o; o = align_up(o + e_std, 256);
+  w.el = o; o = align_up(o + e_std, 256);
+  w.ph = o; o = align_up(o + p_std, 256);
+  w.pl = o; o = align_up(o + p_std, 256);
+  w.pth = o; o = align_up(o + p_t, 256);
+  w.ptl = o; o = align_up(o + p_t, 256);
+  w.eth = o; o = align_up(o + e_t, 256);
+  w.etl = o; o = align_up(o + e_t, 256);
+  w.gscale = o; o = align_up(o + (size_t)n_problems * 4 + 16, 256);
+  w.rowscale = o; o = align_up(o + (size_t)t.P * 4, 256);
+  w.codes = o; o = align_up(o + (size_t)t.MT * 32 * 8, 256);
+  w.pxcodes = o; o = align_up(o + (size_t)t.PT * 32 * 8, 256);
+  w.coef = o; o = align_up(o + (size_t)t.PT * 32 * 16, 256);
+  w.partial = o; o = align_up(o + (size_t)t.part * 16, 256);
+  w.dp64 = 0;
+  if (deterministic_mode()) { w.dp64 = o; o = align_up(o + (size_t)t.M * D * 8, 256); }
+  w.total = o;
+  return w;
+}
+
+bool batched_supported(int D, int mode) {
+  if (D <= 0 || mode < 0 || mode > (SPML_NLL_TAGSET | SPML_NLL_PLAIN | SPML_NLL_CODE32)) return false;
+  if (!(mode & SPML_NLL_CODE32) || ks_bucket((D + 15) / 16) != 5) return false;
+  // SPML_NLL_FWD2=0: the single-problem forward takes another kernel, which has no batched form.  It turns the
+  // batched backward off with it, although the single-problem backward does not read the switch: forward and
+  // backward are one autograd node, supported together or not at all (the op then takes the looped path)
+  const char* env2 = getenv("SPML_NLL_FWD2");
+  return !(env2 && env2[0] == '0');
+}
+
+int nll_batched(bool backward, const float* emb, const int64_t* own, const int64_t* px_code, const int64_t* p_off,
+                const float* protos, const int64_t* pr_code, const int64_t* m_off, int n_problems, int D, float kappa,
+                int mode, float* nll, float* stats, const float* d_nll, float* d_emb, float* d_protos, void* ws,
+                size_t ws_bytes, hipStream_t s) {
+  if (n_problems < 0 || D <= 0) return SPML_ERR_INVALID_ARG;
+  if (mode < 0 || mode > (SPML_NLL_TAGSET | SPML_NLL_PLAIN | SPML_NLL_CODE32)) return SPML_ERR_INVALID_ARG;
+  NllBatchTotals t;
+  if (!batch_totals(n_problems, p_off, m_off, D, t)) return SPML_ERR_INVALID_ARG;
+  if (!batched_supported(D, mode)) return SPML_ERR_UNSUPPORTED;
+  if (n_problems == 0 || t.P == 0) return SPML_OK;
+  if (!emb || !own || !px_code || !protos || !pr_code || !stats) return SPML_ERR_INVALID_ARG;
+  if (backward ? (!d_nll || !d_emb || !d_protos) : !nll) return SPML_ERR_INVALID_ARG;
+  constexpr int KS = 5, DT = 3;                               // the bucket's template tile counts (dt_per_launch)
+  const NllBatchWs w = nll_batch_ws(t, n_problems, D, KS, DT);
+  if (!ws || ws_bytes < w.total) return SPML_ERR_WORKSPACE;
+  unsigned char* base = static_cast<unsigned char*>(ws);
+  const bool tag = (mode & SPML_NLL_TAGSET) != 0;
+
+  NllBatch b{};
+  NllArgs& a = b.a;
+  a.n = nll_dims(0, 0, D);
+  a.n.KS = KS; a.n.DT = DT;
+  a.eh = reinterpret_cast<_Float16*>(base + w.eh); a.el = reinterpret_cast<_Float16*>(base + w.el);
+  a.ph = reinterpret_cast<_Float16*>(base + w.ph); a.pl = reinterpret_cast<_Float16*>(base + w.pl);
+  a.pth = reinterpret_cast<_Float16*>(base + w.pth); a.ptl = reinterpret_cast<_Float16*>(base + w.ptl);
+  a.eth = reinterpret_cast<_Float16*>(base + w.eth); a.etl = reinterpret_cast<_Float16*>(base + w.etl);
+  a.own = own; a.px_code = px_code; a.pr_code = pr_code;
+  a.pr_code_pad = reinterpret_cast<int64_t*>(base + w.codes);
+  a.px_code_pad = reinterpret_cast<int64_t*>(base + w.pxcodes);
+  a.coef = reinterpret_cast<PixelCoef*>(base + w.coef);
+  a.kappa = kappa;
+  a.kappa_log2e = kappa * 1.4426950408889634f;
+  a.mode = mode; a.nll = nll; a.stats = stats; a.d_nll = d_nll; a.d_emb = d_emb; a.d_protos = d_protos;
+  a.gscale = reinterpret_cast<float*>(base + w.gscale);
+  a.partial = reinterpret_cast<float*>(base + w.partial);
+  a.d_protos64 = backward && w.dp64 ? reinterpret_cast<long long*>(base + w.dp64) : nullptr;
+  a.depth = 2;                                                // (KS <= 5: see SPML_BWD_LAUNCH of the single-problem call)
+  if (const char* e_ = getenv("SPML_NLL_DEPTH_BWD")) { const int v_ = atoi(e_); if (v_ >= 2 && v_ <= 3) a.depth = v_; }
+  a.dt0 = 0; a.dt_all = DT;
+  b.emb = emb; b.protos = protos;
+  b.rowscale = reinterpret_cast<float*>(base + w.rowscale);
+  if (a.d_protos64 &&
+      hipMemsetAsync(base + w.dp64, 0, (size_t)t.M * D * 8, s) != hipSuccess) return SPML_ERR_LAUNCH;
+
+  constexpr int LDS_F = kFwd2TilesPerChunk * 128 + 2 * 2 * 2 * KS * 1024;
+  constexpr int SLOT_DE = (2 * KS + 1 + 4 * DT) * 1024, SLOT_DP = (2 * KS + 2 + 4 * DT) * 1024;
+  int64_t pt_run = 0, mt_run = 0, part_run = 0;
+  for (int g0 = 0; g0 < n_problems; g0 += kNllBatchMax) {
+    const int cnt = std::min(kNllBatchMax, n_problems - g0);
+    b.count = cnt; b.first = g0;
+    int64_t max_p = 0, max_m = 0, max_chunks = 1, max_dpc = 1;
+    for (int i = 0; i <= cnt; ++i) {
+      b.p_off[i] = p_off[g0 + i]; b.m_off[i] = m_off[g0 + i];
+      b.pt_off[i] = pt_run; b.mt_off[i] = mt_run; b.part_off[i] = part_run;
+      if (i == cnt) break;
+      const int64_t P = p_off[g0 + i + 1] - p_off[g0 + i], M = m_off[g0 + i + 1] - m_off[g0 + i];
+      const NllDims n = nll_dims(P, M, D);
+      pt_run += n.PT; mt_run += n.MT; part_run += fwd2_chunks(n) * n.PT * 32;
+      if (P <= 0) continue;
+      max_p = std::max(max_p, P); max_m = std::max(max_m, M);
+      max_chunks = std::max(max_chunks, fwd2_chunks(n));
+      max_dpc = std::max(max_dpc, dp_chunks((n.MT + 3) / 4, n.PT));
+    }
+    if (max_p == 0) continue;
+    const unsigned z = (unsigned)cnt;
+    const int64_t PT = (max_p + 31) / 32, MT = (max_m + 31) / 32;
+    const auto blocks = [](int64_t n, int64_t per) { return (unsigned)((n + per - 1) / per); };
+    hipLaunchKernelGGL(pad_codes_batched, dim3(blocks(MT * 32, 256), 1, z), dim3(256), 0, s, b, 0);
+    if (!backward) {
+      // pixels x 2^3, prototypes x kappa * log2(e) * 2^-3, unscaled residuals (nll_fwd2)
+      hipLaunchKernelGGL(prep_std_batched<true>, dim3(blocks(PT * KS, 4), 1, z), dim3(256), 0, s, b, 1, 8.0f);
+      hipLaunchKernelGGL(prep_std_batched<true>, dim3(blocks(MT * KS, 4), 1, z), dim3(256), 0, s, b, 0,
+                         a.kappa_log2e * 0.125f);
+      const dim3 grid(blocks(PT, 8), (unsigned)max_chunks, z);
+      if (tag) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_fwd2_batched<KS, 2, true>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS_F);
+        hipLaunchKernelGGL((nll_fwd2_batched<KS, 2, true>), grid, dim3(256), LDS_F, s, b);
+      } else {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_fwd2_batched<KS, 2, false>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS_F);
+        hipLaunchKernelGGL((nll_fwd2_batched<KS, 2, false>), grid, dim3(256), LDS_F, s, b);
+      }
+      hipLaunchKernelGGL(nll_finalize_batched, dim3(blocks(max_p, 256), 1, z), dim3(256), 0, s, b);
+      continue;
+    }
+    hipLaunchKernelGGL((prep_std_batched<false>), dim3(blocks(PT * KS, 4), 1, z), dim3(256), 0, s, b, 1, 1.0f);
+    hipLaunchKernelGGL((prep_std_batched<false>), dim3(blocks(MT * KS, 4), 1, z), dim3(256), 0, s, b, 0, a.kappa_log2e);
+    hipLaunchKernelGGL(max_abs_pow2_batched, dim3(1, 1, z), dim3(1024), 0, s, b);
+    {
+      const int64_t lo = p_off[g0], np = p_off[g0 + cnt] - lo;   // kappa g_p: one pass over the launch's pixels
+      hipLaunchKernelGGL(rowscale_kernel, dim3(blocks(np, 256)), dim3(256), 0, s, d_nll + lo, kappa, np,
+                         b.rowscale + lo);
+    }
+    hipLaunchKernelGGL(prep_T_batched, dim3(blocks(MT * DT * 2, 4), 1, z), dim3(256), 0, s, b, 0);
+    hipLaunchKernelGGL(prep_T_batched, dim3(blocks(PT * DT * 2, 4), 1, z), dim3(256), 0, s, b, 1);
+    hipLaunchKernelGGL(pad_codes_batched, dim3(blocks(PT * 32, 256), 1, z), dim3(256), 0, s, b, 1);
+    if (tag) hipLaunchKernelGGL(coef_batched<true>, dim3(blocks(PT * 32, 256), 1, z), dim3(256), 0, s, b);
+    else hipLaunchKernelGGL(coef_batched<false>, dim3(blocks(PT * 32, 256), 1, z), dim3(256), 0, s, b);
+    const dim3 grid_de(blocks(PT, 4), 1, z), grid_dp(blocks(MT, 4), (unsigned)max_dpc, z);
+    if (tag) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_bwd_de_batched<KS, DT, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, a.depth * SLOT_DE);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_bwd_dp_batched<KS, DT, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, a.depth * SLOT_DP);
+      hipLaunchKernelGGL((nll_bwd_de_batched<KS, DT, true>), grid_de, dim3(256), a.depth * SLOT_DE, s, b);
+      hipLaunchKernelGGL((nll_bwd_dp_batched<KS, DT, true>), grid_dp, dim3(256), a.depth * SLOT_DP, s, b);
+    } else {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_bwd_de_batched<KS, DT, false>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, a.depth * SLOT_DE);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_bwd_dp_batched<KS, DT, false>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, a.depth * SLOT_DP);
+      hipLaunchKernelGGL((nll_bwd_de_batched<KS, DT, false>), grid_de, dim3(256), a.depth * SLOT_DE, s, b);
+      hipLaunchKernelGGL((nll_bwd_dp_batched<KS, DT, false>), grid_dp, dim3(256), a.depth * SLOT_DP, s, b);
+    }
+    if (a.d_protos64)
+      hipLaunchKernelGGL(nll_dpr_from_fix_batched, dim3(blocks(max_m * D, 256), 1, z), dim3(256), 0, s, b);
+  }
+  return launch_status();
 }
 
 }  // namespace
@@ -1483,11 +1849,7 @@ static int nll_common(bool backward, const float* emb, const int64_t* own,
   const int64_t mg = m_grad < 0 || m_grad > M ? M : m_grad;
   a.mt_grad = (mg + 31) / 32;
   const int64_t mgroups = (a.mt_grad + 3) / 4;
-  // pixel chunks so that the grid has a few thousand workgroups
-  int64_t chunks = mgroups > 0 ? (2048 + mgroups - 1) / mgroups : 1;
-  if (chunks > (n.PT + 7) / 8) chunks = (n.PT + 7) / 8;
-  if (chunks < 1) chunks = 1;
-  if (chunks > 65535) chunks = 65535;
+  const int64_t chunks = dp_chunks(mgroups, n.PT);
   a.chunks = (int)chunks;
   a.spt0 = 0;
   a.spt1 = n.PT;
@@ -1641,4 +2003,30 @@ extern "C" int spml_segsort_nll_bwd_f32(const float* emb, const int64_t* own,
   return nll_common(true, emb, own, px_code, P, protos, pr_code, M, D, kappa, mode, nullptr,
                     const_cast<float*>(stats), d_nll, d_emb, d_protos, m_grad, ws, ws_bytes,
                     (hipStream_t)stream);
+}
+
+extern "C" int spml_segsort_nll_batched_supported(int D, int mode) { return batched_supported(D, mode) ? 1 : 0; }
+
+extern "C" size_t spml_segsort_nll_batched_workspace_bytes(int n_problems, const int64_t* p_off,
+                                                           const int64_t* m_off, int D) {
+  NllBatchTotals t;
+  if (!batch_totals(n_problems, p_off, m_off, D, t) || ks_bucket((D + 15) / 16) != 5) return 0;
+  return nll_batch_ws(t, n_problems, D, 5, 3).total;
+}
+
+extern "C" int spml_segsort_nll_batched_fwd_f32(const float* emb, const int64_t* own, const int64_t* px_code,
+                                                const int64_t* p_off, const float* protos, const int64_t* pr_code,
+                                                const int64_t* m_off, int n_problems, int D, float kappa, int mode,
+                                                float* nll, float* stats, void* ws, size_t ws_bytes, void* stream) {
+  return nll_batched(false, emb, own, px_code, p_off, protos, pr_code, m_off, n_problems, D, kappa, mode, nll, stats,
+                     nullptr, nullptr, nullptr, ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int spml_segsort_nll_batched_bwd_f32(const float* emb, const int64_t* own, const int64_t* px_code,
+                                                const int64_t* p_off, const float* protos, const int64_t* pr_code,
+                                                const int64_t* m_off, int n_problems, int D, float kappa, int mode,
+                                                const float* stats, const float* d_nll, float* d_emb, float* d_protos,
+                                                void* ws, size_t ws_bytes, void* stream) {
+  return nll_batched(true, emb, own, px_code, p_off, protos, pr_code, m_off, n_problems, D, kappa, mode, nullptr,
+                     const_cast<float*>(stats), d_nll, d_emb, d_protos, ws, ws_bytes, (hipStream_t)stream);
 }

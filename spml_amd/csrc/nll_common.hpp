@@ -90,6 +90,7 @@ struct NllArgs {
   float* partial;              // nll_fwd2: per-chunk partial sums [chunks][PT*32][4]
   int skip_de;                 // the v2 dE kernel has already run
   float* partial_de;           // nll_bwd_de2: [gridDim.y][PT][DT][16][64] accumulator-layout partial gradients
+  int64_t own_base;            // batched calls: `own` counts from this prototype of the concatenation (else 0)
 };
 
 // d_protos[idx] += v.  Deterministic mode: v / gscale (a power of two: exact) joins a 64-bit fixed-point sum instead

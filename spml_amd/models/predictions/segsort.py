@@ -163,7 +163,7 @@ class Segsort(nn.Module):
                                                   with_uniq=False, padded=True)
       # distinct pairs of the images up to and including b = position of (b + 1) * stride among the sorted keys
       bounds = torch.arange(1, n_img + 1, device=uniq.device) * stride
-      sim = (sizes, off, uniq, pair, torch.searchsorted(uniq, bounds) - 1)
+      sim = (sizes, off, uniq, pair, torch.searchsorted(uniq, bounds) - 1, img_of_px)
     last = None
 
     if self.sem_ann_loss is not None or self.sem_occ_loss is not None:
@@ -208,7 +208,7 @@ class Segsort(nn.Module):
       acc = parallel.sharded_retrieval_accuracy(segsort_eval.top_k_ranking, protos, p_sem, 5)
 
     if sim is not None:
-      sizes, off, uniq, pair, last_dev = sim
+      sizes, off, uniq, pair, last_dev, img_of_px = sim
       emb = datas[self.img_sim_embedding_key]
       ins = datas['cluster_instance_label']
       if last is None:
@@ -220,47 +220,65 @@ class Segsort(nn.Module):
       # prototype is normalised on its own), split per image: 1 launch forward + 1 backward instead of 16 + 16
       # (SPML_IMG_SIM_BATCHED_PROTOS=0: one call per image); the pixel rows are split the same way (one concatenation
       # in the backward pass instead of 16 zero-filled [P, D] gradients that are then added up)
-      pr_all = e_all = None
+      pr_all = e_all = nll_all = None
       if os.environ.get('SPML_IMG_SIM_BATCHED_PROTOS') != '0' and sum(sizes) == int(emb.shape[0]):
         counts = [end + 1 - (last[i - 1] + 1 if i else 0) for i, end in enumerate(last)]
-        pr_all = torch.split(segsort_common.calculate_prototypes_from_labels(emb, pair, last[-1] + 1), counts)
-        e_all = torch.split(emb, sizes)
-      # the images' terms are independent and each is a handful of launch-latency-bound kernels (16 900 pixels x ~150
-      # prototypes: 340 us of GPU time per image, forward + backward, on a chip it cannot fill): they are spread over
-      # SPML_IMG_SIM_STREAMS side streams (default 4; the backward of an op runs on its forward's stream)
-      streams = _side_streams(emb.device, int(os.environ.get('SPML_IMG_SIM_STREAMS', '4'))) if emb.is_cuda else []
-      cur = torch.cuda.current_stream(emb.device) if streams else None
-      for st in streams:
-        st.wait_stream(cur)
-      for i, (n_px, end) in enumerate(zip(sizes, last)):
-        lab, c_abs, first_i = ins[lo:lo + n_px], pair[lo:lo + n_px], first        # (views: no launch)
-        e = e_all[i] if e_all is not None else emb[lo:lo + n_px]
-        p_lab = pair_lab[first:end + 1]
-        lo, first = lo + n_px, end + 1
-        if streams:
-          side = streams[i % len(streams)]
-          # (allocated on the current stream, consumed on the side stream -- forward and, through the saved tensors,
-          # backward: tell the caching allocator, so that a block freed host-side while a side-stream kernel still
-          # reads it is not handed out again early)
-          if os.environ.get('SPML_IMG_SIM_RECORD_STREAM') != '0':
-            for t_ in (e, lab, c_abs, p_lab) + ((pr_all[i],) if pr_all is not None else ()):
-              t_.record_stream(side)
-          with torch.cuda.stream(side):
-            c = c_abs - first_i                                # (on the side stream: everything it reads was
-            #                                                    produced before the streams were forked)
-            pr_img = pr_all[i] if pr_all is not None else \
-                segsort_common.calculate_prototypes_from_labels(e, c, p_lab.shape[0])
-            term = self.img_sim_loss(e, lab, c, pr_img, p_lab, codes32=True)   # over-segmentation ids
-            term.record_stream(cur)
-          terms.append(term)
-          continue
-        c = c_abs - first_i
-        pr_img = pr_all[i] if pr_all is not None else \
-            segsort_common.calculate_prototypes_from_labels(e, c, p_lab.shape[0])
-        terms.append(self.img_sim_loss(e, lab, c, pr_img, p_lab, codes32=True))   # over-segmentation ids
-      for st in streams:
-        cur.wait_stream(st)
-      img_sim = sum(terms) / len(terms) * self.img_sim_loss_weight
+        protos_all = segsort_common.calculate_prototypes_from_labels(emb, pair, last[-1] + 1)
+        # ALL images' terms from one forward and one backward call of the library (the image is the grid's z
+        # coordinate of every kernel: ops.segsort_nll_batched) instead of 16 x ~17 launches on side streams;
+        # SPML_IMG_SIM_BATCHED=0, an explicit SPML_IMG_SIM_STREAMS, or a shape the batched kernels do not cover:
+        # the loop below.  `pair` is the own-prototype index into the concatenated prototypes as it stands.
+        nll_all = self.img_sim_loss.batched_nll(emb, ins, pair, sizes, protos_all, pair_lab, counts) \
+            if (emb.is_cuda and os.environ.get('SPML_IMG_SIM_BATCHED') != '0' and
+                'SPML_IMG_SIM_STREAMS' not in os.environ) else None
+        if nll_all is None:
+          pr_all = torch.split(protos_all, counts)
+          e_all = torch.split(emb, sizes)
+      if nll_all is not None:
+        # sum_i mean(nll_i) / n_img: every pixel divided by its image's pixel count, one sum (the divisions in
+        # the order of the looped form, so that the upstream gradient of a pixel has the same bits).  The counts
+        # are formed on the device from the pixels' image index (sums of ones: exact in fp32, whatever their
+        # order): no host-to-device copy, which from pageable memory would make the host wait for the stream
+        n_px = torch.zeros(len(sizes), dtype=torch.float32, device=emb.device)
+        n_px.index_add_(0, img_of_px, torch.ones_like(nll_all))
+        img_sim = (nll_all / n_px[img_of_px]).sum() / len(sizes) * self.img_sim_loss_weight
+      else:
+        # the images' terms are independent and each is a handful of launch-latency-bound kernels (16 900 pixels x ~150
+        # prototypes: 340 us of GPU time per image, forward + backward, on a chip it cannot fill): they are spread over
+        # SPML_IMG_SIM_STREAMS side streams (default 4; the backward of an op runs on its forward's stream)
+        streams = _side_streams(emb.device, int(os.environ.get('SPML_IMG_SIM_STREAMS', '4'))) if emb.is_cuda else []
+        cur = torch.cuda.current_stream(emb.device) if streams else None
+        for st in streams:
+          st.wait_stream(cur)
+        for i, (n_px, end) in enumerate(zip(sizes, last)):
+          lab, c_abs, first_i = ins[lo:lo + n_px], pair[lo:lo + n_px], first        # (views: no launch)
+          e = e_all[i] if e_all is not None else emb[lo:lo + n_px]
+          p_lab = pair_lab[first:end + 1]
+          lo, first = lo + n_px, end + 1
+          if streams:
+            side = streams[i % len(streams)]
+            # (allocated on the current stream, consumed on the side stream -- forward and, through the saved tensors,
+            # backward: tell the caching allocator, so that a block freed host-side while a side-stream kernel still
+            # reads it is not handed out again early)
+            if os.environ.get('SPML_IMG_SIM_RECORD_STREAM') != '0':
+              for t_ in (e, lab, c_abs, p_lab) + ((pr_all[i],) if pr_all is not None else ()):
+                t_.record_stream(side)
+            with torch.cuda.stream(side):
+              c = c_abs - first_i                                # (on the side stream: everything it reads was
+              #                                                    produced before the streams were forked)
+              pr_img = pr_all[i] if pr_all is not None else \
+                  segsort_common.calculate_prototypes_from_labels(e, c, p_lab.shape[0])
+              term = self.img_sim_loss(e, lab, c, pr_img, p_lab, codes32=True)   # over-segmentation ids
+              term.record_stream(cur)
+            terms.append(term)
+            continue
+          c = c_abs - first_i
+          pr_img = pr_all[i] if pr_all is not None else \
+              segsort_common.calculate_prototypes_from_labels(e, c, p_lab.shape[0])
+          terms.append(self.img_sim_loss(e, lab, c, pr_img, p_lab, codes32=True))   # over-segmentation ids
+        for st in streams:
+          cur.wait_stream(st)
+        img_sim = sum(terms) / len(terms) * self.img_sim_loss_weight
 
     return sem_ann, sem_occ, img_sim, acc
 

@@ -126,6 +126,49 @@ def segsort_nll(emb, own, px_code, protos, pr_code, kappa, mode=NLL_LABEL, proto
   return _SegSortNLL.apply(emb, own, px_code, protos, pr_code, float(kappa), int(mode), m_grad)
 
 
+class _SegSortNLLBatched(torch.autograd.Function):
+
+  @staticmethod
+  def forward(ctx, emb, own_abs, px_code, protos, pr_code, p_sizes, m_sizes, kappa, mode):
+    emb, protos = _f32c(emb), _f32c(protos)
+    own_abs, px_code, pr_code = _i64c(own_abs), _i64c(px_code), _i64c(pr_code)
+    nll, stats = _ffi.segsort_nll_batched_fwd(emb, own_abs, px_code, p_sizes, protos, pr_code, m_sizes, kappa, mode)
+    ctx.save_for_backward(emb, own_abs, px_code, protos, pr_code, stats)
+    ctx.p_sizes, ctx.m_sizes, ctx.kappa, ctx.mode = p_sizes, m_sizes, kappa, mode
+    return nll
+
+  @staticmethod
+  def backward(ctx, d_nll):
+    emb, own_abs, px_code, protos, pr_code, stats = ctx.saved_tensors
+    d_emb, d_protos = _ffi.segsort_nll_batched_bwd(emb, own_abs, px_code, ctx.p_sizes, protos, pr_code, ctx.m_sizes,
+                                                   ctx.kappa, ctx.mode, stats, _f32c(d_nll))
+    return d_emb, None, None, d_protos, None, None, None, None, None
+
+
+def segsort_nll_batched_supported(d, mode):
+  """True when `segsort_nll_batched` runs this embedding width and mode on the batched kernels."""
+  return _ffi.segsort_nll_batched_supported(d, mode)
+
+
+def segsort_nll_batched(emb, own_abs, px_code, p_sizes, protos, pr_code, m_sizes, kappa, mode=NLL_LABEL):
+  """A9/A10 over independent problems laid out one after the other: problem i owns `p_sizes[i]` consecutive rows of
+  `emb` / `own_abs` / `px_code` and `m_sizes[i]` consecutive rows of `protos` / `pr_code`; `own_abs` indexes the
+  concatenated prototypes.  -> nll [sum P], one forward and one backward call of the library for all problems.
+  Shapes the batched kernels do not cover run one `segsort_nll` per problem (same values)."""
+  p_sizes, m_sizes = [int(v) for v in p_sizes], [int(v) for v in m_sizes]
+  if emb.shape[0] == 0:
+    return emb.new_zeros((0,))
+  if segsort_nll_batched_supported(emb.shape[1], mode):
+    return _SegSortNLLBatched.apply(emb, own_abs, px_code, protos, pr_code, tuple(p_sizes), tuple(m_sizes),
+                                    float(kappa), int(mode))
+  out, lo, first = [], 0, 0
+  for n_px, n_pr in zip(p_sizes, m_sizes):
+    out.append(segsort_nll(emb[lo:lo + n_px], own_abs[lo:lo + n_px] - first, px_code[lo:lo + n_px],
+                           protos[first:first + n_pr], pr_code[first:first + n_pr], kappa, mode))
+    lo, first = lo + n_px, first + n_pr
+  return torch.cat(out)
+
+
 # ---------------------------------------------------------------------------
 def kmeans(x, seg_offsets, max_seg_len, k, labels_init, iterations, want_centroids=False):
   """A6 over a ragged batch (no gradient: labels are discrete)."""
