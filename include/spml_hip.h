@@ -48,7 +48,7 @@ const char* spml_status_string(int status);
  * 6: the pseudo-label entry points (spml_resample_unit_f32 .. spml_upsample_argmax_i64);
  * 7: the multi-scale inference entry point (spml_view_probs_accumulate_f32);
  * 8: spml_upsample_ce_bwd_path_name (entry points added since leave every earlier signature and flag as it was and
- *    keep the version: spml_view_votes_*, spml_segsort_nll_batched_*). */
+ *    keep the version: spml_view_votes_*, spml_segsort_nll_batched_*, spml_segment_majority_*). */
 #define SPML_ABI_VERSION 8
 int spml_abi_version(void);
 
@@ -928,6 +928,32 @@ int spml_view_probs_accumulate_f32(const float* canvas, int ncls, int Hp, int Wp
 size_t spml_view_votes_workspace_bytes(int m, int ncls);
 int spml_view_votes_accumulate_f32(const int64_t* clu, int rh, int rw, const int64_t* topk, int m, int k, int ncls,
                                    int flip, int h, int w, float* acc, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * N10  memory-bank generation: the majority label per segment (csrc/segment_majority.hip)
+ * replaces: the labels of spml/utils/segsort/common.py:221-267 as pyscripts/inference/prototype.py:200-203 and
+ *           prototype_msc.py:189-192 call it (a [P, ncls] int64 one-hot scatter-added by the segment id, arg-max per row).
+ *
+ *   count[s][c] = #{ p < P : clu[p] = s, sem[p] = c }          major[s] = argmax_c count[s][c]
+ *
+ * clu, sem: int64 [P], the dense segment id and the class of every pixel.  A pixel whose id is outside [0, m) or whose
+ * class is outside [0, ncls) counts nowhere and forms no address.  Ties go to the lowest class (torch.argmax's rule on the
+ * CPU); a row without a counted pixel gives 0.  major: int64 [m].  hist: int64 [m][ncls], the counts, or NULL.
+ * ws: 4-byte aligned, at least spml_segment_majority_workspace_bytes(m, ncls) bytes (that call returns 0 outside the
+ * limits), else SPML_ERR_WORKSPACE; the call zeroes it on `stream` itself, its previous content does not matter.
+ * Counts meet through 32-bit integer atomics only (P < 2^31 bounds every bin): the result does not depend on the arrival
+ * order and is bit-identical from run to run, with and without the deterministic mode.  No host read, three stream
+ * operations (memset, count, arg-max).  ws, major and hist may alias neither an input nor each other
+ * (SPML_ERR_INVALID_ARG, as for a null pointer, P < 0, m < 1 or ncls < 1); m <= 4096, ncls <= 256 and P < 2^31, else
+ * SPML_ERR_UNSUPPORTED.  spml_segment_majority_path_name: which count kernel a shape takes -- "lds_table" (m * ncls <=
+ * 8192: a per-workgroup LDS table flushed once) or "global_table" (global atomics), "unsupported" outside the limits,
+ * "invalid" for a size below the domain.  In both kernels equal keys are merged inside a wave before the atomic; a
+ * library built with SPML_MAJORITY_WAVE_COMBINE=0 (one atomic per counted pixel: the other side of the A/B of
+ * tools/bench_prototype_msc.py) appends "_per_pixel_atomics". */
+size_t spml_segment_majority_workspace_bytes(int m, int ncls);
+int spml_segment_majority_i64(const int64_t* clu, const int64_t* sem, int64_t P, int m, int ncls, int64_t* major,
+                              int64_t* hist, void* ws, size_t ws_bytes, void* stream);
+const char* spml_segment_majority_path_name(int64_t P, int m, int ncls);
 
 #ifdef __cplusplus
 }

@@ -110,5 +110,24 @@ def build(force=False, verbose=True):
   return LIB_PATH
 
 
+def build_variant(source, defines, name, verbose=True):
+  """One source of csrc/ that stands alone (it calls nothing of the other sources), compiled with extra `-D` flags into
+  spml_amd/lib/lib<name>.so: the other side of a timed A/B (tools/bench_prototype_msc.py loads it next to the product
+  library).  A no-op when that file is newer than the sources."""
+  src = os.path.join(CSRC, source)
+  out = os.path.join(LIB_DIR, 'lib%s.so' % name)
+  deps = [src] + [p for p in _deps() if not p.endswith('.hip')]
+  if os.path.exists(out) and all(os.path.getmtime(p) <= os.path.getmtime(out) for p in deps):
+    return out
+  os.makedirs(LIB_DIR, exist_ok=True)
+  cmd = [_hipcc()] + FLAGS + ['-D' + d for d in defines] + ['-DSPML_BUILD_EXPERIMENT=0', '-shared', src, '-o', out]
+  if verbose:
+    print('[spml_amd] hipcc', source, ' '.join(defines), flush=True)
+  r = subprocess.run(cmd, capture_output=True, text=True)
+  if r.returncode != 0:
+    raise RuntimeError('hipcc failed for %s:\n%s' % (src, r.stderr[-4000:]))
+  return out
+
+
 if __name__ == '__main__':
   build(force='--force' in sys.argv)

@@ -147,6 +147,9 @@ _SIGNATURES = {
     'spml_view_votes_workspace_bytes': (c_size_t, [c_int, c_int]),
     'spml_view_votes_accumulate_f32': (c_int, [_P, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P,
                                                c_size_t, _P]),
+    'spml_segment_majority_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'spml_segment_majority_i64': (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    'spml_segment_majority_path_name': (c_char_p, [c_int64, c_int, c_int]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -805,6 +808,42 @@ def view_votes_accumulate(clu, crop_hw, topk, ncls, flip, acc):
       acc.shape[1], acc.shape[2], ptr(acc, torch.float32), ptr(ws), ws.numel(), stream_ptr()),
         'spml_view_votes_accumulate_f32')
   return acc
+
+
+# ---------------------------------------------------------------------------
+# memory-bank generation: majority label per segment (csrc/segment_majority.hip)
+MAX_MAJORITY_SEGMENTS = 4096           # the limits of spml_segment_majority_i64 (include/spml_hip.h)
+MAX_MAJORITY_CLASSES = 256
+
+
+def segment_majority_path_name(p, m, ncls):
+  """Count kernel a call with these sizes takes (a pure function of the library): 'lds_table' or 'global_table'."""
+  return lib().spml_segment_majority_path_name(int(p), int(m), int(ncls)).decode()
+
+
+def segment_majority(clu, sem, m, ncls, want_hist=False):
+  """major int64 `[m]`: the most frequent class of `sem` among the pixels of every segment of `clu` (both int64, one
+  entry per pixel, any shape; made contiguous here), ties to the lowest class, 0 for a segment without a counted pixel
+  (segsort/common.py:221-267 without the list of agreeing pixels).  An id outside `[0, m)` or a class outside
+  `[0, ncls)` counts nowhere.  No host read.  want_hist: -> (major, hist int64 `[m, ncls]`), the counts."""
+  clu, sem = clu.reshape(-1), sem.reshape(-1)
+  if clu.numel() != sem.numel():
+    raise SpmlHipError('segment_majority: %d segment ids for %d labels' % (clu.numel(), sem.numel()))
+  for name, t in (('clu', clu), ('sem', sem)):
+    if t.dtype != torch.int64:
+      raise SpmlHipError('segment_majority: %s must be int64 (got %s)' % (name, t.dtype))
+  clu, sem = clu.contiguous(), sem.contiguous()
+  p, m, ncls = clu.numel(), int(m), int(ncls)
+  if m < 1 or ncls < 1:
+    raise SpmlHipError('segment_majority: needs at least one segment and one class (got %d, %d)' % (m, ncls))
+  ptr(clu), ptr(sem)                                         # (CPU tensors are refused before anything is allocated)
+  major = torch.empty((m,), dtype=torch.int64, device=clu.device)
+  hist = torch.empty((m, ncls), dtype=torch.int64, device=clu.device) if want_hist else None
+  ws = workspace(lib().spml_segment_majority_workspace_bytes(m, ncls), clu.device)
+  check(lib().spml_segment_majority_i64(ptr(clu, torch.int64), ptr(sem, torch.int64), p, m, ncls,
+                                        ptr(major), ptr(hist, None, True), ptr(ws), ws.numel(), stream_ptr()),
+        'spml_segment_majority_i64')
+  return (major, hist) if want_hist else major
 
 
 def affinity_transition(emb, scale=5.0, power=20):

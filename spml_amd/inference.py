@@ -78,6 +78,75 @@ def full_resolution_prototypes(embedding_model, image, semantic_label, crop_size
   return prototypes, prototype_labels, out['cluster_index'].view(h, w)
 
 
+def label_views(label, view_sizes):
+  """The label half of `create_image_pyramid` (spml/utils/general/others.py): the label map `[h,w]` resized by nearest
+  neighbour to each `(rh, rw)` of `view_sizes` -- the second entries of `flip_scale_views`' views, so that the image and
+  the label of a view always have one size.  -> list of int64 `[rh, rw]` maps on the label's device.  A host-side
+  stand-in for the loader (cv2's INTER_NEAREST there, torch's `nearest` here): not parity-pinned; for views that
+  `flip_scale_views` mirrored the caller mirrors the label too (the memory-bank pass makes none)."""
+  label = torch.as_tensor(label)
+  if label.dim() != 2:
+    raise ValueError('label_views expects one label map [h,w]')
+  out = []
+  for rh, rw in view_sizes:
+    if (int(rh), int(rw)) == tuple(label.shape):
+      out.append(label.long())
+    else:
+      # (through float, as general/common.py:11-26 resizes labels: exact for values below 2^24)
+      resized = torch.nn.functional.interpolate(label[None, None].float(), size=(int(rh), int(rw)), mode='nearest')
+      out.append(resized[0, 0].long())
+  return out
+
+
+def multiscale_prototypes(embedding_model, views, label_views, crop_size, stride, semantic_ignore_index=255,
+                          num_classes=256):
+  """One image of the multi-scale memory-bank pass (`pyscripts/inference/prototype_msc.py:92-206`; with one view,
+  `prototype.py:92-211`).  `views`: list of `(image [1,3,Hp,Wp], (rh, rw), is_flip)` (`flip_scale_views` with scales
+  0.5, 1, 1.5 and no flip there); `label_views`: the semantic label `[rh, rw]` of every view (`label_views`; a mirrored
+  view takes a mirrored label).
+
+  Per view: fake labels that make the clustering ignore the zero padding (:109-120), `embed_full_resolution` (:126-173),
+  `generate_clusters` (:176-183), `calculate_prototypes_from_labels` (:186-188) and -- in the place of
+  `find_majority_label_index` (:189-192) -- `segment_majority_labels` with the segment count taken from the prototype
+  rows and `num_classes` classes (256: label maps hold the ignore label 255; such prototypes stay in the bank files, the
+  retrieval side drops them: `drop_ignored_memory`): one HIP count + arg-max, no host read.  The views' prototypes and
+  labels are concatenated in view order (:204-206).  Returns a dict: `prototype` `[sum M, C]`, `prototype_label`
+  `[sum M]` int64, `segment_counts` (list of M per view), `cluster_index` (list of `[rh * rw]` dense segment ids) and
+  `majority_path` (`'hip_majority'`, or `'framework_majority'` where a view is outside the kernel's limits)."""
+  if not views:
+    raise ValueError('multiscale_prototypes needs at least one view')
+  if len(label_views) != len(views):
+    raise ValueError('multiscale_prototypes needs one label map per view (%d for %d views)' % (len(label_views), len(views)))
+  for (image, (rh, rw), _), label in zip(views, label_views):
+    if image.dim() != 4 or image.shape[0] != 1:
+      raise ValueError('multiscale_prototypes expects views of one image [1,3,Hp,Wp]')
+    if tuple(label.shape[-2:]) != (rh, rw) or label.numel() != rh * rw:
+      raise ValueError('multiscale_prototypes: a %d x %d view with a label map of shape %r' % (rh, rw, tuple(label.shape)))
+    if not image.is_cuda:
+      raise _ffi.SpmlHipError('the HIP path needs GPU tensors (a view on %s); there is no CPU fallback' % image.device)
+  device = views[0][0].device
+  prototypes, labels, counts, cluster_index = [], [], [], []
+  majority_path = segsort_common.HIP_MAJORITY_PATH
+  with torch.no_grad():
+    for (image, (rh, rw), _), label in zip(views, label_views):
+      pad_h, pad_w = image.shape[-2:]
+      fake = torch.full((1, pad_h, pad_w), semantic_ignore_index, dtype=torch.long, device=device)
+      fake[:, :rh, :rw] = 0
+      embeddings = embed_full_resolution(embedding_model, image, crop_size, stride)
+      out = embedding_model.generate_clusters(embeddings, fake, fake)
+      protos = segsort_common.calculate_prototypes_from_labels(out['cluster_embedding'], out['cluster_index'])
+      major, path = segsort_common.segment_majority_labels(label.to(device), out['cluster_index'], protos.shape[0],
+                                                           num_classes)
+      if path != segsort_common.HIP_MAJORITY_PATH:
+        majority_path = path
+      prototypes.append(protos)
+      labels.append(major)
+      counts.append(int(protos.shape[0]))
+      cluster_index.append(out['cluster_index'])
+  return {'prototype': torch.cat(prototypes, 0), 'prototype_label': torch.cat(labels, 0), 'segment_counts': counts,
+          'cluster_index': cluster_index, 'majority_path': majority_path}
+
+
 def drop_ignored_memory(prototypes, prototype_labels, semantic_ignore_index=255):
   """The memory bank without the prototypes of the ignore class (inference.py:99-111)."""
   keep = torch.nonzero(prototype_labels != semantic_ignore_index).view(-1)

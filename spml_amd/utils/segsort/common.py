@@ -114,6 +114,31 @@ def find_majority_label_index(semantic_labels, cluster_labels):
   return keep, major
 
 
+HIP_MAJORITY_PATH = 'hip_majority'
+FRAMEWORK_MAJORITY_PATH = 'framework_majority'
+
+
+def segment_majority_labels(semantic_labels, cluster_labels, num_clusters, num_classes=256):
+  """The labels of `find_majority_label_index` alone (what prototype.py:200-203 / prototype_msc.py:189-192 keep of it):
+  the most frequent class among the pixels of each of the `num_clusters` segments, ties to the lowest class, 0 for a
+  segment without a pixel.  The sizes are arguments (the memory-bank pass has `num_clusters` from its prototype rows; a
+  label map holds values up to the ignore label 255), so nothing is read back to the host; a pixel whose id or class is
+  outside them counts nowhere.  -> (labels int64 `[num_clusters]`, path): one HIP count + arg-max
+  (`spml_segment_majority_i64`, `'hip_majority'`), or -- outside that kernel's limits -- the scatter-add formulation of
+  `find_majority_label_index` as framework ops on the tensors' device (`'framework_majority'`)."""
+  sem = semantic_labels.reshape(-1)
+  clu = cluster_labels.reshape(-1)
+  m, ncls = int(num_clusters), int(num_classes)
+  if m <= _ffi.MAX_MAJORITY_SEGMENTS and ncls <= _ffi.MAX_MAJORITY_CLASSES and sem.numel() < 2 ** 31:
+    return _ffi.segment_majority(clu.long(), sem.long(), m, ncls), HIP_MAJORITY_PATH
+  if not sem.is_cuda:
+    raise _ffi.SpmlHipError('the HIP path needs GPU tensors (got %s); there is no CPU fallback' % sem.device)
+  valid = (clu >= 0) & (clu < m) & (sem >= 0) & (sem < ncls)
+  hist = torch.zeros((m * ncls,), dtype=torch.long, device=sem.device)
+  hist.index_add_(0, (clu * ncls + sem) * valid, valid.long())
+  return torch.argmax(hist.view(m, ncls), dim=1), FRAMEWORK_MAJORITY_PATH
+
+
 _grid_ids = BoundedCache(8)
 
 

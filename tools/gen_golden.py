@@ -302,6 +302,34 @@ def gen_n8(ref, out):
   assert size < 600 * 1024, 'n8_softmax_msc.npz is %d bytes' % size
 
 
+def cpu_shimmed_segment_by_kmeans(s_common):
+  """The CPU shim of main(): spml/utils/segsort/common.py:376 reads `tensor.device.index`, None on the CPU."""
+  src = inspect.getsource(s_common.segment_by_kmeans)
+  assert 'cur_cluster_indices.device.index' in src
+  ns = dict(s_common.__dict__)
+  exec(compile(src.replace('cur_cluster_indices.device.index', '(cur_cluster_indices.device.index or 0)'),
+               '<segment_by_kmeans+cpu-shim>', 'exec'), ns)
+  return ns['segment_by_kmeans']
+
+
+def stub_embedder_class(e_dl):
+  """A seeded convolution as `generate_embeddings` with the reference's own `generate_clusters` (N9, N10)."""
+  class StubEmbedder:
+    label_divisor = 2048
+    semantic_ignore_index = 255
+    kmeans_iterations = 10
+
+    def __init__(self, conv, clusters):
+      self.conv, self.kmeans_num_clusters = conv, clusters
+
+    def generate_embeddings(self, datas, targets=None, resize_as_input=False):
+      assert resize_as_input
+      return {'embedding': self.conv(datas['image']), 'local_feature': None}
+
+    generate_clusters = e_dl.ResnetDeeplab.generate_clusters
+  return StubEmbedder
+
+
 def gen_n9(ref, out):
   """N9: multi-scale + flip kNN inference.  pyscripts/inference/inference_msc.py:157-226 exec'd per view (window ends,
   per-crop normalise + overlap average, crop to the un-padded view, k-means, Segsort.predictions against a memory bank,
@@ -337,26 +365,8 @@ def gen_n9(ref, out):
   resize_src = ref_lines(msc_py, 230, 233)
   assert 'cv2.INTER_LINEAR' in resize_src and 'semantic_topk[:, ::-1]' in resize_src
 
-  # the CPU shim of main(): spml/utils/segsort/common.py:376 reads `tensor.device.index`, None on the CPU
-  src = inspect.getsource(s_common.segment_by_kmeans)
-  assert 'cur_cluster_indices.device.index' in src
-  ns = dict(s_common.__dict__)
-  exec(compile(src.replace('cur_cluster_indices.device.index', '(cur_cluster_indices.device.index or 0)'),
-               '<segment_by_kmeans+cpu-shim>', 'exec'), ns)
-
-  class StubEmbedder:
-    label_divisor = 2048
-    semantic_ignore_index = 255
-    kmeans_iterations = 10
-
-    def __init__(self, conv, clusters):
-      self.conv, self.kmeans_num_clusters = conv, clusters
-
-    def generate_embeddings(self, datas, targets=None, resize_as_input=False):
-      assert resize_as_input
-      return {'embedding': self.conv(datas['image']), 'local_feature': None}
-
-    generate_clusters = e_dl.ResnetDeeplab.generate_clusters
+  ns = {'segment_by_kmeans': cpu_shimmed_segment_by_kmeans(s_common)}
+  StubEmbedder = stub_embedder_class(e_dl)
 
   store = {}
   # (seed, C, classes, image, crop, stride, scales, k-means grid, bank size).  (a) one scale, a flip pair, no padding;
@@ -463,6 +473,128 @@ def gen_n9(ref, out):
   assert size < 600 * 1024, 'n9_knn_msc.npz is %d bytes' % size
 
 
+def gen_n10(ref, out):
+  """N10: multi-scale memory-bank generation.  pyscripts/inference/prototype_msc.py:126-197 exec'd per view (window
+  ends, per-crop normalise + overlap average, k-means that ignores the padding, `calculate_prototypes_from_labels`,
+  `find_majority_label_index`, the append to `prototype_results`) and :204-206 once (the concatenation), from the
+  reference's own lines on seeded CPU inputs, with the arrangement of N9: a seeded 5x5 convolution as
+  `generate_embeddings` and the reference's own `generate_clusters` on the CPU-shimmed segment_by_kmeans.  The views are
+  those of `create_image_pyramid(scales=[0.5, 1, 1.5], is_flip=False)` (:92-95) restated with torch (cv2 is not
+  installed): images bilinear, labels `nearest` -- what `spml_amd.inference.flip_scale_views` / `label_views` make.
+  Stored per view: the label view (uint8), the embedding over the un-padded region, `cluster_index` (int16), prototypes
+  and labels; once: the image and the concatenated bank.  The scaled images are NOT stored (with them the file is 948 KB,
+  more than any other N fixture): a test rebuilds them from the image with the same CPU `F.interpolate` call
+  (`flip_scale_views`), and the stored embedding of every view pins the result.  The reference's tie order on a GPU is unspecified
+  (scatter_add_ + argmax): a seed is taken only if in every segment of every view the top-1 and top-2 class counts
+  differ (asserted here)."""
+  import linecache
+  import math
+  import textwrap
+  import spml.models.embeddings.resnet_deeplab as e_dl
+  import spml.utils.general.common as g_common
+  import spml.utils.segsort.common as s_common
+  F = torch.nn.functional
+
+  def ref_lines(path, first, last):
+    txt = ''.join(linecache.getline(path, i) for i in range(first, last + 1))
+    assert txt.strip(), path
+    return textwrap.dedent(txt).replace('.cuda()', '').replace('.to("cuda:0")', '')
+
+  msc_py = os.path.join(ref, 'pyscripts', 'inference', 'prototype_msc.py')
+  src_view, src_once = ref_lines(msc_py, 126, 197), ref_lines(msc_py, 204, 206)
+  assert src_view.lstrip().startswith('# Create the ending index of each patch.') and 'cuda' not in src_view
+  assert 'patch_ind_h' in src_view and 'embeddings[k] /= counts' in src_view and 'generate_clusters' in src_view
+  assert 'segsort_common.calculate_prototypes_from_labels(' in src_view
+  assert 'segsort_common.find_majority_label_index(' in src_view and "label_batch['semantic_label']" in src_view
+  assert src_view.rstrip().endswith("prototype_results['prototype_label'].append(prototype_labels)")
+  assert 'np.concatenate(v, axis=0)' in src_once and 'prototype_results[k] = v' in src_once
+  pyramid = ref_lines(msc_py, 92, 95)
+  assert 'scales=[0.5, 1, 1.5]' in pyramid and 'is_flip=False' in pyramid
+  scales = (0.5, 1, 1.5)
+
+  shimmed = cpu_shimmed_segment_by_kmeans(s_common)
+  StubEmbedder = stub_embedder_class(e_dl)
+  store = {}
+  # (seed, C, classes, image, crop, stride, k-means grid, label cells, share of 255 cells).  Case 0: the views are
+  # 22 x 30 (padded to the crop, one window), 44 x 60 (1 x 2 windows) and 66 x 90 (2 x 3 windows).  Case 1: label cells
+  # hold the ignore value 255, so the class count of the bank pass is 256 and some prototypes carry 255.
+  cases = [(2000, 16, 5, (44, 60), (48, 48), (32, 32), (3, 3), 4, 0.0),
+           (2010, 8, 5, (40, 52), (48, 48), (32, 32), (5, 4), 4, 0.25)]
+  orig = e_dl.segsort_common.segment_by_kmeans
+  e_dl.segsort_common.segment_by_kmeans = shimmed
+  try:
+    for ci, (seed, c, ncls, image_hw, crop, stride, grid, cells, ignored) in enumerate(cases):
+      gen = torch.Generator().manual_seed(seed)
+      torch.manual_seed(seed)
+      image_h, image_w = image_hw
+      conv = torch.nn.Conv2d(3, c, 5, padding=2)
+      base = torch.randn(1, 3, image_h // 8 + 2, image_w // 8 + 2, generator=gen)
+      image = F.interpolate(base, size=image_hw, mode='bilinear', align_corners=False)
+      image = image + 0.05 * torch.randn(1, 3, image_h, image_w, generator=gen)
+      label = blocky_labels(gen, 1, image_h, image_w, cells, 0, ncls)[0]
+      if ignored:
+        drop = blocky_labels(gen, 1, image_h, image_w, cells, 0, 1000)[0] < int(1000 * ignored)
+        label = label.masked_fill(drop, 255)
+      cfg = AttrDict(dataset=AttrDict(semantic_ignore_index=255, num_classes=ncls),
+                     network=AttrDict(label_divisor=2048), test=AttrDict(stride=list(stride), crop_size=list(crop)))
+      t = 'c%d_' % ci
+      views, prototype_results = [], {'prototype': [], 'prototype_label': []}
+      for vi, scale in enumerate(scales):
+        size = (max(int(round(image_h * scale)), 1), max(int(round(image_w * scale)), 1))
+        scaled = image if scale == 1 else F.interpolate(image, size=size, mode='bilinear', align_corners=False)
+        rh, rw = scaled.shape[-2:]
+        lab = label if scale == 1 else F.interpolate(label[None, None].float(), size=(rh, rw), mode='nearest')[0, 0].long()
+        pad_h, pad_w = max(rh, crop[0]), max(rw, crop[1])
+        view = torch.zeros(1, 3, pad_h, pad_w)
+        view[:, :, :rh, :rw] = scaled
+        fake = torch.full((1, pad_h, pad_w), 255, dtype=torch.long)
+        fake[:, :rh, :rw] = 0                                 # :109-120
+        env = {'config': cfg, 'math': math, 'np': np, 'torch': torch, 'image_batch': {'image': view},
+               'pad_image_h': pad_h, 'pad_image_w': pad_w, 'embedding_model': StubEmbedder(conv, list(grid)),
+               'common_utils': g_common, 'segsort_common': s_common,
+               'fake_label_batch': {'semantic_label': fake, 'instance_label': fake.clone()},
+               'label_batch': {'semantic_label': lab.unsqueeze(0)}, 'prototype_results': prototype_results}
+        with torch.no_grad():
+          exec(compile(src_view, msc_py + ':126-197', 'exec'), env)
+        protos, plab = torch.from_numpy(env['prototypes']), torch.from_numpy(env['prototype_labels'])
+        clu = env['embeddings']['cluster_index']
+        m = protos.shape[0]
+        assert clu.shape[0] == rh * rw and int(clu.min()) == 0 and int(clu.max()) + 1 == m == plab.shape[0] <= 32767
+        assert protos.dtype == torch.float32 and plab.dtype == torch.int64
+        # the tie condition: top-1 and top-2 class counts of every segment differ
+        width = int(lab.max()) + 1
+        hist = torch.bincount(clu * width + lab.reshape(-1), minlength=m * width).view(m, width)
+        top2 = hist.topk(2, dim=1).values if width > 1 else torch.cat([hist, hist * 0 - 1], 1)
+        assert (top2[:, 0] > top2[:, 1]).all(), 'case %d view %d: a segment ties -- pick another seed' % (ci, vi)
+        assert torch.equal(hist.argmax(1), plab)
+        views.append([pad_h, pad_w, rh, rw, m])
+        store[t + 'label%d' % vi] = lab.to(torch.uint8)
+        store[t + 'embedding%d' % vi] = env['embeddings']['embedding'][..., :rh, :rw].contiguous()
+        store[t + 'cluster_index%d' % vi] = clu.to(torch.int16)
+        store[t + 'prototypes%d' % vi] = protos
+        store[t + 'prototype_labels%d' % vi] = plab.to(torch.uint8)
+      env = {'np': np, 'prototype_results': prototype_results}
+      exec(compile(src_once, msc_py + ':204-206', 'exec'), env)
+      bank, bank_lab = prototype_results['prototype'], prototype_results['prototype_label']
+      total = sum(v[4] for v in views)
+      assert bank.shape == (total, c) and bank.dtype == np.float32 and bank_lab.shape == (total,)
+      n_ignored = int((bank_lab == 255).sum())
+      print('n10 case %d (seed %d): views %s, %d prototypes, labels %s, %d with the ignore label'
+            % (ci, seed, [(v[2], v[3], v[4]) for v in views], total, np.unique(bank_lab).tolist(), n_ignored))
+      assert np.unique(bank_lab).size >= 3, 'case %d: fewer than 3 labels in the bank -- pick another seed' % ci
+      assert (n_ignored > 0) == bool(ignored) and n_ignored < total // 2, 'case %d: pick another seed' % ci
+      store.update({
+          t + 'conv_w': conv.weight, t + 'conv_b': conv.bias, t + 'views': np.array(views), t + 'image': image,
+          t + 'cfg': np.array([c, ncls, image_h, image_w, crop[0], crop[1], stride[0], stride[1], grid[0], grid[1]]),
+          t + 'bank': bank, t + 'bank_lab': bank_lab.astype(np.uint8)})
+  finally:
+    e_dl.segsort_common.segment_by_kmeans = orig
+  save(out, 'n10_prototype_msc', **store)
+  if ONLY is None or 'n10_prototype_msc' in ONLY:
+    size = os.path.getsize(os.path.join(out, 'n10_prototype_msc.npz'))
+    assert size < 880 * 1024, 'n10_prototype_msc.npz is %d bytes' % size      # (no larger than the largest N fixture)
+
+
 class AttrDict(dict):
   __getattr__ = dict.__getitem__
 
@@ -481,13 +613,15 @@ def main():
 
   sys.path.insert(0, args.ref)
   torch.set_num_threads(1)       # bit-stable fp32 sums
-  if ONLY is not None and ONLY <= {'n7_pseudo_labels', 'n8_softmax_msc', 'n9_knn_msc'}:      # (need none of the imports and shims below)
+  if ONLY is not None and ONLY <= {'n7_pseudo_labels', 'n8_softmax_msc', 'n9_knn_msc', 'n10_prototype_msc'}:      # (need none of the imports and shims below)
     if 'n7_pseudo_labels' in ONLY:
       gen_n7(args.ref, out)
     if 'n8_softmax_msc' in ONLY:
       gen_n8(args.ref, out)
     if 'n9_knn_msc' in ONLY:
       gen_n9(args.ref, out)
+    if 'n10_prototype_msc' in ONLY:
+      gen_n10(args.ref, out)
     return
 
   import spml.utils.general.common as g_common
@@ -1289,6 +1423,8 @@ def main():
   # ======================= N9: multi-scale + flip kNN inference ==============================
   if ONLY is None or 'n9_knn_msc' in ONLY:
     gen_n9(args.ref, out)
+  if ONLY is None or 'n10_prototype_msc' in ONLY:
+    gen_n10(args.ref, out)
 
   # ======================= H2: two steps of the stage-2 classifier training ===============
   # pyscripts/train/train_classifier.py:139-169, the loop body exec'd as it stands on ONE device:
