@@ -48,7 +48,7 @@ const char* spml_status_string(int status);
  * 6: the pseudo-label entry points (spml_resample_unit_f32 .. spml_upsample_argmax_i64);
  * 7: the multi-scale inference entry point (spml_view_probs_accumulate_f32);
  * 8: spml_upsample_ce_bwd_path_name (entry points added since leave every earlier signature and flag as it was and
- *    keep the version: spml_view_votes_*, spml_segsort_nll_batched_*, spml_segment_majority_*). */
+ *    keep the version: spml_view_votes_*, spml_segsort_nll_batched_*, spml_segment_majority_*, spml_tag_normalize_*). */
 #define SPML_ABI_VERSION 8
 int spml_abi_version(void);
 
@@ -954,6 +954,33 @@ size_t spml_segment_majority_workspace_bytes(int m, int ncls);
 int spml_segment_majority_i64(const int64_t* clu, const int64_t* sem, int64_t P, int m, int ncls, int64_t* major,
                               int64_t* hist, void* ws, size_t ws_bytes, void* stream);
 const char* spml_segment_majority_path_name(int64_t P, int m, int ncls);
+
+/* ------------------------------------------------------------------------
+ * N11  tag-recipe kNN pseudo labels: tag-normalised arg-max (csrc/tag_normalize.hip)
+ * replaces: pyscripts/inference/pseudo_inference_crf_msc.py:252-263,275 (mean of the stacked vote maps over the views,
+ *           the maximum of every class over the image, a floor of 0.15, 1 for the classes the image does not carry, the
+ *           division, and -- the denseCRF of :273 left out -- the arg-max over the classes).
+ *
+ *   mean[c][p] = acc[c][p] / (float)num_views          peak[c] = max_p mean[c][p]
+ *   div[c]     = tags[c] ? max(peak[c], floor) : 1     prob[c][p] = mean[c][p] / div[c]
+ *   labels[p]  = the lowest c that attains max_c prob[c][p]
+ *
+ * acc: fp32 [ncls][n], the SUM over the views as spml_view_votes_accumulate_f32 leaves it (n = h * w), finite values of
+ * either sign; it is only read.  tags: one byte per class, non-zero = the image carries the class.  floor: a positive
+ * finite number (the reference's 0.15 as fp32).  labels: int64 [n].  prob: fp32 [ncls][n] or NULL (not written).  divisor:
+ * fp32 [ncls] (div) or NULL.  Both divisions are correctly rounded fp32 divisions and the maximum is exact: divisor and
+ * prob carry the bits of the same chain in numpy or in ATen on the CPU (peak is formed as (max_p acc[c][p]) / num_views:
+ * fp32 division is monotone).  ws: 4-byte aligned, at least spml_tag_normalize_workspace_bytes(ncls, n) bytes (that call
+ * returns 0 outside the limits), else SPML_ERR_WORKSPACE; its previous content does not matter.  Two launches on
+ * `stream` (the maxima of up to 16 parts per class plane; then normalise + arg-max, which finishes the parts in its
+ * prologue), no host read, no atomics: results are bit-identical from call to call, with and without the deterministic
+ * mode.  labels, prob, divisor and ws may alias neither acc, tags nor each other (SPML_ERR_INVALID_ARG, as for a null
+ * acc / tags / labels, n < 1, ncls < 1, num_views < 1 or a floor that is not a positive finite number); ncls <= 64 and
+ * n <= 2^30, else SPML_ERR_UNSUPPORTED. */
+size_t spml_tag_normalize_workspace_bytes(int ncls, int64_t n);
+int spml_tag_normalize_argmax_f32(const float* acc, int ncls, int64_t n, int num_views, const unsigned char* tags,
+                                  float floor, int64_t* labels, float* prob, float* divisor, void* ws, size_t ws_bytes,
+                                  void* stream);
 
 #ifdef __cplusplus
 }

@@ -150,6 +150,8 @@ _SIGNATURES = {
     'spml_segment_majority_workspace_bytes': (c_size_t, [c_int, c_int]),
     'spml_segment_majority_i64': (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     'spml_segment_majority_path_name': (c_char_p, [c_int64, c_int, c_int]),
+    'spml_tag_normalize_workspace_bytes': (c_size_t, [c_int, c_int64]),
+    'spml_tag_normalize_argmax_f32': (c_int, [_P, c_int, c_int64, c_int, _P, c_float, _P, _P, _P, _P, c_size_t, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -844,6 +846,39 @@ def segment_majority(clu, sem, m, ncls, want_hist=False):
                                         ptr(major), ptr(hist, None, True), ptr(ws), ws.numel(), stream_ptr()),
         'spml_segment_majority_i64')
   return (major, hist) if want_hist else major
+
+
+# ---------------------------------------------------------------------------
+# tag-recipe kNN pseudo labels: tag-normalised arg-max (csrc/tag_normalize.hip)
+MAX_TAG_NORMALIZE_CLASSES = 64         # the limit of spml_tag_normalize_argmax_f32 (include/spml_hip.h)
+
+
+def tag_normalize_argmax(acc, num_views, tags, floor=0.15, want_prob=False):
+  """The tail of pseudo_inference_crf_msc.py:252-263,275 on `acc` fp32 `[ncls, h, w]`, the SUM of the vote maps of
+  `num_views` views (what `view_votes_accumulate` leaves; only read): mean over the views, per class the maximum over the
+  image, floored at `floor`, 1 where `tags` (bool or uint8 `[ncls]`) is false, the division, the arg-max (ties to the
+  lowest class).  -> (labels int64 `[h, w]`, prob fp32 `[ncls, h, w]` or None, divisor fp32 `[ncls]`).  All tensors
+  contiguous, on the GPU; two launches, no host read."""
+  if acc.dim() != 3 or tags.dim() != 1 or tags.shape[0] != acc.shape[0]:
+    raise SpmlHipError('tag_normalize_argmax: acc must be [ncls, h, w] and tags [ncls] (got %s, %s)'
+                       % (tuple(acc.shape), tuple(tags.shape)))
+  if tags.dtype not in (torch.bool, torch.uint8):
+    raise SpmlHipError('tag_normalize_argmax: tags must be bool or uint8 (got %s)' % tags.dtype)
+  ncls, h, w = (int(v) for v in acc.shape)
+  ptr(acc, torch.float32), ptr(tags)                         # (CPU tensors are refused before anything is allocated)
+  nbytes = lib().spml_tag_normalize_workspace_bytes(ncls, h * w)
+  if nbytes == 0:
+    raise SpmlHipError('tag_normalize_argmax: %d classes x %d pixels are outside the kernel (1 .. %d classes, at least '
+                       'one pixel)' % (ncls, h * w, MAX_TAG_NORMALIZE_CLASSES))
+  tags8 = tags.view(torch.uint8) if tags.dtype == torch.bool else tags
+  labels = torch.empty((h, w), dtype=torch.int64, device=acc.device)
+  prob = torch.empty_like(acc) if want_prob else None
+  divisor = torch.empty((ncls,), dtype=torch.float32, device=acc.device)
+  ws = workspace(nbytes, acc.device)
+  check(lib().spml_tag_normalize_argmax_f32(ptr(acc, torch.float32), ncls, h * w, int(num_views), ptr(tags8, torch.uint8),
+                                            float(floor), ptr(labels), ptr(prob, None, True), ptr(divisor), ptr(ws),
+                                            ws.numel(), stream_ptr()), 'spml_tag_normalize_argmax_f32')
+  return labels, prob, divisor
 
 
 def affinity_transition(emb, scale=5.0, power=20):

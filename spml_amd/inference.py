@@ -324,6 +324,42 @@ def framework_view_votes_accumulate(clu, crop_hw, topk, ncls, flip, acc):
   return acc
 
 
+def _knn_view_votes_sum(who, embedding_model, prediction_model, views, image_hw, crop_size, stride, memory_prototypes,
+                        memory_prototype_labels, num_classes):
+  """The per-view work of `predict_knn_multiscale` and `pseudo_labels_knn_multiscale` (inference_msc.py:157-234 =
+  pseudo_inference_crf_msc.py:172-249) -> (the un-divided `[ncls,h,w]` sum of the views' vote maps, combine_path, the
+  per-view dense segment ids, the per-view `[m, 20]` retrieved labels).  `who` names the caller in the errors."""
+  if not views:
+    raise ValueError('%s needs at least one view' % who)
+  for image, _, _ in views:
+    if image.dim() != 4 or image.shape[0] != 1:
+      raise ValueError('%s expects views of one image [1,3,Hp,Wp]' % who)
+    if not image.is_cuda:
+      raise _ffi.SpmlHipError('the HIP path needs GPU tensors (a view on %s); there is no CPU fallback' % image.device)
+  h, w = image_hw
+  device = views[0][0].device
+  ncls = int(num_classes)
+  memory = {'semantic_memory_prototype': memory_prototypes, 'semantic_memory_prototype_label': memory_prototype_labels}
+  acc = torch.zeros((ncls, h, w), dtype=torch.float32, device=device)
+  combine_path, cluster_index, segment_topk = HIP_VIEW_VOTES_PATH, [], []
+  with torch.no_grad():
+    for image, (rh, rw), flip in views:
+      embs = embed_full_resolution(embedding_model, image, crop_size, stride)[..., :rh, :rw].contiguous()
+      fake = torch.zeros((1, rh, rw), dtype=torch.long, device=device)
+      out = embedding_model.generate_clusters(embs, fake, fake)
+      topk, clu = prediction_model.segment_predictions(out, memory)
+      if topk is None:
+        raise ValueError('%s needs a memory bank and a clustering' % who)
+      cluster_index.append(clu)
+      segment_topk.append(topk)
+      if ncls <= _ffi.MAX_VIEW_VOTES_CLASSES and topk.shape[0] <= _ffi.MAX_VIEW_VOTES_SEGMENTS:
+        _ffi.view_votes_accumulate(clu, (rh, rw), topk.contiguous(), ncls, flip, acc)
+      else:
+        framework_view_votes_accumulate(clu, (rh, rw), topk, ncls, flip, acc)
+        combine_path = FRAMEWORK_VIEW_VOTES_PATH
+  return acc, combine_path, cluster_index, segment_topk
+
+
 def predict_knn_multiscale(embedding_model, prediction_model, views, image_hw, crop_size, stride, memory_prototypes,
                            memory_prototype_labels, num_classes):
   """One image of the multi-scale + flip kNN label inference (`pyscripts/inference/inference_msc.py:129-242`), the form
@@ -341,37 +377,65 @@ def predict_knn_multiscale(embedding_model, prediction_model, views, image_hw, c
   ops on the device (`framework_view_votes_accumulate`) and `combine_path` names it.  Returns `semantic_prob`
   `[ncls,h,w]`, `semantic_prediction` `[h,w]` int64 and `combine_path`; and, per view, what the tail was fed:
   `cluster_index` (list of `[rh * rw]` dense segment ids) and `segment_topk` (list of `[m, 20]`)."""
-  if not views:
-    raise ValueError('predict_knn_multiscale needs at least one view')
-  for image, _, _ in views:
-    if image.dim() != 4 or image.shape[0] != 1:
-      raise ValueError('predict_knn_multiscale expects views of one image [1,3,Hp,Wp]')
-    if not image.is_cuda:
-      raise _ffi.SpmlHipError('the HIP path needs GPU tensors (a view on %s); there is no CPU fallback' % image.device)
-  h, w = image_hw
-  device = views[0][0].device
-  ncls = int(num_classes)
-  memory = {'semantic_memory_prototype': memory_prototypes, 'semantic_memory_prototype_label': memory_prototype_labels}
-  acc = torch.zeros((ncls, h, w), dtype=torch.float32, device=device)
-  combine_path, cluster_index, segment_topk = HIP_VIEW_VOTES_PATH, [], []
+  acc, combine_path, cluster_index, segment_topk = _knn_view_votes_sum(
+      'predict_knn_multiscale', embedding_model, prediction_model, views, image_hw, crop_size, stride, memory_prototypes,
+      memory_prototype_labels, num_classes)
   with torch.no_grad():
-    for image, (rh, rw), flip in views:
-      embs = embed_full_resolution(embedding_model, image, crop_size, stride)[..., :rh, :rw].contiguous()
-      fake = torch.zeros((1, rh, rw), dtype=torch.long, device=device)
-      out = embedding_model.generate_clusters(embs, fake, fake)
-      topk, clu = prediction_model.segment_predictions(out, memory)
-      if topk is None:
-        raise ValueError('predict_knn_multiscale needs a memory bank and a clustering')
-      cluster_index.append(clu)
-      segment_topk.append(topk)
-      if ncls <= _ffi.MAX_VIEW_VOTES_CLASSES and topk.shape[0] <= _ffi.MAX_VIEW_VOTES_SEGMENTS:
-        _ffi.view_votes_accumulate(clu, (rh, rw), topk.contiguous(), ncls, flip, acc)
-      else:
-        framework_view_votes_accumulate(clu, (rh, rw), topk, ncls, flip, acc)
-        combine_path = FRAMEWORK_VIEW_VOTES_PATH
     acc /= len(views)
-    prediction = _ffi.argmax_channels(acc, h, w)
+    prediction = _ffi.argmax_channels(acc, image_hw[0], image_hw[1])
   return {'semantic_prob': acc, 'semantic_prediction': prediction, 'combine_path': combine_path,
+          'cluster_index': cluster_index, 'segment_topk': segment_topk}
+
+
+HIP_TAG_NORMALIZE_PATH = 'hip_tag_normalize'
+FRAMEWORK_TAG_NORMALIZE_PATH = 'framework_tag_normalize'
+
+
+def framework_tag_normalize_argmax(acc, num_views, tags, floor=0.15, want_prob=False):
+  """The tag-normalised arg-max as torch ops on the tensors' device, what `_ffi.tag_normalize_argmax` computes in two
+  launches: `acc` fp32 `[ncls, h, w]` (the sum over `num_views` views) divided by the view count, per class the maximum
+  over the image, floored at `floor`, 1 where `tags` (bool `[ncls]`) is false, the division, the arg-max over the
+  classes.  The path of `pseudo_labels_knn_multiscale` outside the kernel's limits and the yardstick of
+  tools/bench_pseudo_knn_msc.py.  -> (labels int64 `[h, w]`, prob or None, divisor `[ncls]`)."""
+  # (a 0-dim tensor, not a Python number: by a number ATen's GPU kernel multiplies with the reciprocal instead)
+  mean = acc / torch.full((), float(num_views), dtype=acc.dtype, device=acc.device)
+  peak = torch.amax(mean.reshape(mean.shape[0], -1), dim=1)
+  divisor = torch.where(tags.bool(), torch.clamp_min(peak, float(floor)), torch.ones_like(peak))
+  prob = mean / divisor.view(-1, 1, 1)
+  return torch.argmax(prob, dim=0), (prob if want_prob else None), divisor
+
+
+def pseudo_labels_knn_multiscale(embedding_model, prediction_model, views, image_hw, crop_size, stride, memory_prototypes,
+                                 memory_prototype_labels, num_classes, label_tags, floor=0.15, return_prob=False):
+  """One image of the tag recipe's pseudo-label generation by nearest-neighbour retrieval
+  (`pyscripts/inference/pseudo_inference_crf_msc.py:143-275`), without the denseCRF of :273: the stage ends at the
+  arg-max of what the CRF would have been fed, and `return_prob` hands that tensor out for callers who have a CRF.
+  `views`, `image_hw`, the models and the memory bank are `predict_knn_multiscale`'s, and so is the work per view (one
+  shared helper); `label_tags`: bool `[ncls]` device tensor (`label_tags_from_map`, :138-141).
+
+  After the last view `spml_tag_normalize_argmax_f32` takes the un-divided sum: mean over the views, per class the
+  maximum over the image floored at `floor`, 1 for the classes the image does not carry, the division (:252-263) and the
+  arg-max (:275; ties to the lowest class).  Above 64 classes the same tail runs as torch ops
+  (`framework_tag_normalize_argmax`) and `normalize_path` names which of the two ran.  Returns `semantic_prediction`
+  `[h,w]` int64, `semantic_prob` `[ncls,h,w]` (the normalised map; None unless `return_prob`), `class_divisor` `[ncls]`,
+  `combine_path`, `normalize_path`, and per view `cluster_index` and `segment_topk` as `predict_knn_multiscale`."""
+  if not views:
+    raise ValueError('pseudo_labels_knn_multiscale needs at least one view')
+  if not label_tags.is_cuda:
+    raise _ffi.SpmlHipError('the HIP path needs GPU tensors (label_tags on %s); there is no CPU fallback'
+                            % label_tags.device)
+  if label_tags.dim() != 1 or label_tags.shape[0] != int(num_classes):
+    raise ValueError('pseudo_labels_knn_multiscale expects one tag per class')
+  acc, combine_path, cluster_index, segment_topk = _knn_view_votes_sum(
+      'pseudo_labels_knn_multiscale', embedding_model, prediction_model, views, image_hw, crop_size, stride,
+      memory_prototypes, memory_prototype_labels, num_classes)
+  hip = int(num_classes) <= _ffi.MAX_TAG_NORMALIZE_CLASSES
+  tail = _ffi.tag_normalize_argmax if hip else framework_tag_normalize_argmax
+  with torch.no_grad():
+    prediction, prob, divisor = tail(acc, len(views), label_tags, floor, return_prob)
+  return {'semantic_prediction': prediction, 'semantic_prob': prob, 'class_divisor': divisor,
+          'combine_path': combine_path,
+          'normalize_path': HIP_TAG_NORMALIZE_PATH if hip else FRAMEWORK_TAG_NORMALIZE_PATH,
           'cluster_index': cluster_index, 'segment_topk': segment_topk}
 
 

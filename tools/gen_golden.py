@@ -595,6 +595,285 @@ def gen_n10(ref, out):
     assert size < 880 * 1024, 'n10_prototype_msc.npz is %d bytes' % size      # (no larger than the largest N fixture)
 
 
+class _NumpyWithBool:
+  """`np` for the exec of pseudo_inference_crf_msc.py:138-141: `np.bool` left numpy in 1.24; everything else is numpy's."""
+  bool = bool
+
+  def __getattr__(self, name):
+    return getattr(np, name)
+
+
+def gen_n11(ref, out):
+  """N11: the tag recipe's kNN pseudo labels.  pyscripts/inference/pseudo_inference_crf_msc.py:138-141 exec'd for the
+  tags, :172-241 per view (the lines of inference_msc.py:157-226, see `gen_n9`) and :252-263 + :275 once (mean over the
+  views, per-class maximum, floor 0.15, 1 for the untagged classes, division; arg-max -- the denseCRF of :273 between
+  them is out of scope), with the arrangement of `gen_n9`: stub embedder, CPU-shimmed k-means, the reference's `Segsort`,
+  a perturbed bank, CPU `F.interpolate` in the place of `cv2.resize`.  Both cases use the recipe's four scales x flip.
+  The bank's labels are drawn per coarse cell over the classes but the last; the last class takes a few single entries,
+  so that its votes stay under the floor.  The image's label map (the source of the tags) carries every class but one
+  strong one.  Stored per view what N9 stores (`cluster_index`, per-segment `topk`, the vote map); the image once (the
+  views are `flip_scale_views`' of it: tests rebuild them); once `label_map`, `label_tags`, `divisor`, the normalised
+  `semantic_prob`, `semantic_pred`, the un-normalised `mean_prob` and the top-1 minus top-2 `margin` of the normalised
+  map.  Asserted (seeds are advanced until all hold): every normalisation branch is met, at least 3 classes win, the
+  normalised labels differ from the plain arg-max of the mean on at least 5 % of the pixels, and at most 1 % of the
+  pixels have a margin under 2e-4 * max|semantic_prob| (the N7 rule; the cap is NOT raised: two tagged classes that
+  peak on one vote plateau tie on all of it, and such seeds are rejected)."""
+  import linecache
+  import math
+  import textwrap
+  import spml.models.embeddings.resnet_deeplab as e_dl
+  import spml.models.predictions.segsort as p_segsort
+  import spml.utils.general.common as g_common
+  import spml.utils.segsort.common as s_common
+  F = torch.nn.functional
+
+  def ref_lines(path, first, last):
+    txt = ''.join(linecache.getline(path, i) for i in range(first, last + 1))
+    assert txt.strip(), path
+    return textwrap.dedent(txt).replace('.cuda()', '').replace('.to("cuda:0")', '')
+
+  msc_py = os.path.join(ref, 'pyscripts', 'inference', 'pseudo_inference_crf_msc.py')
+  src_tags, src_view = ref_lines(msc_py, 138, 141), ref_lines(msc_py, 172, 241)
+  src_norm, src_pred = ref_lines(msc_py, 252, 263), ref_lines(msc_py, 275, 275)
+  assert 'np.unique(original_label_batch' in src_tags and 'dtype=np.bool' in src_tags
+  assert 'patch_ind_h' in src_view and '[..., :resize_image_h, :resize_image_w]' in src_view and 'cuda' not in src_view
+  assert 'with_prediction=True' in src_view and 'torch.mean(semantic_topk, dim=1)' in src_view
+  assert src_view.rstrip().endswith('semantic_topk.view(resize_image_h, resize_image_w, -1)')
+  assert 'np.mean(semantic_topks, axis=0)' in src_norm and 'np.maximum(max_prob, 0.15)' in src_norm
+  assert 'max_prob[~label_tags, :, :] = 1' in src_norm and src_norm.rstrip().endswith('semantic_prob / max_prob')
+  assert 'np.argmax(semantic_prob, axis=0)' in src_pred
+  assert 'scales=[0.5, 1, 1.5, 2]' in ref_lines(msc_py, 133, 136)
+  resize_src = ref_lines(msc_py, 245, 248)
+  assert 'cv2.INTER_LINEAR' in resize_src and 'semantic_topk[:, ::-1]' in resize_src
+
+  ns = {'segment_by_kmeans': cpu_shimmed_segment_by_kmeans(s_common)}
+  StubEmbedder = stub_embedder_class(e_dl)
+  scales = (0.5, 1, 1.5, 2)
+  floor32 = np.float32(0.15)
+
+  def one_case(seed, c, ncls, image_hw, crop, stride, grid, n_bank):
+    """-> (store dict, report dict), or (None, reason) when a condition fails for this seed."""
+    gen = torch.Generator().manual_seed(seed)
+    torch.manual_seed(seed)
+    image_h, image_w = image_hw
+    conv = torch.nn.Conv2d(3, c, 5, padding=2)
+    base = torch.randn(1, 3, image_h // 8 + 2, image_w // 8 + 2, generator=gen)
+    image = F.interpolate(base, size=image_hw, mode='bilinear', align_corners=False)
+    image = image + 0.05 * torch.randn(1, 3, image_h, image_w, generator=gen)
+    cfg = AttrDict(
+        train=AttrDict(sem_ann_loss_types='none', sem_occ_loss_types='none', img_sim_loss_types='none',
+                       feat_aff_loss_types='none', sem_ann_concentration=0.0, sem_occ_concentration=0.0,
+                       img_sim_concentration=0.0, feat_aff_concentration=0.0, sem_ann_loss_weight=0.0,
+                       sem_occ_loss_weight=0.0, img_sim_loss_weight=0.0, feat_aff_loss_weight=0.0),
+        dataset=AttrDict(semantic_ignore_index=255, num_classes=ncls),
+        network=AttrDict(label_divisor=2048),
+        test=AttrDict(stride=list(stride), crop_size=list(crop)))
+    predictor = p_segsort.Segsort(cfg)
+    with torch.no_grad():
+      full = g_common.normalize_embedding(conv(image).permute(0, 2, 3, 1).reshape(-1, c))
+    pick = torch.randint(0, full.shape[0], (n_bank,), generator=gen)
+    bank = g_common.normalize_embedding(full[pick] + 0.1 * torch.randn(n_bank, c, generator=gen))
+    bank_lab = blocky_labels(gen, 1, image_h, image_w, 4, 0, ncls - 1)[0].reshape(-1)[pick]
+    weak = ncls - 1                                         # a few single entries: votes of 1/20 or 2/20 at most places
+    bank_lab[torch.randperm(n_bank, generator=gen)[:max(n_bank // 40, 4)]] = weak
+    # the image's label map: every class but one strong one, in stripes, with unlabelled (255) gaps
+    untagged = int(torch.randint(0, ncls - 1, (1,), generator=gen))
+    carried = [k for k in range(ncls) if k != untagged]
+    label_map = np.full(image_hw, 255, dtype=np.uint8)
+    for j, k in enumerate(carried):
+      label_map[:, j * image_w // len(carried):(j + 1) * image_w // len(carried) - 1] = k
+    env = {'np': _NumpyWithBool(), 'config': cfg, 'original_label_batch': {'semantic_label': label_map}}
+    exec(compile(src_tags, msc_py + ':138-141', 'exec'), env)
+    label_tags = env['label_tags']
+    assert label_tags.dtype == np.bool_ and label_tags.tolist() == [k != untagged for k in range(ncls)]
+
+    per_view, views, semantic_topks = {}, [], []
+    for si, scale in enumerate(scales):
+      size = (max(int(round(image_h * scale)), 1), max(int(round(image_w * scale)), 1))
+      scaled = image if scale == 1 else F.interpolate(image, size=size, mode='bilinear', align_corners=False)
+      rh, rw = scaled.shape[-2:]
+      pad_h, pad_w = max(rh, crop[0]), max(rw, crop[1])
+      for flip in (True, False):                            # create_image_pyramid: the flipped view first
+        view = torch.zeros(1, 3, pad_h, pad_w)
+        view[:, :, :rh, :rw] = torch.flip(scaled, dims=[3]) if flip else scaled
+        fake = torch.full((1, pad_h, pad_w), 255, dtype=torch.long)
+        fake[:, :rh, :rw] = 0                               # :155-166
+        env = {'config': cfg, 'math': math, 'np': np, 'torch': torch, 'image_batch': {'image': view},
+               'pad_image_h': pad_h, 'pad_image_w': pad_w, 'resize_image_h': rh, 'resize_image_w': rw,
+               'embedding_model': StubEmbedder(conv, list(grid)), 'prediction_model': predictor,
+               'common_utils': g_common, 'fake_label_batch': {'semantic_label': fake, 'instance_label': fake.clone()},
+               'semantic_memory_prototypes': bank, 'semantic_memory_prototype_labels': bank_lab}
+        with torch.no_grad():
+          exec(compile(src_view, msc_py + ':172-241', 'exec'), env)
+        votes = env['semantic_topk']
+        assert tuple(votes.shape) == (rh, rw, ncls) and votes.dtype == torch.float32
+        # :243-248 with F.interpolate in the place of cv2.resize
+        resized = F.interpolate(votes.permute(2, 0, 1).unsqueeze(0), size=image_hw, mode='bilinear',
+                                align_corners=False)[0].permute(1, 2, 0).numpy().astype(np.float32)
+        if flip:
+          resized = resized[:, ::-1]
+        semantic_topks.append(resized)
+        score = env['outputs']['semantic_score']
+        _, clu = torch.unique(env['embeddings']['cluster_index'], return_inverse=True)
+        m = int(clu.max()) + 1
+        assert tuple(score.shape) == (rh * rw, 20) and clu.shape[0] == rh * rw
+        first = torch.full((m,), rh * rw, dtype=torch.long).scatter_reduce(0, clu, torch.arange(rh * rw), 'amin')
+        topk = score[first]
+        assert torch.equal(topk[clu], score), 'the pixels of a segment disagree on their retrieved labels'
+        assert m <= 32767 and int(topk.max()) < ncls
+        vi = len(views)
+        views.append([si, pad_h, pad_w, rh, rw, int(flip), m])
+        per_view['cluster_index%d' % vi] = clu.to(torch.int16)
+        per_view['topk%d' % vi] = topk.to(torch.uint8)
+        per_view['votes%d' % vi] = np.ascontiguousarray(resized.transpose(2, 0, 1))
+    plain = np.mean(np.stack(semantic_topks, axis=0).astype(np.float32), axis=0).transpose(2, 0, 1)
+    env = {'np': np, 'semantic_topks': semantic_topks, 'label_tags': label_tags}
+    exec(compile(src_norm, msc_py + ':252-263', 'exec'), env)
+    prob, divisor = env['semantic_prob'], env['max_prob'].reshape(-1)
+    exec(compile(src_pred, msc_py + ':275', 'exec'), env)
+    pred = env['semantic_pred']
+    assert prob.shape == (ncls, image_h, image_w) and prob.dtype == np.float32 and divisor.dtype == np.float32
+    assert pred.shape == image_hw and pred.dtype == np.uint8
+    peak = plain.reshape(ncls, -1).max(1)
+    wins = np.bincount(pred.reshape(-1), minlength=ncls)
+    top2 = torch.from_numpy(np.ascontiguousarray(prob)).topk(2, dim=0).values
+    margin = top2[0] - top2[1]
+    low = (margin < 2e-4 * float(np.abs(prob).max())).float().mean().item()
+    moved = float((pred != np.argmax(plain, axis=0)).mean())
+    report = dict(seed=seed, untagged=untagged, peak=np.round(peak, 3).tolist(), wins=wins.tolist(), low=low, moved=moved,
+                  segments=[v[6] for v in views])
+    checks = [
+        ('a tagged class with a peak of at least 0.15', bool((label_tags & (peak >= floor32)).any())),
+        ('a tagged class with votes under the floor', bool((label_tags & (peak < floor32) & (peak > 0)).any())),
+        ('the untagged class has votes and wins pixels', peak[untagged] > 0 and wins[untagged] > 0),
+        ('at least 3 classes win', int((wins > 0).sum()) >= 3),
+        ('the normalisation moves at least 5 % of the labels', moved >= 0.05),
+        ('at most 1 % of the pixels under the margin', low <= 0.01)]
+    failed = [what for what, ok in checks if not ok]
+    if failed:
+      return None, dict(report, failed=failed)
+    assert np.array_equal(divisor, np.where(label_tags, np.maximum(peak, floor32), np.float32(1)))
+    store = dict(per_view)
+    store.update({
+        'image': image, 'conv_w': conv.weight, 'conv_b': conv.bias, 'bank': bank, 'bank_lab': bank_lab,
+        'cfg': np.array([c, ncls, image_h, image_w, crop[0], crop[1], stride[0], stride[1], grid[0], grid[1]]),
+        'scales': np.array(scales, dtype=np.float64), 'views': np.array(views), 'label_map': label_map,
+        'label_tags': label_tags, 'divisor': divisor, 'mean_prob': np.ascontiguousarray(plain),
+        'semantic_prob': np.ascontiguousarray(prob), 'semantic_pred': pred, 'margin': margin})
+    return store, report
+
+  # (first seed, C, classes, image, crop, stride, k-means grid, bank size).  (a) image = crop: the scale-1 views are not
+  # padded; (b) odd width, a padded 0.5 view (18 x 23 in 24 x 24) and 4 x 6 windows at scale 2 (72 x 90, stride 16).
+  cases = [(2100, 16, 5, (44, 60), (44, 60), (30, 30), (4, 4), 400),
+           (2200, 16, 6, (36, 45), (24, 24), (16, 16), (3, 3), 300)]
+  store = {}
+  orig = e_dl.segsort_common.segment_by_kmeans
+  e_dl.segsort_common.segment_by_kmeans = ns['segment_by_kmeans']
+  try:
+    for ci, (seed0, c, ncls, image_hw, crop, stride, grid, n_bank) in enumerate(cases):
+      for seed in range(seed0, seed0 + 40):
+        got, report = one_case(seed, c, ncls, image_hw, crop, stride, grid, n_bank)
+        print('n11 case %d: %s' % (ci, report))
+        if got is not None:
+          break
+      else:
+        raise AssertionError('n11 case %d: no seed in %d .. %d meets the conditions' % (ci, seed0, seed0 + 39))
+      store.update({'c%d_%s' % (ci, k): v for k, v in got.items()})
+      store['c%d_seed' % ci] = np.array(seed)
+  finally:
+    e_dl.segsort_common.segment_by_kmeans = orig
+  save(out, 'n11_pseudo_knn_msc', **store)
+  size = os.path.getsize(os.path.join(out, 'n11_pseudo_knn_msc.npz'))
+  assert size <= 600 * 1024, 'n11_pseudo_knn_msc.npz is %d bytes' % size
+
+
+def gen_n11_instance(ref, out):
+  """The instance-weighted IoU of pyscripts/benchmark/benchmark_by_instance.py: its own `iou_stats` (:27-55) and the
+  lines :88-113 exec'd per image, :115-116 and :139 once, on seeded uint8 maps of 40 x 52 -- three images for 21 classes
+  and two for 15.  Among them: an instance all of whose pixels are 255 in the ground truth (it counts for class 0), an
+  instance tied between two classes (the lower one), an image with all 256 ids (`if i < 255` drops the largest), an
+  image with one id, and ground-truth values between the class count and 255 (outside the histogram's range).  Stored:
+  `pred`, `gt`, `inst` (uint8), the per-image `ninst_`, the final `iou` and `mean_iou`."""
+  import linecache
+  import textwrap
+  py = os.path.join(ref, 'pyscripts', 'benchmark', 'benchmark_by_instance.py')
+
+  def ref_lines(first, last):
+    txt = ''.join(linecache.getline(py, i) for i in range(first, last + 1))
+    assert txt.strip(), py
+    return textwrap.dedent(txt)
+
+  src_stats, src_image, src_final, src_mean = ref_lines(27, 55), ref_lines(88, 113), ref_lines(115, 116), ref_lines(139, 139)
+  assert src_stats.startswith('def iou_stats(') and 'if i < 255:' in src_image and 'ninst += ninst_' in src_image
+  assert 'range=(0, args.num_classes-1)' in src_image and 'iou /= ninst+1e-12' in src_final and 'mean_iou' in src_mean
+  h, w = 40, 52
+  for nc in (15, 21):     # np.histogram(bins=nc, range=(0, nc-1)) bins the integers 0 .. nc-1 as themselves
+    for v in range(nc):
+      hist, _ = np.histogram(np.array([v], dtype=np.uint8), bins=nc, range=(0, nc - 1))
+      assert int(np.argmax(hist)) == v and hist.sum() == 1, (nc, v)
+    assert np.histogram(np.array([nc, 254, 255], dtype=np.uint8), bins=nc, range=(0, nc - 1))[0].sum() == 0
+
+  def blocky(rng, cells_y, cells_x, values):
+    grid = rng.choice(values, size=(cells_y, cells_x))
+    return np.ascontiguousarray(grid[np.arange(h) * cells_y // h][:, np.arange(w) * cells_x // w].astype(np.uint8))
+
+  def blocky_image(rng, nc):
+    """A few instances (ids 0, 3, 5, 9, 200, 255 ...) over a blocky ground truth; id 3 is unlabelled throughout and
+    id 5 is split evenly between two classes."""
+    inst = blocky(rng, 4, 4, np.array([0, 3, 5, 9, 200, 255]))
+    inst[:10, :13], inst[10:20, :13], inst[:10, 13:26] = 3, 5, 0              # (every special id occurs)
+    gt = blocky(rng, 5, 6, np.arange(nc))
+    gt[rng.random((h, w)) < 0.1] = 255
+    gt[rng.random((h, w)) < 0.03] = min(nc + 2, 254)                           # neither a class nor 255
+    gt[inst == 3] = 255
+    five = np.flatnonzero(inst.reshape(-1) == 5)
+    assert five.size % 2 == 0 and five.size > 0
+    a, b = sorted(rng.choice(np.arange(1, nc), size=2, replace=False).tolist())
+    flat = gt.reshape(-1)
+    assert flat.base is gt
+    flat[five[:five.size // 2]], flat[five[five.size // 2:]] = b, a
+    return inst, gt, (a, b)
+
+  store = {}
+  for nc, kinds in ((21, ('blocky', 'all_ids', 'one_id')), (15, ('blocky', 'all_ids'))):
+    rng = np.random.default_rng(1100 + nc)
+    env = {'np': np}
+    exec(compile(src_stats, py + ':27-55', 'exec'), env)
+    env.update(args=AttrDict(num_classes=nc), iou=np.zeros(nc, dtype=np.float64), ninst=np.zeros(nc, dtype=np.float64))
+    for ii, kind in enumerate(kinds):
+      if kind == 'blocky':
+        inst, gt, (a, b) = blocky_image(rng, nc)
+      elif kind == 'all_ids':
+        inst = rng.permutation(np.arange(h * w) % 256).reshape(h, w).astype(np.uint8)
+        gt = rng.integers(0, nc, size=(h, w)).astype(np.uint8)
+        gt[rng.random((h, w)) < 0.2] = 255
+      else:
+        inst = np.full((h, w), 7, dtype=np.uint8)
+        gt = blocky(rng, 3, 3, np.arange(nc))
+      pred = np.where(rng.random((h, w)) < 0.7, np.minimum(gt, nc - 1), rng.integers(0, nc, size=(h, w))).astype(np.uint8)
+      env.update(pred=pred, gt=gt, inst=inst)
+      exec(compile(src_image, py + ':88-113', 'exec'), env)
+      ninst_ = env['ninst_']
+      ids = np.unique(inst)
+      if kind == 'blocky':
+        assert {0, 3, 5, 255} <= set(ids.tolist()) and (gt[inst == 3] == 255).all()
+        counts5 = np.bincount(gt[inst == 5], minlength=256)
+        assert counts5[a] == counts5[b] == counts5[:nc].max() and a < b
+        assert ninst_.sum() == ids.size
+      elif kind == 'all_ids':
+        assert ids.size == 256 and ninst_.sum() == 255
+      else:
+        assert ids.size == 1 and ninst_.sum() == 1
+      t = 'n%d_i%d_' % (nc, ii)
+      store.update({t + 'pred': pred, t + 'gt': gt, t + 'inst': inst, t + 'ninst': ninst_.copy()})
+    exec(compile(src_final, py + ':115-116', 'exec'), env)
+    exec(compile(src_mean, py + ':139', 'exec'), env)
+    assert np.isfinite(env['iou']).all() and 0.0 < env['mean_iou'] < 100.0
+    store.update({'n%d_images' % nc: np.array(len(kinds)), 'n%d_iou' % nc: env['iou'], 'n%d_mean_iou' % nc: np.array(env['mean_iou'])})
+    print('n11 instance IoU, %d classes: %d images, mean IoU %.4f' % (nc, len(kinds), env['mean_iou']))
+  save(out, 'n11_instance_iou', **store)
+
+
 class AttrDict(dict):
   __getattr__ = dict.__getitem__
 
@@ -613,7 +892,8 @@ def main():
 
   sys.path.insert(0, args.ref)
   torch.set_num_threads(1)       # bit-stable fp32 sums
-  if ONLY is not None and ONLY <= {'n7_pseudo_labels', 'n8_softmax_msc', 'n9_knn_msc', 'n10_prototype_msc'}:      # (need none of the imports and shims below)
+  if ONLY is not None and ONLY <= {'n7_pseudo_labels', 'n8_softmax_msc', 'n9_knn_msc', 'n10_prototype_msc',
+                                   'n11_pseudo_knn_msc', 'n11_instance_iou'}:      # (need none of the imports and shims below)
     if 'n7_pseudo_labels' in ONLY:
       gen_n7(args.ref, out)
     if 'n8_softmax_msc' in ONLY:
@@ -622,6 +902,10 @@ def main():
       gen_n9(args.ref, out)
     if 'n10_prototype_msc' in ONLY:
       gen_n10(args.ref, out)
+    if 'n11_pseudo_knn_msc' in ONLY:
+      gen_n11(args.ref, out)
+    if 'n11_instance_iou' in ONLY:
+      gen_n11_instance(args.ref, out)
     return
 
   import spml.utils.general.common as g_common
@@ -1425,6 +1709,12 @@ def main():
     gen_n9(args.ref, out)
   if ONLY is None or 'n10_prototype_msc' in ONLY:
     gen_n10(args.ref, out)
+
+  # ======================= N11: tag-recipe kNN pseudo labels, instance-weighted IoU ==========
+  if ONLY is None or 'n11_pseudo_knn_msc' in ONLY:
+    gen_n11(args.ref, out)
+  if ONLY is None or 'n11_instance_iou' in ONLY:
+    gen_n11_instance(args.ref, out)
 
   # ======================= H2: two steps of the stage-2 classifier training ===============
   # pyscripts/train/train_classifier.py:139-169, the loop body exec'd as it stands on ONE device:
