@@ -6,7 +6,7 @@
       --kmeans_num_clusters 12,12 --label_divisor 2048
 
 One view per image at its own size: the pass of `prototype_msc.py` with the scales `[1]`; the bank of every image goes
-to `<save_dir>/semantic_prototype/<name>.npy`; see spml_amd/prototype_cli.py."""
+to `<save_dir>/semantic_prototype/<name>.npy`; see `run_prototypes` of spml_amd/inference_cli.py."""
 import os
 import sys
 
@@ -17,8 +17,8 @@ SCALES = [1]
 
 
 def main(argv=None):
-  from spml_amd.prototype_cli import run
-  run('Inference for generating memory banks.', SCALES, argv)
+  from spml_amd.inference_cli import run_prototypes
+  run_prototypes('Inference for generating memory banks.', SCALES, argv)
 
 
 if __name__ == '__main__':

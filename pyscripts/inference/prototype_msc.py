@@ -7,7 +7,7 @@
 
 Three views per image (scales 0.5, 1, 1.5, no flip: :92-95); per view the sliding-window embedding, k-means that ignores
 the padding, prototypes and their majority labels; the views' banks concatenated into
-`<save_dir>/semantic_prototype/<name>.npy`; see spml_amd/prototype_cli.py."""
+`<save_dir>/semantic_prototype/<name>.npy`; see `run_prototypes` of spml_amd/inference_cli.py."""
 import os
 import sys
 
@@ -18,8 +18,8 @@ SCALES = [0.5, 1, 1.5]
 
 
 def main(argv=None):
-  from spml_amd.prototype_cli import run
-  run('Inference for generating memory banks.', SCALES, argv)
+  from spml_amd.inference_cli import run_prototypes
+  run_prototypes('Inference for generating memory banks.', SCALES, argv)
 
 
 if __name__ == '__main__':

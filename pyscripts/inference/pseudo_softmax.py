@@ -6,7 +6,8 @@
 
 Flip pairs at scales 0.75 and 1, mean of the views' logits and one softmax, WALK_STEPS = 0: the class maps go once
 through the transition matrix, without squarings (:29, :108-111, :144-150).  The script's CRF lines are commented out,
-so the labels written as `semantic_gray/<name>.npy` are its output; see spml_amd/pseudo_labels_cli.py."""
+so the labels written as `semantic_gray/<name>.npy` are its output; see `run_pseudo_softmax` of
+spml_amd/inference_cli.py."""
 import os
 import sys
 
@@ -17,8 +18,8 @@ SCALES, COMBINE, WALK_STEPS = (0.75, 1), 'logit_mean', 0
 
 
 def main(argv=None):
-  from spml_amd.pseudo_labels_cli import run
-  run('Generate pseudo labels by softmax classifier.', SCALES, COMBINE, WALK_STEPS, argv)
+  from spml_amd.inference_cli import run_pseudo_softmax
+  run_pseudo_softmax('Generate pseudo labels by softmax classifier.', SCALES, COMBINE, WALK_STEPS, argv)
 
 
 if __name__ == '__main__':

@@ -7,7 +7,7 @@ box recipes run it between stage 1 and stage 2):
 
 Flip pair at scale 1, softmax per view and mean of the probabilities, WALK_STEPS = 6 squarings of the transition
 matrix (:29, :109-112, :143-147).  Writes the labels of :176 (before the denseCRF refinement, which is outside this
-repository) as `semantic_gray/<name>.npy`; see spml_amd/pseudo_labels_cli.py."""
+repository) as `semantic_gray/<name>.npy`; see `run_pseudo_softmax` of spml_amd/inference_cli.py."""
 import os
 import sys
 
@@ -18,8 +18,8 @@ SCALES, COMBINE, WALK_STEPS = (1,), 'prob_mean', 6
 
 
 def main(argv=None):
-  from spml_amd.pseudo_labels_cli import run
-  run('Generate pseudo labels by softmax classifier and random walk.', SCALES, COMBINE, WALK_STEPS, argv)
+  from spml_amd.inference_cli import run_pseudo_softmax
+  run_pseudo_softmax('Generate pseudo labels by softmax classifier and random walk.', SCALES, COMBINE, WALK_STEPS, argv)
 
 
 if __name__ == '__main__':

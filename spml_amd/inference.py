@@ -23,6 +23,69 @@ def sliding_window_ends(pad_size, crop_size, stride):
   return np.linspace(crop_size, pad_size, n, dtype=np.int32)
 
 
+def _is_channels_last(embedding_model):
+  first = next(embedding_model.parameters(), None)
+  return first is not None and first.is_cuda and first.dim() == 4 and \
+      first.is_contiguous(memory_format=torch.channels_last) and not first.is_contiguous()
+
+
+def _check_views(who, views, also=None):
+  """What every multi-view routine asks of `views`: at least one, each one image `[1,3,Hp,Wp]`, each on the GPU.  `who`
+  names the caller in the errors; `also(i)` is the caller's own check of view `i`, run before that view's device check."""
+  if not views:
+    raise ValueError('%s needs at least one view' % who)
+  for i, (image, _, _) in enumerate(views):
+    if image.dim() != 4 or image.shape[0] != 1:
+      raise ValueError('%s expects views of one image [1,3,Hp,Wp]' % who)
+    if also is not None:
+      also(i)
+    if not image.is_cuda:
+      raise _ffi.SpmlHipError('the HIP path needs GPU tensors (a view on %s); there is no CPU fallback' % image.device)
+
+
+def _group_by_padded_size(views):
+  """Consecutive views of one padded size (a flip pair, or several scales that all pad up to the crop size) -> list of
+  lists of views, in call order."""
+  groups = []
+  for view in views:
+    if groups and groups[-1][0][0].shape == view[0].shape:
+      groups[-1].append(view)
+    else:
+      groups.append([view])
+  return groups
+
+
+def _padding_ignored_labels(pad_hw, valid_hw, ignore_index, device):
+  """Fake labels `[1,Hp,Wp]` that make the clustering ignore the zero padding outside the top-left `valid_hw` region
+  (prototype.py:117-131)."""
+  fake = torch.full((1,) + tuple(pad_hw), ignore_index, dtype=torch.long, device=device)
+  fake[:, :valid_hw[0], :valid_hw[1]] = 0
+  return fake
+
+
+def _window_embeddings(embedding_model, images, crop_size, stride):
+  """The sliding-window loop of prototype.py:134-181 (= inference_softmax.py:105-128) over `images`, padded images
+  `[1,3,Hp,Wp]` of ONE size: yields `(k, sh, sw, embedding [1,C,crop_h,crop_w])` for every crop -- image after image,
+  each in the reference's window order.  The crops go through the network in groups of 8 that may span images (eval mode:
+  every sample is independent, the reference's one-crop-at-a-time loop gives the same embeddings), in the memory format
+  of the model."""
+  pad_h, pad_w = images[0].shape[-2:]
+  crop_h, crop_w = crop_size
+  ends_h = sliding_window_ends(pad_h, crop_h, stride[0])
+  ends_w = sliding_window_ends(pad_w, crop_w, stride[1])
+  windows = [(k, int(eh) - crop_h, int(ew) - crop_w) for k in range(len(images)) for eh in ends_h for ew in ends_w]
+  nhwc = _is_channels_last(embedding_model)
+  group = 8
+  for g0 in range(0, len(windows), group):
+    part = windows[g0:g0 + group]
+    crops = torch.cat([images[k][:, :, sh:sh + crop_h, sw:sw + crop_w] for k, sh, sw in part], 0)
+    if nhwc:
+      crops = crops.contiguous(memory_format=torch.channels_last)
+    embs = embedding_model.generate_embeddings({'image': crops}, resize_as_input=True)['embedding']
+    for i, (k, sh, sw) in enumerate(part):
+      yield k, sh, sw, embs[i:i + 1]
+
+
 def embed_full_resolution(embedding_model, image, crop_size, stride):
   """Sliding-window embedding `[1,C,Hp,Wp]` of a padded image `[1,3,Hp,Wp]`
   (prototype.py:134-181): crops are embedded with `generate_embeddings(...,
@@ -30,30 +93,14 @@ def embed_full_resolution(embedding_model, image, crop_size, stride):
   if image.dim() != 4 or image.shape[0] != 1:
     raise ValueError('embed_full_resolution expects one image [1,3,H,W]')
   pad_h, pad_w = image.shape[-2:]
-  crop_h, crop_w = crop_size
-  ends_h = sliding_window_ends(pad_h, crop_h, stride[0])
-  ends_w = sliding_window_ends(pad_w, crop_w, stride[1])
   acc = None
   counts = torch.zeros((pad_h, pad_w), dtype=torch.float32, device=image.device)
-  windows = [(int(eh) - crop_h, int(ew) - crop_w) for eh in ends_h for ew in ends_w]
-  # the crops of one image go through the network together (eval mode: every sample is independent, the
-  # reference's one-crop-at-a-time loop gives the same embeddings) -- in the memory format of the model
-  first = next(embedding_model.parameters(), None)
-  nhwc = first is not None and first.is_cuda and first.dim() == 4 and \
-      first.is_contiguous(memory_format=torch.channels_last) and not first.is_contiguous()
-  group = 8
   with torch.no_grad():
-    for g0 in range(0, len(windows), group):
-      part = windows[g0:g0 + group]
-      crops = torch.cat([image[:, :, sh:sh + crop_h, sw:sw + crop_w] for sh, sw in part], 0)
-      if nhwc:
-        crops = crops.contiguous(memory_format=torch.channels_last)
-      embs = embedding_model.generate_embeddings({'image': crops}, resize_as_input=True)['embedding']
-      for (sh, sw), emb in zip(part, embs):
-        emb = emb.float().contiguous()
-        if acc is None:
-          acc = torch.zeros((emb.shape[0], pad_h, pad_w), dtype=torch.float32, device=image.device)
-        _ffi.window_accumulate(emb, acc, counts, sh, sw)
+    for _, sh, sw, emb in _window_embeddings(embedding_model, [image], crop_size, stride):
+      emb = emb[0].float().contiguous()
+      if acc is None:
+        acc = torch.zeros((emb.shape[0], pad_h, pad_w), dtype=torch.float32, device=image.device)
+      _ffi.window_accumulate(emb, acc, counts, sh, sw)
     acc /= counts
   return acc.unsqueeze(0)
 
@@ -64,10 +111,7 @@ def full_resolution_prototypes(embedding_model, image, semantic_label, crop_size
   `[1,3,Hp,Wp]`, `semantic_label` `[h,w]` of the un-padded (top-left) region ->
   (prototypes [M,C], majority label per prototype [M], cluster index map [h,w])."""
   h, w = semantic_label.shape[-2:]
-  pad_h, pad_w = image.shape[-2:]
-  fake = torch.full((1, pad_h, pad_w), semantic_ignore_index, dtype=torch.long,
-                    device=image.device)
-  fake[:, :h, :w] = 0                 # clustering ignores the padding (prototype.py:117-131)
+  fake = _padding_ignored_labels(image.shape[-2:], (h, w), semantic_ignore_index, image.device)
   embeddings = embed_full_resolution(embedding_model, image, crop_size, stride)
   with torch.no_grad():
     out = embedding_model.generate_clusters(embeddings, fake, fake)
@@ -113,25 +157,20 @@ def multiscale_prototypes(embedding_model, views, label_views, crop_size, stride
   labels are concatenated in view order (:204-206).  Returns a dict: `prototype` `[sum M, C]`, `prototype_label`
   `[sum M]` int64, `segment_counts` (list of M per view), `cluster_index` (list of `[rh * rw]` dense segment ids) and
   `majority_path` (`'hip_majority'`, or `'framework_majority'` where a view is outside the kernel's limits)."""
-  if not views:
-    raise ValueError('multiscale_prototypes needs at least one view')
-  if len(label_views) != len(views):
+  if views and len(label_views) != len(views):        # (an empty list is reported first, by _check_views)
     raise ValueError('multiscale_prototypes needs one label map per view (%d for %d views)' % (len(label_views), len(views)))
-  for (image, (rh, rw), _), label in zip(views, label_views):
-    if image.dim() != 4 or image.shape[0] != 1:
-      raise ValueError('multiscale_prototypes expects views of one image [1,3,Hp,Wp]')
+
+  def label_fits(i):
+    (rh, rw), label = views[i][1], label_views[i]
     if tuple(label.shape[-2:]) != (rh, rw) or label.numel() != rh * rw:
       raise ValueError('multiscale_prototypes: a %d x %d view with a label map of shape %r' % (rh, rw, tuple(label.shape)))
-    if not image.is_cuda:
-      raise _ffi.SpmlHipError('the HIP path needs GPU tensors (a view on %s); there is no CPU fallback' % image.device)
+  _check_views('multiscale_prototypes', views, label_fits)
   device = views[0][0].device
   prototypes, labels, counts, cluster_index = [], [], [], []
   majority_path = segsort_common.HIP_MAJORITY_PATH
   with torch.no_grad():
     for (image, (rh, rw), _), label in zip(views, label_views):
-      pad_h, pad_w = image.shape[-2:]
-      fake = torch.full((1, pad_h, pad_w), semantic_ignore_index, dtype=torch.long, device=device)
-      fake[:, :rh, :rw] = 0
+      fake = _padding_ignored_labels(image.shape[-2:], (rh, rw), semantic_ignore_index, device)
       embeddings = embed_full_resolution(embedding_model, image, crop_size, stride)
       out = embedding_model.generate_clusters(embeddings, fake, fake)
       protos = segsort_common.calculate_prototypes_from_labels(out['cluster_embedding'], out['cluster_index'])
@@ -164,9 +203,7 @@ def predict_full_resolution(embedding_model, prediction_model, image, valid_hw, 
   (what :231-237 turns into the label image), `semantic_score` (the retrieved labels, `[h*w,20]`)
   and `cluster_index` `[h*w]`."""
   h, w = valid_hw
-  pad_h, pad_w = image.shape[-2:]
-  fake = torch.full((1, pad_h, pad_w), semantic_ignore_index, dtype=torch.long, device=image.device)
-  fake[:, :h, :w] = 0
+  fake = _padding_ignored_labels(image.shape[-2:], valid_hw, semantic_ignore_index, image.device)
   embeddings = {'embedding': embed_full_resolution(embedding_model, image, crop_size, stride)}
   with torch.no_grad():
     embeddings.update(embedding_model.generate_clusters(embeddings['embedding'], fake, fake))
@@ -189,33 +226,15 @@ def window_counts(pad_size, crop_size, stride):
   return counts
 
 
-def _is_channels_last(embedding_model):
-  first = next(embedding_model.parameters(), None)
-  return first is not None and first.is_cuda and first.dim() == 4 and \
-      first.is_contiguous(memory_format=torch.channels_last) and not first.is_contiguous()
-
-
 def _accumulate_window_logits(embedding_model, prediction_model, images, canvases, crop_size, stride):
   """The sliding-window loop of inference_softmax.py:105-137 (= inference_softmax_msc.py:107-134 without the counts) over
   `images`, padded images `[1,3,Hp,Wp]` of ONE size: the crops of all of them -- image after image, each in the
   reference's window order -- go through the backbone in groups of 8, and each crop's logits are added into the canvas
   `[1,ncls,Hp,Wp]` of its own image, so the fp32 sum order of a pixel is the reference's.  Returns the name of the path
   `SoftmaxClassifier.accumulate_logits` took."""
-  pad_h, pad_w = images[0].shape[-2:]
-  crop_h, crop_w = crop_size
-  ends_h = sliding_window_ends(pad_h, crop_h, stride[0])
-  ends_w = sliding_window_ends(pad_w, crop_w, stride[1])
-  windows = [(k, int(eh) - crop_h, int(ew) - crop_w) for k in range(len(images)) for eh in ends_h for ew in ends_w]
-  nhwc = _is_channels_last(embedding_model)
-  group, path = 8, None
-  for g0 in range(0, len(windows), group):
-    part = windows[g0:g0 + group]
-    crops = torch.cat([images[k][:, :, sh:sh + crop_h, sw:sw + crop_w] for k, sh, sw in part], 0)
-    if nhwc:
-      crops = crops.contiguous(memory_format=torch.channels_last)
-    embs = embedding_model.generate_embeddings({'image': crops}, resize_as_input=True)['embedding']
-    for i, (k, sh, sw) in enumerate(part):
-      path = prediction_model.accumulate_logits(embs[i:i + 1], canvases[k], sh, sw)
+  path = None
+  for k, sh, sw, emb in _window_embeddings(embedding_model, images, crop_size, stride):
+    path = prediction_model.accumulate_logits(emb, canvases[k], sh, sw)
   return path
 
 
@@ -271,28 +290,16 @@ def predict_softmax_multiscale(embedding_model, prediction_model, views, image_h
   ops on the device instead (`framework_view_probs_accumulate`); `combine_path` names which of the two ran, as
   `head_path` does for the classifier head.  Returns `semantic_prob` `[ncls,h,w]` (the sum over the views, :147),
   `semantic_prediction` `[h,w]` int64, `head_path` and `combine_path`."""
-  if not views:
-    raise ValueError('predict_softmax_multiscale needs at least one view')
-  for image, _, _ in views:
-    if image.dim() != 4 or image.shape[0] != 1:
-      raise ValueError('predict_softmax_multiscale expects views of one image [1,3,Hp,Wp]')
-    if not image.is_cuda:
-      raise _ffi.SpmlHipError('the HIP path needs GPU tensors (a view on %s); there is no CPU fallback' % image.device)
+  _check_views('predict_softmax_multiscale', views)
   h, w = image_hw
   device = views[0][0].device
   ncls = prediction_model.num_classes
   combine_path = HIP_VIEW_PROBS_PATH if ncls <= MAX_VIEW_PROBS_CLASSES else FRAMEWORK_VIEW_PROBS_PATH
   combine = _ffi.view_probs_accumulate if combine_path == HIP_VIEW_PROBS_PATH else framework_view_probs_accumulate
   prediction_model.prepare_inference()          # once per image, as in predict_softmax_full_resolution
-  groups = []                                   # consecutive views of one padded size
-  for view in views:
-    if groups and groups[-1][0][0].shape == view[0].shape:
-      groups[-1].append(view)
-    else:
-      groups.append([view])
   acc, path = torch.zeros((ncls, h, w), dtype=torch.float32, device=device), None
   with torch.no_grad():
-    for part in groups:
+    for part in _group_by_padded_size(views):
       pad_h, pad_w = part[0][0].shape[-2:]
       cnt_y = torch.from_numpy(window_counts(pad_h, crop_size[0], stride[0])).to(device)
       cnt_x = torch.from_numpy(window_counts(pad_w, crop_size[1], stride[1])).to(device)
@@ -329,13 +336,7 @@ def _knn_view_votes_sum(who, embedding_model, prediction_model, views, image_hw,
   """The per-view work of `predict_knn_multiscale` and `pseudo_labels_knn_multiscale` (inference_msc.py:157-234 =
   pseudo_inference_crf_msc.py:172-249) -> (the un-divided `[ncls,h,w]` sum of the views' vote maps, combine_path, the
   per-view dense segment ids, the per-view `[m, 20]` retrieved labels).  `who` names the caller in the errors."""
-  if not views:
-    raise ValueError('%s needs at least one view' % who)
-  for image, _, _ in views:
-    if image.dim() != 4 or image.shape[0] != 1:
-      raise ValueError('%s expects views of one image [1,3,Hp,Wp]' % who)
-    if not image.is_cuda:
-      raise _ffi.SpmlHipError('the HIP path needs GPU tensors (a view on %s); there is no CPU fallback' % image.device)
+  _check_views(who, views)
   h, w = image_hw
   device = views[0][0].device
   ncls = int(num_classes)
@@ -520,16 +521,10 @@ def pseudo_labels_softmax(embedding_model, prediction_model, views, image_hw, la
   `[n,n]` (before the squarings) only with `return_transition`."""
   if combine not in _ffi.COMBINE_MODES:
     raise ValueError("combine must be 'prob_mean' or 'logit_mean'")
-  if not views:
-    raise ValueError('pseudo_labels_softmax needs at least one view')
-  if not label_tags.is_cuda:
+  if views and not label_tags.is_cuda:                # (an empty list is reported first, by _check_views)
     raise _ffi.SpmlHipError('the HIP path needs GPU tensors (label_tags on %s); there is no CPU fallback'
                             % label_tags.device)
-  for image, _, _ in views:
-    if image.dim() != 4 or image.shape[0] != 1:
-      raise ValueError('pseudo_labels_softmax expects views of one image [1,3,Hp,Wp]')
-    if not image.is_cuda:
-      raise _ffi.SpmlHipError('the HIP path needs GPU tensors (a view on %s); there is no CPU fallback' % image.device)
+  _check_views('pseudo_labels_softmax', views)
   h, w = image_hw
   out_hw = (h // 8, w // 8)
   if out_hw[0] < 1 or out_hw[1] < 1:
@@ -537,19 +532,11 @@ def pseudo_labels_softmax(embedding_model, prediction_model, views, image_hw, la
   n = out_hw[0] * out_hw[1]
   device = views[0][0].device
   ncls = prediction_model.num_classes
-  first = next(embedding_model.parameters(), None)
-  nhwc = first is not None and first.is_cuda and first.dim() == 4 and \
-      first.is_contiguous(memory_format=torch.channels_last) and not first.is_contiguous()
+  nhwc = _is_channels_last(embedding_model)
   prediction_model.prepare_inference()          # once per image, as in predict_softmax_full_resolution
-  groups = []                                   # consecutive views of one padded size
-  for view in views:
-    if groups and groups[-1][0][0].shape == view[0].shape:
-      groups[-1].append(view)
-    else:
-      groups.append([view])
   units, acc, path, b = None, torch.zeros((ncls, n), dtype=torch.float32, device=device), None, 0
   with torch.no_grad():
-    for part in groups:
+    for part in _group_by_padded_size(views):
       images = torch.cat([v[0] for v in part], 0) if len(part) > 1 else part[0][0]
       if nhwc:
         images = images.contiguous(memory_format=torch.channels_last)

@@ -322,7 +322,7 @@ def tiny_snapshot(tmp_path_factory):
 
 @pytest.mark.parametrize('name,num_views', [('prototype', 1), ('prototype_msc', 3)])
 def test_programs_write_banks_the_loader_reads(name, num_views, tiny_snapshot, tmp_path, capsys, monkeypatch):
-  import spml_amd.prototype_cli as cli
+  import spml_amd.inference_cli as cli
   cfg, snap = tiny_snapshot
   monkeypatch.setattr(cli, 'NUM_SYNTHETIC_IMAGES', 2)
   prog = load_program(name)

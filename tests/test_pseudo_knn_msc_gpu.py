@@ -397,6 +397,7 @@ def test_entry_point_builds_its_bank_and_writes_label_maps(tmp_path, capsys):
   import json
   import os
   from test_train_cli import YAML
+  from spml_amd import inference_cli
   yaml = (YAML.replace('panoptic_deeplab_50', 'panoptic_deeplab_101').replace('num_classes: 21', 'num_classes: 2')
           .replace('image_size: 97', 'image_size: 65').replace('- 97', '- 65'))
   yaml = yaml.replace('stride:\n    - 65\n    - 65', 'stride:\n    - 43\n    - 43')
@@ -413,7 +414,7 @@ def test_entry_point_builds_its_bank_and_writes_label_maps(tmp_path, capsys):
   torch.save({'embedding_model': resnet_101_deeplab(config).state_dict(), 'prediction_model': segsort(config).state_dict()},
              str(snap / 'model-{:d}.pth'.format(config.train.max_iteration - 1)))
   prog = load_program()
-  assert prog.NUM_SYNTHETIC_IMAGES == 4
+  assert inference_cli.NUM_SYNTHETIC_IMAGES == 4
   save = tmp_path / 'results'
   capsys.readouterr()
   prog.main(['--snapshot_dir', str(snap), '--cfg_path', str(cfg), '--save_dir', str(save), '--data_list', 'synthetic',
