@@ -1242,13 +1242,24 @@ struct NllWs {
   size_t eh, el, ph, pl, pth, ptl, eth, etl, gscale, rowscale, codes, pxcodes, coef, ownterm, dprows, tde, tdp, partial, partial_de, dp64, total;
 };
 
+// The environment switches of the loss, read once per call (the library keeps no state, and the tests change them
+// between calls): nothing else in this file reads the environment.
+struct NllEnv {
+  bool de3, dp3;             // SPML_NLL_DE3=0 / SPML_NLL_DP3=0: the 64-channel backward without nll_de3.hip / nll_dp3.hip
+  int64_t tcache_mb;         // SPML_NLL_TCACHE_MB: see tcache_strip_tiles
+};
+NllEnv nll_env() {
+  const auto off = [](const char* name) { const char* e = getenv(name); return e && e[0] == '0'; };
+  NllEnv env{!off("SPML_NLL_DE3"), !off("SPML_NLL_DP3"), 8192};
+  if (const char* e = getenv("SPML_NLL_TCACHE_MB")) { const long long v = atoll(e); if (v > 0) env.tcache_mb = v; }
+  return env;
+}
+
 // Wide embeddings: pixel tiles per strip of the backward.  The kept weight tiles cost strip x M x 4 B per
 // cache; a strip is as long as SPML_NLL_TCACHE_MB (default 8192 MB per cache) allows, so that the
 // workspace stays bounded when the global prototype count grows with the number of ranks (P x M x 8 B
 // would be 130 GB per GPU for BASELINE config 5 on 8 ranks).  A function of (P, M) only.
-inline int64_t tcache_strip_tiles(const NllDims& n) {
-  int64_t mb = 8192;
-  if (const char* e = getenv("SPML_NLL_TCACHE_MB")) { const long long v = atoll(e); if (v > 0) mb = v; }
+inline int64_t tcache_strip_tiles(const NllDims& n, int64_t mb) {
   int64_t tiles = (mb << 20) / (n.MT * 4096);
   tiles = tiles / 8 * 8;
   if (tiles < 8) tiles = 8;
@@ -1268,7 +1279,7 @@ __host__ __device__ inline int64_t dp_chunks(int64_t mgroups, int64_t PT) {
   return chunks;
 }
 
-NllWs nll_ws(const NllDims& n) {
+NllWs nll_ws(const NllDims& n, const NllEnv& env) {
   NllWs w{};
   size_t o = 0;
   const size_t e_std = (size_t)n.PT * n.KS * 512 * 2, p_std = (size_t)n.MT * n.KS * 512 * 2;
@@ -1290,7 +1301,7 @@ NllWs nll_ws(const NllDims& n) {
   w.dprows = o; o = align_up(o + nll_dp3_rows_bytes(n.PT), 256);
   w.tde = w.tdp = 0;
   if (n.KS > 17) {           // several d-chunk launches: the T tiles of the first one are kept (see NllArgs),
-    const size_t tiles = (size_t)tcache_strip_tiles(n) * n.MT * 4096;     // one strip of pixel tiles at a time
+    const size_t tiles = (size_t)tcache_strip_tiles(n, env.tcache_mb) * n.MT * 4096;     // one strip of pixel tiles at a time
     w.tde = o; o = align_up(o + tiles, 256);
     w.tdp = o; o = align_up(o + tiles, 256);
   }
@@ -1340,33 +1351,51 @@ int ks_bucket(int ks) {
 // pixel fragments + the transposed fragments of the chunk) only leaves room for 3, so the
 // backward kernels are launched once per chunk of 96 channels (each recomputes the
 // similarity tile -- "works on the stress configuration", not tuned for it).
-int dt_per_launch(int ks) { return ks <= 17 ? (ks + 1) / 2 : 3; }
+constexpr int dt_per_launch(int ks) { return ks <= 17 ? (ks + 1) / 2 : 3; }
 
-void launch_prep_std(const float* x, int64_t R, int D, int KS, float scale, _Float16* h,
-                     _Float16* l, hipStream_t s) {
-  const int64_t nfrag = ((R + 31) / 32) * KS;
-  hipLaunchKernelGGL(prep_std<false>, dim3((unsigned)((nfrag + 3) / 4)), dim3(256), 0, s, x, R, D, KS,
-                     scale, h, l);
-}
-void launch_prep_raw(const float* x, int64_t R, int D, int KS, float scale, _Float16* h,
-                     _Float16* l, hipStream_t s) {
-  const int64_t nfrag = ((R + 31) / 32) * KS;
-  hipLaunchKernelGGL(prep_std<true>, dim3((unsigned)((nfrag + 3) / 4)), dim3(256), 0, s, x, R, D, KS,
-                     scale, h, l);
-}
-void launch_prep_T(const float* x, int64_t R, int D, int DT, const float* rowscale,
-                   const float* gscale, _Float16* h, _Float16* l, hipStream_t s) {
-  const int64_t nfrag = ((R + 31) / 32) * DT * 2;
-  hipLaunchKernelGGL(prep_T<false>, dim3((unsigned)((nfrag + 3) / 4)), dim3(256), 0, s, x, R, D, DT,
-                     rowscale, gscale, 1.0f, h, l);
-}
-void launch_prep_T_raw(const float* x, int64_t R, int D, int DT, const float* rowscale,
-                       const float* gscale, float scale, _Float16* h, _Float16* l, hipStream_t s) {
-  const int64_t nfrag = ((R + 31) / 32) * DT * 2;
-  hipLaunchKernelGGL(prep_T<true>, dim3((unsigned)((nfrag + 3) / 4)), dim3(256), 0, s, x, R, D, DT,
-                     rowscale, gscale, scale, h, l);
+// the call's sizes with the template tile counts: KS its bucket, DT whole d-chunks (D > 528, no bucket: unchanged)
+NllDims nll_bucket_dims(int64_t P, int64_t M, int D) {
+  NllDims n = nll_dims(P, M, D);
+  if (const int ksb = ks_bucket(n.KS)) {
+    const int per = dt_per_launch(ksb);
+    n.KS = ksb;
+    n.DT = ((ksb + 1) / 2 + per - 1) / per * per;
+  }
+  return n;
 }
 
+// The fragment arrays are written here and read by the kernels: the call keeps them as NllArgs does, read-only.
+template <bool RAW>
+void launch_prep_std(const float* x, int64_t R, int D, int KS, float scale, const _Float16* h, const _Float16* l,
+                     hipStream_t s) {
+  const int64_t nfrag = ((R + 31) / 32) * KS;
+  hipLaunchKernelGGL(prep_std<RAW>, dim3((unsigned)((nfrag + 3) / 4)), dim3(256), 0, s, x, R, D, KS, scale,
+                     const_cast<_Float16*>(h), const_cast<_Float16*>(l));
+}
+// RAW: unscaled residuals and `scale`, else the pre-scaled form (scale 1)
+template <bool RAW>
+void launch_prep_T(const float* x, int64_t R, int D, int DT, const float* rowscale, const float* gscale, float scale,
+                   const _Float16* h, const _Float16* l, hipStream_t s) {
+  const int64_t nfrag = ((R + 31) / 32) * DT * 2;
+  hipLaunchKernelGGL(prep_T<RAW>, dim3((unsigned)((nfrag + 3) / 4)), dim3(256), 0, s, x, R, D, DT, rowscale, gscale,
+                     scale, const_cast<_Float16*>(h), const_cast<_Float16*>(l));
+}
+
+// The workspace arrays that both layouts (NllWs, NllBatchWs) have, bound into the kernel arguments.
+template <typename Ws>
+void bind_ws(NllArgs& a, unsigned char* base, const Ws& w, bool backward) {
+  const auto f16 = [&](size_t off) { return reinterpret_cast<const _Float16*>(base + off); };
+  a.eh = f16(w.eh); a.el = f16(w.el); a.ph = f16(w.ph); a.pl = f16(w.pl);
+  a.pth = f16(w.pth); a.ptl = f16(w.ptl); a.eth = f16(w.eth); a.etl = f16(w.etl);
+  a.pr_code_pad = reinterpret_cast<const int64_t*>(base + w.codes);
+  a.px_code_pad = reinterpret_cast<const int64_t*>(base + w.pxcodes);
+  a.coef = reinterpret_cast<const PixelCoef*>(base + w.coef);
+  a.gscale = reinterpret_cast<const float*>(base + w.gscale);
+  a.partial = reinterpret_cast<float*>(base + w.partial);
+  // deterministic mode: the prototype gradient is accumulated in fixed point (relative to gscale) and converted
+  // once, at the end of the call
+  a.d_protos64 = backward && w.dp64 ? reinterpret_cast<long long*>(base + w.dp64) : nullptr;
+}
 
 // ------------------------------- batched calls ------------------------------
 // N independent problems of one shape class (same D, kappa, mode, kernel instantiation) in one launch per kernel:
@@ -1545,12 +1574,7 @@ NllBatchWs nll_batch_ws(const NllBatchTotals& t, int n_problems, int D, int KS, 
 
 bool batched_supported(int D, int mode) {
   if (D <= 0 || mode < 0 || mode > (SPML_NLL_TAGSET | SPML_NLL_PLAIN | SPML_NLL_CODE32)) return false;
-  if (!(mode & SPML_NLL_CODE32) || ks_bucket((D + 15) / 16) != 5) return false;
-  // SPML_NLL_FWD2=0: the single-problem forward takes another kernel, which has no batched form.  It turns the
-  // batched backward off with it, although the single-problem backward does not read the switch: forward and
-  // backward are one autograd node, supported together or not at all (the op then takes the looped path)
-  const char* env2 = getenv("SPML_NLL_FWD2");
-  return !(env2 && env2[0] == '0');
+  return (mode & SPML_NLL_CODE32) && ks_bucket((D + 15) / 16) == 5;
 }
 
 int nll_batched(bool backward, const float* emb, const int64_t* own, const int64_t* px_code, const int64_t* p_off,
@@ -1575,27 +1599,17 @@ int nll_batched(bool backward, const float* emb, const int64_t* own, const int64
   NllArgs& a = b.a;
   a.n = nll_dims(0, 0, D);
   a.n.KS = KS; a.n.DT = DT;
-  a.eh = reinterpret_cast<_Float16*>(base + w.eh); a.el = reinterpret_cast<_Float16*>(base + w.el);
-  a.ph = reinterpret_cast<_Float16*>(base + w.ph); a.pl = reinterpret_cast<_Float16*>(base + w.pl);
-  a.pth = reinterpret_cast<_Float16*>(base + w.pth); a.ptl = reinterpret_cast<_Float16*>(base + w.ptl);
-  a.eth = reinterpret_cast<_Float16*>(base + w.eth); a.etl = reinterpret_cast<_Float16*>(base + w.etl);
+  bind_ws(a, base, w, backward);
   a.own = own; a.px_code = px_code; a.pr_code = pr_code;
-  a.pr_code_pad = reinterpret_cast<int64_t*>(base + w.codes);
-  a.px_code_pad = reinterpret_cast<int64_t*>(base + w.pxcodes);
-  a.coef = reinterpret_cast<PixelCoef*>(base + w.coef);
   a.kappa = kappa;
   a.kappa_log2e = kappa * 1.4426950408889634f;
   a.mode = mode; a.nll = nll; a.stats = stats; a.d_nll = d_nll; a.d_emb = d_emb; a.d_protos = d_protos;
-  a.gscale = reinterpret_cast<float*>(base + w.gscale);
-  a.partial = reinterpret_cast<float*>(base + w.partial);
-  a.d_protos64 = backward && w.dp64 ? reinterpret_cast<long long*>(base + w.dp64) : nullptr;
-  a.depth = 2;                                                // (KS <= 5: see SPML_BWD_LAUNCH of the single-problem call)
-  if (const char* e_ = getenv("SPML_NLL_DEPTH_BWD")) { const int v_ = atoi(e_); if (v_ >= 2 && v_ <= 3) a.depth = v_; }
+  a.depth = 2;                                                // (KS <= 5: see launch_bwd_pair of the single-problem call)
   a.dt0 = 0; a.dt_all = DT;
   b.emb = emb; b.protos = protos;
   b.rowscale = reinterpret_cast<float*>(base + w.rowscale);
   if (a.d_protos64 &&
-      hipMemsetAsync(base + w.dp64, 0, (size_t)t.M * D * 8, s) != hipSuccess) return SPML_ERR_LAUNCH;
+      hipMemsetAsync(a.d_protos64, 0, (size_t)t.M * D * 8, s) != hipSuccess) return SPML_ERR_LAUNCH;
 
   constexpr int LDS_F = kFwd2TilesPerChunk * 128 + 2 * 2 * 2 * KS * 1024;
   constexpr int SLOT_DE = (2 * KS + 1 + 4 * DT) * 1024, SLOT_DP = (2 * KS + 2 + 4 * DT) * 1024;
@@ -1626,16 +1640,8 @@ int nll_batched(bool backward, const float* emb, const int64_t* own, const int64
       hipLaunchKernelGGL(prep_std_batched<true>, dim3(blocks(PT * KS, 4), 1, z), dim3(256), 0, s, b, 1, 8.0f);
       hipLaunchKernelGGL(prep_std_batched<true>, dim3(blocks(MT * KS, 4), 1, z), dim3(256), 0, s, b, 0,
                          a.kappa_log2e * 0.125f);
-      const dim3 grid(blocks(PT, 8), (unsigned)max_chunks, z);
-      if (tag) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_fwd2_batched<KS, 2, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS_F);
-        hipLaunchKernelGGL((nll_fwd2_batched<KS, 2, true>), grid, dim3(256), LDS_F, s, b);
-      } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_fwd2_batched<KS, 2, false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS_F);
-        hipLaunchKernelGGL((nll_fwd2_batched<KS, 2, false>), grid, dim3(256), LDS_F, s, b);
-      }
+      launch_dyn(tag ? nll_fwd2_batched<KS, 2, true> : nll_fwd2_batched<KS, 2, false>,
+                 dim3(blocks(PT, 8), (unsigned)max_chunks, z), LDS_F, s, b);
       hipLaunchKernelGGL(nll_finalize_batched, dim3(blocks(max_p, 256), 1, z), dim3(256), 0, s, b);
       continue;
     }
@@ -1650,28 +1656,288 @@ int nll_batched(bool backward, const float* emb, const int64_t* own, const int64
     hipLaunchKernelGGL(prep_T_batched, dim3(blocks(MT * DT * 2, 4), 1, z), dim3(256), 0, s, b, 0);
     hipLaunchKernelGGL(prep_T_batched, dim3(blocks(PT * DT * 2, 4), 1, z), dim3(256), 0, s, b, 1);
     hipLaunchKernelGGL(pad_codes_batched, dim3(blocks(PT * 32, 256), 1, z), dim3(256), 0, s, b, 1);
-    if (tag) hipLaunchKernelGGL(coef_batched<true>, dim3(blocks(PT * 32, 256), 1, z), dim3(256), 0, s, b);
-    else hipLaunchKernelGGL(coef_batched<false>, dim3(blocks(PT * 32, 256), 1, z), dim3(256), 0, s, b);
-    const dim3 grid_de(blocks(PT, 4), 1, z), grid_dp(blocks(MT, 4), (unsigned)max_dpc, z);
-    if (tag) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_bwd_de_batched<KS, DT, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, a.depth * SLOT_DE);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_bwd_dp_batched<KS, DT, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, a.depth * SLOT_DP);
-      hipLaunchKernelGGL((nll_bwd_de_batched<KS, DT, true>), grid_de, dim3(256), a.depth * SLOT_DE, s, b);
-      hipLaunchKernelGGL((nll_bwd_dp_batched<KS, DT, true>), grid_dp, dim3(256), a.depth * SLOT_DP, s, b);
-    } else {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_bwd_de_batched<KS, DT, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, a.depth * SLOT_DE);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_bwd_dp_batched<KS, DT, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, a.depth * SLOT_DP);
-      hipLaunchKernelGGL((nll_bwd_de_batched<KS, DT, false>), grid_de, dim3(256), a.depth * SLOT_DE, s, b);
-      hipLaunchKernelGGL((nll_bwd_dp_batched<KS, DT, false>), grid_dp, dim3(256), a.depth * SLOT_DP, s, b);
-    }
+    hipLaunchKernelGGL(tag ? coef_batched<true> : coef_batched<false>, dim3(blocks(PT * 32, 256), 1, z), dim3(256), 0,
+                       s, b);
+    launch_dyn(tag ? nll_bwd_de_batched<KS, DT, true> : nll_bwd_de_batched<KS, DT, false>, dim3(blocks(PT, 4), 1, z),
+               a.depth * SLOT_DE, s, b);
+    launch_dyn(tag ? nll_bwd_dp_batched<KS, DT, true> : nll_bwd_dp_batched<KS, DT, false>,
+               dim3(blocks(MT, 4), (unsigned)max_dpc, z), a.depth * SLOT_DP, s, b);
     if (a.d_protos64)
       hipLaunchKernelGGL(nll_dpr_from_fix_batched, dim3(blocks(max_m * D, 256), 1, z), dim3(256), 0, s, b);
   }
   return launch_status();
+}
+
+// ------------------------------- single-problem call ------------------------
+// What the host paths of one call share: the kernels' arguments, and what only the host needs.
+struct NllCall {
+  NllArgs a;
+  const float *emb, *protos;           // [P][D], [M][D]
+  unsigned char* ws;
+  NllWs w;                             // offsets into ws
+  NllEnv env;
+  hipStream_t s;
+};
+
+// f(std::integral_constant<int, KS>) for the call's bucket: the kernels take the k-step count as a template parameter
+template <typename F>
+int with_ks(int ks, F&& f) {
+  switch (ks) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 9: return f(std::integral_constant<int, 9>{});
+    case 17: return f(std::integral_constant<int, 17>{});
+    case 33: return f(std::integral_constant<int, 33>{});
+    default: return SPML_ERR_UNSUPPORTED;
+  }
+}
+
+// std fragments of the pixels and the prototypes.  RAW: unscaled residuals (the v2 / v3 kernels), pixels x 2^3 and
+// prototypes x kappa * log2(e) * 2^-3 (exact powers of two); else the round-2 form, kappa * log2(e) folded into the
+// prototype fragments: the MFMA result is the exp2 argument
+template <bool RAW>
+void prep_std_fragments(const NllCall& c) {
+  const NllArgs& a = c.a;
+  launch_prep_std<RAW>(c.emb, a.n.P, a.n.D, a.n.KS, RAW ? 8.0f : 1.0f, a.eh, a.el, c.s);
+  launch_prep_std<RAW>(c.protos, a.n.M, a.n.D, a.n.KS, RAW ? a.kappa_log2e * 0.125f : a.kappa_log2e, a.ph, a.pl, c.s);
+}
+
+int nll_forward(NllCall& c) {
+  NllArgs& a = c.a;
+  const NllDims& n = a.n;
+  const bool tag = (a.mode & SPML_NLL_TAGSET) != 0, c32 = (a.mode & SPML_NLL_CODE32) != 0;
+  if (n.KS <= 5 && c32) {              // v2 forward: narrow embeddings, 32-bit codes
+    prep_std_fragments<true>(c);
+    const int64_t chunks = fwd2_chunks(n);
+    const dim3 grid((unsigned)((n.PT + 7) / 8), (unsigned)chunks);      // 4 waves x 2 pixel tiles
+    const int rc = with_ks(n.KS, [&](auto K) -> int {
+      constexpr int KS = decltype(K)::value;
+      if constexpr (KS <= 5) {
+        constexpr int MTB = KS <= 4 ? 4 : 2;
+        constexpr int LDS2 = kFwd2TilesPerChunk * 128 + 2 * MTB * 2 * KS * 1024;
+        launch_dyn(tag ? nll_fwd2<KS, MTB, true> : nll_fwd2<KS, MTB, false>, grid, LDS2, c.s, a);
+        return SPML_OK;
+      } else {
+        return SPML_ERR_UNSUPPORTED;
+      }
+    });
+    if (rc != SPML_OK) return rc;
+    hipLaunchKernelGGL(nll_finalize, dim3((unsigned)((n.P + 255) / 256)), dim3(256), 0, c.s, a.partial, (int)chunks,
+                       n.P, n.PT * 32, (a.mode & SPML_NLL_PLAIN) ? 1 : 0, a.nll, a.stats);
+    return launch_status();
+  }
+  prep_std_fragments<false>(c);
+  return with_ks(n.KS, [&](auto K) -> int {
+    constexpr int KS = decltype(K)::value;
+    constexpr int SLOT_F = (2 * KS + 1) * 1024;
+    // narrow embeddings: a 2-slot ring (18 KB) lets five workgroups share a CU -- 5-7 % faster than 4 slots
+    constexpr int DEPTH = KS <= 5 ? 2 : (4 * SLOT_F <= 160 * 1024 ? 4 : 2);
+    a.depth_fwd = DEPTH;
+    const dim3 grid((unsigned)((n.PT + 3) / 4));                        // one pixel tile per wave
+    // (32-bit codes at KS <= 5 went to nll_fwd2 above: those forms of nll_fwd do not exist)
+    if constexpr (KS > 5) {
+      if (c32) {
+        launch_dyn(tag ? nll_fwd<KS, 1, true, true> : nll_fwd<KS, 1, false, true>, grid, DEPTH * SLOT_F, c.s, a);
+        return launch_status();
+      }
+    }
+    launch_dyn(tag ? nll_fwd<KS, 1, true, false> : nll_fwd<KS, 1, false, false>, grid, DEPTH * SLOT_F, c.s, a);
+    return launch_status();
+  });
+}
+
+// One launch of the round-2 gradient kernels over the pixel tiles [a.spt0, a.spt1) and the d-tiles [a.dt0, a.dt0 + DT).
+// TM: 0, or the wide-embedding forms (1 keeps the weight tiles, 2 reads them back).
+// SPML_NLL_CODE32 only selects the forward variant: the backward kernels measured 6-12 % slower with 32-bit
+// predicates (profiles/r02_nll_scaling.md), the 64-bit form is exact for both.
+template <int KS, int DT, int TM>
+int launch_bwd_pair(NllArgs& a, hipStream_t s) {
+  constexpr int STD_DE = TM == 2 ? 0 : 2 * KS + 1, STD_DP = TM == 2 ? 0 : 2 * KS + 2;
+  constexpr int SLOT_DE = (STD_DE + 4 * DT) * 1024, SLOT_DP = (STD_DP + 4 * DT) * 1024;
+  // narrow embeddings: 2 slots (36 KB) -> three workgroups of the dE kernel per CU (3-4 % faster);
+  // otherwise 3 slots while two workgroups still fit
+  constexpr int DEPTH = KS <= 5 ? 2 : (3 * SLOT_DP <= 80 * 1024 ? 3 : 2);
+  a.depth = DEPTH;
+  if (2 * SLOT_DP > 160 * 1024) return SPML_ERR_UNSUPPORTED;
+  const bool tag = (a.mode & SPML_NLL_TAGSET) != 0;
+  const int64_t mgroups = (a.mt_grad + 3) / 4;
+  if (!a.skip_de)
+    launch_dyn(tag ? nll_bwd_de<KS, DT, true, false, TM> : nll_bwd_de<KS, DT, false, false, TM>,
+               dim3((unsigned)((a.spt1 - a.spt0 + 3) / 4)), DEPTH * SLOT_DE, s, a);
+  if (mgroups > 0)
+    launch_dyn(tag ? nll_bwd_dp<KS, DT, true, false, TM> : nll_bwd_dp<KS, DT, false, false, TM>,
+               dim3((unsigned)mgroups, (unsigned)a.chunks), DEPTH * SLOT_DP, s, a);
+  return SPML_OK;
+}
+
+// Wide embeddings (KS = 33), strip by strip of pixel tiles (bounded workspace): the first launch (3 d-tiles) computes
+// the weight tiles and keeps them, the others read them back and contract 7 d-tiles each (no similarity GEMM, no
+// resident pixel fragments: the registers go to the accumulators)
+int nll_bwd_wide_strips(NllCall& c) {
+  constexpr int KS = 33, DT = dt_per_launch(KS);
+  NllArgs& a = c.a;
+  const NllDims& n = a.n;
+  const int64_t strip = tcache_strip_tiles(n, c.env.tcache_mb), chunks = a.chunks;
+  for (int64_t t0 = 0; t0 < n.PT; t0 += strip) {
+    a.spt0 = t0;
+    a.spt1 = t0 + strip < n.PT ? t0 + strip : n.PT;
+    const int64_t ch = std::min(chunks, (a.spt1 - a.spt0 + 7) / 8);
+    a.chunks = (int)(ch < 1 ? 1 : ch);
+    a.dt0 = 0;
+    int rc = launch_bwd_pair<KS, DT, 1>(a, c.s);
+    for (int dt0 = DT; rc == SPML_OK && 32 * dt0 < n.D; dt0 += 7) {
+      a.dt0 = dt0;
+      rc = launch_bwd_pair<KS, 7, 2>(a, c.s);
+    }
+    if (rc != SPML_OK) return rc;
+  }
+  return SPML_OK;
+}
+
+// The round-2 kernels nll_bwd_de (unless a.skip_de) and nll_bwd_dp: one launch per d-chunk
+int nll_bwd_round2(NllCall& c) {
+  NllArgs& a = c.a;
+  a.dt_all = a.n.DT;
+  return with_ks(a.n.KS, [&](auto K) -> int {
+    constexpr int KS = decltype(K)::value, DT = dt_per_launch(KS);
+    if constexpr (KS > 17) {
+      if (a.tcache_de != nullptr && 32 * DT < a.n.D) return nll_bwd_wide_strips(c);
+    }
+    for (int dt0 = 0; dt0 < a.n.DT && 32 * dt0 < a.n.D; dt0 += DT) {
+      a.dt0 = dt0;
+      const int rc = launch_bwd_pair<KS, DT, 0>(a, c.s);
+      if (rc != SPML_OK) return rc;
+    }
+    return SPML_OK;
+  });
+}
+
+// Embedding gradient of narrow embeddings with 32-bit codes, on the v2 kernel or (v3) the pipelined one of
+// nll_de3.hip: unscaled residuals, transposed prototypes x 2^3 (folded back in nll_de_finalize)
+int nll_bwd_de_v2(NllCall& c, bool v3, float* own_term) {
+  NllArgs& a = c.a;
+  const NllDims& n = a.n;
+  const bool tag = (a.mode & SPML_NLL_TAGSET) != 0;
+  prep_std_fragments<true>(c);
+  launch_prep_T<true>(c.protos, n.M, n.D, n.DT, nullptr, nullptr, 8.0f, a.pth, a.ptl, c.s);
+  a.partial_de = reinterpret_cast<float*>(c.ws + c.w.partial_de);
+  const int rows = bwd2_rows(n);
+  hipLaunchKernelGGL(tag ? own_term_kernel<true> : own_term_kernel<false>, dim3((unsigned)((n.PT * 32 + 255) / 256)),
+                     dim3(256), 0, c.s, a.stats, a.own, a.px_code, a.pr_code, c.emb, c.protos, n.P, n.PT * 32, n.M, n.D,
+                     a.kappa_log2e, own_term);
+  if (v3) {
+    const int rc = nll_launch_bwd_de3(a, rows, c.s);
+    if (rc != SPML_OK) return rc;
+  } else {
+    const int rc = with_ks(n.KS, [&](auto K) -> int {
+      constexpr int KS = decltype(K)::value;
+      if constexpr (KS <= 4) {
+        constexpr int DT = (KS + 1) / 2;
+        constexpr int LDSB = kFwd2TilesPerChunk * 128 + 2 * 2 * (2 * KS + 4 * DT) * 1024;
+        launch_dyn(tag ? nll_bwd_de2<KS, DT, 2, true> : nll_bwd_de2<KS, DT, 2, false>,
+                   dim3((unsigned)((n.PT + 7) / 8), (unsigned)rows), LDSB, c.s, a);
+        return SPML_OK;
+      } else {
+        return SPML_ERR_UNSUPPORTED;
+      }
+    });
+    if (rc != SPML_OK) return rc;
+  }
+  hipLaunchKernelGGL(nll_de_finalize, dim3((unsigned)n.PT), dim3(256), (size_t)32 * (n.DT * 32 + 1) * sizeof(float), c.s,
+                     a.partial_de, rows, n.P, n.PT, n.D, n.DT, a.d_nll, a.kappa * 0.125f, a.d_emb,
+                     (const float*)own_term, a.own, c.protos, 8.0f, a.coef);
+  return SPML_OK;
+}
+
+// Prototype gradient on the pipelined kernel of nll_dp3.hip: it takes the std fragments nll_bwd_de_v2 left; the
+// transposed pixel fragments with unscaled residuals, x 2^8
+int nll_bwd_dp_v3(NllCall& c, float* rowscale, const float* own_term) {
+  NllArgs& a = c.a;
+  hipLaunchKernelGGL(rowscale_ts_kernel, dim3((unsigned)((a.n.P + 255) / 256)), dim3(256), 0, c.s, a.d_nll, a.kappa,
+                     a.coef, a.n.P, rowscale);
+  launch_prep_T<true>(c.emb, a.n.P, a.n.D, a.n.DT, rowscale, a.gscale, 16.0f, a.eth, a.etl, c.s);
+  return nll_launch_bwd_dp3(a, own_term, c.emb, reinterpret_cast<float*>(c.ws + c.w.dprows), c.s);
+}
+
+// prototypes [0, m_grad) receive a gradient (the rest, e.g. a detached memory bank, is skipped)
+int nll_backward(NllCall& c, int64_t m_grad) {
+  NllArgs& a = c.a;
+  const NllDims& n = a.n;
+  hipStream_t s = c.s;
+  const bool c32 = (a.mode & SPML_NLL_CODE32) != 0;
+  float* gscale = reinterpret_cast<float*>(c.ws + c.w.gscale);
+  float* rowscale = reinterpret_cast<float*>(c.ws + c.w.rowscale);
+  float* own_term = reinterpret_cast<float*>(c.ws + c.w.ownterm);
+  if (a.d_protos64 && hipMemsetAsync(a.d_protos64, 0, (size_t)n.M * n.D * 8, s) != hipSuccess) return SPML_ERR_LAUNCH;
+  hipLaunchKernelGGL(max_abs_pow2, dim3(1), dim3(1024), 0, s, a.d_nll, n.P, gscale);
+  hipLaunchKernelGGL(rowscale_kernel, dim3((unsigned)((n.P + 255) / 256)), dim3(256), 0, s, a.d_nll, a.kappa, n.P,
+                     rowscale);
+  // gscale bounds |g|; kappa is folded into rowscale (kappa * g / gscale stays O(kappa))
+  launch_prep_T<false>(c.protos, n.M, n.D, n.DT, nullptr, nullptr, 1.0f, a.pth, a.ptl, s);
+  // v2 / v3 paths: narrow embeddings, 32-bit codes; the pipelined kernels (64 channels) prepare their own pixel fragments
+  const bool de2 = n.KS <= 4 && c32;
+  const bool v3 = de2 && n.KS == 4 && c.env.de3, dp3 = v3 && c.env.dp3;
+  if (!dp3) launch_prep_T<false>(c.emb, n.P, n.D, n.DT, rowscale, gscale, 1.0f, a.eth, a.etl, s);
+  a.tcache_de = c.w.tde ? reinterpret_cast<float*>(c.ws + c.w.tde) : nullptr;
+  a.tcache_dp = c.w.tdp ? reinterpret_cast<float*>(c.ws + c.w.tdp) : nullptr;
+  hipLaunchKernelGGL(pad_codes_kernel, dim3((unsigned)((n.PT * 32 + 255) / 256)), dim3(256), 0, s, a.px_code, n.P,
+                     n.PT * 32, const_cast<int64_t*>(a.px_code_pad));
+  hipLaunchKernelGGL((a.mode & SPML_NLL_TAGSET) ? coef_kernel<true> : coef_kernel<false>,
+                     dim3((unsigned)((n.PT * 32 + 255) / 256)), dim3(256), 0, s, a.stats, a.own, a.px_code, a.pr_code,
+                     n.M, n.P, n.PT * 32, const_cast<PixelCoef*>(a.coef));
+  const int64_t mg = m_grad < 0 || m_grad > n.M ? n.M : m_grad;
+  a.mt_grad = (mg + 31) / 32;
+  a.chunks = (int)dp_chunks((a.mt_grad + 3) / 4, n.PT);
+  a.spt0 = 0;
+  a.spt1 = n.PT;
+
+  int rc = de2 ? nll_bwd_de_v2(c, v3, own_term) : SPML_OK;
+  if (rc != SPML_OK) return rc;
+  if (dp3) {
+    rc = nll_bwd_dp_v3(c, rowscale, own_term);
+  } else {
+    // after the v2 / v3 dE kernel too: the round-2 dPr kernel takes the pre-scaled fragments (a v2 form of it -- two
+    // prototype tiles per wave, pixel tiles streamed -- measured slower: 19 vs 15.5 ms for the live third at
+    // M = 139 k, profiles/r03_nll.md)
+    prep_std_fragments<false>(c);
+    a.skip_de = de2 ? 1 : 0;
+    rc = nll_bwd_round2(c);
+  }
+  if (rc != SPML_OK) return rc;
+  if (a.d_protos64)                    // only after a successful launch sequence
+    hipLaunchKernelGGL(nll_dpr_from_fix, dim3((unsigned)((n.M * n.D + 255) / 256)), dim3(256), 0, s, a.d_protos64,
+                       n.M * n.D, (const float*)gscale, a.d_protos);
+  return launch_status();
+}
+
+int nll_single(bool backward, const float* emb, const int64_t* own, const int64_t* px_code, int64_t P,
+               const float* protos, const int64_t* pr_code, int64_t M, int D, float kappa, int mode, float* nll,
+               float* stats, const float* d_nll, float* d_emb, float* d_protos, int64_t m_grad, void* ws,
+               size_t ws_bytes, hipStream_t s) {
+  if (!emb || !own || !px_code || !protos || !pr_code || P < 0 || M <= 0 || D <= 0 || !stats)
+    return SPML_ERR_INVALID_ARG;
+  if (mode < 0 || mode > (SPML_NLL_TAGSET | SPML_NLL_PLAIN | SPML_NLL_CODE32)) return SPML_ERR_INVALID_ARG;
+  if (backward ? (!d_nll || !d_emb || !d_protos) : !nll) return SPML_ERR_INVALID_ARG;
+  if (!ks_bucket((D + 15) / 16)) return SPML_ERR_UNSUPPORTED;            // D <= 528
+  NllCall c{};
+  NllArgs& a = c.a;
+  a.n = nll_bucket_dims(P, M, D);
+  c.env = nll_env();
+  c.w = nll_ws(a.n, c.env);
+  if (!ws || ws_bytes < c.w.total) return SPML_ERR_WORKSPACE;
+  if (P == 0) return SPML_OK;
+  c.emb = emb; c.protos = protos; c.s = s;
+  c.ws = static_cast<unsigned char*>(ws);
+  bind_ws(a, c.ws, c.w, backward);
+  a.own = own; a.px_code = px_code; a.pr_code = pr_code;
+  a.kappa = kappa;
+  a.kappa_log2e = kappa * 1.4426950408889634f;
+  a.mode = mode; a.nll = nll; a.stats = stats; a.d_nll = d_nll; a.d_emb = d_emb; a.d_protos = d_protos;
+  hipLaunchKernelGGL(pad_codes_kernel, dim3((unsigned)((a.n.MT * 32 + 255) / 256)), dim3(256), 0, s, pr_code, M,
+                     a.n.MT * 32, const_cast<int64_t*>(a.pr_code_pad));
+  return backward ? nll_backward(c, m_grad) : nll_forward(c);
 }
 
 }  // namespace
@@ -1681,308 +1947,7 @@ using namespace spml;
 
 extern "C" size_t spml_segsort_nll_workspace_bytes(int64_t P, int64_t M, int D) {
   if (P < 0 || M <= 0 || D <= 0) return 0;
-  NllDims n = nll_dims(P, M, D);
-  if (ks_bucket(n.KS)) {
-    n.KS = ks_bucket(n.KS);
-    const int per = dt_per_launch(n.KS);
-    n.DT = ((n.KS + 1) / 2 + per - 1) / per * per;      // whole chunks
-  }
-  return nll_ws(n).total;
-}
-
-static int nll_common(bool backward, const float* emb, const int64_t* own,
-                      const int64_t* px_code, int64_t P, const float* protos,
-                      const int64_t* pr_code, int64_t M, int D, float kappa, int mode,
-                      float* nll, float* stats, const float* d_nll, float* d_emb,
-                      float* d_protos, int64_t m_grad, void* ws, size_t ws_bytes, hipStream_t s) {
-  if (!emb || !own || !px_code || !protos || !pr_code || P < 0 || M <= 0 || D <= 0 || !stats)
-    return SPML_ERR_INVALID_ARG;
-  if (mode < 0 || mode > (SPML_NLL_TAGSET | SPML_NLL_PLAIN | SPML_NLL_CODE32)) return SPML_ERR_INVALID_ARG;
-  if (backward ? (!d_nll || !d_emb || !d_protos) : !nll) return SPML_ERR_INVALID_ARG;
-  NllDims n = nll_dims(P, M, D);
-  const int ksb = ks_bucket(n.KS);
-  if (!ksb) return SPML_ERR_UNSUPPORTED;                    // D <= 528
-  n.KS = ksb;
-  const int dt_launch = dt_per_launch(ksb);                 // template tile counts
-  n.DT = ((ksb + 1) / 2 + dt_launch - 1) / dt_launch * dt_launch;
-  const NllWs w = nll_ws(n);
-  if (!ws || ws_bytes < w.total) return SPML_ERR_WORKSPACE;
-  if (P == 0) return SPML_OK;
-  unsigned char* b = static_cast<unsigned char*>(ws);
-  NllArgs a{};
-  a.n = n;
-  _Float16* eh = reinterpret_cast<_Float16*>(b + w.eh);
-  _Float16* el = reinterpret_cast<_Float16*>(b + w.el);
-  _Float16* ph = reinterpret_cast<_Float16*>(b + w.ph);
-  _Float16* pl = reinterpret_cast<_Float16*>(b + w.pl);
-  a.eh = eh; a.el = el; a.ph = ph; a.pl = pl;
-  a.own = own; a.px_code = px_code; a.pr_code = pr_code;
-  a.kappa = kappa;
-  a.kappa_log2e = kappa * 1.4426950408889634f;
-  a.mode = mode; a.nll = nll; a.stats = stats; a.d_nll = d_nll; a.d_emb = d_emb;
-  a.d_protos = d_protos;
-  int64_t* codes = reinterpret_cast<int64_t*>(b + w.codes);
-  a.pr_code_pad = codes;
-  hipLaunchKernelGGL(pad_codes_kernel, dim3((unsigned)((n.MT * 32 + 255) / 256)), dim3(256), 0, s,
-                     pr_code, M, n.MT * 32, codes);
-  // v2 forward (narrow embeddings, 32-bit codes; SPML_NLL_FWD2=0 selects the round-2 kernels): unscaled
-  // residuals, pixels x 2^3 and prototypes x kappa * log2(e) * 2^-3 (exact powers of two)
-  const char* env2 = getenv("SPML_NLL_FWD2");
-  const bool fwd2 = !backward && n.KS <= 5 && (mode & SPML_NLL_CODE32) && !(env2 && env2[0] == '0');
-  if (fwd2) {
-    launch_prep_raw(emb, P, D, n.KS, 8.0f, eh, el, s);
-    launch_prep_raw(protos, M, D, n.KS, a.kappa_log2e * 0.125f, ph, pl, s);
-    a.partial = reinterpret_cast<float*>(b + w.partial);
-    const int64_t chunks = fwd2_chunks(n);
-    const unsigned groups = (unsigned)((n.PT + 7) / 8);         // 4 waves x 2 pixel tiles
-#define SPML_FWD2(KS_, MTB_)                                                                        \
-    {                                                                                               \
-      constexpr int LDS2 = kFwd2TilesPerChunk * 128 + 2 * MTB_ * 2 * KS_ * 1024;                                         \
-      if (mode & SPML_NLL_TAGSET) {                                                                 \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_fwd2<KS_, MTB_, true>),        \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS2);                \
-        hipLaunchKernelGGL((nll_fwd2<KS_, MTB_, true>), dim3(groups, (unsigned)chunks), dim3(256), LDS2, s, a); \
-      } else {                                                                                      \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_fwd2<KS_, MTB_, false>),       \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS2);                \
-        hipLaunchKernelGGL((nll_fwd2<KS_, MTB_, false>), dim3(groups, (unsigned)chunks), dim3(256), LDS2, s, a); \
-      }                                                                                             \
-    }
-    switch (n.KS) {
-      case 2: SPML_FWD2(2, 4); break;
-      case 3: SPML_FWD2(3, 4); break;
-      case 4: SPML_FWD2(4, 4); break;
-      default: SPML_FWD2(5, 2); break;
-    }
-#undef SPML_FWD2
-    hipLaunchKernelGGL(nll_finalize, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, a.partial, (int)chunks, P,
-                       n.PT * 32, (mode & SPML_NLL_PLAIN) ? 1 : 0, nll, stats);
-    return launch_status();
-  }
-  // kappa * log2(e) is folded into the prototype fragments: the MFMA result is the exp2 argument
-  launch_prep_std(emb, P, D, n.KS, 1.0f, eh, el, s);
-  launch_prep_std(protos, M, D, n.KS, a.kappa_log2e, ph, pl, s);
-
-#define SPML_KS_SWITCH(MACRO)             \
-  switch (n.KS) {                         \
-    case 2: MACRO(2); break;              \
-    case 3: MACRO(3); break;              \
-    case 4: MACRO(4); break;              \
-    case 5: MACRO(5); break;              \
-    case 9: MACRO(9); break;              \
-    case 17: MACRO(17); break;            \
-    case 33: MACRO(33); break;            \
-    default: return SPML_ERR_UNSUPPORTED; \
-  }
-  if (!backward) {
-#define SPML_FWD_ONE(KS_, TAG_, C32_)                                                      \
-    if (((mode & SPML_NLL_TAGSET) != 0) == TAG_ && ((mode & SPML_NLL_CODE32) != 0) == C32_) { \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_fwd<KS_, NB, TAG_, C32_>), \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_f);        \
-      hipLaunchKernelGGL((nll_fwd<KS_, NB, TAG_, C32_>), dim3((unsigned)((waves + 3) / 4)), dim3(256), lds_f, s, a); \
-    }
-#define SPML_FWD(KS_)                                                                      \
-  {                                                                                        \
-    constexpr int NB = 1;                                                                  \
-    constexpr int SLOT_F = (2 * KS_ + 1) * 1024;                                           \
-    /* narrow embeddings: a 2-slot ring (18 KB) lets five workgroups share a CU -- 5-7 % faster than 4 slots */ \
-    a.depth_fwd = KS_ <= 5 ? 2 : (4 * SLOT_F <= 160 * 1024 ? 4 : 2);                       \
-    if (const char* e_ = getenv("SPML_NLL_DEPTH_FWD")) { const int v_ = atoi(e_); if (v_ >= 2 && v_ <= 4) a.depth_fwd = v_; } \
-    const int lds_f = a.depth_fwd * SLOT_F;                                                \
-    const int64_t waves = (n.PT + NB - 1) / NB;                                            \
-    SPML_FWD_ONE(KS_, true, true) SPML_FWD_ONE(KS_, true, false)                           \
-    SPML_FWD_ONE(KS_, false, true) SPML_FWD_ONE(KS_, false, false)                         \
-  }
-    SPML_KS_SWITCH(SPML_FWD)
-#undef SPML_FWD
-#undef SPML_FWD_ONE
-    return launch_status();
-  }
-
-  // ---- backward ----
-  _Float16* pth = reinterpret_cast<_Float16*>(b + w.pth);
-  _Float16* ptl = reinterpret_cast<_Float16*>(b + w.ptl);
-  _Float16* eth = reinterpret_cast<_Float16*>(b + w.eth);
-  _Float16* etl = reinterpret_cast<_Float16*>(b + w.etl);
-  float* gscale = reinterpret_cast<float*>(b + w.gscale);
-  float* rowscale = reinterpret_cast<float*>(b + w.rowscale);
-  a.pth = pth; a.ptl = ptl; a.eth = eth; a.etl = etl; a.gscale = gscale;
-  // deterministic mode: the prototype gradient is accumulated in fixed point (relative to gscale) and converted
-  // once, at the end of the call
-  a.d_protos64 = nullptr;
-  if (w.dp64) {
-    a.d_protos64 = reinterpret_cast<long long*>(b + w.dp64);
-    if (hipMemsetAsync(a.d_protos64, 0, (size_t)M * D * 8, s) != hipSuccess) return SPML_ERR_LAUNCH;
-  }
-  auto finish = [&](int rc) -> int {
-    if (rc != SPML_OK) return rc;
-    if (a.d_protos64)
-      hipLaunchKernelGGL(nll_dpr_from_fix, dim3((unsigned)(((int64_t)M * D + 255) / 256)), dim3(256), 0, s,
-                         a.d_protos64, (int64_t)M * D, (const float*)gscale, d_protos);
-    return launch_status();
-  };
-  hipLaunchKernelGGL(max_abs_pow2, dim3(1), dim3(1024), 0, s, d_nll, P, gscale);
-  hipLaunchKernelGGL(rowscale_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, d_nll,
-                     kappa, P, rowscale);
-  // gscale bounds |g|; kappa is folded into rowscale (kappa * g / gscale stays O(kappa))
-  launch_prep_T(protos, M, D, n.DT, nullptr, nullptr, pth, ptl, s);
-  // (the pipelined kernels of nll_de3.hip / nll_dp3.hip -- narrow embeddings, 32-bit codes -- prepare their own)
-  const auto env_off = [](const char* name) { const char* e = getenv(name); return e && e[0] == '0'; };
-  const bool v3 = n.KS == 4 && (mode & SPML_NLL_CODE32) && !env_off("SPML_NLL_BWD2") && !env_off("SPML_NLL_DE3");
-  const bool dp3 = v3 && !env_off("SPML_NLL_DP3");
-  if (!dp3) launch_prep_T(emb, P, D, n.DT, rowscale, gscale, eth, etl, s);
-  int64_t* pxcodes = reinterpret_cast<int64_t*>(b + w.pxcodes);
-  PixelCoef* coef = reinterpret_cast<PixelCoef*>(b + w.coef);
-  a.px_code_pad = pxcodes;
-  a.coef = coef;
-  a.tcache_de = w.tde ? reinterpret_cast<float*>(b + w.tde) : nullptr;
-  a.tcache_dp = w.tdp ? reinterpret_cast<float*>(b + w.tdp) : nullptr;
-  hipLaunchKernelGGL(pad_codes_kernel, dim3((unsigned)((n.PT * 32 + 255) / 256)), dim3(256), 0, s,
-                     px_code, P, n.PT * 32, pxcodes);
-  if (mode & SPML_NLL_TAGSET)
-    hipLaunchKernelGGL(coef_kernel<true>, dim3((unsigned)((n.PT * 32 + 255) / 256)), dim3(256), 0, s, stats, own, px_code,
-                       pr_code, M, P, n.PT * 32, coef);
-  else
-    hipLaunchKernelGGL(coef_kernel<false>, dim3((unsigned)((n.PT * 32 + 255) / 256)), dim3(256), 0, s, stats, own, px_code,
-                       pr_code, M, P, n.PT * 32, coef);
-  // prototypes [0, m_grad) receive a gradient (the rest, e.g. a detached memory bank, is skipped)
-  const int64_t mg = m_grad < 0 || m_grad > M ? M : m_grad;
-  a.mt_grad = (mg + 31) / 32;
-  const int64_t mgroups = (a.mt_grad + 3) / 4;
-  const int64_t chunks = dp_chunks(mgroups, n.PT);
-  a.chunks = (int)chunks;
-  a.spt0 = 0;
-  a.spt1 = n.PT;
-
-  // v2 dE kernel (narrow embeddings, 32-bit codes; SPML_NLL_BWD2=0: round-2 kernels): unscaled residuals,
-  // pixels x 2^3, prototypes x kappa * log2(e) * 2^-3, transposed prototypes x 2^3 (folded back below)
-  const char* envb = getenv("SPML_NLL_BWD2");
-  const bool de2 = n.KS <= 4 && (mode & SPML_NLL_CODE32) && !(envb && envb[0] == '0');
-  if (de2) {
-    launch_prep_raw(emb, P, D, n.KS, 8.0f, eh, el, s);
-    launch_prep_raw(protos, M, D, n.KS, a.kappa_log2e * 0.125f, ph, pl, s);
-    launch_prep_T_raw(protos, M, D, n.DT, nullptr, nullptr, 8.0f, pth, ptl, s);
-    a.partial_de = reinterpret_cast<float*>(b + w.partial_de);
-    const int rows = bwd2_rows(n);
-    const unsigned groups = (unsigned)((n.PT + 7) / 8);
-#define SPML_DE2(KS_, DT_)                                                                          \
-    {                                                                                               \
-      constexpr int LDSB = kFwd2TilesPerChunk * 128 + 2 * 2 * (2 * KS_ + 4 * DT_) * 1024;           \
-      if (mode & SPML_NLL_TAGSET) {                                                                 \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_bwd_de2<KS_, DT_, 2, true>),   \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDSB);                \
-        hipLaunchKernelGGL((nll_bwd_de2<KS_, DT_, 2, true>), dim3(groups, (unsigned)rows), dim3(256), LDSB, s, a); \
-      } else {                                                                                      \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_bwd_de2<KS_, DT_, 2, false>),  \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDSB);                \
-        hipLaunchKernelGGL((nll_bwd_de2<KS_, DT_, 2, false>), dim3(groups, (unsigned)rows), dim3(256), LDSB, s, a); \
-      }                                                                                             \
-    }
-    const bool use3 = v3;
-    float* own_term = reinterpret_cast<float*>(b + w.ownterm);
-    if (mode & SPML_NLL_TAGSET)
-      hipLaunchKernelGGL(own_term_kernel<true>, dim3((unsigned)((n.PT * 32 + 255) / 256)), dim3(256), 0, s, stats, own,
-                         px_code, pr_code, emb, protos, P, n.PT * 32, M, D, a.kappa_log2e, own_term);
-    else
-      hipLaunchKernelGGL(own_term_kernel<false>, dim3((unsigned)((n.PT * 32 + 255) / 256)), dim3(256), 0, s, stats, own,
-                         px_code, pr_code, emb, protos, P, n.PT * 32, M, D, a.kappa_log2e, own_term);
-    if (use3) {
-      const int rc3 = nll_launch_bwd_de3(a, rows, s);
-      if (rc3 != SPML_OK) return rc3;
-    } else {
-      switch (n.KS) {
-        case 2: SPML_DE2(2, 1); break;
-        case 3: SPML_DE2(3, 2); break;
-        default: SPML_DE2(4, 2); break;
-      }
-    }
-#undef SPML_DE2
-    hipLaunchKernelGGL(nll_de_finalize, dim3((unsigned)n.PT), dim3(256), (size_t)32 * (n.DT * 32 + 1) * sizeof(float), s, a.partial_de, rows, P, n.PT, D, n.DT,
-                       d_nll, kappa * 0.125f, d_emb, (const float*)own_term, own, protos, 8.0f, (const PixelCoef*)coef);
-    if (dp3) {
-      // prototype gradient on the pipelined kernel too: it takes the same std fragments; the transposed pixel
-      // fragments with unscaled residuals, x 2^8 (nll_dp3.hip)
-      hipLaunchKernelGGL(rowscale_ts_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, d_nll, kappa,
-                         (const PixelCoef*)coef, P, rowscale);
-      launch_prep_T_raw(emb, P, D, n.DT, rowscale, gscale, 16.0f, eth, etl, s);
-      return finish(nll_launch_bwd_dp3(a, own_term, emb, reinterpret_cast<float*>(b + w.dprows), s));
-    }
-    // the round-2 dPr kernel takes the pre-scaled fragments (a v2 form of it -- two prototype tiles per wave, pixel
-    // tiles streamed -- measured slower: 19 vs 15.5 ms for the live third at M = 139 k, profiles/r03_nll.md)
-    launch_prep_std(emb, P, D, n.KS, 1.0f, eh, el, s);
-    launch_prep_std(protos, M, D, n.KS, a.kappa_log2e, ph, pl, s);
-  }
-  a.skip_de = de2 ? 1 : 0;
-
-#define SPML_BWD_LAUNCH(KS_, DT_, TAG_, C32_, TM_)                                                    \
-  {                                                                                              \
-    constexpr int STD_DE = TM_ == 2 ? 0 : 2 * KS_ + 1, STD_DP = TM_ == 2 ? 0 : 2 * KS_ + 2;      \
-    constexpr int SLOT_DE = (STD_DE + 4 * DT_) * 1024, SLOT_DP = (STD_DP + 4 * DT_) * 1024;      \
-    /* narrow embeddings: 2 slots (36 KB) -> three workgroups of the dE kernel per CU (3-4 % faster); \
-       otherwise 3 slots while two workgroups still fit */                                      \
-    a.depth = KS_ <= 5 ? 2 : (3 * SLOT_DP <= 80 * 1024 ? 3 : 2);                                 \
-    if (const char* e_ = getenv("SPML_NLL_DEPTH_BWD")) { const int v_ = atoi(e_); if (v_ >= 2 && v_ <= 3) a.depth = v_; } \
-    if (2 * SLOT_DP > 160 * 1024) return SPML_ERR_UNSUPPORTED;                                   \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_bwd_de<KS_, DT_, TAG_, C32_, TM_>),   \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, a.depth * SLOT_DE);    \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_bwd_dp<KS_, DT_, TAG_, C32_, TM_>),   \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, a.depth * SLOT_DP);    \
-    if (!a.skip_de)                                                                              \
-      hipLaunchKernelGGL((nll_bwd_de<KS_, DT_, TAG_, C32_, TM_>), dim3((unsigned)((a.spt1 - a.spt0 + 3) / 4)), \
-                         dim3(256), a.depth * SLOT_DE, s, a);                                    \
-    if (mgroups > 0)                                                                             \
-      hipLaunchKernelGGL((nll_bwd_dp<KS_, DT_, TAG_, C32_, TM_>), dim3((unsigned)mgroups, (unsigned)a.chunks), \
-                         dim3(256), a.depth * SLOT_DP, s, a);                                    \
-  }
-#define SPML_BWD_DT(KS_, DT_, TAG_, C32_)                                                              \
-  {                                                                                              \
-    a.dt_all = n.DT;                                                                             \
-    if constexpr (KS_ > 17) {                                                                    \
-      /* wide embeddings: the first launch (3 d-tiles) computes the weight tiles and keeps them, \
-         the others read them back and contract 7 d-tiles each (no similarity GEMM, no resident  \
-         pixel fragments: the registers go to the accumulators) */                               \
-      if (a.tcache_de != nullptr && 32 * DT_ < D) {                                              \
-        const int64_t strip = tcache_strip_tiles(n);                                             \
-        for (int64_t t0 = 0; t0 < n.PT; t0 += strip) {       /* bounded workspace: strip by strip */ \
-          a.spt0 = t0;                                                                           \
-          a.spt1 = t0 + strip < n.PT ? t0 + strip : n.PT;                                        \
-          int64_t ch = chunks;                                                                   \
-          if (ch > (a.spt1 - a.spt0 + 7) / 8) ch = (a.spt1 - a.spt0 + 7) / 8;                    \
-          a.chunks = (int)(ch < 1 ? 1 : ch);                                                     \
-          a.dt0 = 0;                                                                             \
-          SPML_BWD_LAUNCH(KS_, DT_, TAG_, C32_, 1)                                               \
-          for (int dt0 = DT_; 32 * dt0 < D; dt0 += 7) {                                          \
-            a.dt0 = dt0;                                                                         \
-            SPML_BWD_LAUNCH(KS_, 7, TAG_, C32_, 2)                                               \
-          }                                                                                      \
-        }                                                                                        \
-      } else {                                                                                   \
-        for (int dt0 = 0; dt0 < n.DT && 32 * dt0 < D; dt0 += DT_) {                              \
-          a.dt0 = dt0;                                                                           \
-          SPML_BWD_LAUNCH(KS_, DT_, TAG_, C32_, 0)                                               \
-        }                                                                                        \
-      }                                                                                          \
-    } else {                                                                                     \
-      for (int dt0 = 0; dt0 < n.DT && 32 * dt0 < D; dt0 += DT_) {    /* one launch per d-chunk */ \
-        a.dt0 = dt0;                                                                             \
-        SPML_BWD_LAUNCH(KS_, DT_, TAG_, C32_, 0)                                                 \
-      }                                                                                          \
-    }                                                                                            \
-  }
-#define SPML_BWD(KS_)                                          \
-  {                                                            \
-    constexpr int DTM = KS_ <= 17 ? (KS_ + 1) / 2 : 3;         \
-    /* SPML_NLL_CODE32 only selects the forward variant: the backward kernels measured 6-12 %  \
-       slower with 32-bit predicates (profiles/r02_nll_scaling.md), the 64-bit form is exact for both */ \
-    if (mode & SPML_NLL_TAGSET) SPML_BWD_DT(KS_, DTM, true, false)   \
-    else SPML_BWD_DT(KS_, DTM, false, false)                   \
-  }
-  SPML_KS_SWITCH(SPML_BWD)
-#undef SPML_BWD
-#undef SPML_BWD_DT
-#undef SPML_BWD_LAUNCH
-#undef SPML_KS_SWITCH
-  return finish(SPML_OK);
+  return nll_ws(nll_bucket_dims(P, M, D), nll_env()).total;
 }
 
 extern "C" int spml_segsort_nll_fwd_f32(const float* emb, const int64_t* own,
@@ -1990,7 +1955,7 @@ extern "C" int spml_segsort_nll_fwd_f32(const float* emb, const int64_t* own,
                                         const int64_t* pr_code, int64_t M, int D, float kappa,
                                         int mode, float* nll, float* stats, void* ws,
                                         size_t ws_bytes, void* stream) {
-  return nll_common(false, emb, own, px_code, P, protos, pr_code, M, D, kappa, mode, nll, stats,
+  return nll_single(false, emb, own, px_code, P, protos, pr_code, M, D, kappa, mode, nll, stats,
                     nullptr, nullptr, nullptr, -1, ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -2000,7 +1965,7 @@ extern "C" int spml_segsort_nll_bwd_f32(const float* emb, const int64_t* own,
                                         int mode, const float* stats, const float* d_nll,
                                         float* d_emb, float* d_protos, int64_t m_grad, void* ws,
                                         size_t ws_bytes, void* stream) {
-  return nll_common(true, emb, own, px_code, P, protos, pr_code, M, D, kappa, mode, nullptr,
+  return nll_single(true, emb, own, px_code, P, protos, pr_code, M, D, kappa, mode, nullptr,
                     const_cast<float*>(stats), d_nll, d_emb, d_protos, m_grad, ws, ws_bytes,
                     (hipStream_t)stream);
 }

@@ -3,6 +3,7 @@
 #pragma once
 
 #include <type_traits>
+#include <utility>
 
 #include "common.hpp"
 
@@ -122,6 +123,14 @@ __device__ __forceinline__ void dma_block(const void* src_lane, void* dst_wave_u
 }
 __device__ __forceinline__ void dma_wait_and_sync() {
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+// Launch of a 256-thread kernel whose dynamic LDS may exceed the 64-KB default: the attribute, then the launch.
+// A tag / no-tag pair is one call: launch_dyn(tag ? k<..., true> : k<..., false>, ...).
+template <typename... Params, typename... Args>
+inline void launch_dyn(void (*kernel)(Params...), dim3 grid, int lds_bytes, hipStream_t s, Args&&... args) {
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), lds_bytes, s, std::forward<Args>(args)...);
 }
 
 // nll_de3.hip: the software-pipelined embedding-gradient kernel (KS <= 4, 32-bit codes); `rows` = grid

@@ -320,15 +320,8 @@ int nll_launch_bwd_de3(const NllArgs& a, int rows, hipStream_t s) {
   if (a.n.KS != 4 || a.n.DT != 2) return SPML_ERR_UNSUPPORTED;
   const unsigned groups = (unsigned)((a.n.PT + 15) / 16);        // 4 waves x 4 pixel tiles
   constexpr int LDS3 = kFwd2TilesPerChunk * 128 + 3 * 2 * (2 * 4 + 4 * 2) * 1024;
-  if (a.mode & SPML_NLL_TAGSET) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_bwd_de3<4, 2, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS3);
-    hipLaunchKernelGGL((nll_bwd_de3<4, 2, true>), dim3(groups, (unsigned)rows), dim3(256), LDS3, s, a);
-  } else {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_bwd_de3<4, 2, false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS3);
-    hipLaunchKernelGGL((nll_bwd_de3<4, 2, false>), dim3(groups, (unsigned)rows), dim3(256), LDS3, s, a);
-  }
+  launch_dyn((a.mode & SPML_NLL_TAGSET) ? nll_bwd_de3<4, 2, true> : nll_bwd_de3<4, 2, false>, dim3(groups, (unsigned)rows),
+             LDS3, s, a);
   return launch_status();
 }
 

@@ -381,15 +381,8 @@ int nll_launch_bwd_dp3(const NllArgs& a, const float* own_term, const float* emb
   NllArgs b = a;
   b.chunks = (int)chunks;
   constexpr int LDS3 = 3 * 2 * (2 * 4 + 4 * 2 + 1) * 1024;
-  if (a.mode & SPML_NLL_TAGSET) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_bwd_dp3<4, 2, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS3);
-    hipLaunchKernelGGL((nll_bwd_dp3<4, 2, true>), dim3(groups, (unsigned)chunks), dim3(256), LDS3, s, b, (const float*)rows);
-  } else {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nll_bwd_dp3<4, 2, false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS3);
-    hipLaunchKernelGGL((nll_bwd_dp3<4, 2, false>), dim3(groups, (unsigned)chunks), dim3(256), LDS3, s, b, (const float*)rows);
-  }
+  launch_dyn((a.mode & SPML_NLL_TAGSET) ? nll_bwd_dp3<4, 2, true> : nll_bwd_dp3<4, 2, false>,
+             dim3(groups, (unsigned)chunks), LDS3, s, b, (const float*)rows);
   hipLaunchKernelGGL(dp3_own_term_kernel, dim3((unsigned)((a.n.P + 3) / 4)), dim3(256), 0, s, own_term, a.own, emb, a.d_nll,
                      a.n.P, a.n.D, a.kappa, a.mt_grad * 32 < a.n.M ? a.mt_grad * 32 : a.n.M, a.d_protos, a.d_protos64, a.gscale);
   return launch_status();

@@ -932,6 +932,47 @@ def test_pipelined_prototype_gradient_kernel_matches_the_round_2_kernel(p, m, mo
     assert (dp3 - dp2).abs().max().item() <= 2e-5 * scale, (m_grad, (dp3 - dp2).abs().max().item() / scale)
 
 
+@pytest.mark.parametrize('mode', [4, 5])
+@pytest.mark.parametrize('var,value,d', [('SPML_NLL_FWD2', '0', 66), ('SPML_NLL_FWD2', '0', 64),
+                                         ('SPML_NLL_BWD2', '0', 64), ('SPML_NLL_BWD2', '0', 34),
+                                         ('SPML_NLL_DEPTH_FWD', '4', 130), ('SPML_NLL_DEPTH_BWD', '3', 64)])
+def test_retired_nll_switches_are_not_read(var, value, d, mode, monkeypatch):
+  """SPML_NLL_FWD2, SPML_NLL_BWD2, SPML_NLL_DEPTH_FWD and SPML_NLL_DEPTH_BWD once selected the round-2 kernels for
+  narrow embeddings with 32-bit codes and overrode the ring depths; the library no longer reads them.  With one of
+  them set, forward and backward (ragged tiles: P = 70, M = 40) are bit-identical to a call without it -- the
+  prototype gradient in deterministic mode, where it does not depend on the order of atomics -- and the batched
+  entry points stay available."""
+  gen = torch.Generator().manual_seed(d + mode)
+  p, m = 70, 40
+  protos = O.normalize_embedding(torch.randn(m, d, generator=gen)).to(DEV)
+  own = torch.randint(0, m, (p,), generator=gen).to(DEV)
+  emb = O.normalize_embedding(protos[own].cpu() + 0.8 * torch.randn(p, d, generator=gen)).to(DEV)
+  pr_code = (_sparse_tag_codes(m, gen) if mode & 1 else torch.randint(0, 21, (m,), generator=gen)).to(DEV)
+  px_code = pr_code[own]
+  g = (torch.rand(p, generator=gen) / p).to(DEV)
+  F = ffi()
+
+  def run():
+    nll, stats = F.segsort_nll_fwd(emb, own, px_code, protos, pr_code, 12.0, mode)
+    de, _ = F.segsort_nll_bwd(emb, own, px_code, protos, pr_code, 12.0, mode, stats0, g)
+    before = F.set_deterministic(True)
+    try:
+      de_det, dp_det = F.segsort_nll_bwd(emb, own, px_code, protos, pr_code, 12.0, mode, stats0, g)
+    finally:
+      F.set_deterministic(before)
+    return nll, stats, de, de_det, dp_det
+
+  monkeypatch.delenv(var, raising=False)
+  _, stats0 = F.segsort_nll_fwd(emb, own, px_code, protos, pr_code, 12.0, mode)
+  want = run()
+  assert torch.isfinite(want[0]).all() and want[4].abs().max().item() > 0
+  monkeypatch.setenv(var, value)
+  got = run()
+  for name, a, b in zip(('nll', 'stats', 'd_emb', 'd_emb (deterministic)', 'd_protos (deterministic)'), want, got):
+    assert torch.equal(a, b), (var, name)
+  assert F.segsort_nll_batched_supported(66, 4)
+
+
 def test_nll_at_the_eight_gpu_prototype_count_against_the_oracle():
   """M = 100 003 prototypes (what every rank sees on 8 GPUs incl. the memory bank), D = 64, tag-set predicate,
   image-major codes: forward, dEmbedding and the dPrototypes of the live third against the CPU oracle evaluated

@@ -45,8 +45,8 @@ for mode in (1 | 4, 1):
   print('mode', mode, 'num rel err max %.2e, den rel err max %.2e; nll abs err max %.2e' % (
       ((st[:, 0] - num64).abs() / num64.abs()).max().item(), ((st[:, 1] - den64).abs() / den64.abs()).max().item(),
       (nll.cpu().double() - n64).abs().max().item()))
-  for env in ({}, {'SPML_NLL_DE3': '0'}, {'SPML_NLL_BWD2': '0'}):
-    for k in ('SPML_NLL_DE3', 'SPML_NLL_BWD2'): os.environ.pop(k, None)
+  for env in ({}, {'SPML_NLL_DE3': '0'}):
+    os.environ.pop('SPML_NLL_DE3', None)
     os.environ.update(env)
     de, dp = _ffi.segsort_nll_bwd(emb.to(DEV), own.to(DEV), px_code, protos.to(DEV), pr_code, kappa, mode, stats, wgt.to(DEV), m_grad=m // 3)
     err = (de.cpu().double() - de64).abs()
@@ -56,7 +56,7 @@ for mode in (1 | 4, 1):
         (dp.cpu().double()[:m // 3] - dp64[:m // 3]).abs().max().item() / dp64[:m // 3].abs().max().item()), flush=True)
   # exact stats from fp64 fed to the backward
   st64 = stats.clone(); st64[:, 0] = num64.float().to(DEV); st64[:, 1] = den64.float().to(DEV)
-  for k in ('SPML_NLL_DE3', 'SPML_NLL_BWD2'): os.environ.pop(k, None)
+  os.environ.pop('SPML_NLL_DE3', None)
   de, dp = _ffi.segsort_nll_bwd(emb.to(DEV), own.to(DEV), px_code, protos.to(DEV), pr_code, kappa, mode, st64, wgt.to(DEV), m_grad=m // 3)
   err = (de.cpu().double() - de64).abs()
   print('   with fp64 num/den: dE err max %.2e mean %.2e' % (err.max().item() / scale, err.mean().item() / scale))
