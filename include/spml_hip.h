@@ -48,7 +48,8 @@ const char* spml_status_string(int status);
  * 6: the pseudo-label entry points (spml_resample_unit_f32 .. spml_upsample_argmax_i64);
  * 7: the multi-scale inference entry point (spml_view_probs_accumulate_f32);
  * 8: spml_upsample_ce_bwd_path_name (entry points added since leave every earlier signature and flag as it was and
- *    keep the version: spml_view_votes_*, spml_segsort_nll_batched_*, spml_segment_majority_*, spml_tag_normalize_*). */
+ *    keep the version: spml_view_votes_*, spml_segsort_nll_batched_*, spml_segment_majority_*, spml_tag_normalize_*,
+ *    spml_dense_crf_*). */
 #define SPML_ABI_VERSION 8
 int spml_abi_version(void);
 
@@ -981,6 +982,43 @@ size_t spml_tag_normalize_workspace_bytes(int ncls, int64_t n);
 int spml_tag_normalize_argmax_f32(const float* acc, int ncls, int64_t n, int num_views, const unsigned char* tags,
                                   float floor, int64_t* labels, float* prob, float* divisor, void* ws, size_t ws_bytes,
                                   void* stream);
+
+/* ------------------------------------------------------------------------
+ * N12  dense CRF refinement: exact mean-field inference over all pixel pairs (csrc/dense_crf.hip)
+ * replaces: spml/models/crf.py:23-41 (unary_from_softmax, DenseCRF2D, addPairwiseGaussian, addPairwiseBilateral,
+ *           inference(iter_max)) -- restated from the model, not ported: the reference approximates the two filters
+ *           with a permutohedral lattice, this is the filter itself.
+ *
+ *   U = -log(clip(probmap, 1e-5, 1))                       Q_0 = softmax_c(-U)
+ *   K1[i,j] = exp(-|p_i-p_j|^2 / (2 pos_xy_std^2))         K2[i,j] = exp(-|p_i-p_j|^2 / (2 bi_xy_std^2)
+ *                                                                        - |I_i-I_j|^2 / (2 bi_rgb_std^2))
+ *   n_m = 1 / sqrt(K_m 1 + 1e-20)                          M_m(Q)[c,i] = n_m[i] sum_j K_m[i,j] n_m[j] Q[c,j]
+ *   Q <- softmax_c(-U + pos_w M_1(Q) + bi_w M_2(Q))        iter_max times (i = j included; Potts compatibility)
+ *
+ * One image per call; h, w <= 2048 and ncls <= 64, else SPML_ERR_UNSUPPORTED (spml_dense_crf_workspace_bytes returns 0
+ * and spml_dense_crf_path_name "unsupported").  ws: 256-byte aligned, at least spml_dense_crf_workspace_bytes(h, w,
+ * ncls) bytes, else SPML_ERR_WORKSPACE; its head is what prepare leaves for infer, the rest is scratch of infer.
+ *
+ * spml_dense_crf_prepare_u8 (spml/models/crf.py:23-41, the two addPairwise* calls): image uint8 [h][w][3]; the three
+ *   standard deviations are positive finite numbers.  Writes the MFMA operands of the pair exponent and both norms n_1,
+ *   n_2 into ws (its size does not depend on ncls: one prepared image serves any class count and any weights).
+ * spml_dense_crf_infer_f32 (spml/models/crf.py:23-41, unary_from_softmax and inference): probmap fp32 [ncls][h][w], not
+ *   necessarily normalised, zeros allowed; iter_max >= 0; q fp32 [ncls][h][w] (the result); labels int64 [h][w] or NULL:
+ *   the lowest class that attains the maximum of q at a pixel, from the epilogue that writes q.  ws as prepare left it,
+ *   for the same h and w.
+ * spml_dense_crf_path_name (spml/models/crf.py:23-41; host only): "pairs_mfma_f16x2_c<32|64>+separable_r<R>" -- the
+ *   class columns of the pair kernel and the taps R = ceil(6 pos_xy_std) kept on either side by the separable spatial
+ *   filter (the tail it drops is below 4e-9 of the kernel's mass).
+ *
+ * Launches on `stream` only, no allocation, no host read, no atomics: results are bit-identical from call to call, with
+ * and without the deterministic mode.  Numerics are fp32-class: squared feature distances are formed exactly on the
+ * matrix cores, K and n Q enter the message product as split-f16 pairs (three MFMAs). */
+size_t spml_dense_crf_workspace_bytes(int h, int w, int ncls);
+int spml_dense_crf_prepare_u8(const unsigned char* image, int h, int w, float pos_xy_std, float bi_xy_std,
+                              float bi_rgb_std, void* ws, size_t ws_bytes, void* stream);
+int spml_dense_crf_infer_f32(const float* probmap, int ncls, int h, int w, int iter_max, float pos_w, float bi_w,
+                             float* q, int64_t* labels, void* ws, size_t ws_bytes, void* stream);
+const char* spml_dense_crf_path_name(int h, int w, int ncls, float pos_xy_std);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Pseudo-label generation by nearest-neighbour retrieval for the image-tag recipe, with the reference's command line and
 config surface (`pyscripts/inference/pseudo_inference_crf_msc.py:38-289` of twke18/SPML) without its `--crf_*` options:
-the denseCRF (:265-273) is outside this repository, the stage ends at the arg-max of what the CRF would have been fed.
+the stage ends at the arg-max of what the denseCRF (:265-273) would have been fed; `pseudo_inference_crf_msc.py` adds it.
 
   python3 pyscripts/inference/pseudo_inference_msc.py --snapshot_dir S --cfg_path C.yaml --save_dir OUT --data_list L \\
       --semantic_memory_dir BANK --kmeans_num_clusters 12,12 --label_divisor 2048

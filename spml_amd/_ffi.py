@@ -152,6 +152,10 @@ _SIGNATURES = {
     'spml_segment_majority_path_name': (c_char_p, [c_int64, c_int, c_int]),
     'spml_tag_normalize_workspace_bytes': (c_size_t, [c_int, c_int64]),
     'spml_tag_normalize_argmax_f32': (c_int, [_P, c_int, c_int64, c_int, _P, c_float, _P, _P, _P, _P, c_size_t, _P]),
+    'spml_dense_crf_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'spml_dense_crf_prepare_u8': (c_int, [_P, c_int, c_int, c_float, c_float, c_float, _P, c_size_t, _P]),
+    'spml_dense_crf_infer_f32': (c_int, [_P, c_int, c_int, c_int, c_int, c_float, c_float, _P, _P, _P, c_size_t, _P]),
+    'spml_dense_crf_path_name': (c_char_p, [c_int, c_int, c_int, c_float]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -1440,3 +1444,47 @@ def upsample_ce_bwd(logits_nhwc, labels, lse, ignore_index, scale):
                                        ptr(lse, torch.float32), n, c, h, w, hh, ww, int(ignore_index),
                                        ptr(scale, torch.float32), ptr(d), stream_ptr()), 'spml_upsample_ce_bwd_f32')
   return d
+
+
+# ---------------------------------------------------------------------------
+# dense CRF refinement (csrc/dense_crf.hip)
+MAX_DENSE_CRF_CLASSES = 64
+MAX_DENSE_CRF_SIDE = 2048
+
+
+def dense_crf_path_name(h, w, ncls, pos_xy_std):
+  """Route a dense-CRF call of this shape takes: 'pairs_mfma_f16x2_c<32|64>+separable_r<R>' or 'unsupported' (a pure
+  host function of the library)."""
+  return lib().spml_dense_crf_path_name(int(h), int(w), int(ncls), float(pos_xy_std)).decode()
+
+
+def dense_crf_workspace(h, w, ncls, device):
+  nbytes = lib().spml_dense_crf_workspace_bytes(int(h), int(w), int(ncls))
+  if nbytes == 0:
+    raise SpmlHipError('the dense CRF takes one image of at most %d x %d pixels and %d classes (got %d x %d, %d classes)'
+                       % (MAX_DENSE_CRF_SIDE, MAX_DENSE_CRF_SIDE, MAX_DENSE_CRF_CLASSES, h, w, ncls))
+  return workspace(nbytes, device)
+
+
+def dense_crf_prepare(image, pos_xy_std, bi_xy_std, bi_rgb_std, ws):
+  """image uint8 [h, w, 3] -> the pair-exponent operands and both norms inside `ws` (dense_crf_workspace of any class
+  count): once per image and set of standard deviations."""
+  if image.dim() != 3 or image.shape[2] != 3:
+    raise SpmlHipError('dense_crf_prepare: expected a uint8 [h, w, 3] image')
+  h, w = int(image.shape[0]), int(image.shape[1])
+  check(lib().spml_dense_crf_prepare_u8(ptr(image, torch.uint8), h, w, float(pos_xy_std), float(bi_xy_std),
+                                        float(bi_rgb_std), ptr(ws), ws.numel(), stream_ptr()),
+        'spml_dense_crf_prepare_u8')
+
+
+def dense_crf_infer(probmap, iter_max, pos_w, bi_w, ws, want_labels=True):
+  """probmap fp32 [ncls, h, w] and a prepared `ws` -> (Q fp32 [ncls, h, w], arg-max int64 [h, w] or None)."""
+  if probmap.dim() != 3:
+    raise SpmlHipError('dense_crf_infer: expected a [ncls, h, w] probability map')
+  ncls, h, w = (int(v) for v in probmap.shape)
+  q = torch.empty_like(probmap)
+  labels = torch.empty((h, w), dtype=torch.int64, device=probmap.device) if want_labels else None
+  check(lib().spml_dense_crf_infer_f32(ptr(probmap, torch.float32), ncls, h, w, int(iter_max), float(pos_w), float(bi_w),
+                                       ptr(q), ptr(labels, torch.int64, True), ptr(ws), ws.numel(), stream_ptr()),
+        'spml_dense_crf_infer_f32')
+  return q, labels

@@ -1,0 +1,458 @@
+// N12: fully connected CRF refinement, spml/models/crf.py:23-41 -- the exact mean-field filter that
+// pydensecrf's permutohedral lattice approximates, over all N x N pixel pairs of one image.
+//
+//   U = -log(clip(probmap, 1e-5, 1))                     Q_0 = softmax_c(-U)
+//   K1[i,j] = exp(-|p_i - p_j|^2 / (2 pos_xy_std^2))
+//   K2[i,j] = exp(-|p_i - p_j|^2 / (2 bi_xy_std^2) - |I_i - I_j|^2 / (2 bi_rgb_std^2))          (i = j included)
+//   n_m = 1 / sqrt(K_m 1 + 1e-20)                        M_m(Q)[c,i] = n_m[i] sum_j K_m[i,j] n_m[j] Q[c,j]
+//   Q <- softmax_c(-U + pos_w M_1(Q) + bi_w M_2(Q))      iter_max times
+//
+// The bilateral message is the hot path: N^2 exponentials per iteration.  crf_pairs is flash-style without the online
+// maximum (the exponent is never positive).  A wave owns 32 pixels i and walks every 32-pixel tile of j:
+//
+//   D_xy[j][i], D_rgb[j][i]   two 32x32x16 f16 MFMAs.  Centred coordinates (|x'|, |y'| <= 1024) and uint8 colours are
+//                             integers that f16 holds exactly, |f|^2 enters as two 11-bit pieces, every product and
+//                             every partial sum is an integer below 2^24: |f_i - f_j|^2 = |f_j|^2 + |f_i|^2 - 2 f_j.f_i
+//                             is formed with no rounding (and is exactly 0 for i = j).
+//   K = exp2(a D_xy + b D_rgb)  in registers (v_exp_f32), split into hi + lo / 2048 (common.hpp).
+//   Y[c][i] += Qn^T[c][j] K[j][i]   the accumulator tile has j in its 16 registers and i on the lane, which is the B
+//                             operand of the next MFMA as it stands (no LDS, no lane movement); Qn = n_2[j] Q[c,j] is
+//                             kept as split-f16 A fragments in that k order by whoever wrote Q.  Three MFMAs per k step
+//                             and 32 classes: hi.hi, hi.lo, lo.hi -- fp32-class.
+//   epilogue                  n_2[i], bi_w, + log p + the spatial message, softmax over the classes of a pixel (16
+//                             registers x 2 lane halves x CT), the next Q in fp32 and as the next operand, the arg-max.
+//
+// The norms K_2 1 come from the same loop with a row of ones as the A operand (kNorm).  The spatial kernel is separable,
+// K1 = g(dx) g(dy): two 1-D passes over n_1 Q with the taps cut at R = ceil(6 pos_xy_std) (the dropped tail is below
+// 4e-9 of the kernel's mass), and n_1 in closed form from the same taps.  No atomics anywhere; Q is double-buffered;
+// every launch is ordered by the stream alone: a call is bit-reproducible.
+#include <math.h>
+#include <stdio.h>
+
+#include "common.hpp"
+
+namespace spml {
+namespace {
+
+constexpr int kMaxClasses = 64;
+constexpr int kMaxSide = 2048;
+constexpr int kBlock = 256;
+constexpr int kTile = 32;
+constexpr int kMaxRadius = 2047;
+constexpr float kClipLo = 1e-5f;                  // unary_from_softmax's default clip
+constexpr float kNormEps = 1e-20f;
+
+struct CrfHeader {
+  float a2, b2;       // -log2(e) / (2 bi_xy_std^2), -log2(e) / (2 bi_rgb_std^2)
+  float pos_c;        // 1 / (2 pos_xy_std^2)
+  int radius;         // taps of the separable spatial kernel on either side
+};
+
+inline int spatial_radius(float pos_xy_std) {
+  const double r = ceil(6.0 * (double)pos_xy_std);
+  return r < 1.0 ? 1 : r > (double)kMaxRadius ? kMaxRadius : (int)r;
+}
+
+struct Layout {
+  int64_t n, npad, tiles;
+  int cpad, ct;
+  size_t hdr, faxy, fargb, fbxy, fbrgb, n1, n2, prepared_end;        // what prepare writes (independent of ncls)
+  size_t logp, spatial, tmp, qa, qb, op0, op1, total;                // what inference uses
+  size_t map_bytes, op_bytes;
+};
+
+inline bool make_layout(int h, int w, int ncls, Layout& l) {
+  if (h < 1 || w < 1 || h > kMaxSide || w > kMaxSide || ncls < 1 || ncls > kMaxClasses) return false;
+  l.n = (int64_t)h * w;
+  l.tiles = (l.n + kTile - 1) / kTile;
+  l.npad = l.tiles * kTile;
+  l.cpad = ncls <= 32 ? 32 : 64;
+  l.ct = l.cpad / 32;
+  const size_t frag = align_up((size_t)l.tiles * 64 * 16, 256);
+  const size_t vec = align_up((size_t)l.npad * sizeof(float), 256);
+  l.map_bytes = (size_t)ncls * (size_t)l.n * sizeof(float);
+  l.op_bytes = (size_t)l.npad * (size_t)l.cpad * 4;                  // hi + lo, 2 bytes each
+  const size_t map = align_up(l.map_bytes, 256);
+  size_t o = 0;
+  l.hdr = o, o += 256;
+  l.faxy = o, o += frag;
+  l.fargb = o, o += frag;
+  l.fbxy = o, o += frag;
+  l.fbrgb = o, o += frag;
+  l.n1 = o, o += vec;
+  l.n2 = o, o += vec;
+  l.prepared_end = o;
+  l.logp = o, o += map;
+  l.spatial = o, o += map;
+  l.tmp = o, o += map;
+  l.qa = o, o += map;
+  l.qb = o, o += map;
+  l.op0 = o, o += align_up(l.op_bytes, 256);
+  l.op1 = o, o += align_up(l.op_bytes, 256);
+  l.total = o;
+  return true;
+}
+
+// Where Qn[c][j] sits in the operand image: [tile of j][k step s][class tile][hi | lo][lane][element], so that a wave reads
+// one A fragment of 32 classes x 16 pixels with one 16-byte load per lane.  Element e of lane half hh is pixel
+// 16 s + 8 (e >> 2) + 4 hh + (e & 3) of the tile: the row order of accumulator registers 8 s .. 8 s + 7.
+__device__ __forceinline__ size_t operand_index(int64_t j, int c, int ct_count, int part) {
+  const int64_t t = j >> 5;
+  const int jj = (int)(j & 31), s = jj >> 4, m = jj & 15;
+  const int e = ((m >> 3) << 2) | (m & 3), hh = (m >> 2) & 1;
+  const int lane = (c & 31) + 32 * hh;
+  return ((((size_t)(t * 2 + s) * ct_count + (c >> 5)) * 2 + part) * 64 + lane) * 8 + e;
+}
+
+__device__ __forceinline__ void store_operand(_Float16* op, int64_t j, int c, int ct_count, float v) {
+  _Float16 hi, lo;
+  split_f16(v, hi, lo);
+  op[operand_index(j, c, ct_count, 0)] = hi;
+  op[operand_index(j, c, ct_count, 1)] = lo;
+}
+
+// thread = padded pixel j: the A (pixel as a row of the pair tile) and B (pixel as a column) fragments of both exponent
+// MFMAs; k slots 0..7 live in lanes 0..31, lanes 32..63 (k 8..15) are zero.  A padded pixel is all zeros.
+//   xy : A = [x, y, nlo, nhi, 1, 2048, 0, 0]      B = [-2x, -2y, 1, 2048, nlo, nhi, 0, 0]      n = x^2 + y^2 <= 2^21
+//   rgb: A = [r, g, b, nlo, nhi, 1, 2048, 0]      B = [-2r, -2g, -2b, 1, 2048, nlo, nhi, 0]    n <= 195075
+// with n = nlo + 2048 nhi, nlo < 2048: A . B = |f_j|^2 + |f_i|^2 - 2 f_j . f_i.
+__global__ __launch_bounds__(kBlock) void crf_features(const unsigned char* __restrict__ image, int h, int w, int64_t n,
+                                                       int64_t npad, CrfHeader hdr, CrfHeader* __restrict__ hdr_out,
+                                                       half8* __restrict__ faxy, half8* __restrict__ fargb,
+                                                       half8* __restrict__ fbxy, half8* __restrict__ fbrgb) {
+  const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (j == 0) *hdr_out = hdr;
+  if (j >= npad) return;
+  half8 axy, argb, bxy, brgb;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) axy[e] = argb[e] = bxy[e] = brgb[e] = (_Float16)0.f;
+  const half8 zero = axy;
+  if (j < n) {
+    const int y = (int)(j / w) - (h >> 1), x = (int)(j % w) - (w >> 1);
+    const int nxy = x * x + y * y;
+    const int r = image[j * 3 + 0], g = image[j * 3 + 1], b = image[j * 3 + 2];
+    const int nc = r * r + g * g + b * b;
+    const _Float16 one = (_Float16)1.f, big = (_Float16)2048.f;
+    axy[0] = (_Float16)(float)x, axy[1] = (_Float16)(float)y;
+    axy[2] = (_Float16)(float)(nxy & 2047), axy[3] = (_Float16)(float)(nxy >> 11), axy[4] = one, axy[5] = big;
+    bxy[0] = (_Float16)(float)(-2 * x), bxy[1] = (_Float16)(float)(-2 * y);
+    bxy[2] = one, bxy[3] = big, bxy[4] = axy[2], bxy[5] = axy[3];
+    argb[0] = (_Float16)(float)r, argb[1] = (_Float16)(float)g, argb[2] = (_Float16)(float)b;
+    argb[3] = (_Float16)(float)(nc & 2047), argb[4] = (_Float16)(float)(nc >> 11), argb[5] = one, argb[6] = big;
+    brgb[0] = (_Float16)(float)(-2 * r), brgb[1] = (_Float16)(float)(-2 * g), brgb[2] = (_Float16)(float)(-2 * b);
+    brgb[3] = one, brgb[4] = big, brgb[5] = argb[3], brgb[6] = argb[4];
+  }
+  const size_t lo = (size_t)(j >> 5) * 64 + (size_t)(j & 31), hi = lo + 32;
+  faxy[lo] = axy, fargb[lo] = argb, fbxy[lo] = bxy, fbrgb[lo] = brgb;
+  faxy[hi] = zero, fargb[hi] = zero, fbxy[hi] = zero, fbrgb[hi] = zero;
+}
+
+__device__ __forceinline__ void spatial_taps(const CrfHeader* hdr, float* g) {
+  const int radius = hdr->radius;
+  const float c = hdr->pos_c;
+  for (int d = threadIdx.x; d <= radius; d += kBlock) g[d] = expf(-(float)(d * d) * c);
+  __syncthreads();
+}
+
+// n_1 = 1 / sqrt(K1 1 + 1e-20) with K1 1 = (sum of the taps inside the row) * (sum of the taps inside the column).
+__global__ __launch_bounds__(kBlock) void crf_spatial_norm(const CrfHeader* __restrict__ hdr, int h, int w,
+                                                           float* __restrict__ n1) {
+  __shared__ float g[kMaxRadius + 1];
+  spatial_taps(hdr, g);
+  const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (p >= (int64_t)h * w) return;
+  const int radius = hdr->radius, y = (int)(p / w), x = (int)(p % w);
+  float sx = 0.f, sy = 0.f;
+  for (int xx = max(0, x - radius); xx <= min(w - 1, x + radius); ++xx) sx += g[abs(x - xx)];
+  for (int yy = max(0, y - radius); yy <= min(h - 1, y + radius); ++yy) sy += g[abs(y - yy)];
+  n1[p] = 1.0f / sqrtf(sx * sy + kNormEps);
+}
+
+// thread = (c, y, x).  kVertical = false: out = sum_x' g(x - x') n_1[y,x'] q[c,y,x'];  true: out = pos_w n_1[y,x]
+// sum_y' g(y - y') q[c,y',x] (q = the first pass).
+template <bool kVertical>
+__global__ __launch_bounds__(kBlock) void crf_spatial_pass(const CrfHeader* __restrict__ hdr, const float* __restrict__ q,
+                                                           const float* __restrict__ n1, int ncls, int h, int w,
+                                                           float pos_w, float* __restrict__ out) {
+  __shared__ float g[kMaxRadius + 1];
+  spatial_taps(hdr, g);
+  const int64_t n = (int64_t)h * w;
+  const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (idx >= n * ncls) return;
+  const int64_t p = idx % n;
+  const float* plane = q + (idx - p);
+  const int radius = hdr->radius, y = (int)(p / w), x = (int)(p % w);
+  float sum = 0.f;
+  if (!kVertical) {
+    const float* row = plane + (int64_t)y * w;
+    const float* nrow = n1 + (int64_t)y * w;
+    for (int xx = max(0, x - radius); xx <= min(w - 1, x + radius); ++xx) sum += g[abs(x - xx)] * (nrow[xx] * row[xx]);
+    out[idx] = sum;
+  } else {
+    for (int yy = max(0, y - radius); yy <= min(h - 1, y + radius); ++yy) sum += g[abs(y - yy)] * plane[(int64_t)yy * w + x];
+    out[idx] = pos_w * (n1[p] * sum);
+  }
+}
+
+// thread = pixel: log of the clipped probabilities, Q_0 = clip(p) / sum_c clip(p) (= softmax(-U)) in fp32 and as the first
+// operand, and -- when the call runs no iteration -- the labels.
+__global__ __launch_bounds__(kBlock) void crf_init(const float* __restrict__ prob, int ncls, int64_t n, int ct_count,
+                                                   const float* __restrict__ n2, float* __restrict__ logp,
+                                                   float* __restrict__ q, _Float16* __restrict__ op,
+                                                   int64_t* __restrict__ labels) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  float sum = 0.f;
+  for (int c = 0; c < ncls; ++c) sum += fminf(fmaxf(prob[(size_t)c * n + i], kClipLo), 1.0f);
+  const float ni = n2[i];
+  float best = 0.f;
+  int best_c = 0;
+  for (int c = 0; c < ncls; ++c) {
+    const float p = fminf(fmaxf(prob[(size_t)c * n + i], kClipLo), 1.0f);
+    const float v = p / sum;
+    logp[(size_t)c * n + i] = logf(p);
+    q[(size_t)c * n + i] = v;
+    store_operand(op, i, c, ct_count, ni * v);
+    if (c == 0 || v > best) best = v, best_c = c;
+  }
+  if (labels != nullptr) labels[i] = best_c;
+}
+
+// wave = 32 pixels i (the columns of every pair tile), all tiles of j.  kNorm: the A operand is a row of ones over the
+// valid j, the result K_2 1 becomes n_2.  Otherwise the mean-field update of the wave's pixels (see the head of the file).
+template <int CT, bool kNorm>
+__global__ __launch_bounds__(kBlock) void crf_pairs(const CrfHeader* __restrict__ hdr, const half8* __restrict__ faxy,
+                                                    const half8* __restrict__ fargb, const half8* __restrict__ fbxy,
+                                                    const half8* __restrict__ fbrgb, const half8* __restrict__ op,
+                                                    int64_t n, int tiles, int ncls, const float* __restrict__ logp,
+                                                    const float* __restrict__ spatial, const float* __restrict__ n2,
+                                                    float bi_w, float* __restrict__ q_next,
+                                                    _Float16* __restrict__ op_next, int64_t* __restrict__ labels,
+                                                    float* __restrict__ norm_out) {
+  const int lane = threadIdx.x & 63;
+  const int it = blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
+  if (it >= tiles) return;                                         // (wave-uniform; the kernel has no barrier)
+  const float a2 = hdr->a2, b2 = hdr->b2;
+  const half8 bxy = fbxy[(size_t)it * 64 + lane], brgb = fbrgb[(size_t)it * 64 + lane];
+  float16v acc0[CT], acc1[CT];
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc0[ct][r] = 0.f, acc1[ct][r] = 0.f;
+  float16v zero16;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
+
+  for (int jt = 0; jt < tiles; ++jt) {
+    const half8 axy = faxy[(size_t)jt * 64 + lane], argb = fargb[(size_t)jt * 64 + lane];
+    half8 qh[2][CT], ql[2][CT];
+    if (!kNorm) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) {
+          const size_t f = (((size_t)jt * 2 + s) * CT + ct) * 2 * 64 + lane;
+          qh[s][ct] = op[f];
+          ql[s][ct] = op[f + 64];
+        }
+    }
+    const float16v dxy = mfma32(axy, bxy, zero16);
+    const float16v drgb = mfma32(argb, brgb, zero16);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      half8 kh, kl;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int r = 8 * s + e;
+        const float k = __builtin_amdgcn_exp2f(fmaf(b2, drgb[r], a2 * dxy[r]));
+        _Float16 hi, lo;
+        split_f16(k, hi, lo);
+        kh[e] = hi, kl[e] = lo;
+      }
+      if (kNorm) {
+        // ones[c = 0][j] for the valid j of this k step, in the operand's k order (operand_index)
+        half8 ones;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const int64_t j = (int64_t)jt * 32 + 16 * s + 8 * (e >> 2) + 4 * (lane >> 5) + (e & 3);
+          ones[e] = ((lane & 31) == 0 && j < n) ? (_Float16)1.f : (_Float16)0.f;
+        }
+        acc0[0] = mfma32(ones, kh, acc0[0]);
+        acc1[0] = mfma32(ones, kl, acc1[0]);
+      } else {
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) {
+          acc0[ct] = mfma32(qh[s][ct], kh, acc0[ct]);
+          acc1[ct] = mfma32(qh[s][ct], kl, acc1[ct]);
+          acc1[ct] = mfma32(ql[s][ct], kh, acc1[ct]);
+        }
+      }
+    }
+  }
+
+  const int col = lane & 31, hh = lane >> 5;
+  const int64_t i = (int64_t)it * 32 + col;
+  const bool valid = i < n;
+  if (kNorm) {
+    // row c = 0 of the result: register 0 of lanes 0..31
+    if (hh == 0 && valid) norm_out[i] = 1.0f / sqrtf((acc0[0][0] + acc1[0][0] * kSplitInv) + kNormEps);
+    return;
+  }
+  const int64_t ir = valid ? i : n - 1;                            // (a padded column computes a copy of the last pixel)
+  const float ni = n2[ir];
+  float v[CT][16];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int c = 32 * ct + (r & 3) + 8 * (r >> 2) + 4 * hh;
+      float x = -INFINITY;
+      if (c < ncls) {
+        const float m = acc0[ct][r] + acc1[ct][r] * kSplitInv;
+        x = (logp[(size_t)c * n + ir] + spatial[(size_t)c * n + ir]) + bi_w * (ni * m);
+      }
+      v[ct][r] = x;
+      mx = fmaxf(mx, x);
+    }
+  mx = fmaxf(mx, __shfl_xor(mx, 32, kWave));
+  float sum = 0.f;
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int c = 32 * ct + (r & 3) + 8 * (r >> 2) + 4 * hh;
+      const float e = c < ncls ? expf(v[ct][r] - mx) : 0.f;
+      v[ct][r] = e;
+      sum += e;
+    }
+  sum += __shfl_xor(sum, 32, kWave);
+  float best = -1.f;
+  int best_c = 0;
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int c = 32 * ct + (r & 3) + 8 * (r >> 2) + 4 * hh;         // (ascending in (ct, r) for a lane)
+      if (c < ncls) {
+        const float qv = v[ct][r] / sum;
+        if (valid) {
+          q_next[(size_t)c * n + i] = qv;
+          store_operand(op_next, i, c, CT, ni * qv);
+        }
+        if (qv > best) best = qv, best_c = c;
+      }
+    }
+  if (labels != nullptr) {                                          // (uniform)
+    const float other = __shfl_xor(best, 32, kWave);
+    const int other_c = __shfl_xor(best_c, 32, kWave);
+    if (other > best || (other == best && other_c < best_c)) best_c = other_c;
+    if (hh == 0 && valid) labels[i] = best_c;
+  }
+}
+
+inline bool good_std(float s) { return isfinite(s) && s > 0.f; }
+
+}  // namespace
+}  // namespace spml
+
+using namespace spml;
+
+extern "C" size_t spml_dense_crf_workspace_bytes(int h, int w, int ncls) {
+  Layout l;
+  return make_layout(h, w, ncls, l) ? l.total : 0;
+}
+
+extern "C" const char* spml_dense_crf_path_name(int h, int w, int ncls, float pos_xy_std) {
+  static thread_local char name[64];
+  Layout l;
+  if (!make_layout(h, w, ncls, l) || !good_std(pos_xy_std)) return "unsupported";
+  snprintf(name, sizeof(name), "pairs_mfma_f16x2_c%d+separable_r%d", l.cpad, spatial_radius(pos_xy_std));
+  return name;
+}
+
+extern "C" int spml_dense_crf_prepare_u8(const unsigned char* image, int h, int w, float pos_xy_std, float bi_xy_std,
+                                         float bi_rgb_std, void* ws, size_t ws_bytes, void* stream) {
+  if (!image || h < 1 || w < 1 || !good_std(pos_xy_std) || !good_std(bi_xy_std) || !good_std(bi_rgb_std))
+    return SPML_ERR_INVALID_ARG;
+  Layout l;
+  if (!make_layout(h, w, 1, l)) return SPML_ERR_UNSUPPORTED;
+  if (!ws || ws_bytes < l.prepared_end || ((uintptr_t)ws & 255) != 0) return SPML_ERR_WORKSPACE;
+  char* base = static_cast<char*>(ws);
+  CrfHeader hdr;
+  const double log2e = 1.4426950408889634;
+  hdr.a2 = (float)(-log2e / (2.0 * (double)bi_xy_std * (double)bi_xy_std));
+  hdr.b2 = (float)(-log2e / (2.0 * (double)bi_rgb_std * (double)bi_rgb_std));
+  hdr.pos_c = (float)(1.0 / (2.0 * (double)pos_xy_std * (double)pos_xy_std));
+  hdr.radius = spatial_radius(pos_xy_std);
+  hipStream_t s = (hipStream_t)stream;
+  CrfHeader* dhdr = reinterpret_cast<CrfHeader*>(base + l.hdr);
+  half8* faxy = reinterpret_cast<half8*>(base + l.faxy);
+  half8* fargb = reinterpret_cast<half8*>(base + l.fargb);
+  half8* fbxy = reinterpret_cast<half8*>(base + l.fbxy);
+  half8* fbrgb = reinterpret_cast<half8*>(base + l.fbrgb);
+  float* n1 = reinterpret_cast<float*>(base + l.n1);
+  float* n2 = reinterpret_cast<float*>(base + l.n2);
+  const unsigned px_blocks = (unsigned)((l.npad + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(crf_features, dim3(px_blocks), dim3(kBlock), 0, s, image, h, w, l.n, l.npad, hdr, dhdr, faxy, fargb,
+                     fbxy, fbrgb);
+  hipLaunchKernelGGL(crf_spatial_norm, dim3(px_blocks), dim3(kBlock), 0, s, dhdr, h, w, n1);
+  const unsigned wave_blocks = (unsigned)((l.tiles + kBlock / kWave - 1) / (kBlock / kWave));
+  hipLaunchKernelGGL((crf_pairs<1, true>), dim3(wave_blocks), dim3(kBlock), 0, s, dhdr, faxy, fargb, fbxy, fbrgb,
+                     (const half8*)nullptr, l.n, (int)l.tiles, 1, (const float*)nullptr, (const float*)nullptr,
+                     (const float*)nullptr, 0.f, (float*)nullptr, (_Float16*)nullptr, (int64_t*)nullptr, n2);
+  return launch_status();
+}
+
+extern "C" int spml_dense_crf_infer_f32(const float* probmap, int ncls, int h, int w, int iter_max, float pos_w,
+                                        float bi_w, float* q, int64_t* labels, void* ws, size_t ws_bytes,
+                                        void* stream) {
+  if (!probmap || !q || ncls < 1 || h < 1 || w < 1 || iter_max < 0 || !isfinite(pos_w) || !isfinite(bi_w) ||
+      ((uintptr_t)probmap & 3) != 0 || ((uintptr_t)q & 3) != 0 || ((uintptr_t)labels & 7) != 0)
+    return SPML_ERR_INVALID_ARG;
+  Layout l;
+  if (!make_layout(h, w, ncls, l)) return SPML_ERR_UNSUPPORTED;
+  if (!ws || ws_bytes < l.total || ((uintptr_t)ws & 255) != 0) return SPML_ERR_WORKSPACE;
+  char* base = static_cast<char*>(ws);
+  hipStream_t s = (hipStream_t)stream;
+  const CrfHeader* dhdr = reinterpret_cast<const CrfHeader*>(base + l.hdr);
+  const half8* faxy = reinterpret_cast<const half8*>(base + l.faxy);
+  const half8* fargb = reinterpret_cast<const half8*>(base + l.fargb);
+  const half8* fbxy = reinterpret_cast<const half8*>(base + l.fbxy);
+  const half8* fbrgb = reinterpret_cast<const half8*>(base + l.fbrgb);
+  const float* n1 = reinterpret_cast<const float*>(base + l.n1);
+  const float* n2 = reinterpret_cast<const float*>(base + l.n2);
+  float* logp = reinterpret_cast<float*>(base + l.logp);
+  float* spatial = reinterpret_cast<float*>(base + l.spatial);
+  float* tmp = reinterpret_cast<float*>(base + l.tmp);
+  float* qbuf[2] = {reinterpret_cast<float*>(base + l.qa), reinterpret_cast<float*>(base + l.qb)};
+  _Float16* opbuf[2] = {reinterpret_cast<_Float16*>(base + l.op0), reinterpret_cast<_Float16*>(base + l.op1)};
+  // the padded pixels and classes of both operand images stay zero: they contribute nothing to any message
+  if (hipMemsetAsync(base + l.op0, 0, l.total - l.op0, s) != hipSuccess) return SPML_ERR_LAUNCH;
+  const unsigned px_blocks = (unsigned)((l.n + kBlock - 1) / kBlock);
+  const unsigned map_blocks = (unsigned)((l.n * ncls + kBlock - 1) / kBlock);
+  const unsigned wave_blocks = (unsigned)((l.tiles + kBlock / kWave - 1) / (kBlock / kWave));
+  hipLaunchKernelGGL(crf_init, dim3(px_blocks), dim3(kBlock), 0, s, probmap, ncls, l.n, l.ct, n2, logp,
+                     iter_max == 0 ? q : qbuf[0], opbuf[0], iter_max == 0 ? labels : (int64_t*)nullptr);
+  for (int t = 0; t < iter_max; ++t) {
+    const bool last = t + 1 == iter_max;
+    const float* q_cur = qbuf[t & 1];
+    float* q_out = last ? q : qbuf[(t + 1) & 1];
+    int64_t* lab = last ? labels : (int64_t*)nullptr;
+    hipLaunchKernelGGL((crf_spatial_pass<false>), dim3(map_blocks), dim3(kBlock), 0, s, dhdr, q_cur, n1, ncls, h, w, pos_w,
+                       tmp);
+    hipLaunchKernelGGL((crf_spatial_pass<true>), dim3(map_blocks), dim3(kBlock), 0, s, dhdr, (const float*)tmp, n1, ncls,
+                       h, w, pos_w, spatial);
+    const half8* op = reinterpret_cast<const half8*>(opbuf[t & 1]);
+    _Float16* op_next = opbuf[(t + 1) & 1];
+    if (l.ct == 1)
+      hipLaunchKernelGGL((crf_pairs<1, false>), dim3(wave_blocks), dim3(kBlock), 0, s, dhdr, faxy, fargb, fbxy, fbrgb, op,
+                         l.n, (int)l.tiles, ncls, (const float*)logp, (const float*)spatial, n2, bi_w, q_out, op_next, lab,
+                         (float*)nullptr);
+    else
+      hipLaunchKernelGGL((crf_pairs<2, false>), dim3(wave_blocks), dim3(kBlock), 0, s, dhdr, faxy, fargb, fbxy, fbrgb, op,
+                         l.n, (int)l.tiles, ncls, (const float*)logp, (const float*)spatial, n2, bi_w, q_out, op_next, lab,
+                         (float*)nullptr);
+  }
+  return launch_status();
+}

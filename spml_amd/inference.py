@@ -557,3 +557,32 @@ def pseudo_labels_softmax(embedding_model, prediction_model, views, image_hw, la
   if return_transition:
     out['transition'] = trans
   return out
+
+
+def denormalized_uint8(image, pixel_means, pixel_stds):
+  """The uint8 image the reference hands to its CRF (`pyscripts/inference/inference_softmax_crf_msc.py:159-164`), on the
+  image's device: `image` float `[3,h,w]` (or `[1,3,h,w]`), the network's normalised input -> uint8 `[h,w,3]`.  numpy
+  computes `image *= stds` and `image += means` (float32 by float64) in float64 and rounds each result to float32,
+  multiplies by 255 in float32 and truncates; the same steps here.  (A value outside 0..255 wraps modulo 256, as numpy's
+  cast does on the hosts this was compared on; the reference's images do not produce one.)"""
+  if image.dim() == 4 and image.shape[0] == 1:
+    image = image[0]
+  if image.dim() != 3 or image.shape[0] != 3:
+    raise ValueError('denormalized_uint8 expects one image [3,h,w]')
+  stds = torch.as_tensor(np.asarray(pixel_stds, dtype=np.float64), device=image.device).view(1, 1, 3)
+  means = torch.as_tensor(np.asarray(pixel_means, dtype=np.float64), device=image.device).view(1, 1, 3)
+  x = image.float().permute(1, 2, 0)
+  x = (x.double() * stds).float()
+  x = (x.double() + means).float()
+  x = x * torch.full((), 255.0, dtype=torch.float32, device=image.device)
+  return (x.to(torch.int32) & 255).to(torch.uint8).contiguous()
+
+
+def dense_crf_refine(image_u8, prob, crf):
+  """The denseCRF tail of the reference's `*_crf*.py` programs (`inference_softmax_crf_msc.py:166-168`): `image_u8`
+  uint8 `[h,w,3]` and `prob` fp32 `[ncls,h,w]` device tensors through `crf` (`spml_amd.models.crf.DenseCRF`).  Returns
+  `semantic_prob` `[ncls,h,w]` (the refined marginals), `semantic_prediction` `[h,w]` int64 (their arg-max, from the
+  kernel that writes them) and `crf_path`, the route the call took."""
+  prob_out, prediction = crf.refine(image_u8, prob)
+  return {'semantic_prob': prob_out, 'semantic_prediction': prediction,
+          'crf_path': crf.path_name(prob.shape[1], prob.shape[2], prob.shape[0])}

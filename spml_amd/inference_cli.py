@@ -1,4 +1,4 @@
-"""Shared body of the eight inference programs under `pyscripts/inference/`: the reference's command line and config
+"""Shared body of the eleven inference programs under `pyscripts/inference/`: the reference's command line and config
 surface (`parse_args`), the argument guards, snapshot loading, the seeded synthetic images that stand in for the
 file-list loader (outside this repository, DESIGN 9: `--data_list synthetic`), the self-built memory bank of the kNN
 programs, the timed loop over the images and the JSON line.  A program's `main` holds what is specific to its recipe:
@@ -197,7 +197,7 @@ def run_pseudo_softmax(description, scales, combine, walk_steps, argv=None):
   `spml_amd.inference.pseudo_labels_softmax`; the programs differ in three constants only (scales of the image pyramid,
   how the views' class scores are combined, squarings of the transition matrix).  The label maps of the synthetic images
   give the image tags (:102-106) and the mIoU of the JSON line; the labels written are those of :176, before the denseCRF
-  refinement, which is outside this repository."""
+  refinement (built for other programs; for these two it is the follow-up named there)."""
   from spml_amd import inference
   from spml_amd.utils.general import metrics
   config, args, device = parse(description, argv, 'pseudo_labels_softmax')
@@ -219,3 +219,36 @@ def run_pseudo_softmax(description, scales, combine, walk_steps, argv=None):
   done, seconds = timed_images(one)
   report(done, seconds, **scores(counts), scales=list(scales), is_flip=True, combine=combine, walk_steps=walk_steps,
          head_path=out['head_path'], snapshot=path, save_dir=semantic_dir)
+
+
+class CrfStage(object):
+  """The denseCRF stage of the `*_crf*.py` programs: the reference's `postprocessor` built from the six `--crf_*` options
+  (inference_softmax_crf_msc.py:80-87) and device events around every call, for the stage's share of the image time."""
+
+  def __init__(self, config, args):
+    from spml_amd.models.crf import DenseCRF
+    self.crf = DenseCRF(iter_max=args.crf_iter_max, pos_xy_std=args.crf_pos_xy_std, pos_w=args.crf_pos_w,
+                        bi_xy_std=args.crf_bi_xy_std, bi_rgb_std=args.crf_bi_rgb_std, bi_w=args.crf_bi_w)
+    self.pixel_means, self.pixel_stds = config.network.pixel_means, config.network.pixel_stds
+    self.events, self.path = [], None
+
+  def image_u8(self, image, valid_hw):
+    """The uint8 image the reference rebuilds from the network's input (:159-164), cropped to the un-padded size."""
+    from spml_amd import inference
+    h, w = valid_hw
+    return inference.denormalized_uint8(image, self.pixel_means, self.pixel_stds)[:h, :w].contiguous()
+
+  def __call__(self, image_u8, prob):
+    from spml_amd import inference
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    out = inference.dense_crf_refine(image_u8, prob, self.crf)
+    end.record()
+    self.events.append((start, end))
+    self.path = out['crf_path']
+    return out
+
+  def fields(self, seconds):
+    """Read after the loop's closing synchronisation: `crf_path` and the stage's share of the timed seconds."""
+    ms = sum(a.elapsed_time(b) for a, b in self.events)
+    return {'crf_path': self.path, 'crf_share': round(ms / (seconds * 1e3), 4)}

@@ -1,0 +1,62 @@
+"""Dense CRF post-processing with the reference's interface (`spml/models/crf.py:14-41` of twke18/SPML).
+
+The reference hands the image and the probability map to pydensecrf, which approximates the two fully connected
+filters with a permutohedral lattice on the CPU.  This class runs the mean-field iteration itself, over all pixel pairs,
+as HIP kernels (`csrc/dense_crf.hip`): same constructor, same call, no CPU fallback."""
+import numpy as np
+import torch
+
+from spml_amd import _ffi
+
+
+class DenseCRF(object):
+
+  def __init__(self, iter_max, pos_w, pos_xy_std, bi_w, bi_xy_std, bi_rgb_std):
+    self.iter_max = iter_max
+    self.pos_w = pos_w
+    self.pos_xy_std = pos_xy_std
+    self.bi_w = bi_w
+    self.bi_xy_std = bi_xy_std
+    self.bi_rgb_std = bi_rgb_std
+
+  def path_name(self, h, w, ncls):
+    """The route a `[ncls, h, w]` call takes (host only)."""
+    return _ffi.dense_crf_path_name(h, w, ncls, self.pos_xy_std)
+
+  def prepare(self, image, ncls):
+    """image: uint8 `[h, w, 3]` device tensor -> the prepared workspace of `infer` (reusable with other weights)."""
+    if not torch.is_tensor(image) or not image.is_cuda:
+      raise _ffi.SpmlHipError('the HIP path needs GPU tensors (the dense CRF has no CPU fallback)')
+    ws = _ffi.dense_crf_workspace(image.shape[0], image.shape[1], ncls, image.device)
+    _ffi.dense_crf_prepare(image, self.pos_xy_std, self.bi_xy_std, self.bi_rgb_std, ws)
+    return ws
+
+  def infer(self, ws, probmap, want_labels=True, iter_max=None, pos_w=None, bi_w=None):
+    """probmap fp32 `[C, h, w]` device tensor and a prepared workspace -> (Q `[C, h, w]`, arg-max `[h, w]` or None)."""
+    return _ffi.dense_crf_infer(probmap, self.iter_max if iter_max is None else iter_max,
+                                self.pos_w if pos_w is None else pos_w, self.bi_w if bi_w is None else bi_w, ws,
+                                want_labels)
+
+  def refine(self, image, probmap):
+    """Device tensors in, device tensors out: (Q `[C, h, w]` fp32, arg-max `[h, w]` int64)."""
+    if not (torch.is_tensor(image) and torch.is_tensor(probmap) and image.is_cuda and probmap.is_cuda):
+      raise _ffi.SpmlHipError('the HIP path needs GPU tensors (the dense CRF has no CPU fallback)')
+    if probmap.dim() != 3 or image.dim() != 3 or tuple(image.shape) != (probmap.shape[1], probmap.shape[2], 3):
+      raise ValueError('DenseCRF expects an image [h, w, 3] and a probability map [C, h, w] of the same size')
+    if image.dtype != torch.uint8:
+      raise ValueError('DenseCRF expects a uint8 image')
+    with torch.no_grad():
+      ws = self.prepare(image.contiguous(), probmap.shape[0])
+      return self.infer(ws, probmap.float().contiguous())
+
+  def __call__(self, image, probmap):
+    """numpy arrays (HWC uint8, CHW float32) -> numpy CHW float32 through the GPU, as the reference; device tensors ->
+    a device tensor.  Without a GPU, or for CPU tensors, `SpmlHipError`."""
+    if torch.is_tensor(image) or torch.is_tensor(probmap):
+      return self.refine(image, probmap)[0]
+    if not torch.cuda.is_available():
+      raise _ffi.SpmlHipError('the dense CRF needs an MI355X (the HIP path has no CPU fallback)')
+    device = torch.device('cuda', torch.cuda.current_device())
+    image_d = torch.from_numpy(np.ascontiguousarray(image)).to(device)
+    prob_d = torch.from_numpy(np.ascontiguousarray(probmap, dtype=np.float32)).to(device)
+    return self.refine(image_d, prob_d)[0].cpu().numpy()
