@@ -225,6 +225,9 @@ int spml_kmeans_init_grid_i64(int H, int W, int Ky, int Kx, int64_t* out,
                                        assign + accumulate passes on 64-pixel tiles ("mfma_f16x2_v4k"); the call
                                        takes the many-cluster kernels ("mfma_f16x2_bigk") (testing / A-B) */
 
+/* Bytes of `ws` for any k-means entry point with these sizes, whatever its flags and iterations.  The size does not
+ * depend on the deterministic mode (the fixed-point scratch of the generic route's sums, n_img * K * D * 8 bytes, is
+ * always reserved): a workspace sized before spml_set_deterministic(1) serves the calls after it. */
 size_t spml_kmeans_workspace_bytes(int64_t P, int D, int K, int n_img,
                                    int64_t max_seg_len);
 

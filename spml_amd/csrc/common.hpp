@@ -4,6 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+#include <utility>
+
 #include "spml_hip.h"
 
 namespace spml {
@@ -120,5 +123,26 @@ inline int launch_status() {
 }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// Launch of a kernel whose dynamic LDS may exceed the 64-KB default: the attribute, then the launch.
+template <typename... Params, typename... Args>
+inline void launch_dyn_block(void (*kernel)(Params...), dim3 grid, dim3 block, int lds_bytes, hipStream_t s,
+                             Args&&... args) {
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, s, std::forward<Args>(args)...);
+}
+// ... of a 256-thread kernel.  A pair of variants is one call: launch_dyn(tag ? k<..., true> : k<..., false>, ...).
+template <typename... Params, typename... Args>
+inline void launch_dyn(void (*kernel)(Params...), dim3 grid, int lds_bytes, hipStream_t s, Args&&... args) {
+  launch_dyn_block(kernel, grid, dim3(256), lds_bytes, s, std::forward<Args>(args)...);
+}
+
+// f(std::integral_constant<int, V>{}) for the V of the list that equals v, or `none`: a run-time value becomes the
+// template argument of a kernel (the list is the set of instantiations)
+template <int... Vs, typename R, typename F>
+inline R select_int(int v, R none, F&& f) {
+  (void)((v == Vs ? (none = f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+  return none;
+}
 
 }  // namespace spml

@@ -13,7 +13,7 @@
 // (iterations + 1 passes: the first is M-only on the initial labels, the last
 // E-only).  Algorithmic HBM bytes per pass: P*D*4 (+ P*4 labels).
 //
-// Code paths, chosen per shape by make_plan (spml_kmeans_last_path() names the one taken):
+// Code paths, chosen per shape by kmeans_route (spml_kmeans_path_name names the one taken):
 //   kmeans_pass16<MT16,Q,TAIL,PRE>   D = 32q + tail (q in {1,2,4,8}), K <= 64: the main
 //       kernel (below, "v3"): 16x16x32 MFMA tiles, prototypes of a wave register-resident,
 //       32-pixel tiles as split-f16 fragment blocks in a 2-slot LDS ring fed by direct-to-LDS
@@ -34,7 +34,8 @@
 // reference) and emits the split-f16 prototypes of the next pass.
 #include <stdio.h>
 #include <stdlib.h>
-#include <vector>
+
+#include <algorithm>
 
 #include "common.hpp"
 #include "kmeans_tile.hpp"
@@ -59,11 +60,7 @@ constexpr int kKsMax = 5;
 // store of a converted tile by the seed pass (273 MB per 513x513x258 call, read back by the
 // next pass): non-temporal stores keep the lines out of the L2 / Infinity-Cache write-back
 // queue the first fused pass would otherwise have to wait behind
-#ifdef SPML_SEED_PLAIN_STORE
-#define SPML_SEED_STORE(ptr, val) (*(ptr) = (val))
-#else
 #define SPML_SEED_STORE(ptr, val) __builtin_nontemporal_store((val), (ptr))
-#endif
 
 constexpr int kNBuf = 3;      // LDS tile ring: one being computed, two in flight
 
@@ -1564,122 +1561,120 @@ __global__ void generic_ids(const int32_t* labels, const int64_t* seg_off, int n
 }
 
 // ------------------------- host side --------------------------------------
-struct Plan {
-  bool fast;
-  bool v3;                     // kmeans_pass16 (16x16x32 tiles, in-LDS split)
-  int NT, KS, KSPLIT, G, kpad, dpad, nvt;
-  int MT16, Q, TAIL;
-  bool pre;                    // v3 on pre-converted tiles
-  bool v3k;                    // kmeans_pass16k (64 < K <= 256, small D, pre-converted tiles)
-  bool v4k;                    // kmeans_assign64k + kmeans_accum64k (64 < K <= 144, D >= 128, pre-converted tiles)
-  int MTW;
-  size_t lds;
-};
+// A call: kmeans_route (what runs, decided once from the host-visible arguments) -> one of three runners (the tile
+// kernels here, bigk_run of kmeans_big.hip, the generic kernels) -> launches.
 
 // shapes kmeans_pass16 covers: D = 32*Q + tail, Q in {1, 2, 4, 8}, K <= 64.  tail in {0, 2}
 // (embedding, + (y, x) location) runs everywhere; other tails up to 8 (location + colours
 // of the DensePose recipe: 5) only on pre-converted tiles, i.e. for >= 3 passes
 inline bool v3_shape(int D, int K, bool pre = false) {
-  const int q = D / 32, tl = D - 32 * q;
-  const bool tail_ok = tl == 0 || tl == 2 || (pre && tl <= 8);
-  return K >= 1 && K <= 64 && tail_ok && (q == 1 || q == 2 || q == 4 || q == 8);
+  const RowShape r = row_shape(D);
+  const bool tail_ok = r.tail == 0 || r.tail == 2 || (pre && r.tail <= 8);
+  return K >= 1 && K <= 64 && tail_ok && (r.q == 1 || r.q == 2 || r.q == 4 || r.q == 8);
 }
 // shapes kmeans_pass16k covers: 64 < K <= 256 with the wave's prototype fragments and
 // M-step accumulators inside the register budget: MTW * (8*QE + 4*NDT) <= 176
+constexpr bool v3k_fits(int mtw, int q, int tail) { return mtw * (8 * (q + tail) + 4 * (2 * q + tail)) <= 176; }
 inline bool v3k_shape(int D, int K) {
-  const int q = D / 32, tl = D - 32 * q;
-  if (K <= 64 || K > 256 || tl > 8 || !(q == 1 || q == 2 || q == 4)) return false;
-  const int mtw = ((K + 15) / 16 + 3) / 4, qe = q + (tl ? 1 : 0), ndt = 2 * q + (tl ? 1 : 0);
-  return mtw * (8 * qe + 4 * ndt) <= 176;
+  const RowShape r = row_shape(D);
+  if (K <= 64 || K > 256 || r.tail > 8 || !(r.q == 1 || r.q == 2 || r.q == 4)) return false;
+  return v3k_fits(((K + 15) / 16 + 3) / 4, r.q, r.tail ? 1 : 0);
 }
 
-Plan make_plan(const float* x, int64_t P, int D, int K, int n_img, int64_t max_seg_len,
-               int flags, bool want_pre) {
-  Plan pl{};
-  pl.fast = false;
-  if (flags & SPML_KMEANS_FORCE_GENERIC) return pl;
-  if (reinterpret_cast<uintptr_t>(x) & 15) return pl;
-  if (P * (int64_t)D * 4 < 16) return pl;
-  if (want_pre && !(flags & (SPML_KMEANS_NO_PRECONVERT | SPML_KMEANS_FORCE_V2)) && v3k_shape(D, K)) {
-    const int q = D / 32, tl = D - 32 * q;
-    pl.fast = true; pl.v3k = true; pl.pre = true;
-    pl.Q = q; pl.TAIL = tl ? 1 : 0;
-    pl.MT16 = (K + 15) / 16; pl.MTW = (pl.MT16 + 3) / 4;
-    pl.kpad = 16 * pl.MT16; pl.dpad = 32 * (q + pl.TAIL);
-    pl.lds = pass16_lds_bytes(D, true);
-    const int64_t tiles = (max_seg_len + 31) / 32;
-    int64_t gI = (256 * pass16k_wg_per_cu(pl.MTW, pl.Q, pl.TAIL) + n_img - 1) / n_img;
-    if (gI > tiles) gI = tiles;
-    if (gI < 1) gI = 1;
-    pl.G = (int)gI;
-    return pl;
+enum Path { kGeneric, kBigK, kV2, kV3, kV3p, kV4p, kV3k, kV4k };      // (the tile-kernel paths: from kV2 on)
+const char* const kPathName[] = {"generic",        "mfma_f16x2_bigk", "mfma_f16x2",     "mfma_f16x2_v3",
+                                 "mfma_f16x2_v3p", "mfma_f16x2_v4p",  "mfma_f16x2_v3k", "mfma_f16x2_v4k"};
+
+// What a k-means call does, and every consequence of it.  Beyond `path` the fields are those of the tile paths.
+struct Route {
+  Path path;
+  bool tile() const { return path >= kV2; }
+  bool pre;                    // the passes read pre-converted tiles ...
+  bool seed_converts;          // ... which the seed pass (its in-LDS conversion variant, seed_lds) writes itself;
+                               // else kmeans_preconvert does, or the caller did (given centroids)
+  int G, G64;                  // workgroups per image: of every pass; of the kmeans_pass64 passes (kV4p)
+  int kpad, dpad, nvt;
+  size_t lds, seed_lds;
+  int frag_major;              // prototype fragments in the order the 64-pixel-tile kernels load them
+  int mt16, q, tail, mtw;      // template arguments of kmeans_pass16 / kmeans_pass16k / kmeans_preconvert
+  int nt, ks, ksplit;          // ... of kmeans_pass (kV2)
+};
+
+// given: the assign / fused-pass entry points (prototypes from the caller); iterations: of a run
+Route kmeans_route(const float* x, int64_t P, int D, int K, int n_img, int64_t max_seg_len, bool given,
+                   int iterations, int flags) {
+  Route r{};
+  const auto no_tiles = [&]() {
+    r.path = !(flags & SPML_KMEANS_FORCE_GENERIC) && bigk_shape(P, D, K, n_img) ? kBigK : kGeneric;
+    return r;
+  };
+  if (flags & SPML_KMEANS_FORCE_GENERIC) return no_tiles();
+  if (reinterpret_cast<uintptr_t>(x) & 15) return no_tiles();
+  if (P * (int64_t)D * 4 < 16) return no_tiles();
+  // pre-converting X pays for itself from the third pass on; given centroids: only when
+  // the caller says the workspace already holds the converted tiles
+  const bool want_pre = (given ? (flags & SPML_KMEANS_WS_PRECONVERTED) != 0 : iterations >= 2) &&
+                        !(flags & SPML_KMEANS_NO_PRECONVERT);
+  const RowShape row = row_shape(D);
+  const int64_t tiles = (max_seg_len + 31) / 32, tiles64 = (max_seg_len + 63) / 64;
+  r.q = row.q; r.tail = row.tail ? 1 : 0;
+  r.mt16 = (K + 15) / 16;
+  r.kpad = 16 * r.mt16; r.dpad = 32 * (r.q + r.tail);
+  if (want_pre && !(flags & SPML_KMEANS_FORCE_V2) && v3k_shape(D, K)) {
+    r.path = kV3k; r.pre = true;
+    r.mtw = (r.mt16 + 3) / 4;
+    r.lds = pass16_lds_bytes(D, true);
+    r.G = wg_per_image(256 * pass16k_wg_per_cu(r.mtw, r.q, r.tail), n_img, tiles);
+    return r;
   }
-  if (want_pre && !(flags & (SPML_KMEANS_NO_PRECONVERT | SPML_KMEANS_FORCE_V2 | SPML_KMEANS_NO_V4K)) &&
-      assign64k_shape(D, K)) {
+  if (want_pre && !(flags & (SPML_KMEANS_FORCE_V2 | SPML_KMEANS_NO_V4K)) && assign64k_shape(D, K)) {
     // wide rows, 64 < K <= 144 (the 12 x 12 grid at 513 x 513 x 258): assign and accumulate as two passes over
     // the pre-converted 64-pixel tiles, one workgroup per CU
-    const int q = D / 32, tl = D - 32 * q;
-    pl.fast = true; pl.v4k = true; pl.pre = true;
-    pl.Q = q; pl.TAIL = tl ? 1 : 0;
-    pl.kpad = assign64k_kpad(K); pl.MT16 = pl.kpad / 16;
-    pl.dpad = 32 * (q + pl.TAIL);
-    pl.lds = p64_lds(q, pl.TAIL);
-    const int64_t tiles = (max_seg_len + 63) / 64;
-    int64_t gI = (256 + n_img - 1) / n_img;
-    if (gI > tiles) gI = tiles;
-    if (gI < 1) gI = 1;
-    pl.G = (int)gI;
-    return pl;
+    r.path = kV4k; r.pre = true; r.frag_major = 1;
+    r.kpad = assign64k_kpad(K); r.mt16 = r.kpad / 16;
+    r.lds = p64_lds(r.q, r.tail);
+    r.G = wg_per_image(256, n_img, tiles64);
+    return r;
   }
-  {
-    // v3: D = 32*Q + tail, Q in {1, 2, 4, 8}
-    const int q = D / 32, tl = D - 32 * q;
-    const bool pre = want_pre && !(flags & SPML_KMEANS_NO_PRECONVERT);
-    if (!(flags & SPML_KMEANS_FORCE_V2) && v3_shape(D, K, pre)) {
-      pl.fast = true; pl.v3 = true;
-      pl.pre = pre;
-      pl.Q = q; pl.MT16 = (K + 15) / 16;
-      pl.kpad = 16 * pl.MT16; pl.dpad = 32 * (q + (tl ? 1 : 0));
-      pl.TAIL = tl ? 1 : 0;
-      pl.nvt = pass_nvt(D, 4);
-      pl.lds = pass16_lds_bytes(D, pl.pre);
-      const int64_t tiles = (max_seg_len + 31) / 32;
-      int per_cu = (int)(160 * 1024 / pl.lds);
-      if (per_cu > pass16_wg_per_cu(pl.MT16, pl.Q)) per_cu = pass16_wg_per_cu(pl.MT16, pl.Q);
-      if (per_cu < 1) per_cu = 1;
-      int64_t gI = (256 * per_cu + n_img - 1) / n_img;
-      if (gI > tiles) gI = tiles;
-      if (gI < 1) gI = 1;
-      pl.G = (int)gI;
-      return pl;
+  if (!(flags & SPML_KMEANS_FORCE_V2) && v3_shape(D, K, want_pre)) {
+    r.pre = want_pre;
+    r.nvt = pass_nvt(D, 4);
+    r.lds = pass16_lds_bytes(D, r.pre);
+    int per_cu = (int)(160 * 1024 / r.lds);
+    if (per_cu > pass16_wg_per_cu(r.mt16, r.q)) per_cu = pass16_wg_per_cu(r.mt16, r.q);
+    if (per_cu < 1) per_cu = 1;
+    r.G = wg_per_image(256 * per_cu, n_img, tiles);
+    // v3: the seed pass converts (in LDS) and writes the tiles out itself
+    r.seed_converts = !given && r.pre && (row.tail == 0 || row.tail == 2) && !(flags & SPML_KMEANS_SEPARATE_PRECONVERT);
+    r.seed_lds = pass16_lds_bytes(D, false);
+    // passes with an E-step on pre-converted tiles (K <= 48): the pixel-split kernel on 64-pixel tiles
+    // (kmeans64.hip) with its own grid; the M-only seed pass stays on kmeans_pass16
+    const bool use64 = r.pre && pass64_shape(D, K) && !(flags & SPML_KMEANS_NO_PASS64);
+    r.path = use64 ? kV4p : r.pre ? kV3p : kV3;
+    if (use64) {                                 // (the slab area of the workspace is sized for G)
+      r.G64 = std::min(r.G, wg_per_image(256 * pass64_wg_per_cu(D, K), n_img, tiles64));
+      r.frag_major = 1;
     }
+    return r;
   }
-  if (K < 1 || K > 64 || (D & 1) || D < 2) return pl;
+  if (K < 1 || K > 64 || (D & 1) || D < 2) return no_tiles();
   const int steps = (D + 15) / 16;
-  int ksplit = 0, ks = 0;
   for (int s : {1, 2, 4}) {
     const int need = (steps + s - 1) / s;
-    if (need <= kKsMax) { ksplit = s; ks = need; break; }
+    if (need <= kKsMax) { r.ksplit = s; r.ks = need <= 2 ? 2 : (need <= 3 ? 3 : 5); break; }
   }
-  if (!ksplit) return pl;
-  ks = ks <= 2 ? 2 : (ks <= 3 ? 3 : 5);
-  const int nt = K <= 32 ? 1 : 2;
-  const size_t lds = pass_lds_bytes(D, nt, ksplit);
-  if (lds > 160 * 1024) return pl;
-  pl.fast = true;
-  pl.NT = nt; pl.KS = ks; pl.KSPLIT = ksplit; pl.lds = lds;
-  pl.kpad = 32 * nt;
-  pl.dpad = 16 * ks * ksplit;
-  pl.nvt = pass_nvt(D, ksplit);
-  const int tpw = 32 * (4 / ksplit);
-  const int64_t tiles = (max_seg_len + tpw - 1) / tpw;
+  if (!r.ksplit) return no_tiles();
+  r.nt = K <= 32 ? 1 : 2;
+  r.lds = pass_lds_bytes(D, r.nt, r.ksplit);
+  if (r.lds > 160 * 1024) return no_tiles();
+  r.path = kV2;
+  r.kpad = 32 * r.nt;
+  r.dpad = 16 * r.ks * r.ksplit;
+  r.nvt = pass_nvt(D, r.ksplit);
+  const int tpw = 32 * (4 / r.ksplit);
   // ~2 workgroups per CU across all images (1 when LDS allows only one)
-  const int per_cu = lds > 80 * 1024 ? 1 : 2;
-  int64_t gI = (256 * per_cu + n_img - 1) / n_img;
-  if (gI > tiles) gI = tiles;
-  if (gI < 1) gI = 1;
-  pl.G = (int)gI;
-  return pl;
+  r.G = wg_per_image(256 * (r.lds > 80 * 1024 ? 1 : 2), n_img, (max_seg_len + tpw - 1) / tpw);
+  return r;
 }
 
 struct WsLayout {
@@ -1687,7 +1682,7 @@ struct WsLayout {
 };
 
 WsLayout ws_layout(int64_t P, int D, int K, int n_img, int64_t max_seg_len) {
-  // sized for the worst of the fast / generic plans
+  // sized for the worst of the routes, and the same in either setting of the deterministic mode
   WsLayout w{};
   size_t o = 0;
   w.lab32 = o; o = align_up(o + (size_t)P * 4, 256);
@@ -1702,9 +1697,6 @@ WsLayout ws_layout(int64_t P, int D, int K, int n_img, int64_t max_seg_len) {
   w.ids = o; o = align_up(o + (size_t)P * 8, 256);
   w.sums = o; o = align_up(o + (size_t)n_img * K * D * 4, 256);
   w.ssq = o; o = align_up(o + (size_t)n_img * K * ((D + 63) / 64) * 4, 256);
-  // deterministic mode, generic route: fixed-point image of the M-step sums (segsum.hip)
-  w.det64 = o;
-  if (deterministic_mode()) o = align_up(o + (size_t)n_img * K * D * 8, 256);
   // pre-converted tiles (same 4 B per element as X), only for the shapes that use them
   w.xc = o;
   if (v3_shape(D, K, true) || v3k_shape(D, K) || assign64k_shape(D, K))
@@ -1712,61 +1704,76 @@ WsLayout ws_layout(int64_t P, int D, int K, int n_img, int64_t max_seg_len) {
   // many-cluster kernels (kmeans_big.hip): keys, sort buffers, fixed-point sums, fragments
   w.big = o;
   if (bigk_shape(P, D, K, n_img)) o = align_up(o + bigk_workspace_bytes(P, D, K, n_img), 256);
+  // deterministic mode, generic route: fixed-point image of the M-step sums (segsum.hip).  Reserved in either mode,
+  // and last: every other region lies where it does in a layout without it
+  w.det64 = o; o = align_up(o + (size_t)n_img * K * D * 8, 256);
   w.total = o;
   return w;
 }
 
-template <int NT, int KS, int KSPLIT>
-int launch_pass_t(const PassArgs& a, const Plan& pl, hipStream_t s) {
-  auto kern = kmeans_pass<NT, KS, KSPLIT>;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
-  hipLaunchKernelGGL(kern, dim3(pl.G, a.n_img), dim3(256), pl.lds, s, a);
-  return launch_status();
+struct Ws {
+  int32_t* lab32;
+  _Float16 *cent_h, *cent_l;
+  float *cent_f, *slabs, *sums, *ssq;
+  int64_t* ids;
+  long long* det64;
+  unsigned char *xc, *big;
+};
+
+Ws bind_ws(void* ws, const WsLayout& wl) {
+  unsigned char* base = static_cast<unsigned char*>(ws);
+  Ws w{};
+  w.lab32 = reinterpret_cast<int32_t*>(base + wl.lab32);
+  w.cent_h = reinterpret_cast<_Float16*>(base + wl.cent_h);
+  w.cent_l = reinterpret_cast<_Float16*>(base + wl.cent_l);
+  w.cent_f = reinterpret_cast<float*>(base + wl.cent_f);
+  w.slabs = reinterpret_cast<float*>(base + wl.slabs);
+  w.sums = reinterpret_cast<float*>(base + wl.sums);
+  w.ssq = reinterpret_cast<float*>(base + wl.ssq);
+  w.ids = reinterpret_cast<int64_t*>(base + wl.ids);
+  w.det64 = reinterpret_cast<long long*>(base + wl.det64);
+  w.xc = base + wl.xc;
+  w.big = base + wl.big;
+  return w;
 }
 
-template <int MT16, int Q, int TAIL, bool PRE>
-int launch_pass16_t(const PassArgs& a, const Plan& pl, hipStream_t s) {
-  auto kern = kmeans_pass16<MT16, Q, TAIL, PRE>;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
-  PassArgs b = a;
-  { const char* e = getenv("SPML_KMEANS_STRIDED"); b.strided = !(e && e[0] == '0'); }
-  hipLaunchKernelGGL(kern, dim3(pl.G, a.n_img), dim3(256), pl.lds, s, b);
-  return launch_status();
+// ---- kernel selection: run-time shape -> instantiation (null: none) ----
+PassKernel pass_kernel(const Route& r) {                       // kmeans_pass<NT, KS, KSPLIT>
+  const PassKernel none = nullptr;
+  return select_int<1, 2>(r.nt, none, [&](auto NT_) {
+    return select_int<2, 3, 5>(r.ks, none, [&](auto KS_) {
+      return select_int<1, 2, 4>(r.ksplit, none, [&](auto SP_) -> PassKernel {
+        return kmeans_pass<decltype(NT_)::value, decltype(KS_)::value, decltype(SP_)::value>;
+      });
+    });
+  });
 }
 
-int launch_preconvert(const float* x, int D, const int64_t* seg_off, int n_img, int64_t max_seg_len,
-                      const Plan& pl, unsigned char* xc, hipStream_t s) {
-  const int64_t tiles = (max_seg_len + 31) / 32;
-  int64_t gx = (4096 + n_img - 1) / n_img;
-  if (gx > tiles) gx = tiles;
-  if (gx < 1) gx = 1;
-  const dim3 grid((unsigned)gx, (unsigned)n_img);
-#define SPML_PC(Q_)                                                                              \
-  if (pl.Q == Q_) {                                                                              \
-    if (pl.TAIL) hipLaunchKernelGGL((kmeans_preconvert<Q_, 1>), grid, dim3(256), 0, s, x, D, seg_off, xc); \
-    else hipLaunchKernelGGL((kmeans_preconvert<Q_, 0>), grid, dim3(256), 0, s, x, D, seg_off, xc); \
-    return launch_status();                                                                      \
-  }
-  SPML_PC(1) SPML_PC(2) SPML_PC(4) SPML_PC(8)
-#undef SPML_PC
-  return SPML_ERR_UNSUPPORTED;
+PassKernel pass16_kernel(const Route& r, bool pre) {           // kmeans_pass16<MT16, Q, TAIL, PRE>
+  const PassKernel none = nullptr;
+  return select_int<1, 2, 3, 4>(r.mt16, none, [&](auto M_) {
+    return select_int<1, 2, 4, 8>(r.q, none, [&](auto Q_) -> PassKernel {
+      constexpr int M = decltype(M_)::value, Q = decltype(Q_)::value;
+      if (pre) return r.tail ? kmeans_pass16<M, Q, 1, true> : kmeans_pass16<M, Q, 0, true>;
+      return r.tail ? kmeans_pass16<M, Q, 1, false> : kmeans_pass16<M, Q, 0, false>;
+    });
+  });
 }
 
-template <int MTW, int Q, int TAIL>
-int launch_pass16k_t(const PassArgs& a, const Plan& pl, hipStream_t s) {
-  auto kern = kmeans_pass16k<MTW, Q, TAIL>;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
-  PassArgs b = a;
-  { const char* e = getenv("SPML_KMEANS_STRIDED"); b.strided = !(e && e[0] == '0'); }
-  hipLaunchKernelGGL(kern, dim3(pl.G, a.n_img), dim3(256), pl.lds, s, b);
-  return launch_status();
+PassKernel pass16k_kernel(const Route& r) {                    // kmeans_pass16k<MTW, Q, TAIL> inside the register budget
+  const PassKernel none = nullptr;
+  return select_int<2, 3, 4>(r.mtw, none, [&](auto W_) {
+    return select_int<1, 2, 4>(r.q, none, [&](auto Q_) -> PassKernel {
+      constexpr int W = decltype(W_)::value, Q = decltype(Q_)::value;
+      if constexpr (v3k_fits(W, Q, 1)) return r.tail ? kmeans_pass16k<W, Q, 1> : kmeans_pass16k<W, Q, 0>;
+      else return nullptr;
+    });
+  });
 }
 
-int launch_pass(const PassArgs& a, const Plan& pl, hipStream_t s) {
-  if (pl.v4k) {                                  // assign, then (fused pass) accumulate on the labels just written
+// one pass of a tile path on the route's grid; pre: on pre-converted tiles (a.xc), else the in-LDS conversion
+int launch_pass(const PassArgs& a, const Route& r, bool pre, hipStream_t s) {
+  if (r.path == kV4k) {                          // assign, then (fused pass) accumulate on the labels just written
     if (a.do_assign) {
       PassArgs e = a;
       e.do_accum = 0;
@@ -1777,62 +1784,290 @@ int launch_pass(const PassArgs& a, const Plan& pl, hipStream_t s) {
     m.do_assign = 0;
     if (a.do_assign) {
       m.labels_in64 = nullptr;
-      if (m.clocks) m.clocks += (size_t)2 * pl.G * a.n_img;     // (profiling: the second kernel of the pass)
+      if (m.clocks) m.clocks += (size_t)2 * r.G * a.n_img;      // (profiling: the second kernel of the pass)
     }
     return launch_accum64k(m, s);
   }
-  if (pl.v3k) {
-#define SPML_V3K(W_, Q_)                                                            \
-  if (pl.MTW == W_ && pl.Q == Q_)                                                   \
-    return pl.TAIL ? launch_pass16k_t<W_, Q_, 1>(a, pl, s) : launch_pass16k_t<W_, Q_, 0>(a, pl, s);
-    SPML_V3K(2, 1) SPML_V3K(3, 1) SPML_V3K(4, 1)
-    SPML_V3K(2, 2) SPML_V3K(3, 2) SPML_V3K(4, 2)
-    SPML_V3K(2, 4)
-#undef SPML_V3K
-    return SPML_ERR_UNSUPPORTED;
-  }
-  if (pl.v3) {
-#define SPML_V3(M_, Q_)                                                             \
-  if (pl.MT16 == M_ && pl.Q == Q_) {                                                \
-    if (pl.pre)                                                                     \
-      return pl.TAIL ? launch_pass16_t<M_, Q_, 1, true>(a, pl, s)                   \
-                     : launch_pass16_t<M_, Q_, 0, true>(a, pl, s);                  \
-    return pl.TAIL ? launch_pass16_t<M_, Q_, 1, false>(a, pl, s)                    \
-                   : launch_pass16_t<M_, Q_, 0, false>(a, pl, s);                   \
-  }
-#define SPML_V3Q(M_) SPML_V3(M_, 1) SPML_V3(M_, 2) SPML_V3(M_, 4) SPML_V3(M_, 8)
-    SPML_V3Q(1) SPML_V3Q(2) SPML_V3Q(3) SPML_V3Q(4)
-#undef SPML_V3Q
-#undef SPML_V3
-    return SPML_ERR_UNSUPPORTED;
-  }
-#define SPML_CASE(NT_, KS_, SP_) \
-  if (pl.NT == NT_ && pl.KS == KS_ && pl.KSPLIT == SP_) return launch_pass_t<NT_, KS_, SP_>(a, pl, s);
-#define SPML_CASES(NT_) \
-  SPML_CASE(NT_, 2, 1) SPML_CASE(NT_, 3, 1) SPML_CASE(NT_, 5, 1) \
-  SPML_CASE(NT_, 2, 2) SPML_CASE(NT_, 3, 2) SPML_CASE(NT_, 5, 2) \
-  SPML_CASE(NT_, 2, 4) SPML_CASE(NT_, 3, 4) SPML_CASE(NT_, 5, 4)
-  SPML_CASES(1)
-  SPML_CASES(2)
-#undef SPML_CASES
-#undef SPML_CASE
-  return SPML_ERR_UNSUPPORTED;
+  const PassKernel kern = r.path == kV3k ? pass16k_kernel(r) : r.path == kV2 ? pass_kernel(r) : pass16_kernel(r, pre);
+  if (!kern) return SPML_ERR_UNSUPPORTED;
+  launch_dyn(kern, dim3(r.G, a.n_img), (int)(pre == r.pre ? r.lds : r.seed_lds), s, a);
+  return launch_status();
 }
 
-int generic_assign_launch(const float* x, int64_t P, int D, const int64_t* seg_off, int n_img,
-                          int K, const float* cent, int32_t* labels, hipStream_t s) {
-  const dim3 grid((unsigned)((P + 15) / 16));
-  const int nc = (D + 63) / 64;
-#define SPML_GA(NC) \
-  hipLaunchKernelGGL(generic_assign<NC>, grid, dim3(256), 0, s, x, P, D, seg_off, n_img, K, cent, labels)
-  if (nc <= 1) SPML_GA(1);
-  else if (nc <= 2) SPML_GA(2);
-  else if (nc <= 3) SPML_GA(3);
-  else if (nc <= 5) SPML_GA(5);
-  else if (nc <= 9) SPML_GA(9);
-  else if (nc <= 17) SPML_GA(17);
-  else return SPML_ERR_UNSUPPORTED;
-#undef SPML_GA
+int launch_preconvert(const float* x, int D, const int64_t* seg_off, int n_img, int64_t max_seg_len,
+                      const Route& r, unsigned char* xc, hipStream_t s) {
+  typedef void (*Kernel)(const float*, int, const int64_t*, unsigned char*);
+  const Kernel kern = select_int<1, 2, 4, 8>(r.q, Kernel(nullptr), [&](auto Q_) -> Kernel {
+    constexpr int Q = decltype(Q_)::value;
+    return r.tail ? kmeans_preconvert<Q, 1> : kmeans_preconvert<Q, 0>;
+  });
+  if (!kern) return SPML_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)wg_per_image(4096, n_img, (max_seg_len + 31) / 32), (unsigned)n_img);
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, x, D, seg_off, xc);
+  return launch_status();
+}
+
+// The arguments of a call (what, not how: `op` and `repeats` are the runner's), its route and its bound workspace.
+struct Call {
+  const float* x;
+  int64_t P;
+  int D;
+  const int64_t* seg_off;
+  int n_img;
+  int64_t max_seg_len;
+  int K;
+  const int64_t* labels_init;      // a run
+  const float* given;              // assign / fused pass: the caller's prototypes
+  int iterations;
+  int64_t* labels_out;
+  float* sums_out;                 // fused pass
+  int flags;
+  unsigned long long* clocks;      // profiled run, or null
+  Route r;
+  Ws w;
+  hipStream_t s;
+};
+
+enum class Op { run, assign, fused_pass };
+
+// SPML_KMEANS_STRIDED=0: contiguous tile ranges in kmeans_pass16 / kmeans_pass16k (A/B); read once per call
+int strided_from_env() {
+  const char* e = getenv("SPML_KMEANS_STRIDED");
+  return !(e && e[0] == '0');
+}
+
+// ---- phase instrumentation (-DSPML_TRACE builds, SPML_KM_TRACE=1) ----
+#ifdef SPML_TRACE
+unsigned long long* trace_buffer() {
+  static unsigned long long* buf = nullptr;
+  if (!getenv("SPML_KM_TRACE")) return nullptr;
+  if (!buf) (void)hipMalloc(&buf, (40 + 2048) * 8);
+  return buf;
+}
+void trace_dump(const unsigned long long* trace, Path path, hipStream_t s) {
+  if (!trace) return;
+  (void)hipStreamSynchronize(s);
+  static unsigned long long h[40 + 2048];
+  (void)hipMemcpy(h, trace, sizeof(h), hipMemcpyDeviceToHost);
+  const char* nm16[8] = {"wait", "convert|epilogue", "barrier+dma", "E", "barrier", "labels", "M", "prologue"};
+  const char* nm64[8] = {"wait+barrier", "epilogue", "dma-issue", "E-mfma", "argmax+publish+barrier", "onehot", "M-mfma", "prologue"};
+  const char* nm64k[8] = {"dma-wait", "barrier", "label-read", "epilogue", "-", "onehot", "M-mfma", "prologue"};   // (the accumulate kernel)
+  const char** nm = path == kV4k ? nm64k : path == kV4p ? nm64 : nm16;
+  for (int w = 0; w < 4; ++w) {
+    fprintf(stderr, "wave%d:", w);
+    for (int i = 0; i < 8; ++i) fprintf(stderr, " %s=%llu", nm[i], h[w * 8 + i]);
+    fprintf(stderr, " wall_us=%.2f\n", h[32 + w] * 0.01);
+  }
+}
+#else
+inline unsigned long long* trace_buffer() { return nullptr; }
+inline void trace_dump(const unsigned long long*, Path, hipStream_t) {}
+#endif
+
+// ---- runner of the tile paths ----
+struct TileRun {
+  const Call& c;
+  PassArgs a;
+  int pass_index;              // (profiling) entries of c.clocks written so far
+  int last_G;                  // slabs the last M-step pass wrote per image
+};
+
+// slabs -> prototypes (normalize), or the caller's prototypes as they are: fp32 + split-f16 fragments
+void tile_finalize(const TileRun& t, bool normalize, const float* src, int G) {
+  const Call& c = t.c;
+  const Route& r = c.r;
+  const int nchunk = (c.D + 63) / 64;
+  // one launch when there are enough (cluster, image) rows to fill the chip: a block pulls its whole row
+  // (G x D x 4 bytes) at ~50 GB/s, so 36 blocks of a single 513 x 513 x 258 image take longer (~10 us) than
+  // the two launches of kmeans_reduce_slabs (5 x 36 blocks) + kmeans_normalize (7 + 5 us); 16 training
+  // images: 34.8 instead of 38.5 us per iteration
+  const int nl = ((c.flags & SPML_KMEANS_TWO_KERNEL_FINALIZE) || r.kpad * c.n_img < 128) ? 0 : finalize_loads(G, c.D);
+  if (normalize && nl) {
+    select_int<8, 16, 32, 56>(nl, 0, [&](auto N_) {
+      hipLaunchKernelGGL(kmeans_finalize<decltype(N_)::value>, dim3(r.kpad, c.n_img), dim3(1024), 0, c.s, src, G, c.K,
+                         c.D, r.kpad, r.dpad, r.frag_major, c.w.cent_f, c.w.cent_h, c.w.cent_l);
+      return 0;
+    });
+  } else if (normalize) {
+    hipLaunchKernelGGL(kmeans_reduce_slabs, dim3(nchunk, c.K, c.n_img), dim3(1024), 0, c.s, src, G, c.K, c.D,
+                       c.w.sums, c.w.ssq);
+    hipLaunchKernelGGL(kmeans_normalize, dim3(r.kpad, c.n_img), dim3(256), 0, c.s, c.w.sums, c.w.ssq, nchunk, c.K,
+                       c.D, r.kpad, r.dpad, 1, r.frag_major, c.w.cent_f, c.w.cent_h, c.w.cent_l);
+  } else {                                      // given prototypes: split only
+    hipLaunchKernelGGL(kmeans_normalize, dim3(r.kpad, c.n_img), dim3(256), 0, c.s, src, (const float*)nullptr,
+                       nchunk, c.K, c.D, r.kpad, r.dpad, 0, r.frag_major, (float*)nullptr, c.w.cent_h, c.w.cent_l);
+  }
+}
+
+// the pass t.a describes; convert: the seed pass that converts the tiles itself
+int tile_pass(TileRun& t, bool convert = false) {
+  const Route& r = t.c.r;
+  PassArgs& a = t.a;
+  a.clocks = t.c.clocks ? t.c.clocks + (size_t)t.pass_index * 2 * r.G * a.n_img : nullptr;
+  t.pass_index += (r.path == kV4k && a.do_assign && a.do_accum) ? 2 : 1;
+  if (r.path == kV4p && a.do_assign) {
+    PassArgs b = a;
+    b.G = t.last_G = r.G64;
+    return launch_pass64(b, t.c.s);
+  }
+  t.last_G = r.G;
+  return launch_pass(a, r, r.pre && !convert, t.c.s);
+}
+
+// repeats: launches of the pass of a SPML_KMEANS_PASS_ONLY call (measurement), else 1
+int run_tiles(Op op, int repeats, const Call& c) {
+  const Route& r = c.r;
+  TileRun t{c, PassArgs{}, 0, r.G};
+  PassArgs& a = t.a;
+  a.x = c.x; a.x_bytes = c.P * (int64_t)c.D * 4; a.P = c.P; a.D = c.D; a.K = c.K; a.n_img = c.n_img; a.G = r.G;
+  a.nvt = r.nvt;
+  a.seg_off = c.seg_off; a.cent_h = c.w.cent_h; a.cent_l = c.w.cent_l; a.kpad = r.kpad;
+  a.dpad = r.dpad; a.labels = c.w.lab32; a.slabs = c.w.slabs;
+  a.cent_f32 = c.given ? c.given : c.w.cent_f;
+  a.strided = strided_from_env();
+  a.trace = trace_buffer();
+  int rc = SPML_OK;
+  if (c.given && r.pre) {
+    a.xc = c.w.xc;                              // converted by spml_kmeans_preconvert_f32
+  } else if (r.pre && !r.seed_converts) {       // (the many-cluster tile kernels only exist on pre-converted tiles)
+    rc = launch_preconvert(c.x, c.D, c.seg_off, c.n_img, c.max_seg_len, r, c.w.xc, c.s);
+    if (rc != SPML_OK) return rc;
+    a.xc = c.w.xc;
+  }
+  if (c.given) {
+    const bool pass_only = op == Op::fused_pass && (c.flags & SPML_KMEANS_PASS_ONLY) &&
+                           (c.flags & SPML_KMEANS_WS_PRECONVERTED);
+    if (!pass_only) tile_finalize(t, false, c.given, 1);
+    a.do_assign = 1; a.do_accum = op == Op::fused_pass ? 1 : 0;
+    a.labels_out64 = c.labels_out;
+    for (int rep = 0; rep < (pass_only ? repeats : 1); ++rep) {
+      rc = tile_pass(t);
+      if (rc != SPML_OK) return rc;
+    }
+    if (op == Op::fused_pass && !pass_only)     // raw sums of X by the new labels
+      hipLaunchKernelGGL(kmeans_reduce_slabs, dim3((c.D + 63) / 64, c.K, c.n_img), dim3(1024), 0, c.s, c.w.slabs,
+                         t.last_G, c.K, c.D, c.sums_out, c.w.ssq);
+  } else {
+    if (c.iterations > 0) {
+      a.do_assign = 0; a.do_accum = 1;          // M-step on the initial labels
+      a.labels_in64 = c.labels_init;
+      if (r.seed_converts) a.xc_out = c.w.xc;
+      rc = tile_pass(t, r.seed_converts);
+      if (rc != SPML_OK) return rc;
+      if (r.seed_converts) { a.xc_out = nullptr; a.xc = c.w.xc; }
+      a.labels_in64 = nullptr;
+      tile_finalize(t, true, c.w.slabs, t.last_G);
+    } else if (c.labels_out != c.labels_init &&
+               hipMemcpyAsync(c.labels_out, c.labels_init, (size_t)c.P * 8, hipMemcpyDeviceToDevice, c.s) !=
+                   hipSuccess) {                // zero iterations: the labels pass through
+      return SPML_ERR_LAUNCH;
+    }
+    for (int it = 0; it < c.iterations; ++it) {
+      const bool last = (it == c.iterations - 1);
+      a.do_assign = 1; a.do_accum = last ? 0 : 1;
+      a.labels_out64 = last ? c.labels_out : nullptr;
+      rc = tile_pass(t);
+      if (rc != SPML_OK) return rc;
+      if (!last) tile_finalize(t, true, c.w.slabs, t.last_G);
+    }
+  }
+  trace_dump(a.trace, r.path, c.s);
+  return SPML_OK;
+}
+
+// ---- runner of the generic path (labels in c.w.lab32) ----
+int generic_assign_launch(const Call& c, const float* cent) {
+  typedef void (*Kernel)(const float*, int64_t, int, const int64_t*, int, int, const float*, int32_t*);
+  const int nc = (c.D + 63) / 64;               // 64-channel chunks of a row, rounded up to an instantiation
+  const int bucket = nc <= 3 ? nc : nc <= 5 ? 5 : nc <= 9 ? 9 : nc <= 17 ? 17 : 0;
+  const Kernel kern = select_int<1, 2, 3, 5, 9, 17>(bucket, Kernel(nullptr), [](auto NC_) -> Kernel {
+    return generic_assign<decltype(NC_)::value>;
+  });
+  if (!kern) return SPML_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((c.P + 15) / 16)), dim3(256), 0, c.s, c.x, c.P, c.D, c.seg_off, c.n_img,
+                     c.K, cent, c.w.lab32);
+  return launch_status();
+}
+
+// dst [n_img * K][D] = sums of the rows of X by (image, label)
+int generic_sums(const Call& c, float* dst) {
+  const int64_t M = (int64_t)c.n_img * c.K;
+  hipLaunchKernelGGL(generic_ids, dim3((unsigned)((c.P + 255) / 256)), dim3(256), 0, c.s, c.w.lab32, c.seg_off,
+                     c.n_img, c.K, c.P, c.w.ids);
+  if (deterministic_mode()) {                   // fixed-point sums (order-independent), converted once
+    long long* acc = c.w.det64;
+    if (hipMemsetAsync(acc, 0, (size_t)M * c.D * 8, c.s) != hipSuccess) return SPML_ERR_LAUNCH;
+    const int rc = segment_sum_launch(c.x, c.w.ids, c.P, c.D, M, dst, c.s, acc);
+    if (rc != SPML_OK) return rc;
+    hipLaunchKernelGGL(fix_to_f32, dim3((unsigned)((M * c.D + 255) / 256)), dim3(256), 0, c.s, acc, M * c.D, dst);
+    return launch_status();
+  }
+  if (hipMemsetAsync(dst, 0, (size_t)M * c.D * 4, c.s) != hipSuccess) return SPML_ERR_LAUNCH;
+  return segment_sum_launch(c.x, c.w.ids, c.P, c.D, M, dst, c.s);
+}
+
+int run_generic(Op op, const Call& c) {
+  int rc = SPML_OK;
+  if (c.given) {
+    rc = generic_assign_launch(c, c.given);
+    if (rc == SPML_OK && op == Op::fused_pass) rc = generic_sums(c, c.sums_out);
+    return rc;
+  }
+  for (int it = 0; it < c.iterations; ++it) {
+    rc = generic_sums(c, c.w.slabs);
+    if (rc != SPML_OK) return rc;
+    rc = spml_normalize_rows_f32(c.w.slabs, (int64_t)c.n_img * c.K, c.D, c.w.cent_f, c.s);
+    if (rc != SPML_OK) return rc;
+    rc = generic_assign_launch(c, c.w.cent_f);
+    if (rc != SPML_OK) return rc;
+  }
+  return SPML_OK;
+}
+
+// (alignment of x is checked at call time; the host-only queries assume a 16-byte aligned pointer)
+const float* const kAlignedX = reinterpret_cast<const float*>(uintptr_t(256));
+
+// repeats: see run_tiles
+int kmeans_common(Op op, int repeats, const float* x, int64_t P, int D, const int64_t* seg_off, int n_img,
+                  int64_t max_seg_len, int K, const int64_t* labels_init, const float* given_centroids,
+                  int iterations, int64_t* labels_out, float* centroids_out, float* sums_out, int flags, void* ws,
+                  size_t ws_bytes, unsigned long long* clocks, hipStream_t s) {
+  if (!x || !seg_off || !labels_out || P < 0 || D <= 0 || K <= 0 || n_img <= 0 ||
+      max_seg_len <= 0 || iterations < 0)
+    return SPML_ERR_INVALID_ARG;
+  if (!given_centroids && !labels_init) return SPML_ERR_INVALID_ARG;
+  if (D > 1088 && K > 64) return SPML_ERR_UNSUPPORTED;
+  const WsLayout wl = ws_layout(P, D, K, n_img, max_seg_len);
+  if (!ws || ws_bytes < wl.total) return SPML_ERR_WORKSPACE;
+  if (P == 0) return SPML_OK;
+  const Call c{x, P, D, seg_off, n_img, max_seg_len, K, labels_init, given_centroids, iterations, labels_out, sums_out,
+               flags, clocks,
+               kmeans_route(x, P, D, K, n_img, max_seg_len, given_centroids != nullptr, iterations, flags),
+               bind_ws(ws, wl), s};
+  const bool tiles = c.r.tile();
+  if (given_centroids && (flags & SPML_KMEANS_WS_PRECONVERTED) && !(tiles && c.r.pre))
+    return SPML_ERR_INVALID_ARG;
+  // tile-kernel paths read the int64 labels in their seed pass and write the int64 result in
+  // their last pass; the other paths go through the int32 work array
+  const unsigned pblocks = (unsigned)((P + 255) / 256);
+  if (labels_init && !tiles)
+    hipLaunchKernelGGL(labels_i64_to_i32, dim3(pblocks), dim3(256), 0, s, labels_init, c.w.lab32, P);
+  int rc;
+  if (tiles)
+    rc = run_tiles(op, repeats, c);
+  else if (c.r.path == kBigK)
+    rc = bigk_run(x, P, D, seg_off, n_img, max_seg_len, K, given_centroids, iterations, c.w.lab32, c.w.cent_f,
+                  op == Op::fused_pass ? sums_out : nullptr, flags, c.w.big, s);
+  else
+    rc = run_generic(op, c);
+  if (rc != SPML_OK) return rc;
+  if (!tiles)
+    hipLaunchKernelGGL(labels_i32_to_i64, dim3(pblocks), dim3(256), 0, s, c.w.lab32, labels_out, P);
+  if (centroids_out && !given_centroids && iterations > 0) {
+    if (hipMemcpyAsync(centroids_out, c.w.cent_f, (size_t)n_img * K * D * 4,
+                       hipMemcpyDeviceToDevice, s) != hipSuccess)
+      return SPML_ERR_LAUNCH;
+  }
   return launch_status();
 }
 
@@ -1841,44 +2076,11 @@ int generic_assign_launch(const float* x, int64_t P, int D, const int64_t* seg_o
 
 using namespace spml;
 
-namespace {
-
-// What a k-means call does, decided from host-visible arguments only.
-struct Route {
-  Plan pl;
-  bool big;                 // kmeans_big.hip
-  const char* name;
-};
-
-// run_iterations: iterations of a spml_kmeans_run_f32 call, 0 for the given-prototype entry points
-Route route_for(const float* x, int64_t P, int D, int K, int n_img, int64_t max_seg_len,
-                int flags, bool want_pre, int run_iterations = 0) {
-  Route r{};
-  r.pl = make_plan(x, P, D, K, n_img, max_seg_len, flags, want_pre);
-  r.big = !r.pl.fast && !(flags & SPML_KMEANS_FORCE_GENERIC) && bigk_shape(P, D, K, n_img);
-  if (r.pl.fast)
-    r.name = r.pl.v4k ? "mfma_f16x2_v4k" : r.pl.v3k ? "mfma_f16x2_v3k"
-                      : r.pl.v3 ? (r.pl.pre ? ((pass64_shape(D, K) && !(flags & SPML_KMEANS_NO_PASS64)) ? "mfma_f16x2_v4p"
-                                                                                                       : "mfma_f16x2_v3p")
-                                            : "mfma_f16x2_v3")
-                                : "mfma_f16x2";
-  else
-    r.name = r.big ? "mfma_f16x2_bigk" : "generic";
-  return r;
-}
-
-}  // namespace
-
 extern "C" const char* spml_kmeans_path_name(int64_t P, int D, int K, int n_img,
                                              int64_t max_seg_len, int iterations,
                                              int given_centroids, int flags) {
   if (P < 0 || D <= 0 || K <= 0 || n_img <= 0 || max_seg_len <= 0) return "invalid";
-  // (alignment of x is checked at call time; a 16-byte aligned pointer is assumed here)
-  const float* aligned = reinterpret_cast<const float*>(uintptr_t(256));
-  const bool want_pre = given_centroids ? (flags & SPML_KMEANS_WS_PRECONVERTED) != 0
-                                        : iterations >= 2;
-  return route_for(aligned, P, D, K, n_img, max_seg_len, flags, want_pre,
-                   given_centroids ? 0 : iterations).name;
+  return kPathName[kmeans_route(kAlignedX, P, D, K, n_img, max_seg_len, given_centroids != 0, iterations, flags).path];
 }
 
 extern "C" size_t spml_kmeans_workspace_bytes(int64_t P, int D, int K, int n_img,
@@ -1892,254 +2094,12 @@ extern "C" int spml_kmeans_profile_layout(int64_t P, int D, int K, int n_img, in
   if (!n_passes || !workgroups_per_pass || P < 0 || D <= 0 || K <= 0 || n_img <= 0 ||
       max_seg_len <= 0 || iterations < 1)
     return SPML_ERR_INVALID_ARG;
-  const float* aligned = reinterpret_cast<const float*>(uintptr_t(256));
-  const Route r = route_for(aligned, P, D, K, n_img, max_seg_len, 0, iterations >= 2, iterations);
-  if (!r.pl.fast) return SPML_ERR_UNSUPPORTED;
+  const Route r = kmeans_route(kAlignedX, P, D, K, n_img, max_seg_len, false, iterations, 0);
+  if (!r.tile()) return SPML_ERR_UNSUPPORTED;
   // (v4k: an iteration that also accumulates is two kernels = two entries)
-  *n_passes = r.pl.v4k ? 2 * iterations : iterations + 1;
-  *workgroups_per_pass = r.pl.G * n_img;
+  *n_passes = r.path == kV4k ? 2 * iterations : iterations + 1;
+  *workgroups_per_pass = r.G * n_img;
   return SPML_OK;
-}
-
-// mode: 0 = run (labels_init, iterations), 1 = assign (given centroids -> labels),
-//       2 = fused pass (given centroids -> labels + raw sums of X by the new labels)
-static int kmeans_common(int mode, const float* x, int64_t P, int D, const int64_t* seg_off,
-                         int n_img, int64_t max_seg_len, int K, const int64_t* labels_init,
-                         const float* given_centroids, int iterations, int64_t* labels_out,
-                         float* centroids_out, float* sums_out, int flags, void* ws,
-                         size_t ws_bytes, unsigned long long* clocks, hipStream_t s) {
-  if (!x || !seg_off || !labels_out || P < 0 || D <= 0 || K <= 0 || n_img <= 0 ||
-      max_seg_len <= 0 || iterations < 0)
-    return SPML_ERR_INVALID_ARG;
-  if (!given_centroids && !labels_init) return SPML_ERR_INVALID_ARG;
-  if (D > 1088 && K > 64) return SPML_ERR_UNSUPPORTED;
-  const WsLayout wl = ws_layout(P, D, K, n_img, max_seg_len);
-  if (!ws || ws_bytes < wl.total) return SPML_ERR_WORKSPACE;
-  if (P == 0) return SPML_OK;
-  unsigned char* base = static_cast<unsigned char*>(ws);
-  int32_t* lab32 = reinterpret_cast<int32_t*>(base + wl.lab32);
-  _Float16* cent_h = reinterpret_cast<_Float16*>(base + wl.cent_h);
-  _Float16* cent_l = reinterpret_cast<_Float16*>(base + wl.cent_l);
-  float* cent_f = reinterpret_cast<float*>(base + wl.cent_f);
-  float* slabs = reinterpret_cast<float*>(base + wl.slabs);
-  int64_t* ids = reinterpret_cast<int64_t*>(base + wl.ids);
-  float* sums_buf = reinterpret_cast<float*>(base + wl.sums);
-  float* ssq_buf = reinterpret_cast<float*>(base + wl.ssq);
-
-  // pre-converting X pays for itself from the third pass on; given centroids: only when
-  // the caller says the workspace already holds the converted tiles
-  const bool want_pre = given_centroids ? (flags & SPML_KMEANS_WS_PRECONVERTED) != 0
-                                        : iterations >= 2;
-  const Route route = route_for(x, P, D, K, n_img, max_seg_len, flags, want_pre,
-                                (mode == 0 && !given_centroids) ? iterations : 0);
-  const Plan& pl = route.pl;
-  if (given_centroids && (flags & SPML_KMEANS_WS_PRECONVERTED) && !(pl.fast && pl.pre))
-    return SPML_ERR_INVALID_ARG;
-  const unsigned pblocks = (unsigned)((P + 255) / 256);
-  const int nchunk = (D + 63) / 64;
-  int rc = SPML_OK;
-
-  // tile-kernel paths read the int64 labels in their seed pass and write the int64 result in
-  // their last pass; the other paths go through the int32 work array
-  if (labels_init && !pl.fast)
-    hipLaunchKernelGGL(labels_i64_to_i32, dim3(pblocks), dim3(256), 0, s, labels_init, lab32, P);
-
-  if (pl.fast) {
-    PassArgs a{};
-    a.x = x; a.x_bytes = P * (int64_t)D * 4; a.P = P; a.D = D; a.K = K; a.n_img = n_img; a.G = pl.G;
-    a.nvt = pl.nvt;
-    a.seg_off = seg_off; a.cent_h = cent_h; a.cent_l = cent_l; a.kpad = pl.kpad;
-    a.dpad = pl.dpad; a.labels = lab32; a.slabs = slabs;
-    a.cent_f32 = given_centroids ? given_centroids : cent_f;
-    a.trace = nullptr;
-    a.xc = nullptr;
-    a.xc_out = nullptr;
-    a.clocks = nullptr;
-    a.labels_in64 = nullptr;
-    a.labels_out64 = nullptr;
-    unsigned char* xc_buf = base + wl.xc;
-    // v3: the seed pass converts (in LDS) and writes the tiles out itself; the
-    // many-cluster kernel only exists on pre-converted tiles -> separate conversion
-    const int tail_ch = D - 32 * (D / 32);
-    const bool seed_converts = !given_centroids && pl.pre && pl.v3 && !pl.v3k &&
-                               (tail_ch == 0 || tail_ch == 2) &&
-                               !(flags & SPML_KMEANS_SEPARATE_PRECONVERT);
-    if (given_centroids && pl.pre) {
-      a.xc = xc_buf;                            // converted by spml_kmeans_preconvert_f32
-    } else if (pl.pre && !seed_converts) {
-      rc = launch_preconvert(x, D, seg_off, n_img, max_seg_len, pl, xc_buf, s);
-      if (rc != SPML_OK) return rc;
-      a.xc = xc_buf;
-    }
-#ifdef SPML_TRACE
-    static unsigned long long* trace_buf = nullptr;
-    if (getenv("SPML_KM_TRACE")) {
-      if (!trace_buf) (void)hipMalloc(&trace_buf, (40 + 2048) * 8);
-      a.trace = trace_buf;
-    }
-#endif
-    // passes with an E-step on pre-converted tiles (K <= 48): the pixel-split kernel on 64-pixel tiles
-    // (kmeans64.hip) with its own grid; the M-only seed pass stays on kmeans_pass16
-    const bool use64 = pl.v3 && !pl.v3k && pl.pre && pass64_shape(D, K) && !(flags & SPML_KMEANS_NO_PASS64);
-    int G64 = pl.G;
-    if (use64) {
-      const int64_t tiles64 = (max_seg_len + 63) / 64;
-      int64_t gI = (256 * pass64_wg_per_cu(D, K) + n_img - 1) / n_img;
-      if (gI > pl.G) gI = pl.G;                  // (the slab area of the workspace is sized for pl.G)
-      if (gI > tiles64) gI = tiles64;
-      G64 = (int)(gI < 1 ? 1 : gI);
-    }
-    const int frag_major = (use64 || pl.v4k) ? 1 : 0;     // prototype fragments in the order the 64-pixel kernels load them
-    auto finalize = [&](int normalize, const float* src, int G) {
-      // one launch when there are enough (cluster, image) rows to fill the chip: a block pulls its whole row
-      // (G x D x 4 bytes) at ~50 GB/s, so 36 blocks of a single 513 x 513 x 258 image take longer (~10 us) than
-      // the two launches of kmeans_reduce_slabs (5 x 36 blocks) + kmeans_normalize (7 + 5 us); 16 training
-      // images: 34.8 instead of 38.5 us per iteration
-      const int nl = ((flags & SPML_KMEANS_TWO_KERNEL_FINALIZE) || pl.kpad * n_img < 128) ? 0 : finalize_loads(G, D);
-      if (normalize && nl) {
-#define SPML_FIN(N_)                                                                                              \
-        if (nl == N_)                                                                                              \
-          hipLaunchKernelGGL(kmeans_finalize<N_>, dim3(pl.kpad, n_img), dim3(1024), 0, s, src, G, K, D, pl.kpad,    \
-                             pl.dpad, frag_major, cent_f, cent_h, cent_l);
-        SPML_FIN(8) SPML_FIN(16) SPML_FIN(32) SPML_FIN(56)
-#undef SPML_FIN
-      } else if (normalize) {
-        hipLaunchKernelGGL(kmeans_reduce_slabs, dim3(nchunk, K, n_img), dim3(1024), 0, s, src, G, K,
-                           D, sums_buf, ssq_buf);
-        hipLaunchKernelGGL(kmeans_normalize, dim3(pl.kpad, n_img), dim3(256), 0, s, sums_buf, ssq_buf,
-                           nchunk, K, D, pl.kpad, pl.dpad, 1, frag_major, cent_f, cent_h, cent_l);
-      } else {                                  // given prototypes: split only
-        hipLaunchKernelGGL(kmeans_normalize, dim3(pl.kpad, n_img), dim3(256), 0, s, src,
-                           (const float*)nullptr, nchunk, K, D, pl.kpad, pl.dpad, 0, frag_major,
-                           (float*)nullptr, cent_h, cent_l);
-      }
-    };
-    int pass_index = 0;
-    int last_G = pl.G;                          // slabs the last M-step pass wrote per image
-    auto run_pass = [&](const Plan& plan) -> int {
-      a.clocks = clocks ? clocks + (size_t)pass_index * 2 * pl.G * n_img : nullptr;
-      pass_index += (pl.v4k && a.do_assign && a.do_accum) ? 2 : 1;
-      if (use64 && a.do_assign && a.xc) {
-        PassArgs b = a;
-        b.G = G64;
-        last_G = G64;
-        return launch_pass64(b, s);
-      }
-      last_G = plan.G;
-      return launch_pass(a, plan, s);
-    };
-    const bool pass_only = mode == 2 && (flags & SPML_KMEANS_PASS_ONLY) && (flags & SPML_KMEANS_WS_PRECONVERTED);
-    if (given_centroids) {
-      if (!pass_only) finalize(0, given_centroids, 1);          // split only
-      a.do_assign = 1; a.do_accum = mode == 2 ? 1 : 0;
-      a.labels_out64 = labels_out;
-      rc = run_pass(pl);
-      if (rc != SPML_OK) return rc;
-      for (int rep = 1; pass_only && rep < ((flags >> 16) & 0xff); ++rep) {    // (measurement: back-to-back launches)
-        --pass_index;
-        rc = run_pass(pl);
-        if (rc != SPML_OK) return rc;
-      }
-      if (mode == 2 && !pass_only)              // raw sums of X by the new labels
-        hipLaunchKernelGGL(kmeans_reduce_slabs, dim3(nchunk, K, n_img), dim3(1024), 0, s, slabs, last_G,
-                           K, D, sums_out, ssq_buf);
-    } else {
-      if (iterations > 0) {
-        a.do_assign = 0; a.do_accum = 1;        // M-step on the initial labels
-        a.labels_in64 = labels_init;
-        if (seed_converts) {
-          Plan seed = pl;                       // same grid, in-LDS conversion variant
-          seed.pre = false;
-          seed.lds = pass16_lds_bytes(D, false);
-          a.xc_out = xc_buf;
-          rc = run_pass(seed);
-          a.xc_out = nullptr;
-          a.xc = xc_buf;
-        } else {
-          rc = run_pass(pl);
-        }
-        if (rc != SPML_OK) return rc;
-        a.labels_in64 = nullptr;
-        finalize(1, slabs, last_G);
-      } else if (labels_out != labels_init &&
-                 hipMemcpyAsync(labels_out, labels_init, (size_t)P * 8, hipMemcpyDeviceToDevice, s) !=
-                     hipSuccess) {              // zero iterations: the labels pass through
-        return SPML_ERR_LAUNCH;
-      }
-      for (int it = 0; it < iterations; ++it) {
-        const bool last = (it == iterations - 1);
-        a.do_assign = 1; a.do_accum = last ? 0 : 1;
-        a.labels_out64 = last ? labels_out : nullptr;
-        rc = run_pass(pl);
-        if (rc != SPML_OK) return rc;
-        if (!last) finalize(1, slabs, last_G);
-      }
-    }
-#ifdef SPML_TRACE
-    if (a.trace) {
-      (void)hipStreamSynchronize(s);
-      static unsigned long long h[40 + 2048];
-      (void)hipMemcpy(h, a.trace, sizeof(h), hipMemcpyDeviceToHost);
-      const char* nm16[8] = {"wait", "convert|epilogue", "barrier+dma", "E", "barrier", "labels", "M", "prologue"};
-      const char* nm64[8] = {"wait+barrier", "epilogue", "dma-issue", "E-mfma", "argmax+publish+barrier", "onehot", "M-mfma", "prologue"};
-      const char* nm64k[8] = {"dma-wait", "barrier", "label-read", "epilogue", "-", "onehot", "M-mfma", "prologue"};   // (the accumulate kernel)
-      const char** nm = pl.v4k ? nm64k : use64 ? nm64 : nm16;
-      for (int w = 0; w < 4; ++w) {
-        fprintf(stderr, "wave%d:", w);
-        for (int i = 0; i < 8; ++i) fprintf(stderr, " %s=%llu", nm[i], h[w * 8 + i]);
-        fprintf(stderr, " wall_us=%.2f\n", h[32 + w] * 0.01);
-      }
-    }
-#endif
-  } else if (route.big) {
-    rc = bigk_run(x, P, D, seg_off, n_img, max_seg_len, K, given_centroids, iterations, lab32, cent_f,
-                  mode == 2 ? sums_out : nullptr, flags, base + wl.big, s);
-    if (rc != SPML_OK) return rc;
-  } else {
-    auto assign = [&](const float* cent) -> int {
-      return generic_assign_launch(x, P, D, seg_off, n_img, K, cent, lab32, s);
-    };
-    const int64_t M = (int64_t)n_img * K;
-    auto msums = [&](float* dst) -> int {
-      hipLaunchKernelGGL(generic_ids, dim3(pblocks), dim3(256), 0, s, lab32, seg_off, n_img, K, P,
-                         ids);
-      if (deterministic_mode()) {                // fixed-point sums (order-independent), converted once
-        long long* acc = reinterpret_cast<long long*>(base + wl.det64);
-        if (hipMemsetAsync(acc, 0, (size_t)M * D * 8, s) != hipSuccess) return SPML_ERR_LAUNCH;
-        const int rc_ = segment_sum_launch(x, ids, P, D, M, dst, s, acc);
-        if (rc_ != SPML_OK) return rc_;
-        hipLaunchKernelGGL(fix_to_f32, dim3((unsigned)((M * D + 255) / 256)), dim3(256), 0, s, acc, M * D, dst);
-        return launch_status();
-      }
-      if (hipMemsetAsync(dst, 0, (size_t)M * D * 4, s) != hipSuccess) return SPML_ERR_LAUNCH;
-      return segment_sum_launch(x, ids, P, D, M, dst, s);
-    };
-    if (given_centroids) {
-      rc = assign(given_centroids);
-      if (rc != SPML_OK) return rc;
-      if (mode == 2) {
-        rc = msums(sums_out);
-        if (rc != SPML_OK) return rc;
-      }
-    } else {
-      for (int it = 0; it < iterations; ++it) {
-        rc = msums(slabs);
-        if (rc != SPML_OK) return rc;
-        rc = spml_normalize_rows_f32(slabs, M, D, cent_f, s);
-        if (rc != SPML_OK) return rc;
-        rc = assign(cent_f);
-        if (rc != SPML_OK) return rc;
-      }
-    }
-  }
-  if (!pl.fast)
-    hipLaunchKernelGGL(labels_i32_to_i64, dim3(pblocks), dim3(256), 0, s, lab32, labels_out, P);
-  if (centroids_out && !given_centroids && iterations > 0) {
-    if (hipMemcpyAsync(centroids_out, cent_f, (size_t)n_img * K * D * 4,
-                       hipMemcpyDeviceToDevice, s) != hipSuccess)
-      return SPML_ERR_LAUNCH;
-  }
-  return launch_status();
 }
 
 extern "C" int spml_kmeans_run_f32(const float* x, int64_t P, int D, const int64_t* seg_offsets,
@@ -2148,7 +2108,7 @@ extern "C" int spml_kmeans_run_f32(const float* x, int64_t P, int D, const int64
                                    int64_t* labels_out, float* centroids_out, int flags,
                                    void* ws, size_t ws_bytes, void* stream) {
   if (!labels_init) return SPML_ERR_INVALID_ARG;
-  return kmeans_common(0, x, P, D, seg_offsets, n_img, max_seg_len, K, labels_init, nullptr,
+  return kmeans_common(Op::run, 1, x, P, D, seg_offsets, n_img, max_seg_len, K, labels_init, nullptr,
                        iterations, labels_out, centroids_out, nullptr, flags, ws, ws_bytes, nullptr,
                        (hipStream_t)stream);
 }
@@ -2164,7 +2124,7 @@ extern "C" int spml_kmeans_run_profiled_f32(const float* x, int64_t P, int D,
   const int rc = spml_kmeans_profile_layout(P, D, K, n_img, max_seg_len, iterations, &n_pass, &wgs);
   if (rc != SPML_OK) return rc;
   if (pass_clocks_len < (size_t)n_pass * wgs * 2) return SPML_ERR_WORKSPACE;
-  return kmeans_common(0, x, P, D, seg_offsets, n_img, max_seg_len, K, labels_init, nullptr,
+  return kmeans_common(Op::run, 1, x, P, D, seg_offsets, n_img, max_seg_len, K, labels_init, nullptr,
                        iterations, labels_out, nullptr, nullptr,
                        flags & ~SPML_KMEANS_FORCE_GENERIC, ws,
                        ws_bytes, reinterpret_cast<unsigned long long*>(pass_clocks),
@@ -2177,7 +2137,7 @@ extern "C" int spml_kmeans_assign_f32(const float* x, int64_t P, int D,
                                       int64_t* labels_out, int flags, void* ws, size_t ws_bytes,
                                       void* stream) {
   if (!centroids) return SPML_ERR_INVALID_ARG;
-  return kmeans_common(1, x, P, D, seg_offsets, n_img, max_seg_len, K, nullptr, centroids, 1,
+  return kmeans_common(Op::assign, 1, x, P, D, seg_offsets, n_img, max_seg_len, K, nullptr, centroids, 1,
                        labels_out, nullptr, nullptr, flags, ws, ws_bytes, nullptr,
                        (hipStream_t)stream);
 }
@@ -2188,8 +2148,9 @@ extern "C" int spml_kmeans_fused_pass_f32(const float* x, int64_t P, int D,
                                           int64_t* labels_out, float* centroid_sums_out, int flags,
                                           void* ws, size_t ws_bytes, void* stream) {
   if (!centroids_in || !centroid_sums_out) return SPML_ERR_INVALID_ARG;
-  return kmeans_common(2, x, P, D, seg_offsets, n_img, max_seg_len, K, nullptr, centroids_in, 1,
-                       labels_out, nullptr, centroid_sums_out, flags, ws, ws_bytes, nullptr,
+  const int repeats = (flags >> 16) & 0xff;     // (SPML_KMEANS_PASS_ONLY: back-to-back launches, 0 = 1)
+  return kmeans_common(Op::fused_pass, repeats < 1 ? 1 : repeats, x, P, D, seg_offsets, n_img, max_seg_len, K,
+                       nullptr, centroids_in, 1, labels_out, nullptr, centroid_sums_out, flags, ws, ws_bytes, nullptr,
                        (hipStream_t)stream);
 }
 
@@ -2201,9 +2162,9 @@ extern "C" int spml_kmeans_preconvert_f32(const float* x, int64_t P, int D,
     return SPML_ERR_INVALID_ARG;
   const WsLayout wl = ws_layout(P, D, K, n_img, max_seg_len);
   if (!ws || ws_bytes < wl.total) return SPML_ERR_WORKSPACE;
-  const Route r = route_for(x, P, D, K, n_img, max_seg_len, 0, true);
-  if (!(r.pl.fast && r.pl.pre)) return SPML_ERR_UNSUPPORTED;
+  // the route of an assign / fused pass that takes the converted tiles
+  const Route r = kmeans_route(x, P, D, K, n_img, max_seg_len, true, 1, SPML_KMEANS_WS_PRECONVERTED);
+  if (!(r.tile() && r.pre)) return SPML_ERR_UNSUPPORTED;
   if (P == 0) return SPML_OK;
-  return launch_preconvert(x, D, seg_offsets, n_img, max_seg_len, r.pl,
-                           static_cast<unsigned char*>(ws) + wl.xc, (hipStream_t)stream);
+  return launch_preconvert(x, D, seg_offsets, n_img, max_seg_len, r, bind_ws(ws, wl).xc, (hipStream_t)stream);
 }

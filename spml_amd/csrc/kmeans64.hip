@@ -524,48 +524,38 @@ __global__ __launch_bounds__(256, p64_wgpc(MT16, Q, TAIL)) void kmeans_pass64(Pa
 #undef P64_NOP_0
 #undef P64_NOP_1
 
-template <int MT16, int Q, int TAIL>
-int launch64_t(const PassArgs& a, hipStream_t s) {
-  const int lds = p64_lds(Q, TAIL);
-  if (a.do_accum) {
-    auto kern = kmeans_pass64<MT16, Q, TAIL, true>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    hipLaunchKernelGGL(kern, dim3(a.G, a.n_img), dim3(256), lds, s, a);
-  } else {
-    auto kern = kmeans_pass64<MT16, Q, TAIL, false>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    hipLaunchKernelGGL(kern, dim3(a.G, a.n_img), dim3(256), lds, s, a);
-  }
-  return launch_status();
-}
-
 }  // namespace
 
 bool pass64_shape(int D, int K) {
-  const int q = D / 32, tl = D - 32 * q;
-  return K >= 1 && K <= 16 * k64MaxMT && tl <= 8 && (q == 1 || q == 2 || q == 4 || q == 8);
+  const RowShape r = row_shape(D);
+  return K >= 1 && K <= 16 * k64MaxMT && r.tail <= 8 && (r.q == 1 || r.q == 2 || r.q == 4 || r.q == 8);
 }
 
 int pass64_wg_per_cu(int D, int K) {
-  const int q = D / 32, tl = D - 32 * q;
-  return p64_wgpc((K + 15) / 16, q, tl ? 1 : 0);
+  const RowShape r = row_shape(D);
+  return p64_wgpc((K + 15) / 16, r.q, r.tail ? 1 : 0);
 }
 
 size_t pass64_lds_bytes(int D) {
-  const int q = D / 32, tl = D - 32 * q;
-  return (size_t)p64_lds(q, tl ? 1 : 0);
+  const RowShape r = row_shape(D);
+  return (size_t)p64_lds(r.q, r.tail);
 }
 
 int launch_pass64(const PassArgs& a, hipStream_t s) {
   if (!a.do_assign || !a.xc || !pass64_shape(a.D, a.K)) return SPML_ERR_UNSUPPORTED;
-  const int q = a.D / 32, tail = (a.D - 32 * q) ? 1 : 0, mt = (a.K + 15) / 16;
-#define SPML_P64(M_, Q_)                                                         \
-  if (mt == M_ && q == Q_) return tail ? launch64_t<M_, Q_, 1>(a, s) : launch64_t<M_, Q_, 0>(a, s);
-#define SPML_P64Q(M_) SPML_P64(M_, 1) SPML_P64(M_, 2) SPML_P64(M_, 4) SPML_P64(M_, 8)
-  SPML_P64Q(1) SPML_P64Q(2) SPML_P64Q(3)
-#undef SPML_P64Q
-#undef SPML_P64
-  return SPML_ERR_UNSUPPORTED;
+  const RowShape r = row_shape(a.D);
+  const bool tail = r.tail != 0, fused = a.do_accum != 0;
+  const PassKernel none = nullptr;
+  const PassKernel kern = select_int<1, 2, 3>((a.K + 15) / 16, none, [&](auto M_) {
+    return select_int<1, 2, 4, 8>(r.q, none, [&](auto Q_) -> PassKernel {
+      constexpr int M = decltype(M_)::value, Q = decltype(Q_)::value;
+      if (fused) return tail ? kmeans_pass64<M, Q, 1, true> : kmeans_pass64<M, Q, 0, true>;
+      return tail ? kmeans_pass64<M, Q, 1, false> : kmeans_pass64<M, Q, 0, false>;
+    });
+  });
+  if (!kern) return SPML_ERR_UNSUPPORTED;
+  launch_dyn(kern, dim3(a.G, a.n_img), p64_lds(r.q, r.tail), s, a);
+  return launch_status();
 }
 
 }  // namespace spml

@@ -275,15 +275,6 @@ __global__ __launch_bounds__(512, 2) void kmeans_assign64k(PassArgs a) {
   KM_CLOCK_END
 }
 
-template <int MT, int Q, int TAIL>
-int launch64k_t(const PassArgs& a, hipStream_t s) {
-  const int lds = 4 * p64_slot_bytes(Q, TAIL) + 16384;
-  auto kern = kmeans_assign64k<MT, Q, TAIL>;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL(kern, dim3(a.G, a.n_img), dim3(512), lds, s, a);
-  return launch_status();
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // M-step of the same shapes (calculate_prototypes_from_labels, segsort/common.py:11-41: sums of the rows of X by
 // label) on the same tiles and eight waves: sums^T[d][k] += X^T (LDS transpose read of the channel-major fragment
@@ -549,15 +540,6 @@ __global__ __launch_bounds__(512, 2) void kmeans_accum64k(PassArgs a) {
 }
 #undef K64_MFMA
 
-template <int MT, int Q, int TAIL>
-int launch64k_accum_t(const PassArgs& a, hipStream_t s) {
-  const int lds = 4 * p64_slot_bytes(Q, TAIL) + 4096;
-  auto kern = kmeans_accum64k<MT, Q, TAIL>;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL(kern, dim3(a.G, a.n_img), dim3(512), lds, s, a);
-  return launch_status();
-}
-
 #undef P64_MFMA
 #undef P64_MFMA0
 #undef P64_NOP_0
@@ -572,31 +554,42 @@ int assign64k_kpad(int K) {
 }
 
 bool assign64k_shape(int D, int K) {
-  const int q = D / 32, tl = D - 32 * q;
-  return K > 64 && K <= 144 && tl <= 8 && (q == 4 || q == 8);
+  const RowShape r = row_shape(D);
+  return K > 64 && K <= 144 && r.tail <= 8 && (r.q == 4 || r.q == 8);
 }
 
+namespace {
+
+// the assign (LDS: four tile slots + 16 KB) or the accumulate kernel (+ 4 KB) of the call's shape on its G x n_img grid
+// of 512-thread workgroups
+int launch64k(const PassArgs& a, bool assign, hipStream_t s) {
+  if (!a.xc || !assign64k_shape(a.D, a.K) || a.kpad != assign64k_kpad(a.K)) return SPML_ERR_UNSUPPORTED;
+  const RowShape r = row_shape(a.D);
+  const bool tail = r.tail != 0;
+  const PassKernel none = nullptr;
+  const PassKernel kern = select_int<5, 6, 8, 9>(a.kpad / 16, none, [&](auto M_) {
+    return select_int<4, 8>(r.q, none, [&](auto Q_) -> PassKernel {
+      constexpr int M = decltype(M_)::value, Q = decltype(Q_)::value;
+      if (assign) return tail ? kmeans_assign64k<M, Q, 1> : kmeans_assign64k<M, Q, 0>;
+      return tail ? kmeans_accum64k<M, Q, 1> : kmeans_accum64k<M, Q, 0>;
+    });
+  });
+  if (!kern) return SPML_ERR_UNSUPPORTED;
+  launch_dyn_block(kern, dim3(a.G, a.n_img), dim3(512), 4 * p64_slot_bytes(r.q, r.tail) + (assign ? 16384 : 4096), s, a);
+  return launch_status();
+}
+
+}  // namespace
+
 int launch_assign64k(const PassArgs& a, hipStream_t s) {
-  if (!a.do_assign || a.do_accum || !a.xc || !assign64k_shape(a.D, a.K) || a.kpad != assign64k_kpad(a.K))
-    return SPML_ERR_UNSUPPORTED;
-  const int q = a.D / 32, tail = (a.D - 32 * q) ? 1 : 0, mt = a.kpad / 16;
-#define SPML_K648(M_, Q_) \
-  if (mt == M_ && q == Q_) return tail ? launch64k_t<M_, Q_, 1>(a, s) : launch64k_t<M_, Q_, 0>(a, s);
-  SPML_K648(5, 4) SPML_K648(5, 8) SPML_K648(6, 4) SPML_K648(6, 8) SPML_K648(8, 4) SPML_K648(8, 8) SPML_K648(9, 4) SPML_K648(9, 8)
-#undef SPML_K648
-  return SPML_ERR_UNSUPPORTED;
+  if (!a.do_assign || a.do_accum) return SPML_ERR_UNSUPPORTED;
+  return launch64k(a, true, s);
 }
 
 // M-step only on the same tiles, labels from a.labels / a.labels_in64
 int launch_accum64k(const PassArgs& a, hipStream_t s) {
-  if (a.do_assign || !a.do_accum || !a.xc || !assign64k_shape(a.D, a.K) || a.kpad != assign64k_kpad(a.K))
-    return SPML_ERR_UNSUPPORTED;
-  const int q = a.D / 32, tail = (a.D - 32 * q) ? 1 : 0, mt = a.kpad / 16;
-#define SPML_K64A(M_, Q_) \
-  if (mt == M_ && q == Q_) return tail ? launch64k_accum_t<M_, Q_, 1>(a, s) : launch64k_accum_t<M_, Q_, 0>(a, s);
-  SPML_K64A(5, 4) SPML_K64A(5, 8) SPML_K64A(6, 4) SPML_K64A(6, 8) SPML_K64A(8, 4) SPML_K64A(8, 8) SPML_K64A(9, 4) SPML_K64A(9, 8)
-#undef SPML_K64A
-  return SPML_ERR_UNSUPPORTED;
+  if (a.do_assign || !a.do_accum) return SPML_ERR_UNSUPPORTED;
+  return launch64k(a, false, s);
 }
 
 }  // namespace spml

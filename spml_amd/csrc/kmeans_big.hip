@@ -690,7 +690,9 @@ inline int bigk_nk16(int D) {
   const int n = (D + 15) / 16;
   return n <= 5 ? 5 : n <= 9 ? 9 : n <= 17 ? 17 : n <= 33 ? 33 : 0;
 }
-inline int bigk_npt(int nk16) { return nk16 <= 17 ? 2 : 1; }
+// 32-pixel tiles per wave of the exact kernels / of the screening kernel
+constexpr int bigk_npt(int nk16) { return nk16 <= 17 ? 2 : 1; }
+constexpr int bigk_npts(int nk16) { return nk16 == 33 ? 2 : 4; }
 
 BigWs bigk_ws(int64_t P, int D, int K, int n_img) {
   BigWs w{};
@@ -732,28 +734,6 @@ __global__ __launch_bounds__(256) void bigk_cmax(const float* __restrict__ cent,
   if (lane == 0) red[wv] = m;
   __syncthreads();
   if (threadIdx.x == 0) cmax[img] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) * 1.000001f;
-}
-
-template <int NK16, int NPT, int NPTS>
-int launch_screened_t(const BigArgs& a, const BigArgs& as, int grid_screen, int grid_list, hipStream_t s) {
-  auto ks = bigk_screen<NK16, NPTS>;
-  auto kl = bigk_assign_list<NK16, NPT>;
-  const int lds_s = 2 * NK16 * 1024, lds_l = 2 * NK16 * 2048;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, lds_s);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kl), hipFuncAttributeMaxDynamicSharedMemorySize, lds_l);
-  hipLaunchKernelGGL(ks, dim3(grid_screen), dim3(256), lds_s, s, as);
-  hipLaunchKernelGGL(kl, dim3(grid_list), dim3(256), lds_l, s, a);
-  return launch_status();
-}
-
-template <int NK16, int NPT>
-int launch_assign_t(const BigArgs& a, int grid, hipStream_t s) {
-  auto kern = bigk_assign<NK16, NPT>;
-  const int lds = 2 * NK16 * 2048;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a);
-  return launch_status();
 }
 
 }  // namespace
@@ -814,7 +794,7 @@ int bigk_run(const float* x, int64_t P, int D, const int64_t* seg_off, int n_img
   // every pixel whose top-2 margin exceeds the error bound of the hi-only score; the exact
   // kernel then runs over the ambiguous pixels only.  Worth it from a few hundred clusters on.
   const bool screen = !(flags & SPML_KMEANS_NO_SCREEN) && K >= 256;
-  const int npts = nk16 == 33 ? 2 : 4;            // 32-pixel tiles per wave of the screening kernel
+  const int npts = bigk_npts(nk16);
   BigArgs as = a;
   int grid_screen = 0;
   // exact kernel over the lists: at most ceil(P / tile) + n_img tiles, or 256 items when split
@@ -833,17 +813,17 @@ int bigk_run(const float* x, int64_t P, int D, const int64_t* seg_off, int n_img
     hipLaunchKernelGGL(bigk_cmax, dim3(n_img), dim3(256), 0, s, given_centroids, K, D, cmax, 1.0f);
   }
   auto estep = [&]() -> int {
-    if (screen) {
-      if (hipMemsetAsync(amb_count, 0, (size_t)n_img * 4, s) != hipSuccess) return SPML_ERR_LAUNCH;
-#define SPML_BIGS(NK_, NP_, NS_) if (nk16 == NK_ && npt == NP_) return launch_screened_t<NK_, NP_, NS_>(a, as, grid_screen, grid_list, s);
-      SPML_BIGS(5, 2, 4) SPML_BIGS(9, 2, 4) SPML_BIGS(17, 2, 4) SPML_BIGS(33, 1, 2)
-#undef SPML_BIGS
-      return SPML_ERR_UNSUPPORTED;
-    }
-#define SPML_BIG(NK_, NP_) if (nk16 == NK_ && npt == NP_) return launch_assign_t<NK_, NP_>(a, grid, s);
-    SPML_BIG(5, 2) SPML_BIG(9, 2) SPML_BIG(17, 2) SPML_BIG(33, 1)
-#undef SPML_BIG
-    return SPML_ERR_UNSUPPORTED;
+    if (screen && hipMemsetAsync(amb_count, 0, (size_t)n_img * 4, s) != hipSuccess) return SPML_ERR_LAUNCH;
+    return select_int<5, 9, 17, 33>(nk16, (int)SPML_ERR_UNSUPPORTED, [&](auto NK_) -> int {
+      constexpr int NK = decltype(NK_)::value, NPT = bigk_npt(NK), NPTS = bigk_npts(NK);
+      if (screen) {
+        launch_dyn(bigk_screen<NK, NPTS>, dim3(grid_screen), 2 * NK * 1024, s, as);
+        launch_dyn(bigk_assign_list<NK, NPT>, dim3(grid_list), 2 * NK * 2048, s, a);
+      } else {
+        launch_dyn(bigk_assign<NK, NPT>, dim3(grid), 2 * NK * 2048, s, a);
+      }
+      return launch_status();
+    });
   };
   auto finalize = [&](const float* given) {
     if (!given)

@@ -33,6 +33,19 @@ struct PassArgs {
                               // 100-MHz s_memrealtime ticks, or null (spml_kmeans_run_profiled_f32)
 };
 
+typedef void (*PassKernel)(PassArgs);      // every pass kernel of the tile paths
+
+// a row of D channels as the tile kernels see it: q k-steps of 32 channels + `tail` channels (location, colours)
+struct RowShape { int q, tail; };
+inline RowShape row_shape(int D) { return {D / 32, D - 32 * (D / 32)}; }
+
+// workgroups per image of a pass: `target` over all images, at most one per tile of the largest image, at least one
+inline int wg_per_image(int target, int n_img, int64_t tiles) {
+  int64_t g = (target + n_img - 1) / n_img;
+  if (g > tiles) g = tiles;
+  return (int)(g < 1 ? 1 : g);
+}
+
 // first / last instruction of a pass kernel when a.clocks is set (one lane per workgroup; the
 // end stamp is taken after this workgroup's stores have drained)
 #define KM_CLOCK_BEGIN                                                                     \

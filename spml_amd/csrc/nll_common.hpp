@@ -125,14 +125,6 @@ __device__ __forceinline__ void dma_wait_and_sync() {
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-// Launch of a 256-thread kernel whose dynamic LDS may exceed the 64-KB default: the attribute, then the launch.
-// A tag / no-tag pair is one call: launch_dyn(tag ? k<..., true> : k<..., false>, ...).
-template <typename... Params, typename... Args>
-inline void launch_dyn(void (*kernel)(Params...), dim3 grid, int lds_bytes, hipStream_t s, Args&&... args) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  hipLaunchKernelGGL(kernel, grid, dim3(256), lds_bytes, s, std::forward<Args>(args)...);
-}
-
 // nll_de3.hip: the software-pipelined embedding-gradient kernel (KS <= 4, 32-bit codes); `rows` = grid
 // rows (chunk c is taken by row c mod rows), partial sums into a.partial_de as nll_bwd_de2 writes them
 int nll_launch_bwd_de3(const NllArgs& a, int rows, hipStream_t s);

@@ -211,3 +211,85 @@ def test_upsample_ce_backward_route_of_every_tested_shape(lib_path):
   assert _ffi.upsample_ce_bwd_path_name(65536, 21, 33, 29, 129, 113) == 'gather'    # more images than gridDim.z takes
   assert _ffi.upsample_ce_bwd_path_name(1, 65, 9, 9, 65, 65) == 'unsupported'
   assert {len(_ffi.upsample_ce_bwd_path_name(1, c, 9, 9, 65, 65)) for c in (1, 24, 25, 32, 33, 64)} == {6}
+
+
+# (D, K, n_img, max_seg_len, iterations, given_centroids, flags) -> path; P = n_img * max_seg_len.  The names follow the
+# header's documentation of spml_kmeans_path_name.
+KMEANS_ROUTES = [
+    (66, 36, 1, 4099, 3, 0, 0, 'mfma_f16x2_v4p'),          # the training shape class: >= 3 passes, K <= 48
+    (66, 36, 16, 16900, 10, 0, 0, 'mfma_f16x2_v4p'),
+    (258, 36, 1, 263169, 3, 0, 0, 'mfma_f16x2_v4p'),
+    (66, 36, 1, 4099, 2, 0, 0, 'mfma_f16x2_v4p'),          # two iterations are three passes
+    (37, 25, 1, 4099, 3, 0, 0, 'mfma_f16x2_v4p'),          # location + colours: only on pre-converted tiles ...
+    (37, 25, 1, 4099, 1, 0, 0, 'generic'),                 # ... (and D is odd)
+    (66, 36, 1, 4099, 3, 0, 16, 'mfma_f16x2_v4p'),         # SEPARATE_PRECONVERT, TWO_KERNEL_FINALIZE: same path
+    (66, 36, 1, 4099, 3, 0, 1024, 'mfma_f16x2_v4p'),
+    (66, 36, 1, 4099, 3, 0, 512, 'mfma_f16x2_v3p'),        # NO_PASS64
+    (130, 64, 1, 4099, 3, 0, 0, 'mfma_f16x2_v3p'),         # 48 < K <= 64
+    (66, 49, 3, 4099, 3, 0, 0, 'mfma_f16x2_v3p'),
+    (66, 36, 1, 4099, 1, 0, 0, 'mfma_f16x2_v3'),           # < 3 passes
+    (256, 16, 1, 4099, 1, 0, 0, 'mfma_f16x2_v3'),
+    (66, 36, 1, 4099, 3, 0, 8, 'mfma_f16x2_v3'),           # NO_PRECONVERT
+    (66, 36, 1, 4099, 3, 0, 4, 'mfma_f16x2'),              # FORCE_V2
+    (10, 9, 1, 289, 3, 0, 0, 'mfma_f16x2'),                # even D outside 32 q + {0, 2}
+    (18, 9, 3, 1600, 3, 0, 0, 'mfma_f16x2'),
+    (66, 36, 1, 4099, 3, 0, 1, 'generic'),                 # FORCE_GENERIC
+    (515, 36, 1, 4099, 3, 0, 0, 'generic'),                # odd D
+    (1090, 36, 1, 4099, 3, 0, 0, 'generic'),               # wider than any tile kernel
+    (34, 144, 1, 6007, 2, 0, 0, 'mfma_f16x2_v3k'),         # 64 < K <= 256, narrow rows, >= 3 passes
+    (66, 256, 3, 6007, 3, 0, 0, 'mfma_f16x2_v3k'),
+    (64, 65, 1, 6007, 3, 0, 0, 'mfma_f16x2_v3k'),
+    (34, 144, 1, 6007, 1, 0, 0, 'mfma_f16x2_bigk'),        # ... a single iteration is not worth the conversion
+    (66, 144, 1, 6007, 3, 0, 8, 'mfma_f16x2_bigk'),        # ... nor is there a kernel without it
+    (66, 257, 3, 6007, 3, 0, 0, 'mfma_f16x2_bigk'),
+    (514, 1024, 1, 6000, 3, 0, 0, 'mfma_f16x2_bigk'),
+    (515, 96, 1, 1000, 3, 0, 0, 'mfma_f16x2_bigk'),
+    (258, 144, 1, 263169, 3, 0, 0, 'mfma_f16x2_v4k'),      # 64 < K <= 144 on wide rows
+    (130, 144, 2, 5000, 3, 0, 0, 'mfma_f16x2_v4k'),
+    (256, 80, 2, 4000, 2, 0, 0, 'mfma_f16x2_v4k'),
+    (258, 144, 1, 263169, 3, 0, 2048, 'mfma_f16x2_bigk'),  # NO_V4K
+    (258, 144, 1, 263169, 1, 0, 0, 'mfma_f16x2_bigk'),
+    (66, 36, 1, 4099, 1, 1, 0, 'mfma_f16x2_v3'),           # given centroids: converted tiles only on the caller's word
+    (66, 36, 1, 4099, 1, 1, 32, 'mfma_f16x2_v4p'),         # WS_PRECONVERTED
+    (66, 36, 1, 4099, 1, 1, 32 | 512, 'mfma_f16x2_v3p'),
+    (66, 64, 1, 4099, 1, 1, 32, 'mfma_f16x2_v3p'),
+    (66, 144, 1, 4099, 1, 1, 32, 'mfma_f16x2_v3k'),
+    (258, 144, 1, 4099, 1, 1, 32, 'mfma_f16x2_v4k'),
+    (258, 144, 1, 4099, 1, 1, 0, 'mfma_f16x2_bigk'),
+    (66, 36, 1, 4099, 1, 1, 1, 'generic'),
+]
+
+
+def test_kmeans_route_table(lib_path):
+  """The host side of a k-means call decides its route once (csrc/kmeans.hip: kmeans_route); spml_kmeans_path_name,
+  spml_kmeans_profile_layout and the run read the same record.  Every path name and every flag that changes one; the
+  layout of the profiled run (an iteration of "v4k" is two kernels; no tile kernels, no profile); and the workspace size
+  does not depend on the deterministic mode (a workspace sized before the mode was switched on stays valid)."""
+  import ctypes
+  from spml_amd import _ffi
+  lib = _ffi.lib()
+  assert {r[7] for r in KMEANS_ROUTES} == {'generic', 'mfma_f16x2', 'mfma_f16x2_v3', 'mfma_f16x2_v3p', 'mfma_f16x2_v4p',
+                                           'mfma_f16x2_v3k', 'mfma_f16x2_v4k', 'mfma_f16x2_bigk'}
+  for d, k, n_img, seg, it, given, flags, want in KMEANS_ROUTES:
+    case = (d, k, n_img, seg, it, given, flags)
+    p = n_img * seg
+    assert _ffi.kmeans_path_name(p, d, k, n_img, seg, it, given, flags) == want, case
+    before = _ffi.set_deterministic(False)
+    try:
+      plain = lib.spml_kmeans_workspace_bytes(p, d, k, n_img, seg)
+      _ffi.set_deterministic(True)
+      det = lib.spml_kmeans_workspace_bytes(p, d, k, n_img, seg)
+    finally:
+      _ffi.set_deterministic(before)
+    # (the int32 labels, the fp32 prototypes and sums, the fixed-point image of the sums)
+    assert plain == det >= p * 4 + n_img * k * d * 16, case
+    if given or flags:
+      continue
+    n_pass, wgs = ctypes.c_int(-1), ctypes.c_int(-1)
+    rc = lib.spml_kmeans_profile_layout(p, d, k, n_img, seg, it, ctypes.byref(n_pass), ctypes.byref(wgs))
+    if want in ('generic', 'mfma_f16x2_bigk'):
+      assert rc == -2, case                                   # SPML_ERR_UNSUPPORTED
+      continue
+    assert rc == 0, case
+    assert n_pass.value == (2 * it if want == 'mfma_f16x2_v4k' else it + 1), case
+    assert wgs.value % n_img == 0 and 1 <= wgs.value // n_img <= (seg + 31) // 32, case

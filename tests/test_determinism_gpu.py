@@ -123,6 +123,35 @@ def test_generic_kmeans_route_in_deterministic_mode(deterministic):
   assert (want != runs[0][0][:p1].cpu()).float().mean().item() < 0.02
 
 
+def test_kmeans_workspace_sized_before_the_mode_was_switched_on():
+  """A caller-held k-means workspace (_ffi.kmeans_workspace) sized with the mode off serves a generic-route call made
+  with the mode on: spml_kmeans_workspace_bytes reserves the fixed-point scratch of the M-step sums in either mode.
+  Same labels and sums, bit for bit, as with a workspace sized with the mode on."""
+  g = torch.Generator().manual_seed(9)
+  n_img, p1, d, k = 3, 529, 66, 9
+  x = torch.nn.functional.normalize(torch.randn(n_img * p1, d, generator=g), dim=1).to(DEV)
+  cent = torch.nn.functional.normalize(torch.randn(n_img, k, d, generator=g), dim=2).to(DEV)
+  off = (torch.arange(n_img + 1, device=DEV) * p1).to(torch.int64)
+  before = _ffi.set_deterministic(False)
+  try:
+    ws = _ffi.kmeans_workspace(x, off, p1, k)
+    _ffi.set_deterministic(True)
+    assert ws.numel() == _ffi.kmeans_workspace(x, off, p1, k).numel()
+    lab, sums = _ffi.kmeans_fused_pass(x, off, p1, cent, ws=ws, flags=1)
+    assert _ffi.kmeans_last_path() == 'generic'
+    lab2, sums2 = _ffi.kmeans_fused_pass(x, off, p1, cent, flags=1)
+  finally:
+    _ffi.set_deterministic(before)
+  assert torch.equal(lab, lab2) and torch.equal(sums, sums2)
+  for b in range(n_img):
+    xi, li = x[b * p1:(b + 1) * p1].cpu(), lab[b * p1:(b + 1) * p1].cpu()
+    sims = xi @ cent[b].cpu().t()
+    t2 = sims.topk(2, dim=1).values
+    safe = (t2[:, 0] - t2[:, 1]) > 1e-5
+    assert torch.equal(li[safe], sims.argmax(1)[safe])
+    torch.testing.assert_close(sums[b].cpu(), torch.zeros(k, d).index_add_(0, li, xi), rtol=0, atol=2e-5)
+
+
 def test_narrow_pyramid_forward_without_tap_groups(deterministic, monkeypatch):
   """The 36-tap forward on 64-column tiles splits its taps over workgroups that meet through fp32 atomics; in this mode
   it runs unsplit: bit-identical run to run, same values."""

@@ -212,6 +212,38 @@ def test_kmeans_preconverted_and_in_kernel_split_agree(d, k):
     o += n
 
 
+def _three_images(d, k, seed):
+  """lens [4099, 0, 2513]: an empty image, partial last tiles, unaligned image starts; unit rows, random labels"""
+  gen = torch.Generator().manual_seed(seed)
+  lens = [4099, 0, 2513]
+  xs = [torch.nn.functional.normalize(torch.randn(n, d, generator=gen), dim=1) for n in lens]
+  inits = [torch.randint(0, k, (n,), generator=gen) for n in lens]
+  return xs, inits, lens
+
+
+@pytest.mark.parametrize('d,k', [(66, 36), (34, 25)])
+def test_kmeans_force_v2_where_v3_applies(d, k):
+  """SPML_KMEANS_FORCE_V2 (flag 4) on shapes the 16x16x32-tile kernels cover: the call runs on kmeans_pass (32x32x16
+  tiles, fp32 rows split on the fly, no pre-conversion however many passes).  Every M- and E-step of 3 iterations
+  against the oracle."""
+  xs, inits, lens = _three_images(d, k, 11 * d + k)
+  assert ffi().kmeans_path_name(sum(lens), d, k, len(lens), max(lens), 3) == 'mfma_f16x2_v4p'
+  check_kmeans_stepwise(xs, inits, lens, k, 3, 'mfma_f16x2', flags=4)
+
+
+def test_kmeans_two_kernel_finalize_where_one_launch_is_the_default():
+  """SPML_KMEANS_TWO_KERNEL_FINALIZE (flag 1024) on a batch whose default is the one-launch kmeans_finalize (48 padded
+  clusters x 3 images >= 128 rows): kmeans_reduce_slabs + kmeans_normalize give the prototypes instead.  Every M- and
+  E-step of 3 iterations against the oracle; the flag does not change the path."""
+  d, k = 66, 36
+  xs, inits, lens = _three_images(d, k, 5)
+  check_kmeans_stepwise(xs, inits, lens, k, 3, None, flags=1024)
+  assert ffi().kmeans_last_path() == 'mfma_f16x2_v4p'
+  for it in (1, 2, 3):
+    assert (ffi().kmeans_path_name(sum(lens), d, k, len(lens), max(lens), it, flags=1024) ==
+            ffi().kmeans_path_name(sum(lens), d, k, len(lens), max(lens), it))
+
+
 @pytest.mark.parametrize('d,k', [(34, 144), (66, 144), (66, 256), (32, 100), (130, 128), (64, 65)])
 def test_kmeans_many_clusters_mfma_path(d, k):
   """64 < K <= 256 (12x12 grids of the DensePose recipe / full-resolution inference) runs
