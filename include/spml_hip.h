@@ -605,6 +605,21 @@ int spml_conv_hl8_stats_f32(const void* a, const float* a_bound, const void* b,
                             float* zero_me, int n_img, int H, int W, int K, int N,
                             int taps, int dilation, void* stream);
 
+/* The same convolution as the DATA GRADIENT in front of a training-mode batch norm + ReLU of the backward pass
+ * (the gradients of conv3 and conv2 of a Bottleneck are the dy of bn2 and bn1): the epilogue also reads the tile of
+ * that batch norm's saved input bn_x [R][N], its ReLU mask bytes [R][N/4] and bn_mean [N] and leaves, per row tile
+ * of the launch and per channel, sum dz, sum dz * (bn_x - mean) and max |dz| (dz = out where the mask bit is set,
+ * else 0) in chunk_stats [3][chunks][N] -- what spml_bn_bwd_hl8_chunks_f32 / spml_bn_act_bwd_reduce_ext_chunks_f32
+ * pool instead of a pass over `out` and bn_x -- and resets *zero_me (that call's dx_bound; may be NULL).  `out` is
+ * bit-identical to spml_conv_hl8_f32's.  The layout call follows spml_conv_hl8_stats_layout's rules. */
+int spml_conv_hl8_bwd_stats_layout(int n_img, int H, int W, int K, int N, int taps,
+                                   int* chunks, int* chunk_rows);
+int spml_conv_hl8_bwd_stats_f32(const void* a, const float* a_bound, const void* b,
+                                const float* b_bound, float* out, const float* bn_x,
+                                const unsigned char* relu_mask, const float* bn_mean,
+                                float* chunk_stats, float* zero_me, int n_img, int H, int W,
+                                int K, int N, int taps, int dilation, void* stream);
+
 /* Weight gradient of the same convolutions:
  *   dw[n][tap][k] = sum_r dy[r][n] * x[r + shift(tap)][k]      (dw fp32 [N][taps][K] = the
  * channels-last storage of the weight gradient).  dy: hl8 [R][N], x: hl8 [R][K] (the forward
@@ -721,6 +736,23 @@ int spml_bn_bwd_hl8_f32(const float* dy, const float* y, const unsigned char* re
                         const float* cmin, float* d_gamma, float* d_beta, float* dx,
                         void* dx_hl8, float* dx_bound, float* d_residual, void* ws,
                         size_t ws_bytes, void* stream);
+
+/* spml_bn_bwd_hl8_f32 from the chunk sums left by the producer of dy (spml_conv_hl8_bwd_stats_f32):
+ * chunk_stats [3][chunks][C] = sum dz, sum dz * (x - mean), max |dz| per chunk of chunk_rows rows (the last
+ * chunk shorter); *dx_bound must have been reset by the producer; max_dz [C] receives the channel maxima.
+ * Two launches, dy / x / relu_mask are read once.  Same results as spml_bn_bwd_hl8_f32 up to the fp32
+ * summation order of the two sums (fixed: deterministic). */
+int spml_bn_bwd_hl8_chunks_f32(const float* dy, const unsigned char* relu_mask, const float* x,
+                               const float* chunk_stats, int chunks, int chunk_rows, int64_t R,
+                               int C, const float* mean, const float* invstd, const float* gamma,
+                               const float* cmax, const float* cmin, float* d_gamma,
+                               float* d_beta, float* max_dz, float* dx, void* dx_hl8,
+                               float* dx_bound, float* d_residual, void* stream);
+
+/* spml_bn_act_bwd_reduce_ext_f32 from the same chunk sums (the local half of SyncBatchNorm's backward). */
+int spml_bn_act_bwd_reduce_ext_chunks_f32(const float* chunk_stats, int chunks, int chunk_rows,
+                                          int64_t R, int C, const float* invstd, float* sum_dz,
+                                          float* sum_dz_xhat, float* max_dz, void* stream);
 
 /* Sum of up to four 3x3 convolutions with different dilations over the same input in one launch
  * (the data gradient of the DeepLab-v2 ASPP head, spml/models/heads/spp.py:8-43: four dilated

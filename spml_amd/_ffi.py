@@ -86,6 +86,12 @@ _SIGNATURES = {
     'spml_conv_hl8_stats_f32': (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     'spml_bn_fwd_hl8_chunks_f32': (c_int, [_P, _P, c_int, c_int, _P, _P, c_int64, c_int, _P, _P, _P, _P, c_float, c_float,
                                            c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'spml_conv_hl8_bwd_stats_layout': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    'spml_conv_hl8_bwd_stats_f32': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
+                                            c_int, c_int, _P]),
+    'spml_bn_bwd_hl8_chunks_f32': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P,
+                                           _P, _P, _P, _P, _P]),
+    'spml_bn_act_bwd_reduce_ext_chunks_f32': (c_int, [_P, c_int, c_int, c_int64, c_int, _P, _P, _P, _P, _P]),
     'spml_conv_wgrad_hl8_supported': (c_int, [c_int, c_int, c_int]),
     'spml_conv_wgrad_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     'spml_conv_wgrad_hl8_f32': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P,
@@ -1095,6 +1101,31 @@ def conv_hl8_stats(a, b, n_img, h, w, taps, dilation=1):
   return out, ChunkStats(st, chunks.value, rows.value, bound)
 
 
+def conv_hl8_bwd_stats(a, b, n_img, h, w, taps, dilation, bn_x, relu_mask, bn_mean):
+  """conv_hl8 as the data gradient in front of a batch norm + ReLU (saved input bn_x, mask bytes, batch mean): the
+  epilogue also leaves that batch norm's backward chunk sums -> (out, ChunkStats [3, chunks, N]), or (out, None)
+  where the launch has no per-tile column owner (narrow outputs) or there is no mask.  SPML_CONV_BN_BWD_STATS=0:
+  never."""
+  import ctypes
+  k, n = a.channels, b.rows
+  chunks, rows = ctypes.c_int(0), ctypes.c_int(0)
+  if relu_mask is None or os.environ.get('SPML_CONV_BN_BWD_STATS') == '0' or lib().spml_conv_hl8_bwd_stats_layout(
+      n_img, h, w, k, n, taps, ctypes.byref(chunks), ctypes.byref(rows)) != 0:
+    return conv_hl8(a, b, n_img, h, w, taps, dilation), None
+  if a.rows != n_img * h * w or b.channels != taps * k or bn_x.numel() != a.rows * n or \
+      relu_mask.numel() != a.rows * (n // 4) or bn_mean.numel() != n:
+    raise SpmlHipError('conv_hl8_bwd_stats: operand shapes do not match')
+  dev = a.data.device
+  out = torch.empty((n_img, n, h, w), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+  st = torch.empty((3, chunks.value, n), dtype=torch.float32, device=dev)
+  bound = _f32(1, dev)
+  check(lib().spml_conv_hl8_bwd_stats_f32(ptr(a.data), c_void_p(a.bound.data_ptr()), ptr(b.data),
+                                          c_void_p(b.bound.data_ptr()), _ptr_any(out), _ptr_any(bn_x), _dp(relu_mask),
+                                          _dp(bn_mean), _dp(st), _dp(bound), n_img, h, w, k, n, taps, dilation,
+                                          stream_ptr()), 'spml_conv_hl8_bwd_stats_f32')
+  return out, ChunkStats(st, chunks.value, rows.value, bound)
+
+
 def conv_wgrad_hl8_supported(k, n, taps):
   return bool(lib().spml_conv_wgrad_hl8_supported(int(k), int(n), int(taps)))
 
@@ -1217,9 +1248,16 @@ def bn_act_apply_hl8(x, rows, channels, residual, residual_bound, mean, invstd, 
   return y, (Hl8(yh, bound, rows, channels) if want_hl8 else None), bound, mask
 
 
-def bn_act_bwd_reduce_ext(dy, y, relu_mask, x, rows, channels, mean, invstd):
-  """-> (sum dz, sum dz*xhat, max|dz| per channel); ReLU mask from y (fp32), the mask bytes or none."""
+def bn_act_bwd_reduce_ext(dy, y, relu_mask, x, rows, channels, mean, invstd, chunk_stats=None):
+  """-> (sum dz, sum dz*xhat, max|dz| per channel); ReLU mask from y (fp32), the mask bytes or none.
+  chunk_stats: pooled from the chunk sums the producing data gradient's epilogue left (`conv_hl8_bwd_stats`)
+  instead of reading dy and x."""
   st = torch.empty((3, channels), dtype=torch.float32, device=dy.device)     # rows 0, 1 are all-reduced together
+  if chunk_stats is not None:
+    check(lib().spml_bn_act_bwd_reduce_ext_chunks_f32(
+        _dp(chunk_stats.data), chunk_stats.chunks, chunk_stats.chunk_rows, rows, channels, _dp(invstd), _dp(st[0]),
+        _dp(st[1]), _dp(st[2]), stream_ptr()), 'spml_bn_act_bwd_reduce_ext_chunks_f32')
+    return st
   ws = _bn_workspace(rows, channels, dy.device)
   check(lib().spml_bn_act_bwd_reduce_ext_f32(
       _ptr_any(dy), _ptr_any(y, True), _dp(relu_mask), _ptr_any(x), rows, channels,
@@ -1268,12 +1306,22 @@ def bn_fwd_hl8(x, rows, channels, residual, residual_bound, gamma, beta, running
   return y, (Hl8(yh, bound, rows, channels) if want_hl8 else None), bound, mask, (st[0], st[1], st[2], st[3])
 
 
-def bn_bwd_hl8(dy, relu_mask, x, rows, channels, saved, gamma, want_dres=False):
-  """Single-rank batch norm backward -> (dx Hl8, d_residual|None, d_gamma, d_beta)."""
+def bn_bwd_hl8(dy, relu_mask, x, rows, channels, saved, gamma, want_dres=False, chunk_stats=None):
+  """Single-rank batch norm backward -> (dx Hl8, d_residual|None, d_gamma, d_beta).  chunk_stats: the chunk sums the
+  producer of dy left (`conv_hl8_bwd_stats`, which also reset their bound slot): dy and x are read once."""
   mean, invstd, cmax, cmin = saved
   dxh = torch.empty((rows * channels * 4,), dtype=torch.uint8, device=dy.device)
-  bound = _f32(1, dy.device)
   dres = torch.empty_like(dy) if want_dres else None
+  if chunk_stats is not None:
+    bound = chunk_stats.bound
+    dgb = torch.empty((3, channels), dtype=torch.float32, device=dy.device)      # d_gamma, d_beta, max |dz|
+    check(lib().spml_bn_bwd_hl8_chunks_f32(
+        _ptr_any(dy), _dp(relu_mask), _ptr_any(x), _dp(chunk_stats.data), chunk_stats.chunks, chunk_stats.chunk_rows,
+        rows, channels, _dp(mean), _dp(invstd), ptr(gamma, torch.float32), _dp(cmax), _dp(cmin), _dp(dgb[0]),
+        _dp(dgb[1]), _dp(dgb[2]), c_void_p(0), _dp(dxh), _dp(bound), _ptr_any(dres, True), stream_ptr()),
+          'spml_bn_bwd_hl8_chunks_f32')
+    return Hl8(dxh, bound, rows, channels), dres, dgb[0], dgb[1]
+  bound = _f32(1, dy.device)
   dgb = torch.empty((2, channels), dtype=torch.float32, device=dy.device)
   ws = _bn_workspace(rows, channels, dy.device)
   check(lib().spml_bn_bwd_hl8_f32(

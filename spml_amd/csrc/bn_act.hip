@@ -910,6 +910,58 @@ extern "C" int spml_bn_bwd_hl8_f32(const float* dy, const float* y, const unsign
   return launch_status();
 }
 
+// The same backward when the producer of dy (a data-gradient convolution, spml_conv_hl8_bwd_stats_f32) has already
+// left the chunk sums [3][chunks][C] (sum dz, sum dz * (x - mean), max |dz| per chunk of chunk_rows rows) and reset
+// *dx_bound: two launches, dy / x / the mask are read once.  max_dz [C] is scratch + output.
+extern "C" int spml_bn_bwd_hl8_chunks_f32(const float* dy, const unsigned char* relu_mask, const float* x,
+                                          const float* chunk_stats, int chunks, int chunk_rows, int64_t R, int C,
+                                          const float* mean, const float* invstd, const float* gamma,
+                                          const float* cmax, const float* cmin, float* d_gamma, float* d_beta,
+                                          float* max_dz, float* dx, void* dx_hl8, float* dx_bound, float* d_residual,
+                                          void* stream) {
+  if (!dy || !x || !chunk_stats || !mean || !invstd || !gamma || !cmax || !cmin || !d_gamma || !d_beta || !max_dz ||
+      R <= 0 || C <= 0 || chunks <= 0 || chunk_rows <= 0 || (int64_t)chunks * chunk_rows < R ||
+      (int64_t)(chunks - 1) * chunk_rows >= R || (dx_hl8 && !dx_bound))
+    return SPML_ERR_INVALID_ARG;
+  if ((C & 7) || !bn_ok(dy) || !bn_ok(x) || (dx && !bn_ok(dx)) || (dx_hl8 && !bn_ok(dx_hl8)) ||
+      (d_residual && !bn_ok(d_residual)) || !bn_ok(mean))
+    return SPML_ERR_UNSUPPORTED;
+  const int cq = bn_cq(C), arows = bn_apply_rows(R, C);
+  const float* pa = chunk_stats;
+  const float* pb = pa + (size_t)chunks * C;
+  const float* pc = pb + (size_t)chunks * C;
+  hipStream_t s = (hipStream_t)stream;
+  const int mask = relu_mask ? 2 : 0;
+  hipLaunchKernelGGL(bn_merge<1>, dim3((C + kMergeCh - 1) / kMergeCh), dim3(kMergeCh * kMergeLanes), 0, s, pa, pb, R,
+                     C, chunks, chunk_rows, invstd, d_beta, d_gamma, BnFinal{0, 0.f, 0.f, nullptr, nullptr}, pc,
+                     (const float*)nullptr, max_dz, (float*)nullptr,
+                     BnBound{dx_hl8 ? dx_bound : nullptr, nullptr, gamma, nullptr, mean, cmax, cmin, (float)(1.0 / (double)R)});
+  if (!dx && !dx_hl8 && !d_residual) return launch_status();
+  const dim3 grid(((C >> 2) + cq - 1) / cq, (unsigned)((R + arows - 1) / arows));
+  SPML_BN_BY_MASK(bn_bwd_apply, mask, grid, dim3(256), 0, s, dy, (const float*)nullptr, x, R, C, cq, arows, mean, invstd,
+                  gamma, (const float*)d_beta, (const float*)d_gamma, (float)(1.0 / (double)R), (const float*)nullptr, dx,
+                  d_residual, relu_mask, static_cast<uint2*>(dx_hl8), (const float*)dx_bound);
+  return launch_status();
+}
+
+// spml_bn_act_bwd_reduce_ext_f32 pooled from the same chunk sums instead of a pass over dy and x -- the local half
+// of SyncBatchNorm's backward for the matrix-core units (the caller all-reduces the sums before the apply pass).
+extern "C" int spml_bn_act_bwd_reduce_ext_chunks_f32(const float* chunk_stats, int chunks, int chunk_rows, int64_t R,
+                                                     int C, const float* invstd, float* sum_dz, float* sum_dz_xhat,
+                                                     float* max_dz, void* stream) {
+  if (!chunk_stats || !invstd || !sum_dz || !sum_dz_xhat || !max_dz || R <= 0 || C <= 0 || chunks <= 0 ||
+      chunk_rows <= 0 || (int64_t)chunks * chunk_rows < R || (int64_t)(chunks - 1) * chunk_rows >= R)
+    return SPML_ERR_INVALID_ARG;
+  const float* pa = chunk_stats;
+  const float* pb = pa + (size_t)chunks * C;
+  const float* pc = pb + (size_t)chunks * C;
+  hipLaunchKernelGGL(bn_merge<1>, dim3((C + kMergeCh - 1) / kMergeCh), dim3(kMergeCh * kMergeLanes), 0,
+                     (hipStream_t)stream, pa, pb, R, C, chunks, chunk_rows, invstd, sum_dz, sum_dz_xhat,
+                     BnFinal{0, 0.f, 0.f, nullptr, nullptr}, pc, (const float*)nullptr, max_dz, (float*)nullptr,
+                     BnBound{});
+  return launch_status();
+}
+
 extern "C" int spml_bn_finalize_ranks_f32(const float* stats, int world, int C, float eps, float momentum,
                                           float* running_mean, float* running_var, float* mean, float* invstd,
                                           float* total_count, void* stream) {

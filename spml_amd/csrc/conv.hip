@@ -37,6 +37,8 @@
 namespace spml {
 namespace {
 
+constexpr int BSTAT_BATCH = 8;          // accumulator rows per batch of the backward-statistics epilogue of conv_gemm
+
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -210,6 +212,13 @@ struct ConvArgs {
                              // sum of squared deviations, the max and the min of `out` -- the chunk statistics the
                              // batch norm that follows would otherwise take from a pass of its own (bn_partial)
   float* stats_zero;         // optional: a float this launch resets to 0 (the bound slot bn_merge max-reduces into)
+  // BSTAT launches (data gradients whose output is the dy of a batch norm + ReLU): the backward statistics of that
+  // batch norm, taken from the tile in registers instead of a pass over `out` (bn_partial<1, 2>)
+  const float* bstat_x;      // [R][N] fp32: the batch norm's saved input a
+  const unsigned char* bstat_mask;   // [R][N/4] ReLU mask bytes (same addressing as addend_mask)
+  const float* bstat_mean;   // [N]
+  float* bstats;             // [3][row tiles][N] = per row tile and column sum dz, sum dz * (a - mean), max |dz|,
+                             // dz = out where the mask bit is set, else 0 -- what bn_merge<1> pools
 };
 
 // Workgroup = 4 waves side by side along N: wave w owns output columns [64w, 64w+64) of the
@@ -224,8 +233,12 @@ struct ConvArgs {
 // block ahead of the MFMAs that consume them (counted lgkmcnt waits).
 // NC < 4 (narrow outputs: N a multiple of 128 / 64 only): NC waves side by side along N, the tile is
 // 64 * NC columns wide and RG row groups tall -- (NC, RG) = (2, 2) or (1, 4) keep four waves per workgroup.
-template <int RB, int kStages, int WGS, int RG, bool CHUNK = false, int NC = 4>
+// BSTAT (RG == 1, NC == 4, gridDim.y == 1, no addend / bias / ReLU: the data gradients in front of bn2 and bn1 of a
+// bottleneck unit): the epilogue also reads the tile of the batch norm's saved input and ReLU mask and leaves the three
+// backward partial statistics per column (ConvArgs::bstats).
+template <int RB, int kStages, int WGS, int RG, bool CHUNK = false, int NC = 4, bool BSTAT = false>
 __global__ __launch_bounds__(64 * NC * RG, WGS) void conv_gemm(const ConvArgs a) {
+  static_assert(!BSTAT || (RG == 1 && NC == 4), "backward statistics: a wave owns its 64 columns over the whole tile");
   // CHUNK (very long reductions, e.g. the 36-tap forward of a wide ASPP head, K = 73 728): the MFMA chain
   // is cut every 1024 k -- the running accumulator is added to a second register set and restarted -- so
   // that the fp32 accumulation error stays at the level of a K = 1024 convolution
@@ -426,6 +439,93 @@ __global__ __launch_bounds__(64 * NC * RG, WGS) void conv_gemm(const ConvArgs a)
         for (int r = 0; r < 16; ++r) acc[i][j][r] += tot[i][j][r];
   }
 
+  if constexpr (BSTAT) {
+    // The tile is walked in batches of kB accumulator rows (x 2 column halves).  The saved input and the mask bytes of
+    // batch b + 1 are requested before batch b is stored and folded, the first batch before the scales are read: the
+    // operand registers of the main loop are free here, the accumulators are not, so two batches are what can be in
+    // flight.  All three tensors are addressed through buffer descriptors of the tile's valid rows: the range check
+    // drops the stores and zeroes the loads of rows past R (whose accumulators are zero anyway: their A rows came from
+    // the zero page), so the epilogue is one basic block -- with a branch per row the compiler sinks every sum to the
+    // end of the kernel and spills the values it keeps for them.
+    constexpr int kB = BSTAT_BATCH, kBatches = RB * 16 / kB;
+    const unsigned N = (unsigned)a.N;
+    const unsigned rows_here = (unsigned)(m0 + RB * 32 < a.R ? (int64_t)RB * 32 : a.R - m0);
+    const unsigned tile_bytes = rows_here * N * 4u;
+    const size_t t0e = (size_t)m0 * N;                                     // first element of the tile's rows (uniform)
+    const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.bstat_x + t0e), 0, (int)tile_bytes, 0x00020000);
+    const auto rm = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.bstat_mask + (t0e >> 2)), 0,
+                                                      (int)(tile_bytes >> 4), 0x00020000);
+    const auto ro = __builtin_amdgcn_make_buffer_rsrc(a.out + t0e, 0, (int)tile_bytes, 0x00020000);
+    // (lane constants from an opaque copy of the thread index: derived from `lane` they are computed before the main
+    // loop and spilled across it)
+    unsigned tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const unsigned up = (tid >> 5) & 1u;                                  // this lane's rows are (row + 4 * up)
+    const unsigned col = (unsigned)(col_tile * (64 * NC)) + ((tid >> 6) * 64u + (tid & 31u));      // = n0 + lr
+    const unsigned lo = (up * 4u * N + col) * 4u;                         // byte offset of the lane in the fp32 tile
+    const unsigned lm = up * N + (col >> 2);                              // ... in the mask tile
+    const unsigned bit = 1u << (tid & 3u);
+    float xv[2][kB][2];
+    unsigned mv[2][kB][2];
+    auto fetch = [&](int b, float (&x)[kB][2], unsigned (&m)[kB][2]) {
+#pragma unroll
+      for (int e = 0; e < kB; ++e) {
+        const int idx = b * kB + e;
+        const unsigned ro_e = (unsigned)((idx >> 4) * 32 + acc_row(idx & 15, 0)) * N;      // uniform
+        const unsigned vo = lo + ro_e * 4u, vm = lm + (ro_e >> 2);
+        x[e][0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, vo, 0, 0));
+        x[e][1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, vo + 128u, 0, 0));
+        m[e][0] = __builtin_amdgcn_raw_buffer_load_b8(rm, vm, 0, 0);
+        m[e][1] = __builtin_amdgcn_raw_buffer_load_b8(rm, vm + 8u, 0, 0);
+      }
+    };
+    fetch(0, xv[0], mv[0]);
+    __builtin_amdgcn_sched_barrier(0);
+    if (a.stats_zero && blockIdx.x == 0 && threadIdx.x == 0) *a.stats_zero = 0.f;
+    const float mu[2] = {a.bstat_mean[col], a.bstat_mean[col + 32]};
+    const float mult = 1.0f / ((a.a_bound ? pow2_scale(*a.a_bound) : 1.f) * (a.b_bound ? pow2_scale(*a.b_bound) : 1.f));
+    float s0[2] = {0.f, 0.f}, s1[2] = {0.f, 0.f}, mx[2] = {0.f, 0.f};
+#pragma unroll
+    for (int b = 0; b < kBatches; ++b) {
+      if (b + 1 < kBatches) fetch(b + 1, xv[(b + 1) & 1], mv[(b + 1) & 1]);
+      __builtin_amdgcn_sched_barrier(0);                  // (the scheduler would hoist every batch's loads and spill)
+      float t0[2] = {0.f, 0.f}, t1[2] = {0.f, 0.f};      // the batch's own sums: a fixed, shallower summation tree
+#pragma unroll
+      for (int e = 0; e < kB; ++e) {
+        const int idx = b * kB + e, i = idx >> 4, r = idx & 15;
+        const unsigned vo = lo + (unsigned)(i * 32 + acc_row(r, 0)) * N * 4u;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const float v = acc[i][j][r] * mult;
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ro, vo + 128u * j, 0, 0);
+          const float dz = (mv[b & 1][e][j] & bit) ? v : 0.f;
+          t0[j] += dz;
+          t1[j] += dz * (xv[b & 1][e][j] - mu[j]);
+          mx[j] = fmaxf(mx[j], fabsf(dz));
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 2; ++j) { s0[j] += t0[j]; s1[j] += t1[j]; }
+      // (pins the sums here: left alone they are emitted after the last batch, with every dz and x kept until then)
+      asm volatile("" : "+v"(s0[0]), "+v"(s0[1]), "+v"(s1[0]), "+v"(s1[1]), "+v"(mx[0]), "+v"(mx[1]));
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    const size_t plane = (size_t)gridDim.x / a.n_col_tiles * a.N;         // row tiles x N
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const float p0 = s0[j] + __shfl_xor(s0[j], 32, kWave);              // lane and lane ^ 32: the two halves of a column
+      const float p1 = s1[j] + __shfl_xor(s1[j], 32, kWave);
+      const float pm = fmaxf(mx[j], __shfl_xor(mx[j], 32, kWave));
+      if (!up) {
+        float* dst = a.bstats + (size_t)row_tile * a.N + col + j * 32;
+        dst[0] = p0;
+        dst[plane] = p1;
+        dst[2 * plane] = pm;
+      }
+    }
+    return;
+  }
+
   const float mult = 1.0f / ((a.a_bound ? pow2_scale(*a.a_bound) : 1.f) * (a.b_bound ? pow2_scale(*a.b_bound) : 1.f));
   float vmax = 0.f;
 #pragma unroll
@@ -516,13 +616,13 @@ __global__ __launch_bounds__(64 * NC * RG, WGS) void conv_gemm(const ConvArgs a)
   }
 }
 
-template <int RB, int kStages, int WGS, int RG = 1, bool CHUNK = false, int NC = 4>
+template <int RB, int kStages, int WGS, int RG = 1, bool CHUNK = false, int NC = 4, bool BSTAT = false>
 int launch_conv(const ConvArgs& a0, hipStream_t s) {
   ConvArgs a = a0;
   a.n_col_tiles = a.N / (64 * NC);
   const int64_t row_tiles = (a.R + RG * RB * 32 - 1) / (RG * RB * 32);
   a.n_tiles = (int)(row_tiles * a.n_col_tiles);
-  auto kern = conv_gemm<RB, kStages, WGS, RG, CHUNK, NC>;
+  auto kern = conv_gemm<RB, kStages, WGS, RG, CHUNK, NC, BSTAT>;
   const int lds = kStages * (2 * RB * RG + 4 * NC) * 1024;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   const int groups = a.tap_groups > 1 ? a.tap_groups : 1;
@@ -1028,6 +1128,46 @@ extern "C" int spml_conv_hl8_stats_f32(const void* a, const float* a_bound, cons
     case 3: return launch_conv<3, 3, 2>(c, s);
     case 5: return launch_conv<5, 3, 2>(c, s);
     default: return launch_conv<4, 3, 2>(c, s);
+  }
+}
+
+// The data gradient in front of a batch norm + ReLU of the backward pass: the same launch spml_conv_hl8_f32 picks for
+// the shape (no addend), whose epilogue also leaves that batch norm's backward chunk sums (BSTAT).
+extern "C" int spml_conv_hl8_bwd_stats_layout(int n_img, int H, int W, int K, int N, int taps, int* chunks,
+                                              int* chunk_rows) {
+  return spml_conv_hl8_stats_layout(n_img, H, W, K, N, taps, chunks, chunk_rows);
+}
+
+extern "C" int spml_conv_hl8_bwd_stats_f32(const void* a, const float* a_bound, const void* b, const float* b_bound,
+                                           float* out, const float* bn_x, const unsigned char* relu_mask,
+                                           const float* bn_mean, float* chunk_stats, float* zero_me, int n_img, int H,
+                                           int W, int K, int N, int taps, int dilation, void* stream) {
+  if (!a || !b || !out || !bn_x || !relu_mask || !bn_mean || !chunk_stats || n_img <= 0 || H <= 0 || W <= 0 ||
+      dilation < 1)
+    return SPML_ERR_INVALID_ARG;
+  int chunks = 0, rows = 0;
+  if (spml_conv_hl8_bwd_stats_layout(n_img, H, W, K, N, taps, &chunks, &rows) != SPML_OK || !al16(a) || !al16(b) ||
+      !al16(out) || !al16(bn_x))
+    return SPML_ERR_UNSUPPORTED;
+  ConvArgs c{};
+  c.a = static_cast<const uint4*>(a);
+  c.b = static_cast<const uint4*>(b);
+  c.a_bound = a_bound;
+  c.b_bound = b_bound;
+  c.out = out;
+  c.bstat_x = bn_x;
+  c.bstat_mask = relu_mask;
+  c.bstat_mean = bn_mean;
+  c.bstats = chunk_stats;
+  c.stats_zero = zero_me;
+  c.R = (int64_t)n_img * H * W;
+  c.H = H; c.W = W; c.K = K; c.N = N; c.taps = taps; c.dil = dilation;
+  hipStream_t s = (hipStream_t)stream;
+  if (chunk_long_reduction((int64_t)c.K * c.taps)) return launch_conv<3, 3, 2, 1, true, 4, true>(c, s);
+  switch (rows / 32) {
+    case 3: return launch_conv<3, 3, 2, 1, false, 4, true>(c, s);
+    case 5: return launch_conv<5, 3, 2, 1, false, 4, true>(c, s);
+    default: return launch_conv<4, 3, 2, 1, false, 4, true>(c, s);
   }
 }
 

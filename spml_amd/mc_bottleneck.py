@@ -181,13 +181,17 @@ class _Bn(object):
 
 
 def _bn_backward(dy, a, rows, channels, gamma, saved, count, group, world, mask, want_dres=False,
-                 want_dx_f32=False):
-  """-> (dx fp32 | None, dx hl8, d_residual | None, d_gamma, d_beta)"""
+                 want_dx_f32=False, chunk_stats=None):
+  """-> (dx fp32 | None, dx hl8, d_residual | None, d_gamma, d_beta)
+  chunk_stats: the chunk sums the data gradient that produced dy left (`_ffi.conv_hl8_bwd_stats`): the reduction
+  pass over dy and a is replaced by their merge."""
   if world == 1:
-    dxh, dres, d_gamma, d_beta = _ffi.bn_bwd_hl8(dy, mask, a, rows, channels, saved, gamma, want_dres=want_dres)
+    dxh, dres, d_gamma, d_beta = _ffi.bn_bwd_hl8(dy, mask, a, rows, channels, saved, gamma, want_dres=want_dres,
+                                                 chunk_stats=chunk_stats)
     return None, dxh, dres, d_gamma, d_beta
   mean, invstd, cmax, cmin = saved
-  st = _ffi.bn_act_bwd_reduce_ext(dy, None, mask, a, rows, channels, mean, invstd)   # (sum dz, sum dz*xhat, max|dz|)
+  st = _ffi.bn_act_bwd_reduce_ext(dy, None, mask, a, rows, channels, mean, invstd,
+                                  chunk_stats=chunk_stats)                           # (sum dz, sum dz*xhat, max|dz|)
   local = st[:2].clone()                           # local sums: DDP averages parameter gradients
   d_beta, d_gamma = local[0], local[1]
   dist.all_reduce(st[:2], group=group)
@@ -343,13 +347,15 @@ class _Unit(torch.autograd.Function):
                                             want_dres=has_ds)
     side = _side_stream(d_out.device)
     dw3 = _wgrad(side, da3, y2h, n, h, w, 1)
-    dy2 = _ffi.conv_hl8(da3, w3t, n, h, w, 1)
+    # dy2 / dy1 are the dy of bn2 / bn1: where the tiling allows it (256-column tiles) the data gradient's epilogue
+    # leaves the chunk sums of that batch norm's backward and the reduction pass over (dy, a, mask) is not run
+    dy2, c2 = _ffi.conv_hl8_bwd_stats(da3, w3t, n, h, w, 1, 1, a2, m2, s2[0])
     del da3
-    _, da2, _, dg2, db2 = _bn_backward(dy2, a2, rows, width, g2, s2, m[1][0], m[1][1], m[1][2], m2)
+    _, da2, _, dg2, db2 = _bn_backward(dy2, a2, rows, width, g2, s2, m[1][0], m[1][1], m[1][2], m2, chunk_stats=c2)
     dw2 = _wgrad(side, da2, y1h, n, h, w, 9, dil)
-    dy1 = _ffi.conv_hl8(da2, w2t, n, h, w, 9, dil)
+    dy1, c1 = _ffi.conv_hl8_bwd_stats(da2, w2t, n, h, w, 9, dil, a1, m1, s1[0])
     del da2, dy2
-    _, da1, _, dg1, db1 = _bn_backward(dy1, a1, rows, width, g1, s1, m[0][0], m[0][1], m[0][2], m1)
+    _, da1, _, dg1, db1 = _bn_backward(dy1, a1, rows, width, g1, s1, m[0][0], m[0][1], m[0][2], m1, chunk_stats=c1)
     dw1 = _wgrad(side, da1, xh, n, h, w, 1)
     dx = None
     if has_ds:
