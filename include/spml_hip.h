@@ -1041,6 +1041,15 @@ int spml_tag_normalize_argmax_f32(const float* acc, int ncls, int64_t n, int num
  *   necessarily normalised, zeros allowed; iter_max >= 0; q fp32 [ncls][h][w] (the result); labels int64 [h][w] or NULL:
  *   the lowest class that attains the maximum of q at a pixel, from the epilogue that writes q.  ws as prepare left it,
  *   for the same h and w.
+ * spml_dense_crf_infer_upsampled_f32 (pyscripts/inference/pseudo_softmaxrw_crf.py:172-185 = pseudo_camrw_crf.py:166-179,
+ *   and spml/models/crf.py:23-41): the same inference on probmap = the bilinear up-sampling of lowres fp32
+ *   [ncls][oh][ow] to h x w (F.interpolate, align_corners = False: the taps and the scale expressions of
+ *   spml_upsample_argmax_i64), formed inside the first launch and not stored.  oh, ow >= 1 (else
+ *   SPML_ERR_INVALID_ARG), of any size relative to h x w (the programs pass h/8 x w/8; with oh = h, ow = w the up-sampled
+ *   map is lowres itself); oh * ow <= 2^24, else SPML_ERR_UNSUPPORTED.  q, labels, ws and every other check as
+ *   spml_dense_crf_infer_f32, whose result on the up-sampled map it equals bit for bit.  labels_before int64 [h][w] or
+ *   NULL: the arg-max of the up-sampled values before the clip, equal to spml_upsample_argmax_i64(lowres) on every pixel
+ *   (lowest class on ties, the first NaN wins).  prob_up fp32 [ncls][h][w] or NULL: the up-sampled values themselves.
  * spml_dense_crf_path_name (spml/models/crf.py:23-41; host only): "pairs_mfma_f16x2_c<32|64>+separable_r<R>" -- the
  *   class columns of the pair kernel and the taps R = ceil(6 pos_xy_std) kept on either side by the separable spatial
  *   filter (the tail it drops is below 4e-9 of the kernel's mass).
@@ -1053,6 +1062,9 @@ int spml_dense_crf_prepare_u8(const unsigned char* image, int h, int w, float po
                               float bi_rgb_std, void* ws, size_t ws_bytes, void* stream);
 int spml_dense_crf_infer_f32(const float* probmap, int ncls, int h, int w, int iter_max, float pos_w, float bi_w,
                              float* q, int64_t* labels, void* ws, size_t ws_bytes, void* stream);
+int spml_dense_crf_infer_upsampled_f32(const float* lowres, int ncls, int oh, int ow, int h, int w, int iter_max,
+                                       float pos_w, float bi_w, float* q, int64_t* labels, int64_t* labels_before,
+                                       float* prob_up, void* ws, size_t ws_bytes, void* stream);
 const char* spml_dense_crf_path_name(int h, int w, int ncls, float pos_xy_std);
 
 #ifdef __cplusplus

@@ -1,0 +1,61 @@
+#!/usr/bin/env python3
+"""Generate pseudo labels by the softmax classifier, a random walk over the pixel affinity and denseCRF refinement, with
+the reference's command line and config surface (`pyscripts/inference/pseudo_softmaxrw_crf.py:33-204` of twke18/SPML; the
+scribble / point / box recipes run it between stage 1 and stage 2):
+
+  python3 pyscripts/inference/pseudo_softmaxrw_crf.py --snapshot_dir S --cfg_path C.yaml --save_dir OUT --data_list L \\
+      --crf_iter_max 10 --crf_pos_xy_std 1 --crf_pos_w 3 --crf_bi_xy_std 67 --crf_bi_rgb_std 3 --crf_bi_w 4
+
+Everything up to the walked maps is `pseudo_softmaxrw.py` (flip pair at scale 1, softmax per view and mean of the
+probabilities, WALK_STEPS = 6 squarings of the transition matrix: :29, :109-112, :143-147, :165-170).  The walked maps at
+1/8 of the image then go with the uint8 image rebuilt from the network's input (:179-184, `denormalized_uint8`) through
+one fused call (`spml_amd.inference.pseudo_labels_softmax_crf`): the CRF's first kernel up-samples them
+(:173-175), writes the label before the CRF (:176) and starts the exact mean-field filter (`spml_amd.models.crf.DenseCRF`,
+DESIGN 8j).  Label maps are the arg-max of the refined marginals (:187), written as `semantic_gray/<name>.npy`; the JSON
+line carries what `pseudo_softmaxrw.py` reports, scored on the refined labels, plus `mIoU_before_crf`, `changed_by_crf`
+(the share of pixels whose label the CRF changed), `crf_path` and `crf_share`, the CRF's share of the image time."""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+
+SCALES, COMBINE, WALK_STEPS = (1,), 'prob_mean', 6                                            # :109-112, :143-147, :29
+
+
+def main(argv=None):
+  import torch
+  from spml_amd import inference, inference_cli as cli
+  from spml_amd.utils.general import metrics
+  config, args, device = cli.parse('Generate pseudo labels by softmax classifier, random walk and CRF.', argv,
+                                   'pseudo_labels_softmax_crf')
+  semantic_dir = cli.output_dir(args, 'semantic_gray')
+  embedding_model, prediction_model, path = cli.load_models(config, args, device, 'softmax_classifier')
+  num_classes, crop_size, _, size = cli.geometry(config)
+  crf = cli.CrfStage(config, args)                                                            # :66-73
+  counts, counts_before, out = None, None, None
+  changed = torch.zeros((), dtype=torch.int64, device=device)
+
+  def one(index):
+    nonlocal counts, counts_before, out
+    image, label, _ = cli.synthetic_image(index, size, num_classes, device)
+    views = inference.flip_scale_views(image, SCALES, True, crop_size)                        # :109-125
+    out = inference.pseudo_labels_softmax_crf(embedding_model, prediction_model, views, (size, size),
+                                              inference.label_tags_from_map(label, num_classes),
+                                              crf.image_u8(image, (size, size)), crf, combine=COMBINE,
+                                              walk_steps=WALK_STEPS)                          # :126-187
+    refined, before = out['semantic_prediction'], out['semantic_prediction_before_crf']
+    counts = metrics.iou_stats(refined, label, num_classes, counts)
+    counts_before = metrics.iou_stats(before, label, num_classes, counts_before)
+    changed.add_((refined != before).sum())
+    cli.save_label_map(semantic_dir, index, refined)
+
+  done, seconds = cli.timed_images(one)
+  cli.report(done, seconds, **cli.scores(counts), mIoU_before_crf=cli.scores(counts_before)['mIoU'],
+             changed_by_crf=round(int(changed) / float(max(done, 1) * size * size), 4), scales=list(SCALES),
+             is_flip=True, combine=COMBINE, walk_steps=WALK_STEPS, head_path=out['head_path'], **crf.fields(seconds),
+             snapshot=path, save_dir=semantic_dir)
+
+
+if __name__ == '__main__':
+  main()

@@ -161,6 +161,8 @@ _SIGNATURES = {
     'spml_dense_crf_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'spml_dense_crf_prepare_u8': (c_int, [_P, c_int, c_int, c_float, c_float, c_float, _P, c_size_t, _P]),
     'spml_dense_crf_infer_f32': (c_int, [_P, c_int, c_int, c_int, c_int, c_float, c_float, _P, _P, _P, c_size_t, _P]),
+    'spml_dense_crf_infer_upsampled_f32': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, _P, _P,
+                                                   _P, _P, _P, c_size_t, _P]),
     'spml_dense_crf_path_name': (c_char_p, [c_int, c_int, c_int, c_float]),
 }
 
@@ -1536,3 +1538,25 @@ def dense_crf_infer(probmap, iter_max, pos_w, bi_w, ws, want_labels=True):
                                        ptr(q), ptr(labels, torch.int64, True), ptr(ws), ws.numel(), stream_ptr()),
         'spml_dense_crf_infer_f32')
   return q, labels
+
+
+def dense_crf_infer_upsampled(lowres, image_hw, iter_max, pos_w, bi_w, ws, want_labels=True, want_labels_before=True,
+                              want_prob_up=False):
+  """lowres fp32 [ncls, oh, ow], the image size (h, w) and a prepared `ws` -> (Q fp32 [ncls, h, w], arg-max int64 [h, w]
+  or None, the arg-max of the up-sampled map before the CRF int64 [h, w] or None, the up-sampled map fp32 [ncls, h, w] or
+  None): `dense_crf_infer` on the bilinear up-sampling of `lowres`, which the first launch forms in registers."""
+  if lowres.dim() != 3:
+    raise SpmlHipError('dense_crf_infer_upsampled: expected a [ncls, oh, ow] map')
+  ncls, oh, ow = (int(v) for v in lowres.shape)
+  h, w = (int(v) for v in image_hw)
+  dev = lowres.device
+  q = torch.empty((ncls, h, w), dtype=torch.float32, device=dev)
+  labels = torch.empty((h, w), dtype=torch.int64, device=dev) if want_labels else None
+  before = torch.empty((h, w), dtype=torch.int64, device=dev) if want_labels_before else None
+  prob_up = torch.empty((ncls, h, w), dtype=torch.float32, device=dev) if want_prob_up else None
+  check(lib().spml_dense_crf_infer_upsampled_f32(ptr(lowres, torch.float32), ncls, oh, ow, h, w, int(iter_max),
+                                                 float(pos_w), float(bi_w), ptr(q), ptr(labels, torch.int64, True),
+                                                 ptr(before, torch.int64, True), ptr(prob_up, torch.float32, True),
+                                                 ptr(ws), ws.numel(), stream_ptr()),
+        'spml_dense_crf_infer_upsampled_f32')
+  return q, labels, before, prob_up

@@ -26,9 +26,15 @@
 // K1 = g(dx) g(dy): two 1-D passes over n_1 Q with the taps cut at R = ceil(6 pos_xy_std) (the dropped tail is below
 // 4e-9 of the kernel's mass), and n_1 in closed form from the same taps.  No atomics anywhere; Q is double-buffered;
 // every launch is ordered by the stream alone: a call is bit-reproducible.
+//
+// the random-walk pseudo labels (pseudo_softmaxrw_crf.py:172-187, pseudo_camrw_crf.py:166-181) hand the CRF a
+// 1/8-resolution map up-sampled to the image.  crf_init_upsampled forms the up-sampled values in registers (the taps of
+// bilinear.hpp, as upsample_argmax of pseudo_label.hip) and writes what crf_init writes, plus the labels before the CRF:
+// the [ncls][h][w] map is never stored unless the caller asks for it.  Everything after the first launch is shared.
 #include <math.h>
 #include <stdio.h>
 
+#include "bilinear.hpp"
 #include "common.hpp"
 
 namespace spml {
@@ -214,6 +220,84 @@ __global__ __launch_bounds__(kBlock) void crf_init(const float* __restrict__ pro
     q[(size_t)c * n + i] = v;
     store_operand(op, i, c, ct_count, ni * v);
     if (c == 0 || v > best) best = v, best_c = c;
+  }
+  if (labels != nullptr) labels[i] = best_c;
+}
+
+// The values of classes c0 .. c0 + 7 at the pixel whose taps are `t`, blended from the low-resolution map (0 at and above
+// ncls): the 32 loads are in flight before the first blend.
+constexpr int kInitClasses = 8;
+
+__device__ __forceinline__ void blend_classes(const float* __restrict__ low, size_t plane, const Taps4& t, int c0, int ncls,
+                                              float (&v)[kInitClasses]) {
+  float a[kInitClasses], b[kInitClasses], c[kInitClasses], d[kInitClasses];
+#pragma unroll
+  for (int j = 0; j < kInitClasses; ++j) {
+    const float* base = low + (size_t)(c0 + j < ncls ? c0 + j : 0) * plane;
+    a[j] = base[t.o00]; b[j] = base[t.o01]; c[j] = base[t.o10]; d[j] = base[t.o11];
+  }
+#pragma unroll
+  for (int j = 0; j < kInitClasses; ++j) v[j] = c0 + j < ncls ? blend(t, a[j], b[j], c[j], d[j]) : 0.f;
+}
+
+// crf_init on a map that is up-sampled on the way in (pseudo_softmaxrw_crf.py:172-185): thread = pixel of the h x w
+// image, `low` is [ncls][oh][ow].  The four taps are taken once (make_taps as upsample_argmax of pseudo_label.hip calls
+// it) and every class value v = blend(...) is what F.interpolate(bilinear, align_corners = False) gives.  Every class is
+// blended ONCE and kept in a register (32 CT values, every index a compile-time constant; chunks at and above ncls are
+// skipped by a uniform branch): the compiler fuses the multiplies and adds of `blend` differently from one inlined copy
+// to the next, so a value blended a second time need not have the bits of the first -- and the written prob_up, the
+// sum, log p and Q_0 must all come from the same bits for the call to equal spml_dense_crf_infer_f32 on prob_up.  First
+// loop: sum_c clip(v), the arg-max of the un-clipped v (strict '>', the first NaN wins: the label before the CRF, the
+// rules of upsample_argmax) and, if asked for, v itself.  Second loop: log clip(v), Q_0, the operand, the labels of a
+// call without iterations -- the operations of crf_init, in its order.
+template <int CT>
+__global__ __launch_bounds__(kBlock) void crf_init_upsampled(const float* __restrict__ low, int ncls, int oh, int ow, int h,
+                                                             int w, float scale_h, float scale_w,
+                                                             const float* __restrict__ n2, float* __restrict__ logp,
+                                                             float* __restrict__ q, _Float16* __restrict__ op,
+                                                             int64_t* __restrict__ labels,
+                                                             int64_t* __restrict__ labels_before,
+                                                             float* __restrict__ prob_up) {
+  constexpr int kChunks = 32 * CT / kInitClasses;
+  const int64_t n = (int64_t)h * w;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const Taps4 t = make_taps((int)i, w, scale_h, scale_w, oh, ow, 0, ow, 1);
+  const size_t plane = (size_t)oh * ow;
+  float v[32 * CT];
+  float sum = 0.f, top = 0.f;
+  int top_c = 0;
+#pragma unroll
+  for (int k = 0; k < kChunks; ++k) {
+    if (k * kInitClasses < ncls) {                                  // (uniform)
+      float u[kInitClasses];
+      blend_classes(low, plane, t, k * kInitClasses, ncls, u);
+#pragma unroll
+      for (int j = 0; j < kInitClasses; ++j) {
+        const int c = k * kInitClasses + j;
+        v[c] = u[j];
+        if (c < ncls) {
+          sum += fminf(fmaxf(u[j], kClipLo), 1.0f);
+          if (prob_up != nullptr) prob_up[(size_t)c * n + i] = u[j];
+          if (c == 0 || u[j] > top || (u[j] != u[j] && top == top)) top = u[j], top_c = c;
+        }
+      }
+    }
+  }
+  if (labels_before != nullptr) labels_before[i] = top_c;
+  const float ni = n2[i];
+  float best = 0.f;
+  int best_c = 0;
+#pragma unroll
+  for (int c = 0; c < 32 * CT; ++c) {
+    if (c < ncls) {
+      const float p = fminf(fmaxf(v[c], kClipLo), 1.0f);
+      const float qv = p / sum;
+      logp[(size_t)c * n + i] = logf(p);
+      q[(size_t)c * n + i] = qv;
+      store_operand(op, i, c, CT, ni * qv);
+      if (c == 0 || qv > best) best = qv, best_c = c;
+    }
   }
   if (labels != nullptr) labels[i] = best_c;
 }
@@ -404,17 +488,24 @@ extern "C" int spml_dense_crf_prepare_u8(const unsigned char* image, int h, int 
   return launch_status();
 }
 
-extern "C" int spml_dense_crf_infer_f32(const float* probmap, int ncls, int h, int w, int iter_max, float pos_w,
-                                        float bi_w, float* q, int64_t* labels, void* ws, size_t ws_bytes,
-                                        void* stream) {
-  if (!probmap || !q || ncls < 1 || h < 1 || w < 1 || iter_max < 0 || !isfinite(pos_w) || !isfinite(bi_w) ||
-      ((uintptr_t)probmap & 3) != 0 || ((uintptr_t)q & 3) != 0 || ((uintptr_t)labels & 7) != 0)
+// What both inference entry points check alike, in the order of the status codes; fills the layout.
+static int infer_status(const void* map, int ncls, int h, int w, int iter_max, float pos_w, float bi_w, const float* q,
+                 const int64_t* labels, const void* ws, size_t ws_bytes, Layout& l) {
+  if (!map || !q || ncls < 1 || h < 1 || w < 1 || iter_max < 0 || !isfinite(pos_w) || !isfinite(bi_w) ||
+      ((uintptr_t)map & 3) != 0 || ((uintptr_t)q & 3) != 0 || ((uintptr_t)labels & 7) != 0)
     return SPML_ERR_INVALID_ARG;
-  Layout l;
   if (!make_layout(h, w, ncls, l)) return SPML_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < l.total || ((uintptr_t)ws & 255) != 0) return SPML_ERR_WORKSPACE;
-  char* base = static_cast<char*>(ws);
-  hipStream_t s = (hipStream_t)stream;
+  return SPML_OK;
+}
+
+// The mean-field call around its first launch: the operand images are cleared, `launch_init(n2, logp, q0, op0, labels0)`
+// writes log p, Q_0, the first operand and -- when the call runs no iteration -- the labels (crf_init or
+// crf_init_upsampled, the one thing the two entry points differ in), then iter_max times the two spatial passes and the
+// pair kernel; the last iteration writes the caller's q and labels.
+template <typename Init>
+static int mean_field(const Layout& l, char* base, int ncls, int h, int w, int iter_max, float pos_w, float bi_w, float* q,
+               int64_t* labels, hipStream_t s, Init launch_init) {
   const CrfHeader* dhdr = reinterpret_cast<const CrfHeader*>(base + l.hdr);
   const half8* faxy = reinterpret_cast<const half8*>(base + l.faxy);
   const half8* fargb = reinterpret_cast<const half8*>(base + l.fargb);
@@ -429,11 +520,9 @@ extern "C" int spml_dense_crf_infer_f32(const float* probmap, int ncls, int h, i
   _Float16* opbuf[2] = {reinterpret_cast<_Float16*>(base + l.op0), reinterpret_cast<_Float16*>(base + l.op1)};
   // the padded pixels and classes of both operand images stay zero: they contribute nothing to any message
   if (hipMemsetAsync(base + l.op0, 0, l.total - l.op0, s) != hipSuccess) return SPML_ERR_LAUNCH;
-  const unsigned px_blocks = (unsigned)((l.n + kBlock - 1) / kBlock);
   const unsigned map_blocks = (unsigned)((l.n * ncls + kBlock - 1) / kBlock);
   const unsigned wave_blocks = (unsigned)((l.tiles + kBlock / kWave - 1) / (kBlock / kWave));
-  hipLaunchKernelGGL(crf_init, dim3(px_blocks), dim3(kBlock), 0, s, probmap, ncls, l.n, l.ct, n2, logp,
-                     iter_max == 0 ? q : qbuf[0], opbuf[0], iter_max == 0 ? labels : (int64_t*)nullptr);
+  launch_init(n2, logp, iter_max == 0 ? q : qbuf[0], opbuf[0], iter_max == 0 ? labels : (int64_t*)nullptr);
   for (int t = 0; t < iter_max; ++t) {
     const bool last = t + 1 == iter_max;
     const float* q_cur = qbuf[t & 1];
@@ -455,4 +544,44 @@ extern "C" int spml_dense_crf_infer_f32(const float* probmap, int ncls, int h, i
                          (float*)nullptr);
   }
   return launch_status();
+}
+
+extern "C" int spml_dense_crf_infer_f32(const float* probmap, int ncls, int h, int w, int iter_max, float pos_w,
+                                        float bi_w, float* q, int64_t* labels, void* ws, size_t ws_bytes,
+                                        void* stream) {
+  Layout l;
+  const int status = infer_status(probmap, ncls, h, w, iter_max, pos_w, bi_w, q, labels, ws, ws_bytes, l);
+  if (status != SPML_OK) return status;
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned px_blocks = (unsigned)((l.n + kBlock - 1) / kBlock);
+  return mean_field(l, static_cast<char*>(ws), ncls, h, w, iter_max, pos_w, bi_w, q, labels, s,
+                    [&](const float* n2, float* logp, float* q0, _Float16* op0, int64_t* labels0) {
+                      hipLaunchKernelGGL(crf_init, dim3(px_blocks), dim3(kBlock), 0, s, probmap, ncls, l.n, l.ct, n2, logp,
+                                         q0, op0, labels0);
+                    });
+}
+
+extern "C" int spml_dense_crf_infer_upsampled_f32(const float* lowres, int ncls, int oh, int ow, int h, int w,
+                                                  int iter_max, float pos_w, float bi_w, float* q, int64_t* labels,
+                                                  int64_t* labels_before, float* prob_up, void* ws, size_t ws_bytes,
+                                                  void* stream) {
+  if (oh < 1 || ow < 1 || ((uintptr_t)labels_before & 7) != 0 || ((uintptr_t)prob_up & 3) != 0)
+    return SPML_ERR_INVALID_ARG;
+  Layout l;
+  const int status = infer_status(lowres, ncls, h, w, iter_max, pos_w, bi_w, q, labels, ws, ws_bytes, l);
+  if (status != SPML_OK) return status;
+  if ((int64_t)oh * ow > (1 << 24)) return SPML_ERR_UNSUPPORTED;       // (the limit of spml_upsample_argmax_i64)
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned px_blocks = (unsigned)((l.n + kBlock - 1) / kBlock);
+  // the scale expressions of spml_upsample_argmax_i64: the same taps, the same blended values, the same labels
+  const float scale_h = (float)oh / (float)h, scale_w = (float)ow / (float)w;
+  return mean_field(l, static_cast<char*>(ws), ncls, h, w, iter_max, pos_w, bi_w, q, labels, s,
+                    [&](const float* n2, float* logp, float* q0, _Float16* op0, int64_t* labels0) {
+                      if (l.ct == 1)
+                        hipLaunchKernelGGL(crf_init_upsampled<1>, dim3(px_blocks), dim3(kBlock), 0, s, lowres, ncls, oh, ow,
+                                           h, w, scale_h, scale_w, n2, logp, q0, op0, labels0, labels_before, prob_up);
+                      else
+                        hipLaunchKernelGGL(crf_init_upsampled<2>, dim3(px_blocks), dim3(kBlock), 0, s, lowres, ncls, oh, ow,
+                                           h, w, scale_h, scale_w, n2, logp, q0, op0, labels0, labels_before, prob_up);
+                    });
 }

@@ -29,30 +29,7 @@ constexpr int kSlices = 16;            // lanes per pixel in the view kernels
 constexpr int kViewPix = 16;           // pixels per 256-thread workgroup there
 constexpr int kOwn = 4;                // channels of one 64-channel chunk a lane owns (slice, +16, +32, +48)
 
-// the four element offsets of output pixel p of an oh x ow map over the top-left rh x rw region of a plane with
-// strides (sy, sx); with `flip` logical column x is stored at rw - 1 - x
-struct Taps4 {
-  int64_t o00, o01, o10, o11;
-  float h0, h1, w0, w1;
-};
-
-__device__ __forceinline__ Taps4 make_taps(int p, int ow, float scale_h, float scale_w, int rh, int rw, int flip,
-                                            int64_t sy, int64_t sx) {
-  const int oy = p / ow, ox = p - oy * ow;
-  const Tap ty = make_tap(oy, scale_h, rh), tx = make_tap(ox, scale_w, rw);
-  const int x0 = flip ? rw - 1 - tx.i0 : tx.i0, x1 = flip ? rw - 1 - tx.i1 : tx.i1;
-  Taps4 t;
-  t.o00 = ty.i0 * sy + x0 * sx;
-  t.o01 = ty.i0 * sy + x1 * sx;
-  t.o10 = ty.i1 * sy + x0 * sx;
-  t.o11 = ty.i1 * sy + x1 * sx;
-  t.h0 = ty.l0; t.h1 = ty.l1; t.w0 = tx.l0; t.w1 = tx.l1;
-  return t;
-}
-
-__device__ __forceinline__ float blend(const Taps4& t, float a, float b, float c, float d) {
-  return t.h0 * (t.w0 * a + t.w1 * b) + t.h1 * (t.w0 * c + t.w1 * d);
-}
+// (Taps4, make_taps and blend -- the four taps of an output pixel and their weighted sum -- are in bilinear.hpp)
 
 // sum / max over the 16 lanes of a pixel (xor 8, 4, 2, 1 stays inside an aligned group of 16): every lane ends with the
 // same value, formed in the same order whatever the input's memory layout

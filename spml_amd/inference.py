@@ -504,31 +504,21 @@ def flip_scale_views(image, scales, is_flip, crop_size):
   return views
 
 
-def pseudo_labels_softmax(embedding_model, prediction_model, views, image_hw, label_tags, combine='prob_mean',
-                          walk_steps=6, background_threshold=None, scale=5.0, power=20, return_transition=False):
-  """One image of the pseudo-label generation (`pyscripts/inference/pseudo_softmaxrw_crf.py:116-176` with
-  combine='prob_mean', walk_steps=6; `pseudo_softmax.py:115-179` with combine='logit_mean', walk_steps=0), before
-  the denseCRF.  `views`: list of `(image [1,3,Hp,Wp], (rh, rw), is_flip)` (`flip_scale_views`); `image_hw`: the
-  un-padded image; `label_tags`: bool `[ncls]` device tensor (`label_tags_from_map`).
-
-  Per view the whole padded image goes through `generate_embeddings(..., resize_as_input=True)` and the classifier
-  head (:127-128; consecutive views of one padded size -- a flip pair -- share the backbone call, the head runs through
-  `accumulate_logits` into a zero canvas), then `spml_resample_unit_f32` (crop, un-flip, 1/8 bilinear, unit columns,
-  read through the embedding's strides: no NCHW copy of a channels-last map) and
-  `spml_resample_classes_accumulate_f32` (the same for the logits, soft-maxed and summed in view order).  After the
-  last view: `spml_affinity_transition_f32`, `spml_cam_finalize_f32`, the walk's GEMMs, `spml_upsample_argmax_i64`.
-  Returns `cam`, `cam_rw` `[ncls, h//8, w//8]`, `semantic_prediction` `[h,w]` int64, `head_path`, and `transition`
-  `[n,n]` (before the squarings) only with `return_transition`."""
+def _walked_cams_softmax(name, embedding_model, prediction_model, views, image_hw, label_tags, combine, walk_steps,
+                         background_threshold, scale, power):
+  """`pseudo_labels_softmax` up to the walked maps, shared with `pseudo_labels_softmax_crf`: the argument checks (under
+  the caller's `name`), the per-view launches, the transition matrix, the class maps and the walk.
+  -> (cam, cam_rw `[ncls, h//8, w//8]`, head path, transition before the squarings)."""
   if combine not in _ffi.COMBINE_MODES:
     raise ValueError("combine must be 'prob_mean' or 'logit_mean'")
   if views and not label_tags.is_cuda:                # (an empty list is reported first, by _check_views)
     raise _ffi.SpmlHipError('the HIP path needs GPU tensors (label_tags on %s); there is no CPU fallback'
                             % label_tags.device)
-  _check_views('pseudo_labels_softmax', views)
+  _check_views(name, views)
   h, w = image_hw
   out_hw = (h // 8, w // 8)
   if out_hw[0] < 1 or out_hw[1] < 1:
-    raise ValueError('pseudo_labels_softmax: the image is smaller than 8 x 8')
+    raise ValueError(name + ': the image is smaller than 8 x 8')
   n = out_hw[0] * out_hw[1]
   device = views[0][0].device
   ncls = prediction_model.num_classes
@@ -552,6 +542,29 @@ def pseudo_labels_softmax(embedding_model, prediction_model, views, image_hw, la
     trans = _ffi.affinity_transition(units, scale, power)
     cam = _ffi.cam_finalize(acc, len(views), label_tags, combine, background_threshold).view(ncls, *out_hw)
     cam_rw = _walk(trans, cam, walk_steps)
+  return cam, cam_rw, path, trans
+
+
+def pseudo_labels_softmax(embedding_model, prediction_model, views, image_hw, label_tags, combine='prob_mean',
+                          walk_steps=6, background_threshold=None, scale=5.0, power=20, return_transition=False):
+  """One image of the pseudo-label generation (`pyscripts/inference/pseudo_softmaxrw_crf.py:116-176` with
+  combine='prob_mean', walk_steps=6; `pseudo_softmax.py:115-179` with combine='logit_mean', walk_steps=0), before
+  the denseCRF.  `views`: list of `(image [1,3,Hp,Wp], (rh, rw), is_flip)` (`flip_scale_views`); `image_hw`: the
+  un-padded image; `label_tags`: bool `[ncls]` device tensor (`label_tags_from_map`).
+
+  Per view the whole padded image goes through `generate_embeddings(..., resize_as_input=True)` and the classifier
+  head (:127-128; consecutive views of one padded size -- a flip pair -- share the backbone call, the head runs through
+  `accumulate_logits` into a zero canvas), then `spml_resample_unit_f32` (crop, un-flip, 1/8 bilinear, unit columns,
+  read through the embedding's strides: no NCHW copy of a channels-last map) and
+  `spml_resample_classes_accumulate_f32` (the same for the logits, soft-maxed and summed in view order).  After the
+  last view: `spml_affinity_transition_f32`, `spml_cam_finalize_f32`, the walk's GEMMs, `spml_upsample_argmax_i64`.
+  Returns `cam`, `cam_rw` `[ncls, h//8, w//8]`, `semantic_prediction` `[h,w]` int64, `head_path`, and `transition`
+  `[n,n]` (before the squarings) only with `return_transition`."""
+  h, w = image_hw
+  cam, cam_rw, path, trans = _walked_cams_softmax('pseudo_labels_softmax', embedding_model, prediction_model, views,
+                                                  image_hw, label_tags, combine, walk_steps, background_threshold,
+                                                  scale, power)
+  with torch.no_grad():
     prediction = _ffi.upsample_argmax(cam_rw, h, w)
   out = {'cam': cam, 'cam_rw': cam_rw, 'semantic_prediction': prediction, 'head_path': path}
   if return_transition:
@@ -586,3 +599,60 @@ def dense_crf_refine(image_u8, prob, crf):
   prob_out, prediction = crf.refine(image_u8, prob)
   return {'semantic_prob': prob_out, 'semantic_prediction': prediction,
           'crf_path': crf.path_name(prob.shape[1], prob.shape[2], prob.shape[0])}
+
+
+def random_walk_crf_refine(image_u8, cam_rw, crf):
+  """The tail the two random-walk programs share (`pseudo_softmaxrw_crf.py:172-187` = `pseudo_camrw_crf.py:166-181`):
+  the walked maps `cam_rw` fp32 `[ncls, oh, ow]` (the programs: `h//8 x w//8`) are up-sampled bilinearly to the image,
+  their arg-max is the label before the CRF, and the up-sampled maps go with `image_u8` uint8 `[h,w,3]` through `crf`
+  (`spml_amd.models.crf.DenseCRF`).  One fused call (`spml_dense_crf_infer_upsampled_f32`): the up-sampled
+  maps are formed inside the CRF's first kernel, which also writes the label before the CRF.  Returns `semantic_prob`
+  `[ncls,h,w]` (the refined marginals), `semantic_prediction` `[h,w]` int64 (their arg-max),
+  `semantic_prediction_before_crf` `[h,w]` int64 (what `spml_upsample_argmax_i64` gives) and `crf_path`."""
+  prob, prediction, before = crf.refine_upsampled(image_u8, cam_rw)
+  return {'semantic_prob': prob, 'semantic_prediction': prediction, 'semantic_prediction_before_crf': before,
+          'crf_path': crf.path_name(image_u8.shape[0], image_u8.shape[1], cam_rw.shape[0])}
+
+
+def pseudo_labels_softmax_crf(embedding_model, prediction_model, views, image_hw, label_tags, image_u8, crf,
+                              combine='prob_mean', walk_steps=6, background_threshold=None, scale=5.0, power=20,
+                              return_transition=False):
+  """`pseudo_labels_softmax` with the denseCRF refinement of `pseudo_softmaxrw_crf.py:172-187`: the same chain up to
+  `cam_rw`, then `random_walk_crf_refine` on `image_u8` (uint8 `[h,w,3]`, `denormalized_uint8` of the un-padded image)
+  with `crf`.  Returns the fields of `pseudo_labels_softmax` -- `semantic_prediction` being the refined labels -- plus
+  `semantic_prob`, `semantic_prediction_before_crf` (from the fused launch; equal to `pseudo_labels_softmax`'s
+  `semantic_prediction`) and `crf_path`."""
+  if tuple(image_u8.shape[:2]) != tuple(image_hw):
+    raise ValueError('pseudo_labels_softmax_crf: image_u8 must be the un-padded image [h,w,3]')
+  cam, cam_rw, path, trans = _walked_cams_softmax('pseudo_labels_softmax_crf', embedding_model, prediction_model, views,
+                                                  image_hw, label_tags, combine, walk_steps, background_threshold,
+                                                  scale, power)
+  out = {'cam': cam, 'cam_rw': cam_rw, 'head_path': path}
+  out.update(random_walk_crf_refine(image_u8, cam_rw, crf))
+  if return_transition:
+    out['transition'] = trans
+  return out
+
+
+def cam_with_background(cam_dict, image_hw, num_classes, alpha):
+  """The class activation maps of one image as `pseudo_camrw_crf.py:108-111` stacks them: `cam_dict` `{k: [h,w]}` (the
+  reference's on-disk format, keyed by class - 1) -> fp32 `[num_classes, h, w]` on the entries' device with entry `k` at
+  class `k + 1`, zeros for the classes the dict does not carry and the background `(1 - max over the foreground) **
+  alpha` at class 0.  Framework ops (one pass over the maps, not a hot path)."""
+  h, w = image_hw
+  values = [torch.as_tensor(v) for v in cam_dict.values()]
+  device = values[0].device if values else torch.device('cpu')
+  full = torch.zeros((num_classes, h, w), dtype=torch.float32, device=device)
+  for k, v in zip(cam_dict.keys(), values):
+    full[int(k) + 1] = v.to(torch.float32)
+  if num_classes > 1:
+    full[0] = torch.pow(1 - torch.max(full[1:], dim=0).values, alpha)
+  else:
+    full[0] = 1
+  return full
+
+
+def downsampled_cam(cam_full):
+  """`pseudo_camrw_crf.py:151-152`: `[ncls, h, w]` -> `[ncls, h//8, w//8]` by the framework's own
+  `F.interpolate(scale_factor=1/8, mode='bilinear')` -- the same op, so its `scale_factor` semantics are kept."""
+  return torch.nn.functional.interpolate(cam_full.unsqueeze(0), scale_factor=1 / 8., mode='bilinear').squeeze(0)

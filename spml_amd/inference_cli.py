@@ -1,4 +1,4 @@
-"""Shared body of the eleven inference programs under `pyscripts/inference/`: the reference's command line and config
+"""Shared body of the thirteen inference programs under `pyscripts/inference/`: the reference's command line and config
 surface (`parse_args`), the argument guards, snapshot loading, the seeded synthetic images that stand in for the
 file-list loader (outside this repository, DESIGN 9: `--data_list synthetic`), the self-built memory bank of the kNN
 programs, the timed loop over the images and the JSON line.  A program's `main` holds what is specific to its recipe:
@@ -247,6 +247,22 @@ class CrfStage(object):
     self.events.append((start, end))
     self.path = out['crf_path']
     return out
+
+  def refine_upsampled(self, image_u8, lowres):
+    """The fused call of the random-walk programs (`DenseCRF.refine_upsampled`: the low-resolution walked maps are
+    up-sampled inside the CRF's first kernel) between the same device events.  With this method and `path_name` the stage
+    stands in for its `DenseCRF` as the `crf` of `inference.random_walk_crf_refine` and `pseudo_labels_softmax_crf`, so
+    the events enclose the CRF alone and not the network and the walk in front of it."""
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    out = self.crf.refine_upsampled(image_u8, lowres)
+    end.record()
+    self.events.append((start, end))
+    return out
+
+  def path_name(self, h, w, ncls):
+    self.path = self.crf.path_name(h, w, ncls)
+    return self.path
 
   def fields(self, seconds):
     """Read after the loop's closing synchronisation: `crf_path` and the stage's share of the timed seconds."""

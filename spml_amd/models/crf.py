@@ -49,6 +49,31 @@ class DenseCRF(object):
       ws = self.prepare(image.contiguous(), probmap.shape[0])
       return self.infer(ws, probmap.float().contiguous())
 
+  def infer_upsampled(self, ws, lowres, image_hw, want_labels=True, want_labels_before=True, want_prob_up=False,
+                      iter_max=None, pos_w=None, bi_w=None):
+    """`infer` on the bilinear up-sampling of `lowres` fp32 `[C, oh, ow]` to `image_hw` (`F.interpolate`,
+    align_corners=False), formed inside the first kernel -> (Q `[C, h, w]`, its arg-max `[h, w]` or None, the
+    arg-max of the up-sampled map -- the label before the CRF -- or None, the up-sampled map `[C, h, w]` or None)."""
+    if not torch.is_tensor(lowres) or not lowres.is_cuda:
+      raise _ffi.SpmlHipError('the HIP path needs GPU tensors (the dense CRF has no CPU fallback)')
+    return _ffi.dense_crf_infer_upsampled(lowres, image_hw, self.iter_max if iter_max is None else iter_max,
+                                          self.pos_w if pos_w is None else pos_w, self.bi_w if bi_w is None else bi_w,
+                                          ws, want_labels, want_labels_before, want_prob_up)
+
+  def refine_upsampled(self, image, lowres):
+    """`refine` of the random-walk programs (pseudo_softmaxrw_crf.py:172-187): the image `[h, w, 3]` uint8 and a map
+    `[C, oh, ow]` of any lower (or equal) resolution, device tensors -> (Q `[C, h, w]` fp32, its arg-max `[h, w]` int64,
+    the arg-max of the up-sampled map `[h, w]` int64)."""
+    if not (torch.is_tensor(image) and torch.is_tensor(lowres) and image.is_cuda and lowres.is_cuda):
+      raise _ffi.SpmlHipError('the HIP path needs GPU tensors (the dense CRF has no CPU fallback)')
+    if lowres.dim() != 3 or image.dim() != 3 or image.shape[2] != 3:
+      raise ValueError('DenseCRF expects an image [h, w, 3] and a low-resolution map [C, oh, ow]')
+    if image.dtype != torch.uint8:
+      raise ValueError('DenseCRF expects a uint8 image')
+    with torch.no_grad():
+      ws = self.prepare(image.contiguous(), lowres.shape[0])
+      return self.infer_upsampled(ws, lowres.float().contiguous(), tuple(image.shape[:2]))[:3]
+
   def __call__(self, image, probmap):
     """numpy arrays (HWC uint8, CHW float32) -> numpy CHW float32 through the GPU, as the reference; device tensors ->
     a device tensor.  Without a GPU, or for CPU tensors, `SpmlHipError`."""
