@@ -93,10 +93,22 @@ __global__ __launch_bounds__(256) void bn_partial(const float* __restrict__ x, c
   float4v hi = {-3.4e38f, -3.4e38f, -3.4e38f, -3.4e38f}, lo = {3.4e38f, 3.4e38f, 3.4e38f, 3.4e38f};
   if (MODE == 1) hi = a;
   if (q < cquads) {
-    // MODE 0: sums are taken relative to the chunk's first row (a per-channel shift), so that
-    // sumsq - n * mean^2 does not cancel when |mean| >> std;  MODE 1: the batch mean
-    mu = MODE == 1 ? *reinterpret_cast<const float4v*>(mean + 4 * q)
-                   : *reinterpret_cast<const float4v*>(x + (size_t)r0 * C + 4 * q);
+    // MODE 0: sums are taken relative to the mean of the chunk's first four rows (a per-channel shift), so that
+    // sumsq - n * mean^2 does not cancel when |mean| >> std.  The rounding of the accumulated sumsq is magnified by
+    // 1 + ((shift - chunk mean) / std)^2 in M2: with the first row alone as the shift that was ~10 for the unluckiest
+    // of a few hundred channels (3 sigma), and a whole-tensor M2 4e-6 off where one chunk dominates
+    // (profiles/bn_branch_parity.md); four rows halve the sigma.  1, 2 or 4 rows: a constant channel keeps an exact
+    // shift (pairwise sums, power-of-two count) and M2 = 0.  MODE 1: the batch mean
+    if (MODE == 1) {
+      mu = *reinterpret_cast<const float4v*>(mean + 4 * q);
+    } else {
+      const float* xs = x + (size_t)r0 * C + 4 * q;
+      const float4v s0 = *reinterpret_cast<const float4v*>(xs);
+      const float4v s1 = nrows >= 2 ? *reinterpret_cast<const float4v*>(xs + C) : s0;
+      const float4v s2 = nrows >= 4 ? *reinterpret_cast<const float4v*>(xs + 2 * (size_t)C) : s0;
+      const float4v s3 = nrows >= 4 ? *reinterpret_cast<const float4v*>(xs + 3 * (size_t)C) : s1;
+      mu = ((s0 + s1) + (s2 + s3)) * 0.25f;
+    }
 #pragma unroll 4
     for (int r = ty; r < nrows; r += nty) {
       const size_t o = (size_t)(r0 + r) * C + 4 * q;
@@ -239,6 +251,7 @@ __global__ __launch_bounds__(kMergeCh * kMergeLanes) void bn_merge(
   // MODE 1: invstd, mean, extremes, gamma) are requested here, with the chunk values: behind the reductions they were
   // one more dependent round trip per call
   float p_gamma = 0.f, p_beta = 0.f, p_res = 0.f, p_rm = 0.f, p_rv = 0.f, p_is = 0.f, p_mu = 0.f, p_cmax = 0.f, p_cmin = 0.f;
+  const float p_ref = MODE == 0 ? pa[c] : 0.f;      // chunk 0's mean (every thread of the channel: the shift of the pooled mean)
   if (live) {
     if (MODE == 0) {
       if (f.fin && bb.bound) { p_gamma = bb.gamma[c]; p_beta = bb.beta[c]; p_res = bb.res_bound ? *bb.res_bound : 0.f; }
@@ -278,7 +291,9 @@ __global__ __launch_bounds__(kMergeCh * kMergeLanes) void bn_merge(
     }
   }
   if (MODE == 0) {
-    // pooled mean first, then the M2 terms (Chan): two independent sums, no division in the loops
+    // pooled mean first, then the M2 terms (Chan): two independent sums, no division in the loops.  The means are
+    // pooled relative to chunk 0's: the sum of mean_i * n_i itself rounds at |mean|, which left the mean of a
+    // constant channel one ulp off its value -- M2 > 0 and y = beta + gamma * ulp / sqrt(eps) instead of beta
     float sm = 0.f;
     if (in_regs) {
 #pragma unroll
@@ -286,17 +301,17 @@ __global__ __launch_bounds__(kMergeCh * kMergeLanes) void bn_merge(
         const int i = ty + j * kMergeLanes;
         if (i < chunks) {
           const float nb = (float)min((int64_t)chunk_rows, R - (int64_t)i * chunk_rows);
-          sm += ra[j] * nb;
+          sm += (ra[j] - p_ref) * nb;
         }
       }
     } else {
 #pragma unroll 4
       for (int i = ty; i < chunks; i += kMergeLanes) {
         const float nb = (float)min((int64_t)chunk_rows, R - (int64_t)i * chunk_rows);
-        sm += pa[(size_t)i * C + c] * nb;
+        sm += (pa[(size_t)i * C + c] - p_ref) * nb;
       }
     }
-    const float m = merge_lanes(sm, sh, tx, ty) / (float)R;
+    const float m = p_ref + merge_lanes(sm, sh, tx, ty) / (float)R;
     float m2 = 0.f;
     if (in_regs) {
 #pragma unroll

@@ -43,6 +43,9 @@ def _run(blk, x, up, fused, monkeypatch):
   return y.detach(), xi.grad, grads, stats
 
 
+_X_SEED = {(512, 128): 9}
+
+
 @pytest.mark.parametrize('inplanes,planes,dil,ds,n,h,w', [(1024, 256, 2, False, 2, 17, 19), (512, 256, 1, True, 2, 12, 9),
                                                           (2048, 512, 4, False, 1, 11, 13),
                                                           (512, 128, 1, False, 2, 15, 14),      # res3: 128-wide tiles
@@ -50,7 +53,11 @@ def _run(blk, x, up, fused, monkeypatch):
 def test_unit_matches_framework_ops(inplanes, planes, dil, ds, n, h, w, monkeypatch):
   blk = _make(inplanes, planes, dil, ds, seed=inplanes + dil)
   ref = copy.deepcopy(blk)
-  g = torch.Generator().manual_seed(7)
+  # (512, 128): with seed 7 the float64 pre-activation of bn2 at image 0, pixel (3, 10), channel 39 is 3.8e-7 -- inside the
+  # fp32 rounding of either side, so its ReLU mask bit (and the input gradient of the 3x3 neighbourhood, 2e-3 of the
+  # largest) follows the last bit of the batch statistics.  Seed 9 keeps every pre-activation of the three batch
+  # norms 2e-5 away from zero (float64, CPU); the other shapes keep theirs.
+  g = torch.Generator().manual_seed(_X_SEED.get((inplanes, planes), 7))
   x = torch.randn(n, inplanes, h, w, generator=g).clamp_min(0).to(DEV).contiguous(memory_format=torch.channels_last)
   up = (torch.randn(n, planes * 4, h, w, generator=g) * 1e-3).to(DEV).contiguous(memory_format=torch.channels_last)
   y1, dx1, g1, s1 = _run(blk, x, up, True, monkeypatch)
@@ -174,7 +181,9 @@ def test_two_ranks_with_sync_batchnorm_match_one_rank_on_the_joint_batch(cut, ar
   monkeypatch.setenv('SPML_CONV_BN_STATS', '0')
   blk = _make(*arch, seed=11)
   state = {k: v.cpu() for k, v in blk.state_dict().items()}
-  g = torch.Generator().manual_seed(3)
+  # 1024 input channels: seed 3 leaves a pre-activation 1.5e-6 from zero (float64; the same mask-bit flip as above once
+  # the statistics move in their last bit); seed 12 keeps all of them 1.3e-5 away.  512 channels keep seed 3.
+  g = torch.Generator().manual_seed(12 if arch[0] == 1024 else 3)
   x_all = torch.randn(4, arch[0], 9, 11, generator=g).clamp_min(0)
   up_all = torch.randn(4, 4 * arch[1], 9, 11, generator=g) * 1e-3
   ctx = mp.get_context('spawn')

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from bn_act_ref import decode_hl8
 from conftest import load_golden
 from spml_amd import _ffi, inference
 from spml_amd.models.predictions import softmax_classifier as sc
@@ -26,14 +27,6 @@ class StubEmbedder(torch.nn.Module):
     return {'embedding': self.conv(datas['image'])}
 
 
-def decode_hl8(hl8):
-  """Hl8 -> float64 [rows, C]: (h + l) / S with S = 2^(14 - e) for the smallest e with bound < 2^e (spml_hip.h)."""
-  bound = float(hl8.bound.item())
-  e = int(np.floor(np.log2(bound))) + 1
-  halves = hl8.data.cpu().view(torch.float16).view(hl8.rows, hl8.channels // 8, 2, 8).double()
-  return (halves[:, :, 0] + halves[:, :, 1]).reshape(hl8.rows, hl8.channels) / 2.0 ** (14 - e)
-
-
 @pytest.mark.parametrize('n,c,h,w', [(2, 32, 7, 11), (1, 64, 9, 15), (3, 16, 8, 8), (1, 208, 5, 13)])
 def test_unit_hl8_round_trip(n, c, h, w):
   """h + l against x / |x| in float64 at 2^-22 relative, the width of the format (two 11-bit significands).  The low
@@ -44,7 +37,7 @@ def test_unit_hl8_round_trip(n, c, h, w):
   x[0, :, 1, 2] = 0.0                                              # a zero-norm pixel: zeros, not NaN (outside the contract)
   got = _ffi.unit_hl8_from_nchw(x.to(DEV))
   assert got.rows == n * h * w and got.channels == c and float(got.bound.item()) == 1.0
-  dec = decode_hl8(got).view(n, h, w, c).permute(0, 3, 1, 2)
+  dec = decode_hl8(got).cpu().view(n, h, w, c).permute(0, 3, 1, 2)
   xd = x.double()
   want = xd / xd.norm(dim=1, keepdim=True)
   assert torch.equal(dec[0, :, 1, 2], torch.zeros(c, dtype=torch.float64))
