@@ -1050,6 +1050,18 @@ int spml_tag_normalize_argmax_f32(const float* acc, int ncls, int64_t n, int num
  *   spml_dense_crf_infer_f32, whose result on the up-sampled map it equals bit for bit.  labels_before int64 [h][w] or
  *   NULL: the arg-max of the up-sampled values before the clip, equal to spml_upsample_argmax_i64(lowres) on every pixel
  *   (lowest class on ties, the first NaN wins).  prob_up fp32 [ncls][h][w] or NULL: the up-sampled values themselves.
+ * spml_dense_crf_infer_votes_f32 (pyscripts/inference/inference_crf.py:237-254, and spml/models/crf.py:23-41; DESIGN.md
+ *   8l): the same inference on probmap[c][i] = the share of topk[clu[i]] equal to c -- the vote map of the kNN label
+ *   inference (one_hot, sum over k, / k, transpose), which is not formed: clu int64 [h][w], the dense segment id of every
+ *   pixel (an id outside [0, m) is clamped into it); topk int64 [m][k], the labels retrieved per segment (a label outside
+ *   [0, ncls) adds to no class).  One launch per call computes the votes, log p, Q_0 and both labels per SEGMENT into
+ *   table_ws, the first launch of the inference gathers them per pixel.  m, k >= 1 (else SPML_ERR_INVALID_ARG, as for a
+ *   null clu or topk or a misaligned pointer); m <= 4096, else SPML_ERR_UNSUPPORTED.  table_ws: 16-byte aligned, at least
+ *   spml_dense_crf_votes_workspace_bytes(m, ncls) bytes (0 outside m <= 4096, ncls <= 64), else SPML_ERR_WORKSPACE; it
+ *   may overlap no input, no output and not ws (SPML_ERR_INVALID_ARG); its previous content does not matter.  q, labels,
+ *   ws and every other check as spml_dense_crf_infer_f32, whose result on the vote map it equals bit for bit.
+ *   labels_before int64 [h][w] or NULL: the arg-max of the votes, the lowest class on ties (np.argmax).  prob fp32
+ *   [ncls][h][w] or NULL: the vote map itself, with the bits of spml_view_votes_accumulate_f32's table.
  * spml_dense_crf_path_name (spml/models/crf.py:23-41; host only): "pairs_mfma_f16x2_c<32|64>+separable_r<R>" -- the
  *   class columns of the pair kernel and the taps R = ceil(6 pos_xy_std) kept on either side by the separable spatial
  *   filter (the tail it drops is below 4e-9 of the kernel's mass).
@@ -1065,6 +1077,11 @@ int spml_dense_crf_infer_f32(const float* probmap, int ncls, int h, int w, int i
 int spml_dense_crf_infer_upsampled_f32(const float* lowres, int ncls, int oh, int ow, int h, int w, int iter_max,
                                        float pos_w, float bi_w, float* q, int64_t* labels, int64_t* labels_before,
                                        float* prob_up, void* ws, size_t ws_bytes, void* stream);
+size_t spml_dense_crf_votes_workspace_bytes(int m, int ncls);
+int spml_dense_crf_infer_votes_f32(const int64_t* clu, const int64_t* topk, int m, int k, int ncls, int h, int w,
+                                   int iter_max, float pos_w, float bi_w, float* q, int64_t* labels,
+                                   int64_t* labels_before, float* prob, void* table_ws, size_t table_ws_bytes, void* ws,
+                                   size_t ws_bytes, void* stream);
 const char* spml_dense_crf_path_name(int h, int w, int ncls, float pos_xy_std);
 
 #ifdef __cplusplus

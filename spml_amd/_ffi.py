@@ -163,6 +163,9 @@ _SIGNATURES = {
     'spml_dense_crf_infer_f32': (c_int, [_P, c_int, c_int, c_int, c_int, c_float, c_float, _P, _P, _P, c_size_t, _P]),
     'spml_dense_crf_infer_upsampled_f32': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, _P, _P,
                                                    _P, _P, _P, c_size_t, _P]),
+    'spml_dense_crf_votes_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'spml_dense_crf_infer_votes_f32': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, _P, _P,
+                                               _P, _P, _P, c_size_t, _P, c_size_t, _P]),
     'spml_dense_crf_path_name': (c_char_p, [c_int, c_int, c_int, c_float]),
 }
 
@@ -1560,3 +1563,40 @@ def dense_crf_infer_upsampled(lowres, image_hw, iter_max, pos_w, bi_w, ws, want_
                                                  ptr(ws), ws.numel(), stream_ptr()),
         'spml_dense_crf_infer_upsampled_f32')
   return q, labels, before, prob_up
+
+
+MAX_DENSE_CRF_VOTE_SEGMENTS = 4096     # the limit of spml_dense_crf_infer_votes_f32 (include/spml_hip.h)
+
+
+def dense_crf_infer_votes(clu, topk, ncls, image_hw, iter_max, pos_w, bi_w, ws, want_labels=True, want_labels_before=True,
+                          want_prob=False):
+  """clu int64 `[h * w]` (or `[h, w]`), the dense segment id of every pixel; topk int64 `[m, k]`, the labels retrieved per
+  segment; the class count, the image size (h, w) and a prepared `ws` -> (Q fp32 [ncls, h, w], arg-max int64 [h, w] or
+  None, the arg-max of the votes before the CRF int64 [h, w] or None, the vote map fp32 [ncls, h, w] or None):
+  `dense_crf_infer` on the vote map `one_hot(topk[clu]).sum(1) / k` (inference_crf.py:240-245), which the first launch
+  gathers from a per-segment table instead of forming it.  All tensors contiguous, on the GPU."""
+  for name, t in (('clu', clu), ('topk', topk), ('ws', ws)):
+    if not torch.is_tensor(t) or not t.is_cuda:
+      raise SpmlHipError('dense_crf_infer_votes: the HIP path needs GPU tensors (%s); there is no CPU fallback' % name)
+  h, w = (int(v) for v in image_hw)
+  ncls = int(ncls)
+  if topk.dim() != 2 or h < 1 or w < 1 or clu.numel() != h * w:
+    raise SpmlHipError('dense_crf_infer_votes: expected topk [m, k] and %d x %d segment ids' % (h, w))
+  m, k = (int(v) for v in topk.shape)
+  nbytes = lib().spml_dense_crf_votes_workspace_bytes(m, ncls)
+  if nbytes == 0:
+    raise SpmlHipError('dense_crf_infer_votes: %d segments x %d classes are outside the kernel (at most %d x %d)'
+                       % (m, ncls, MAX_DENSE_CRF_VOTE_SEGMENTS, MAX_DENSE_CRF_CLASSES))
+  dev = clu.device
+  table = workspace(nbytes, dev)
+  q = torch.empty((ncls, h, w), dtype=torch.float32, device=dev)
+  labels = torch.empty((h, w), dtype=torch.int64, device=dev) if want_labels else None
+  before = torch.empty((h, w), dtype=torch.int64, device=dev) if want_labels_before else None
+  prob = torch.empty((ncls, h, w), dtype=torch.float32, device=dev) if want_prob else None
+  check(lib().spml_dense_crf_infer_votes_f32(ptr(clu, torch.int64), ptr(topk, torch.int64), m, k, ncls, h, w,
+                                             int(iter_max), float(pos_w), float(bi_w), ptr(q),
+                                             ptr(labels, torch.int64, True), ptr(before, torch.int64, True),
+                                             ptr(prob, torch.float32, True), ptr(table), table.numel(), ptr(ws),
+                                             ws.numel(), stream_ptr()),
+        'spml_dense_crf_infer_votes_f32')
+  return q, labels, before, prob

@@ -31,6 +31,13 @@
 // 1/8-resolution map up-sampled to the image.  crf_init_upsampled forms the up-sampled values in registers (the taps of
 // bilinear.hpp, as upsample_argmax of pseudo_label.hip) and writes what crf_init writes, plus the labels before the CRF:
 // the [ncls][h][w] map is never stored unless the caller asks for it.  Everything after the first launch is shared.
+//
+// the kNN label inference (inference_crf.py:237-254) hands the CRF the vote map of its segments: one segment
+// id per pixel and one row of k retrieved labels per segment (m <= 144 rows with the largest k-means grid here).  The
+// clip, the sum, the logarithm and the division of crf_init are constant over a segment, so crf_votes_table does them
+// once per segment (votes as votes_table of knn_msc.hip forms them) and crf_init_votes is a gather of that segment's row
+// plus the operand write: no logf and no division per pixel, and the [h w][k] labels, their one-hot and the vote map
+// itself are never formed unless the caller asks for the map.
 #include <math.h>
 #include <stdio.h>
 
@@ -302,6 +309,102 @@ __global__ __launch_bounds__(kBlock) void crf_init_upsampled(const float* __rest
   if (labels != nullptr) labels[i] = best_c;
 }
 
+// One row of the segment table of the kNN entry: [log p | Q_0 | v], `cpad` = 32 CT floats each (zeros from ncls on), then
+// the label before the CRF and the arg-max of Q_0 as two ints and two ints of padding: a multiple of 16 bytes, so that a
+// row is read as float4s.
+constexpr int kMaxVoteSegments = 4096;                            // (the limit of spml_view_votes_accumulate_f32)
+
+__host__ __device__ constexpr int votes_row_floats(int cpad) { return 3 * cpad + 4; }
+
+// (as segment_of of knn_msc.hip: an id outside [0, m) is outside the contract; clamped, so nothing is read out of bounds)
+__device__ __forceinline__ int clamped_segment(int64_t id, int m) {
+  return id < 0 ? 0 : id >= (int64_t)m ? m - 1 : (int)id;
+}
+
+// block = one wave = segment s, lane = class c: what votes_table of knn_msc.hip followed by crf_init computes for every
+// pixel of the segment.  The vote is votes_table's expression -- an exact count, divided once by (float)k; a label outside
+// [0, ncls) matches no column -- then the operations of crf_init in its order: the clip, the sum in ascending class order
+// (every lane walks the classes through __shfl, so every lane holds the same sum), log p, p / sum, and both arg-max rules:
+// strict '>' on the votes (the lowest class of a tie, np.argmax: the label before the CRF) and crf_init's on Q_0.
+__global__ __launch_bounds__(kWave) void crf_votes_table(const int64_t* __restrict__ topk, int k, int ncls, int cpad,
+                                                         float* __restrict__ table) {
+  const int s = blockIdx.x, c = threadIdx.x;
+  const int64_t* row = topk + (size_t)s * k;
+  int count = 0;
+  for (int j = 0; j < k; ++j) count += row[j] == (int64_t)c;
+  const float v = c < ncls ? (float)count / (float)k : 0.f;
+  const float p = fminf(fmaxf(v, kClipLo), 1.0f);
+  float sum = 0.f, top = 0.f;
+  int top_c = 0;
+  for (int cc = 0; cc < ncls; ++cc) {                               // (uniform: all 64 lanes take part in every __shfl)
+    sum += __shfl(p, cc, kWave);
+    const float u = __shfl(v, cc, kWave);
+    if (cc == 0 || u > top) top = u, top_c = cc;
+  }
+  const float qv = p / sum;
+  float best = 0.f;
+  int best_c = 0;
+  for (int cc = 0; cc < ncls; ++cc) {
+    const float u = __shfl(qv, cc, kWave);
+    if (cc == 0 || u > best) best = u, best_c = cc;
+  }
+  float* out = table + (size_t)s * votes_row_floats(cpad);
+  if (c < cpad) {
+    out[c] = c < ncls ? logf(p) : 0.f;
+    out[cpad + c] = c < ncls ? qv : 0.f;
+    out[2 * cpad + c] = v;
+  }
+  if (c < 4) reinterpret_cast<int*>(out + 3 * cpad)[c] = c == 0 ? top_c : c == 1 ? best_c : 0;
+}
+
+// crf_init on the vote map of the kNN inference (inference_crf.py:240-245), which is never formed: thread = pixel i, one
+// segment id (read once, clamped) and that segment's row of crf_votes_table as float4s -- eight classes (four loads) in
+// flight at a time, chunks at and above ncls skipped by a uniform branch, every index into a register array a
+// compile-time constant.  The lanes of a wave hold one or two distinct ids nearly everywhere, so a row load touches one
+// or two lines; the stores are those of crf_init, coalesced over the pixels.
+template <int CT>
+__global__ __launch_bounds__(kBlock) void crf_init_votes(const int64_t* __restrict__ clu, const float* __restrict__ table,
+                                                         int m, int ncls, int64_t n, const float* __restrict__ n2,
+                                                         float* __restrict__ logp, float* __restrict__ q,
+                                                         _Float16* __restrict__ op, int64_t* __restrict__ labels,
+                                                         int64_t* __restrict__ labels_before, float* __restrict__ prob) {
+  constexpr int kCpad = 32 * CT, kQuads = kCpad / 4;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const int s = clamped_segment(clu[i], m);
+  const float* row = table + (size_t)s * votes_row_floats(kCpad);
+  const float4v* row4 = reinterpret_cast<const float4v*>(row);
+  const float ni = n2[i];
+#pragma unroll
+  for (int g = 0; g < kQuads; g += 2) {
+    if (4 * g < ncls) {                                             // (uniform)
+      float4v lp[2], q0[2];
+#pragma unroll
+      for (int e = 0; e < 2; ++e) lp[e] = row4[g + e], q0[e] = row4[kQuads + g + e];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int c = 4 * g + j;
+        if (c < ncls) {
+          logp[(size_t)c * n + i] = lp[j / 4][j % 4];
+          q[(size_t)c * n + i] = q0[j / 4][j % 4];
+          store_operand(op, i, c, CT, ni * q0[j / 4][j % 4]);
+        }
+      }
+      if (prob != nullptr) {                                        // (uniform)
+        float4v v[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) v[e] = row4[2 * kQuads + g + e];
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (4 * g + j < ncls) prob[(size_t)(4 * g + j) * n + i] = v[j / 4][j % 4];
+      }
+    }
+  }
+  const int* lab = reinterpret_cast<const int*>(row + 3 * kCpad);
+  if (labels_before != nullptr) labels_before[i] = lab[0];
+  if (labels != nullptr) labels[i] = lab[1];
+}
+
 // wave = 32 pixels i (the columns of every pair tile), all tiles of j.  kNorm: the A operand is a row of ones over the
 // valid j, the result K_2 1 becomes n_2.  Otherwise the mean-field update of the wave's pixels (see the head of the file).
 template <int CT, bool kNorm>
@@ -436,6 +539,18 @@ __global__ __launch_bounds__(kBlock) void crf_pairs(const CrfHeader* __restrict_
 }
 
 inline bool good_std(float s) { return isfinite(s) && s > 0.f; }
+
+// bytes of the segment table, 0 outside the limits
+inline size_t votes_table_bytes(int m, int ncls) {
+  if (m < 1 || m > kMaxVoteSegments || ncls < 1 || ncls > kMaxClasses) return 0;
+  return (size_t)m * votes_row_floats(ncls <= 32 ? 32 : 64) * sizeof(float);
+}
+
+// (a null pointer overlaps nothing)
+inline bool overlap(const void* p, size_t pn, const void* q, size_t qn) {
+  const uintptr_t p0 = (uintptr_t)p, q0 = (uintptr_t)q;
+  return p != nullptr && q != nullptr && p0 < q0 + qn && q0 < p0 + pn;
+}
 
 }  // namespace
 }  // namespace spml
@@ -583,5 +698,44 @@ extern "C" int spml_dense_crf_infer_upsampled_f32(const float* lowres, int ncls,
                       else
                         hipLaunchKernelGGL(crf_init_upsampled<2>, dim3(px_blocks), dim3(kBlock), 0, s, lowres, ncls, oh, ow,
                                            h, w, scale_h, scale_w, n2, logp, q0, op0, labels0, labels_before, prob_up);
+                    });
+}
+
+extern "C" size_t spml_dense_crf_votes_workspace_bytes(int m, int ncls) { return votes_table_bytes(m, ncls); }
+
+extern "C" int spml_dense_crf_infer_votes_f32(const int64_t* clu, const int64_t* topk, int m, int k, int ncls, int h,
+                                              int w, int iter_max, float pos_w, float bi_w, float* q, int64_t* labels,
+                                              int64_t* labels_before, float* prob, void* table_ws,
+                                              size_t table_ws_bytes, void* ws, size_t ws_bytes, void* stream) {
+  if (!topk || m < 1 || k < 1 || ((uintptr_t)clu & 7) != 0 || ((uintptr_t)topk & 7) != 0 ||
+      ((uintptr_t)labels_before & 7) != 0 || ((uintptr_t)prob & 3) != 0)
+    return SPML_ERR_INVALID_ARG;
+  Layout l;
+  const int status = infer_status(clu, ncls, h, w, iter_max, pos_w, bi_w, q, labels, ws, ws_bytes, l);
+  if (status != SPML_OK) return status;
+  if (m > kMaxVoteSegments) return SPML_ERR_UNSUPPORTED;
+  const size_t need = votes_table_bytes(m, ncls);
+  if (!table_ws || table_ws_bytes < need || ((uintptr_t)table_ws & 15) != 0) return SPML_ERR_WORKSPACE;
+  // the table is written before anything reads it: it may alias no input, no output and not the CRF's workspace
+  const size_t px = (size_t)l.n * sizeof(int64_t);
+  if (overlap(table_ws, need, clu, px) || overlap(table_ws, need, topk, (size_t)m * k * sizeof(int64_t)) ||
+      overlap(table_ws, need, q, l.map_bytes) || overlap(table_ws, need, labels, px) ||
+      overlap(table_ws, need, labels_before, px) || overlap(table_ws, need, prob, l.map_bytes) ||
+      overlap(table_ws, need, ws, l.total))
+    return SPML_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  float* table = static_cast<float*>(table_ws);
+  hipLaunchKernelGGL(crf_votes_table, dim3((unsigned)m), dim3(kWave), 0, s, topk, k, ncls, l.cpad, table);
+  const unsigned px_blocks = (unsigned)((l.n + kBlock - 1) / kBlock);
+  return mean_field(l, static_cast<char*>(ws), ncls, h, w, iter_max, pos_w, bi_w, q, labels, s,
+                    [&](const float* n2, float* logp, float* q0, _Float16* op0, int64_t* labels0) {
+                      if (l.ct == 1)
+                        hipLaunchKernelGGL(crf_init_votes<1>, dim3(px_blocks), dim3(kBlock), 0, s, clu,
+                                           (const float*)table, m, ncls, l.n, n2, logp, q0, op0, labels0, labels_before,
+                                           prob);
+                      else
+                        hipLaunchKernelGGL(crf_init_votes<2>, dim3(px_blocks), dim3(kBlock), 0, s, clu,
+                                           (const float*)table, m, ncls, l.n, n2, logp, q0, op0, labels0, labels_before,
+                                           prob);
                     });
 }

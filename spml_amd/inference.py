@@ -192,6 +192,18 @@ def drop_ignored_memory(prototypes, prototype_labels, semantic_ignore_index=255)
   return prototypes.index_select(0, keep), prototype_labels.index_select(0, keep)
 
 
+def _clustered_full_resolution(embedding_model, image, valid_hw, crop_size, stride, semantic_ignore_index):
+  """The embedding and clustering steps `predict_full_resolution` and `predict_knn_full_resolution_crf` share
+  (`inference.py:145-220` = `inference_crf.py:145-229`): the sliding-window embedding of the padded `image` and the
+  k-means over it with the padding outside the top-left `valid_hw` region ignored -> the dict the prediction model reads
+  (`embedding` plus what `generate_clusters` returns)."""
+  fake = _padding_ignored_labels(image.shape[-2:], valid_hw, semantic_ignore_index, image.device)
+  embeddings = {'embedding': embed_full_resolution(embedding_model, image, crop_size, stride)}
+  with torch.no_grad():
+    embeddings.update(embedding_model.generate_clusters(embeddings['embedding'], fake, fake))
+  return embeddings
+
+
 def predict_full_resolution(embedding_model, prediction_model, image, valid_hw, crop_size, stride,
                             memory_prototypes, memory_prototype_labels, semantic_ignore_index=255):
   """One image of the kNN label inference (`pyscripts/inference/inference.py:145-237`), the composition
@@ -203,10 +215,8 @@ def predict_full_resolution(embedding_model, prediction_model, image, valid_hw, 
   (what :231-237 turns into the label image), `semantic_score` (the retrieved labels, `[h*w,20]`)
   and `cluster_index` `[h*w]`."""
   h, w = valid_hw
-  fake = _padding_ignored_labels(image.shape[-2:], valid_hw, semantic_ignore_index, image.device)
-  embeddings = {'embedding': embed_full_resolution(embedding_model, image, crop_size, stride)}
+  embeddings = _clustered_full_resolution(embedding_model, image, valid_hw, crop_size, stride, semantic_ignore_index)
   with torch.no_grad():
-    embeddings.update(embedding_model.generate_clusters(embeddings['embedding'], fake, fake))
     outputs = prediction_model(
         embeddings,
         {'semantic_memory_prototype': memory_prototypes,
@@ -631,6 +641,75 @@ def pseudo_labels_softmax_crf(embedding_model, prediction_model, views, image_hw
   out.update(random_walk_crf_refine(image_u8, cam_rw, crf))
   if return_transition:
     out['transition'] = trans
+  return out
+
+
+HIP_SEGMENT_VOTES_PATH = 'hip_segment_votes'
+FRAMEWORK_SEGMENT_VOTES_PATH = 'framework_segment_votes'
+
+
+def framework_segment_votes(clu, topk, ncls, hw):
+  """The CRF input of the kNN program as the reference's own ops on the tensors' device (`inference_crf.py:240-245`):
+  gather the retrieved labels per pixel (`topk[clu]`, `[h * w, k]`), one-hot over the classes, sum over the k retrievals,
+  divide by k, `[h, w, C]` -> `[C, h, w]` fp32.  What the fused call gathers from a per-segment table; the route of
+  `knn_votes_crf_refine` outside the kernel's limits and the yardstick of tools/bench_knn_crf.py.  As in the reference,
+  a label outside `[0, ncls)` is an error.  (The divisor is a 0-dim tensor, not a Python number: by a number ATen's GPU
+  kernel multiplies with the reciprocal instead, and count / k is what the reference's values mean.)"""
+  h, w = hw
+  score = topk[clu.reshape(-1)]                                                          # [h * w, k]
+  votes = common_utils.one_hot(score, max_label=int(ncls)).sum(dim=1).float()            # :240-242
+  votes = votes / torch.full((), float(score.shape[1]), dtype=torch.float32, device=votes.device)
+  return votes.view(h, w, -1).permute(2, 0, 1).contiguous()                               # :243-245
+
+
+def knn_votes_crf_refine(image_u8, cluster_index, segment_topk, num_classes, crf):
+  """The tail of the kNN program with the denseCRF (`inference_crf.py:237-257`): `cluster_index` int64 `[h * w]` (or
+  `[h, w]`), the dense segment id of every pixel of `image_u8` uint8 `[h,w,3]`, and `segment_topk` int64 `[m, k]`, the
+  labels retrieved per segment (`Segsort.segment_predictions`), through `crf` (`spml_amd.models.crf.DenseCRF`).  One
+  fused call (`spml_dense_crf_infer_votes_f32`): votes, log p, Q_0 and both labels are formed once per
+  segment and gathered inside the CRF's first kernel; with more than 4096 segments the vote map is formed by
+  `framework_segment_votes` and goes through `crf.refine`, and `votes_path` names which of the two ran.  Returns
+  `semantic_prob` `[ncls,h,w]` (the refined marginals), `semantic_prediction` `[h,w]` int64 (their arg-max),
+  `semantic_prediction_before_crf` `[h,w]` int64 (the arg-max of the votes, lowest class on ties), `crf_path` and
+  `votes_path`."""
+  if not all(torch.is_tensor(t) and t.is_cuda for t in (image_u8, cluster_index, segment_topk)):
+    raise _ffi.SpmlHipError('the HIP path needs GPU tensors (the dense CRF has no CPU fallback)')
+  h, w = int(image_u8.shape[0]), int(image_u8.shape[1])
+  ncls = int(num_classes)
+  if segment_topk.shape[0] <= _ffi.MAX_DENSE_CRF_VOTE_SEGMENTS:
+    prob, prediction, before = crf.refine_votes(image_u8, cluster_index, segment_topk, ncls)
+    votes_path = HIP_SEGMENT_VOTES_PATH
+  else:
+    with torch.no_grad():
+      votes = framework_segment_votes(cluster_index, segment_topk, ncls, (h, w))
+      before = torch.argmax(votes, dim=0)
+    prob, prediction = crf.refine(image_u8, votes)
+    votes_path = FRAMEWORK_SEGMENT_VOTES_PATH
+  return {'semantic_prob': prob, 'semantic_prediction': prediction, 'semantic_prediction_before_crf': before,
+          'crf_path': crf.path_name(h, w, ncls), 'votes_path': votes_path}
+
+
+def predict_knn_full_resolution_crf(embedding_model, prediction_model, image, valid_hw, crop_size, stride,
+                                    memory_prototypes, memory_prototype_labels, num_classes, image_u8, crf,
+                                    semantic_ignore_index=255):
+  """One image of the kNN label inference with the denseCRF (`pyscripts/inference/inference_crf.py:145-257`): the
+  embedding and clustering steps of `predict_full_resolution` (:145-229, one shared helper), then
+  `Segsort.segment_predictions` against the memory bank -- `[m, 20]` labels per segment and one segment id per pixel in
+  the place of the per-pixel gather of :232-237 -- and `knn_votes_crf_refine` on `image_u8` (uint8 `[h,w,3]`,
+  `denormalized_uint8` of the un-padded image: :247-252) with `crf`.  Returns the fields of `knn_votes_crf_refine` plus
+  `cluster_index` `[h * w]` (dense segment ids) and `segment_topk` `[m, 20]`: `segment_topk[cluster_index]` is
+  `predict_full_resolution`'s `semantic_score`."""
+  if tuple(image_u8.shape[:2]) != tuple(valid_hw):
+    raise ValueError('predict_knn_full_resolution_crf: image_u8 must be the un-padded image [h,w,3]')
+  embeddings = _clustered_full_resolution(embedding_model, image, valid_hw, crop_size, stride, semantic_ignore_index)
+  with torch.no_grad():
+    topk, clu = prediction_model.segment_predictions(
+        embeddings, {'semantic_memory_prototype': memory_prototypes,
+                     'semantic_memory_prototype_label': memory_prototype_labels})
+  if topk is None:
+    raise ValueError('predict_knn_full_resolution_crf needs a memory bank and a clustering')
+  out = knn_votes_crf_refine(image_u8, clu, topk.contiguous(), num_classes, crf)
+  out.update(cluster_index=clu, segment_topk=topk)
   return out
 
 

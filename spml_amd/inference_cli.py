@@ -1,4 +1,4 @@
-"""Shared body of the thirteen inference programs under `pyscripts/inference/`: the reference's command line and config
+"""Shared body of the sixteen inference programs under `pyscripts/inference/`: the reference's command line and config
 surface (`parse_args`), the argument guards, snapshot loading, the seeded synthetic images that stand in for the
 file-list loader (outside this repository, DESIGN 9: `--data_list synthetic`), the self-built memory bank of the kNN
 programs, the timed loop over the images and the JSON line.  A program's `main` holds what is specific to its recipe:
@@ -259,6 +259,24 @@ class CrfStage(object):
     end.record()
     self.events.append((start, end))
     return out
+
+  def _timed(self, call, *args):
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    out = call(*args)
+    end.record()
+    self.events.append((start, end))
+    return out
+
+  def refine_votes(self, image_u8, clu, topk, ncls):
+    """The fused call of the kNN program (`DenseCRF.refine_votes`: the vote map is gathered from a per-segment table
+    inside the CRF's first kernel) between the same device events, so that the stage stands in for its `DenseCRF` as the
+    `crf` of `inference.knn_votes_crf_refine` and `predict_knn_full_resolution_crf`; `refine` is the route of that
+    function outside the kernel's limits."""
+    return self._timed(self.crf.refine_votes, image_u8, clu, topk, ncls)
+
+  def refine(self, image_u8, prob):
+    return self._timed(self.crf.refine, image_u8, prob)
 
   def path_name(self, h, w, ncls):
     self.path = self.crf.path_name(h, w, ncls)

@@ -74,6 +74,33 @@ class DenseCRF(object):
       ws = self.prepare(image.contiguous(), lowres.shape[0])
       return self.infer_upsampled(ws, lowres.float().contiguous(), tuple(image.shape[:2]))[:3]
 
+  def infer_votes(self, ws, clu, topk, ncls, image_hw, want_labels=True, want_labels_before=True, want_prob=False,
+                  iter_max=None, pos_w=None, bi_w=None):
+    """`infer` on the vote map of the kNN label inference (inference_crf.py:240-245): `clu` int64 `[h * w]` dense segment
+    ids, `topk` int64 `[m, k]` retrieved labels per segment; the map `one_hot(topk[clu]).sum(1) / k` is gathered from a
+    per-segment table inside the first kernel -> (Q `[C, h, w]`, its arg-max `[h, w]` or None, the arg-max of
+    the votes -- the label before the CRF -- or None, the vote map `[C, h, w]` or None)."""
+    if not (torch.is_tensor(clu) and torch.is_tensor(topk) and clu.is_cuda and topk.is_cuda):
+      raise _ffi.SpmlHipError('the HIP path needs GPU tensors (the dense CRF has no CPU fallback)')
+    return _ffi.dense_crf_infer_votes(clu, topk, ncls, image_hw, self.iter_max if iter_max is None else iter_max,
+                                      self.pos_w if pos_w is None else pos_w, self.bi_w if bi_w is None else bi_w, ws,
+                                      want_labels, want_labels_before, want_prob)
+
+  def refine_votes(self, image, clu, topk, ncls):
+    """`refine` of the kNN program (inference_crf.py:237-257): the image `[h, w, 3]` uint8, one dense segment id per pixel
+    (`[h * w]` or `[h, w]` int64; a strided view, such as the crop of a padded map, is copied) and the retrieved labels
+    `[m, k]` int64, device tensors -> (Q `[C, h, w]` fp32, its arg-max `[h, w]` int64, the arg-max of the votes `[h, w]`
+    int64)."""
+    if not all(torch.is_tensor(t) and t.is_cuda for t in (image, clu, topk)):
+      raise _ffi.SpmlHipError('the HIP path needs GPU tensors (the dense CRF has no CPU fallback)')
+    if image.dim() != 3 or image.shape[2] != 3 or topk.dim() != 2 or clu.numel() != image.shape[0] * image.shape[1]:
+      raise ValueError('DenseCRF expects an image [h, w, 3], one segment id per pixel and labels [m, k]')
+    if image.dtype != torch.uint8:
+      raise ValueError('DenseCRF expects a uint8 image')
+    with torch.no_grad():
+      ws = self.prepare(image.contiguous(), ncls)
+      return self.infer_votes(ws, clu.long().contiguous(), topk.long().contiguous(), ncls, tuple(image.shape[:2]))[:3]
+
   def __call__(self, image, probmap):
     """numpy arrays (HWC uint8, CHW float32) -> numpy CHW float32 through the GPU, as the reference; device tensors ->
     a device tensor.  Without a GPU, or for CPU tensors, `SpmlHipError`."""
