@@ -49,7 +49,7 @@ const char* spml_status_string(int status);
  * 7: the multi-scale inference entry point (spml_view_probs_accumulate_f32);
  * 8: spml_upsample_ce_bwd_path_name (entry points added since leave every earlier signature and flag as it was and
  *    keep the version: spml_view_votes_*, spml_segsort_nll_batched_*, spml_segment_majority_*, spml_tag_normalize_*,
- *    spml_dense_crf_*). */
+ *    spml_dense_crf_*, spml_segment_tag_cam_*). */
 #define SPML_ABI_VERSION 8
 int spml_abi_version(void);
 
@@ -1083,6 +1083,44 @@ int spml_dense_crf_infer_votes_f32(const int64_t* clu, const int64_t* topk, int 
                                    int64_t* labels_before, float* prob, void* table_ws, size_t table_ws_bytes, void* ws,
                                    size_t ws_bytes, void* stream);
 const char* spml_dense_crf_path_name(int h, int w, int ncls, float pos_xy_std);
+
+/* ------------------------------------------------------------------------
+ * DensePose pseudo labels: class maps from propagated segment tags (csrc/segment_cam.hip)
+ * replaces: pyscripts/inference/pseudo_denseposerw_crf.py:159-182 (one-hot of the nearest labelled prototype's label
+ *           [N, ncls + 1], `segment_mean` by the segment id -- two scatter-adds --, the division of every row by its sum,
+ *           `index_select` back to the pixels, transpose, `F.interpolate(mode='bilinear')` to 1/8 of the image).
+ *
+ *   class(p)     = proto_label[nn_index[p]], none where nn_value[p] < threshold or the label is outside [0, ncls)
+ *   counts[s][c] = #{ p < N : cluster_index[p] = s, class(p) = c }            N = h2 * w2
+ *   probs[s][c]  = counts[s][c] / sum_c counts[s][c]                          0 for a row without a counted pixel
+ *   acc[c][y][x] = bilinear_{(h2, w2) -> (oh, ow)}( probs[cluster_index[.]][c] )
+ *
+ * nn_index int64 [N], nn_value fp32 [N]: the nearest labelled prototype of every pixel of the h2 x w2 map and its
+ * similarity (spml_topk_affinity_f32 with k = 1); proto_label int64 [M]; threshold: a number (the program passes -1; NaN
+ * is SPML_ERR_INVALID_ARG; a NaN nn_value is not below it and counts).  cluster_index int64 [h2][w2]: the dense segment
+ * id of every pixel, 0 <= id < S.  A pixel whose nn_index is outside [0, M), whose segment id is outside [0, S) or that has
+ * no class counts nowhere, and a bilinear tap on a segment id outside [0, S) contributes 0: no kernel forms an address
+ * from such a value.  A row without a counted pixel (an empty segment id, a segment without a tagged pixel: the reference
+ * has 0 / 0 there) is written as ncls zeros like any other row; nothing outside the table or the maps is read for it.
+ * probs is one correctly rounded fp32 division of two exact integers (the reference divides segment_mean's row, itself
+ * count / pixels of the segment, by its fp32 sum: the same quotient rounded three times).  Bilinear taps as ATen forms
+ * them (align_corners = False; scale = (float)h2 / (float)oh), combined as h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 +
+ * w1 * v11); the h2 x w2 map of rows is not formed.
+ * acc: fp32 [ncls][oh][ow], overwritten.  counts: int32 [S][ncls] or NULL; probs: fp32 [S][ncls] or NULL (handed out
+ * for tests; they do not change acc).  ws: 4-byte aligned, at least spml_segment_tag_cam_workspace_bytes(S, ncls) bytes
+ * (that call returns 0 outside the limits), else SPML_ERR_WORKSPACE; the call zeroes what it needs zeroed on `stream`
+ * itself.  Counts meet through 32-bit integer atomics only: every output is bit-identical from call to call, with and
+ * without the deterministic mode.  No host read, four stream operations (memset, count, probs, gather).  ws, acc, counts
+ * and probs may alias neither an input nor each other (SPML_ERR_INVALID_ARG, as for a null pointer or M, S, ncls or a
+ * side below 1); S <= 4096, ncls <= 64, N < 2^31 and oh * ow <= 2^24, else SPML_ERR_UNSUPPORTED.
+ * spml_segment_tag_cam_path_name (host only): which count kernel a shape takes -- "lds_table" (S * ncls <= 8192: a
+ * per-workgroup LDS table flushed once) or "global_table" (global atomics), "unsupported" outside the limits, "invalid"
+ * for a size below the domain. */
+size_t spml_segment_tag_cam_workspace_bytes(int S, int ncls);
+int spml_segment_tag_cam_f32(const int64_t* nn_index, const float* nn_value, const int64_t* proto_label, int64_t M,
+                             float threshold, const int64_t* cluster_index, int S, int ncls, int h2, int w2, int oh,
+                             int ow, float* acc, int* counts, float* probs, void* ws, size_t ws_bytes, void* stream);
+const char* spml_segment_tag_cam_path_name(int64_t N, int S, int ncls);
 
 #ifdef __cplusplus
 }

@@ -167,6 +167,10 @@ _SIGNATURES = {
     'spml_dense_crf_infer_votes_f32': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, _P, _P,
                                                _P, _P, _P, c_size_t, _P, c_size_t, _P]),
     'spml_dense_crf_path_name': (c_char_p, [c_int, c_int, c_int, c_float]),
+    'spml_segment_tag_cam_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'spml_segment_tag_cam_f32': (c_int, [_P, _P, _P, c_int64, c_float, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P,
+                                         _P, _P, c_size_t, _P]),
+    'spml_segment_tag_cam_path_name': (c_char_p, [c_int64, c_int, c_int]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -1600,3 +1604,61 @@ def dense_crf_infer_votes(clu, topk, ncls, image_hw, iter_max, pos_w, bi_w, ws, 
                                              ws.numel(), stream_ptr()),
         'spml_dense_crf_infer_votes_f32')
   return q, labels, before, prob
+
+
+# ---------------------------------------------------------------------------
+# DensePose pseudo labels: class maps from propagated segment tags (csrc/segment_cam.hip)
+MAX_SEGMENT_TAG_CAM_CLASSES = 64       # the limits of spml_segment_tag_cam_f32 (include/spml_hip.h)
+MAX_SEGMENT_TAG_CAM_SEGMENTS = 4096
+
+
+def segment_tag_cam_path_name(n, s, ncls):
+  """Count kernel a call with these sizes takes (a pure function of the library): 'lds_table', 'global_table' or, outside
+  the limits, 'unsupported'."""
+  return lib().spml_segment_tag_cam_path_name(int(n), int(s), int(ncls)).decode()
+
+
+def segment_tag_cam(nn_index, nn_value, proto_label, threshold, cluster_index, num_segments, ncls, half_hw, out_hw,
+                    want_tables=False):
+  """acc fp32 `[ncls, oh, ow]`: pseudo_denseposerw_crf.py:159-182 on `nn_index` int64 / `nn_value` fp32 `[N]` (what
+  `topk_affinity(k = 1)` returns per pixel of the `half_hw` map, any shape with N = h2 * w2 entries), `proto_label` int64
+  `[M]` and `cluster_index` int64 `[N]` (dense segment ids in `[0, num_segments)`): a pixel's class is
+  `proto_label[nn_index]` (none where `nn_value < threshold` or the label is outside `[0, ncls)`), the classes are counted
+  per segment, every row divided by its sum (zeros for a row without a count), and the map of rows `probs[cluster_index]`
+  resampled bilinearly from `half_hw` to `out_hw`.  An index or id outside its range counts nowhere.  All tensors on the
+  GPU (made contiguous here); no host read.  want_tables: -> (acc, counts int32 `[S, ncls]`, probs fp32 `[S, ncls]`)."""
+  (h2, w2), (oh, ow) = (int(v) for v in half_hw), (int(v) for v in out_hw)
+  s, ncls = int(num_segments), int(ncls)
+  tensors = (('nn_index', nn_index, torch.int64), ('nn_value', nn_value, torch.float32),
+             ('proto_label', proto_label, torch.int64), ('cluster_index', cluster_index, torch.int64))
+  for name, t, dtype in tensors:
+    if not torch.is_tensor(t) or not t.is_cuda:
+      raise SpmlHipError('segment_tag_cam: the HIP path needs GPU tensors (%s on %s); there is no CPU fallback'
+                         % (name, getattr(t, 'device', type(t).__name__)))
+    if t.dtype != dtype:
+      raise SpmlHipError('segment_tag_cam: %s must be %s (got %s)' % (name, dtype, t.dtype))
+  if h2 < 1 or w2 < 1 or oh < 1 or ow < 1:
+    raise SpmlHipError('segment_tag_cam: the maps need at least one pixel (got %r -> %r)' % ((h2, w2), (oh, ow)))
+  n = h2 * w2
+  for name, t, _ in tensors:
+    if name != 'proto_label' and t.numel() != n:
+      raise SpmlHipError('segment_tag_cam: %s holds %d entries for a %d x %d map' % (name, t.numel(), h2, w2))
+  if proto_label.numel() < 1 or s < 1 or ncls < 1:
+    raise SpmlHipError('segment_tag_cam: needs at least one prototype, one segment and one class (got %d, %d, %d)'
+                       % (proto_label.numel(), s, ncls))
+  nbytes = lib().spml_segment_tag_cam_workspace_bytes(s, ncls)
+  if nbytes == 0:
+    raise SpmlHipError('segment_tag_cam: %d segments x %d classes are outside the kernel (at most %d x %d)'
+                       % (s, ncls, MAX_SEGMENT_TAG_CAM_SEGMENTS, MAX_SEGMENT_TAG_CAM_CLASSES))
+  nn_index, nn_value, proto_label, cluster_index = (t.reshape(-1).contiguous() for _, t, _ in tensors)
+  dev = cluster_index.device
+  acc = torch.empty((ncls, oh, ow), dtype=torch.float32, device=dev)
+  counts = torch.empty((s, ncls), dtype=torch.int32, device=dev) if want_tables else None
+  probs = torch.empty((s, ncls), dtype=torch.float32, device=dev) if want_tables else None
+  ws = workspace(nbytes, dev)
+  check(lib().spml_segment_tag_cam_f32(ptr(nn_index, torch.int64), ptr(nn_value, torch.float32),
+                                       ptr(proto_label, torch.int64), proto_label.numel(), float(threshold),
+                                       ptr(cluster_index, torch.int64), s, ncls, h2, w2, oh, ow, ptr(acc),
+                                       ptr(counts, torch.int32, True), ptr(probs, torch.float32, True), ptr(ws),
+                                       ws.numel(), stream_ptr()), 'spml_segment_tag_cam_f32')
+  return (acc, counts, probs) if want_tables else acc

@@ -7,93 +7,52 @@
 //   count_lds / count_global   clu [P], sem [P] -> table [m][ncls] (uint32)   table[s][c] = #{p : clu[p] = s, sem[p] = c}
 //   row_argmax                 table -> major [m] (int64), and hist [m][ncls] (int64) when asked for
 //
-// A workgroup owns a contiguous run of pixels (segments are spatially coherent: a run touches few bins).  Where the
-// table fits kLdsEntries it is counted in LDS (ds_add_u32) and flushed once per workgroup, skipping the bins that
-// stayed zero; otherwise the adds go to the global table directly (m = 144 segments x 256 classes = 147 KiB: the
-// case of a label map that holds the ignore value 255).  kLdsEntries = 8192 (32 KiB): five workgroups of a CU keep
-// their tables in its 160 KiB of LDS at once, and zeroing plus scanning the table (32 entries per thread) stays in
-// proportion to the 8 pixels a thread counts.
+// The counting body (a contiguous run of pixels per workgroup, an LDS table where m * ncls fits 8192 entries and the
+// global one where it does not -- m = 144 segments x 256 classes = 147 KiB: the case of a label map that holds the ignore
+// value 255 --, equal keys merged inside a wave before the atomic) is segment_count.hpp, shared with segment_cam.hip.
 // Only integer atomics: integer adds commute, so the result does not depend on the arrival order -- two calls are
 // bit-identical, with or without the deterministic mode.  Counters are 32 bits wide: P < 2^31 bounds every bin.
 // A pixel whose id is outside [0, m) or whose label is outside [0, ncls) counts nowhere and forms no address.
-//
-// Equal keys are merged inside a wave before the atomic: segments are spatially coherent, so the 64 lanes of a wave
-// mostly hit one or two bins; groups of equal keys are peeled off the wave (ballot, shuffle of the first pending lane's
-// key, one add of the group's size by that lane).  SPML_MAJORITY_WAVE_COMBINE=0 compiles the plain form (one atomic per
-// counted pixel); tools/bench_prototype_msc.py times the two: on the global table the merged form takes 0.46 - 0.83 x
-// the plain form's time, on the LDS table 0.88 - 1.02 x (profiles/prototype_msc.md).
+// SPML_MAJORITY_WAVE_COMBINE=0 compiles the plain form (one atomic per counted pixel); tools/bench_prototype_msc.py times
+// the two: on the global table the merged form takes 0.46 - 0.83 x the plain form's time, on the LDS table 0.88 - 1.02 x
+// (profiles/prototype_msc.md).
 #include "common.hpp"
-
-#ifndef SPML_MAJORITY_WAVE_COMBINE
-#define SPML_MAJORITY_WAVE_COMBINE 1
-#endif
+#include "segment_count.hpp"
 
 namespace spml {
 namespace {
 
+using segcount::kBlock;
+using segcount::kLdsEntries;
+using segcount::overlap;
+
 constexpr int kMaxSegments = 4096;
 constexpr int kMaxClasses = 256;
-constexpr int kLdsEntries = 8192;          // 32 KiB of uint32 counters per workgroup
-constexpr int kBlock = 256;
-constexpr int kPixelsPerThread = 8;
-constexpr int kMaxBlocks = 2048;
 
 // the bin of pixel p, or -1 when the pixel counts nowhere
-__device__ __forceinline__ int bin_of(const int64_t* __restrict__ clu, const int64_t* __restrict__ sem, int64_t p,
-                                      int64_t end, int m, int ncls) {
-  if (p >= end) return -1;
-  const int64_t s = clu[p], c = sem[p];
-  if (s < 0 || s >= (int64_t)m || c < 0 || c >= (int64_t)ncls) return -1;
-  return (int)s * ncls + (int)c;            // < 4096 * 256
-}
-
-// one count per lane with key >= 0.  Every lane of the wave calls this (the loop bounds of the callers are
-// wave-uniform), so the ballots see the whole wave.
-__device__ __forceinline__ void add_one(unsigned* table, int key) {
-#if SPML_MAJORITY_WAVE_COMBINE
-  const int lane = threadIdx.x & (kWave - 1);
-  bool pending = key >= 0;
-  for (;;) {
-    const unsigned long long todo = __ballot(pending);
-    if (todo == 0) break;
-    const int leader = __ffsll((long long)todo) - 1;
-    const int lead_key = __shfl(key, leader, kWave);
-    const bool mine = pending && key == lead_key;
-    const unsigned long long group = __ballot(mine);
-    if (lane == leader) atomicAdd(table + lead_key, (unsigned)__popcll(group));
-    if (mine) pending = false;
+struct LabelBin {
+  const int64_t* __restrict__ clu;
+  const int64_t* __restrict__ sem;
+  int m, ncls;
+  __device__ __forceinline__ int operator()(int64_t p, int64_t end) const {
+    if (p >= end) return -1;
+    const int64_t s = clu[p], c = sem[p];
+    if (s < 0 || s >= (int64_t)m || c < 0 || c >= (int64_t)ncls) return -1;
+    return (int)s * ncls + (int)c;            // < 4096 * 256
   }
-#else
-  if (key >= 0) atomicAdd(table + key, 1u);
-#endif
-}
+};
 
-// workgroup b counts the pixels [b * chunk, min(P, (b + 1) * chunk)); chunk is a multiple of kBlock
 __global__ __launch_bounds__(kBlock) void count_lds(const int64_t* __restrict__ clu, const int64_t* __restrict__ sem,
                                                     int64_t P, int64_t chunk, int m, int ncls,
                                                     unsigned* __restrict__ table) {
   __shared__ unsigned local[kLdsEntries];
-  const int entries = m * ncls;
-  for (int e = threadIdx.x; e < entries; e += kBlock) local[e] = 0u;
-  __syncthreads();
-  const int64_t begin = (int64_t)blockIdx.x * chunk;
-  const int64_t end = begin + chunk < P ? begin + chunk : P;
-  for (int64_t base = begin; base < end; base += kBlock)
-    add_one(local, bin_of(clu, sem, base + threadIdx.x, end, m, ncls));
-  __syncthreads();
-  for (int e = threadIdx.x; e < entries; e += kBlock) {
-    const unsigned v = local[e];
-    if (v != 0u) atomicAdd(table + e, v);
-  }
+  segcount::count_lds(LabelBin{clu, sem, m, ncls}, P, chunk, m * ncls, local, table);
 }
 
 __global__ __launch_bounds__(kBlock) void count_global(const int64_t* __restrict__ clu,
                                                        const int64_t* __restrict__ sem, int64_t P, int64_t chunk,
                                                        int m, int ncls, unsigned* __restrict__ table) {
-  const int64_t begin = (int64_t)blockIdx.x * chunk;
-  const int64_t end = begin + chunk < P ? begin + chunk : P;
-  for (int64_t base = begin; base < end; base += kBlock)
-    add_one(table, bin_of(clu, sem, base + threadIdx.x, end, m, ncls));
+  segcount::count_global(LabelBin{clu, sem, m, ncls}, P, chunk, table);
 }
 
 // wave = segment s: the lanes stride over the classes, each keeps its best (count, class) -- a later class replaces an
@@ -123,11 +82,6 @@ __global__ __launch_bounds__(kBlock) void row_argmax(const unsigned* __restrict_
 
 inline bool supported(int64_t P, int m, int ncls) {
   return m <= kMaxSegments && ncls <= kMaxClasses && P < ((int64_t)1 << 31);
-}
-
-inline bool overlap(const void* p, size_t pn, const void* q, size_t qn) {
-  const uintptr_t p0 = (uintptr_t)p, q0 = (uintptr_t)q;
-  return pn != 0 && qn != 0 && p0 < q0 + qn && q0 < p0 + pn;
 }
 
 }  // namespace
@@ -173,14 +127,12 @@ extern "C" int spml_segment_majority_i64(const int64_t* clu, const int64_t* sem,
   unsigned* table = static_cast<unsigned*>(ws);
   if (hipMemsetAsync(table, 0, need, s) != hipSuccess) return SPML_ERR_LAUNCH;
   if (P > 0) {
-    int64_t blocks = (P + (int64_t)kBlock * kPixelsPerThread - 1) / ((int64_t)kBlock * kPixelsPerThread);
-    if (blocks > kMaxBlocks) blocks = kMaxBlocks;
-    const int64_t chunk = ((P + blocks - 1) / blocks + kBlock - 1) / kBlock * kBlock;
-    blocks = (P + chunk - 1) / chunk;
+    const segcount::Chunks g = segcount::plan_chunks(P);
     if (entries <= kLdsEntries)
-      hipLaunchKernelGGL(count_lds, dim3((unsigned)blocks), dim3(kBlock), 0, s, clu, sem, P, chunk, m, ncls, table);
+      hipLaunchKernelGGL(count_lds, dim3((unsigned)g.blocks), dim3(kBlock), 0, s, clu, sem, P, g.chunk, m, ncls, table);
     else
-      hipLaunchKernelGGL(count_global, dim3((unsigned)blocks), dim3(kBlock), 0, s, clu, sem, P, chunk, m, ncls, table);
+      hipLaunchKernelGGL(count_global, dim3((unsigned)g.blocks), dim3(kBlock), 0, s, clu, sem, P, g.chunk, m, ncls,
+                         table);
   }
   const int rows_per_block = kBlock / kWave;
   hipLaunchKernelGGL(row_argmax, dim3((unsigned)((m + rows_per_block - 1) / rows_per_block)), dim3(kBlock), 0, s, table,

@@ -14,7 +14,7 @@ import torch
 import spml_amd.utils.general.common as common_utils
 import spml_amd.utils.segsort.common as segsort_common
 import spml_amd.utils.segsort.others as segsort_others
-from spml_amd import _ffi
+from spml_amd import _ffi, ops
 
 
 def sliding_window_ends(pad_size, crop_size, stride):
@@ -735,3 +735,144 @@ def downsampled_cam(cam_full):
   """`pseudo_camrw_crf.py:151-152`: `[ncls, h, w]` -> `[ncls, h//8, w//8]` by the framework's own
   `F.interpolate(scale_factor=1/8, mode='bilinear')` -- the same op, so its `scale_factor` semantics are kept."""
   return torch.nn.functional.interpolate(cam_full.unsqueeze(0), scale_factor=1 / 8., mode='bilinear').squeeze(0)
+
+
+HIP_SEGMENT_CAM_PATH = 'hip_segment_cam'
+FRAMEWORK_SEGMENT_CAM_PATH = 'framework_segment_cam'
+
+
+class NoLabelledPrototypeError(ValueError):
+  """`densepose_segment_cam` found no segment with a label below `num_classes`: the image has no tag to propagate."""
+
+
+def framework_densepose_segment_cam(nn_index, nn_value, proto_label, threshold, cluster_index, ncls, half_hw, out_hw):
+  """The class maps of the DensePose pseudo-label program before their normalisation, as the reference's own ops on the
+  tensors' device (`pseudo_denseposerw_crf.py:159-182`, with the body of
+  `gather_multiset_labels_per_batch_by_nearest_neighbor` for `top_k = 1` from the retrieval on): the label of every
+  pixel's nearest labelled prototype (`num_classes` where `nn_value < threshold`), one-hot over `ncls + 1` classes, `> 0`,
+  the first `ncls` columns, `segment_mean` by the segment id, every row divided by its sum, `index_select` back to the
+  pixels, `[h2, w2, ncls]` -> `[1, ncls, h2, w2]`, `F.interpolate(mode='bilinear')` to `out_hw` -> fp32 `[ncls, oh, ow]`.
+  What `_ffi.segment_tag_cam` computes from a per-segment table; the route of `densepose_segment_cam` outside the
+  kernel's limits and the yardstick of tools/bench_densepose_pseudo.py.  Two things are pinned where the reference is
+  undefined, as the kernel pins them: a label outside `[0, ncls)` is no class (the reference's one_hot fails above
+  `ncls`), and a row without a counted pixel is zeros (the reference has 0 / 0)."""
+  ncls = int(ncls)
+  (h2, w2), n = half_hw, nn_index.numel()
+  labs = proto_label.reshape(-1)[nn_index.reshape(-1)].view(n, 1)
+  labs = labs.masked_fill(nn_value.reshape(n, 1) < threshold, ncls)                      # models/utils.py:207-211
+  labs = labs.masked_fill((labs < 0) | (labs > ncls), ncls)
+  tags = (common_utils.one_hot(labs, ncls + 1).sum(dim=1) > 0).long()[:, :ncls]          # models/utils.py:217-221
+  clu = cluster_index.reshape(-1)
+  probs = common_utils.segment_mean(tags.float(), clu)                                   # :172-173
+  total = probs.sum(dim=1, keepdim=True)
+  probs = torch.where(total > 0, probs / total, torch.zeros_like(probs))                 # :174
+  pixel = torch.index_select(probs, 0, clu).view(1, h2, w2, -1).permute(0, 3, 1, 2).contiguous()      # :175-180
+  return torch.nn.functional.interpolate(pixel, size=tuple(out_hw), mode='bilinear')[0]  # :181-182
+
+
+def densepose_segment_cam(clustered, label_tags, half_hw, out_hw, num_classes, label_divisor,
+                          background_threshold=None):
+  """The class activation maps of the DensePose pseudo-label program from the clustering of the half-resolution map
+  (`pseudo_denseposerw_crf.py:153-190`).  `clustered`: what `generate_clusters` returns for that map (no pixel dropped:
+  N = h2 * w2 rows); `label_tags`: bool `[num_classes]` device tensor.
+
+  `prepare_prototype_labels` splits the segments by their semantic label and `calculate_prototypes_from_labels` forms
+  their prototypes (:153-158); `ops.topk_affinity(k = 1)` retrieves every pixel's nearest prototype among those with a
+  label below `num_classes` (:159-168: the masked retrieval of the training path, threshold -1, one image);
+  `spml_segment_tag_cam_f32` counts the retrieved labels per segment, divides every row by its sum and resamples the map
+  of rows bilinearly to `out_hw` (:169-182) -- above 64 classes or 4096 segments the same runs as framework ops
+  (`framework_densepose_segment_cam`) and `cam_path` names which of the two ran; `spml_cam_finalize_f32` divides every
+  class by its maximum, zeroes the classes the image does not carry and sets class 0 to `background_threshold` when one
+  is given (:183-190; one view, so its division by the view count is exact).  `label_divisor` is what the reference
+  passes to its retrieval, which does not read it.  Raises `NoLabelledPrototypeError` (a ValueError) when no prototype
+  carries a label below `num_classes` (the reference's maps are NaN everywhere then).  Returns `cam` fp32 `[num_classes, oh, ow]`, `cam_path`,
+  and what the new stage was fed: `nn_index`, `nn_value` `[N]`, `proto_label` `[S]`, `cluster_index` `[N]` (the
+  re-indexed segment ids) and `num_segments`."""
+  ncls = int(num_classes)
+  if not label_tags.is_cuda:
+    raise _ffi.SpmlHipError('the HIP path needs GPU tensors (label_tags on %s); there is no CPU fallback'
+                            % label_tags.device)
+  if label_tags.dim() != 1 or label_tags.shape[0] != ncls:
+    raise ValueError('densepose_segment_cam expects one tag per class')
+  sem, embs = clustered['cluster_semantic_label'], clustered['cluster_embedding']
+  (h2, w2) = half_hw
+  if sem.numel() != h2 * w2:
+    raise ValueError('densepose_segment_cam: %d clustered pixels for a %d x %d map (an ignored label drops pixels; map it '
+                     'to num_classes first)' % (sem.numel(), h2, w2))
+  with torch.no_grad():
+    proto_label, clu = segsort_common.prepare_prototype_labels(sem, clustered['cluster_index'], sem.max() + 1)
+    num_segments = int(proto_label.shape[0])
+    protos = segsort_common.calculate_prototypes_from_labels(embs, clu, num_segments)
+    valid = proto_label < ncls
+    if not bool(valid.any()):
+      raise NoLabelledPrototypeError('densepose_segment_cam: no prototype carries a label below num_classes = %d' % ncls)
+    groups = torch.zeros_like(sem), torch.zeros_like(proto_label)
+    nn_index, nn_value = ops.topk_affinity(embs, protos, 1, groups[0], groups[1], valid, masked_value=-2.0)
+    nn_index, nn_value = nn_index.view(-1), nn_value.view(-1)
+    if ncls <= _ffi.MAX_SEGMENT_TAG_CAM_CLASSES and num_segments <= _ffi.MAX_SEGMENT_TAG_CAM_SEGMENTS:
+      acc = _ffi.segment_tag_cam(nn_index, nn_value, proto_label, -1.0, clu, num_segments, ncls, half_hw, out_hw)
+      cam_path = HIP_SEGMENT_CAM_PATH
+    else:
+      acc = framework_densepose_segment_cam(nn_index, nn_value, proto_label, -1.0, clu, ncls, half_hw,
+                                            out_hw).contiguous()
+      cam_path = FRAMEWORK_SEGMENT_CAM_PATH
+    cam = _ffi.cam_finalize(acc, 1, label_tags, 'prob_mean', background_threshold)
+  return {'cam': cam, 'cam_path': cam_path, 'nn_index': nn_index, 'nn_value': nn_value, 'proto_label': proto_label,
+          'cluster_index': clu, 'num_segments': num_segments}
+
+
+def pseudo_labels_densepose_crf(embedding_model, image, valid_hw, semantic_label, instance_label, label_tags, image_u8,
+                                crf, walk_steps=6, background_threshold=None, scale=5.0, power=20):
+  """One image of the DensePose pseudo-label generation (`pyscripts/inference/pseudo_denseposerw_crf.py:112-222`): tags
+  propagated from the labelled points to the segments, a random walk over the pixel affinity, the denseCRF.  `image`:
+  the padded image `[1,3,Hp,Wp]`; `valid_hw`: the un-padded `(h, w)`; `semantic_label`, `instance_label`: int64 `[h,w]`
+  (255 = ignore, a value from `num_classes` up = unlabelled); `label_tags`: bool `[num_classes]` (`label_tags_from_map`);
+  `image_u8`: uint8 `[h,w,3]` (`denormalized_uint8` of the un-padded image); `crf`: `spml_amd.models.crf.DenseCRF`.
+
+  `generate_embeddings(..., resize_as_input=True)` (:128-129), `F.interpolate` to half the padded size, cropped to
+  `h//2 x w//2` (:130-135; framework ops, one pass); `spml_resample_unit_f32` to `h//8 x w//8` and
+  `spml_affinity_transition_f32` on that one view (:137-142, :193-195); `resize_labels` to the half map with 255 mapped to
+  `num_classes` so that no pixel is dropped (:121-123, :145-149); `generate_clusters` (:150-151);
+  `densepose_segment_cam` (:153-190); the walk's GEMMs (:196-201); `random_walk_crf_refine` (:203-218: the up-sampling
+  fused into the CRF's first kernel); the ignored pixels of the original label map set to 255 (:220-222).  Returns `cam`,
+  `cam_rw` `[ncls, h//8, w//8]`, `semantic_prob` `[ncls,h,w]`, `semantic_prediction` `[h,w]` int64 (refined, 255 where
+  ignored), `semantic_prediction_before_crf`, `crf_path`, `cam_path`, `cluster_index` `[h//2 * w//2]` and
+  `num_segments`."""
+  name = 'pseudo_labels_densepose_crf'
+  if image.dim() != 4 or image.shape[0] != 1:
+    raise ValueError(name + ' expects one image [1,3,Hp,Wp]')
+  h, w = valid_hw
+  if tuple(image_u8.shape[:2]) != (h, w) or tuple(semantic_label.shape) != (h, w) or \
+      tuple(instance_label.shape) != (h, w):
+    raise ValueError(name + ': image_u8 must be the un-padded image [h,w,3] and the labels [h,w]')
+  if h < 8 or w < 8:
+    raise ValueError(name + ': the image is smaller than 8 x 8')
+  if not image.is_cuda:
+    raise _ffi.SpmlHipError('the HIP path needs GPU tensors (the image on %s); there is no CPU fallback' % image.device)
+  pad_h, pad_w = image.shape[-2:]
+  half_hw, out_hw = (h // 2, w // 2), (h // 8, w // 8)
+  ncls = int(embedding_model.num_classes)
+  ignore = int(embedding_model.semantic_ignore_index)
+  with torch.no_grad():
+    if _is_channels_last(embedding_model):
+      image = image.contiguous(memory_format=torch.channels_last)
+    embs = embedding_model.generate_embeddings({'image': image}, resize_as_input=True)['embedding'].float()
+    embs = torch.nn.functional.interpolate(embs, size=(pad_h // 2, pad_w // 2), mode='bilinear')
+    embs = embs[:, :, :half_hw[0], :half_hw[1]].contiguous()
+    units = torch.empty((1, embs.shape[1], out_hw[0] * out_hw[1]), dtype=torch.float32, device=image.device)
+    _ffi.resample_unit(embs[0], half_hw, False, out_hw, units, 0)
+    trans = _ffi.affinity_transition(units, scale, power)
+    semantic_label = semantic_label.to(image.device).long()
+    kept = torch.where(semantic_label == ignore, torch.full_like(semantic_label, ncls), semantic_label)
+    s_lab = common_utils.resize_labels(kept.unsqueeze(0), half_hw)
+    i_lab = common_utils.resize_labels(instance_label.to(image.device).long().unsqueeze(0), half_hw)
+    clustered = embedding_model.generate_clusters(embs, s_lab, i_lab)
+  stage = densepose_segment_cam(clustered, label_tags, half_hw, out_hw, ncls, embedding_model.label_divisor,
+                                background_threshold)
+  with torch.no_grad():
+    cam_rw = _walk(trans, stage['cam'], walk_steps)
+  out = {'cam': stage['cam'], 'cam_rw': cam_rw, 'cam_path': stage['cam_path'], 'cluster_index': stage['cluster_index'],
+         'num_segments': stage['num_segments']}
+  out.update(random_walk_crf_refine(image_u8, cam_rw, crf))
+  out['semantic_prediction'] = out['semantic_prediction'].masked_fill(semantic_label == ignore, ignore)
+  return out

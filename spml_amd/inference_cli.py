@@ -1,4 +1,4 @@
-"""Shared body of the sixteen inference programs under `pyscripts/inference/`: the reference's command line and config
+"""Shared body of the seventeen inference programs under `pyscripts/inference/`: the reference's command line and config
 surface (`parse_args`), the argument guards, snapshot loading, the seeded synthetic images that stand in for the
 file-list loader (outside this repository, DESIGN 9: `--data_list synthetic`), the self-built memory bank of the kNN
 programs, the timed loop over the images and the JSON line.  A program's `main` holds what is specific to its recipe:
@@ -52,15 +52,24 @@ def geometry(config):
   return config.dataset.num_classes, crop_size, stride, size
 
 
-def load_models(config, args, device, head):
-  """The embedding network (channels-last, `eval()`) and, for `head` 'segsort' or 'softmax_classifier', the prediction
-  model, both from `model-{max_iteration-1}.pth` of the snapshot directory: `embedding_model` through the reference's name
+def embedding_makers(densepose=False):
+  """`backbone_types` -> constructor of the embedding network.  `densepose`: the PSPNet is the DensePose recipe's
+  (location + colour local features), as `pseudo_denseposerw_crf.py:21` imports it."""
+  from spml_amd.models.embeddings.resnet_deeplab import resnet_101_deeplab
+  if densepose:
+    from spml_amd.models.embeddings.resnet_pspnet_densepose import resnet_101_pspnet
+  else:
+    from spml_amd.models.embeddings.resnet_pspnet import resnet_101_pspnet
+  return {'panoptic_pspnet_101': resnet_101_pspnet, 'panoptic_deeplab_101': resnet_101_deeplab}
+
+
+def load_models(config, args, device, head, densepose=False):
+  """The embedding network (channels-last, `eval()`; `densepose`: see `embedding_makers`) and, for `head` 'segsort' or
+  'softmax_classifier', the prediction model, both from `model-{max_iteration-1}.pth` of the snapshot directory: `embedding_model` through the reference's name
   mapping (`resume=True`); a segsort head strictly; a classifier head non-strictly from the `semantic_classifier.*`
   entries -- a stage-1 `SegsortSoftmax` snapshot carries the same names next to entries that model does not have.
   -> (embedding_model, prediction_model or None, snapshot path)."""
-  from spml_amd.models.embeddings.resnet_deeplab import resnet_101_deeplab
-  from spml_amd.models.embeddings.resnet_pspnet import resnet_101_pspnet
-  makers = {'panoptic_pspnet_101': resnet_101_pspnet, 'panoptic_deeplab_101': resnet_101_deeplab}
+  makers = embedding_makers(densepose)
   if config.network.backbone_types not in makers:
     raise ValueError('Not support ' + str(config.network.backbone_types))
   if head == 'segsort' and config.network.prediction_types != 'segsort':

@@ -874,6 +874,130 @@ def gen_n11_instance(ref, out):
   save(out, 'n11_instance_iou', **store)
 
 
+# (seed, C, image, k-means grid, tagged classes).  (a) half map 20 x 28 -> 5 x 7, scale exactly 4; (b) half map 21 x 30 ->
+# 5 x 7: scales 4.2 and 30 / 7, the taps of the last row and column clamp at the border.  Seeds: the first from 2100 / 2150
+# on that meet every condition asserted in gen_n12 (2100, 2101: a pixel's two nearest prototypes 1.6e-5 apart; 2150
+# passes at once).
+N12_CASES = [(2102, 8, (40, 56), (4, 4), (2, 7, 11)), (2150, 8, (43, 61), (4, 5), (0, 5, 14))]
+
+
+def gen_n12(ref, out):
+  """N12: DensePose pseudo labels.  pyscripts/inference/pseudo_denseposerw_crf.py:137-142 (the affinity), :145-168 (labels
+  to the half map, k-means, tag propagation by the nearest labelled prototype), :172-190 (per-segment shares, the map at
+  1/8 of the image, the normalisation by each class's maximum, the tag mask) and :193-201 (the walk), exec'd from the
+  reference's own lines on seeded CPU inputs, with the stub embedder's `generate_clusters` (the reference's own, on the
+  CPU-shimmed segment_by_kmeans).  The input is the half-resolution embedding itself (what :130-135 leave).  The lines
+  hard-code 15 classes.  cv2 is not installed and :203-207 are the tail that `n7_pseudo_labels` pins already.  The
+  retrieval inside `gather_multiset_labels_per_batch_by_nearest_neighbor` is not visible from outside: the nearest index
+  and value are recomputed with that function's own expressions (models/utils.py:198-206) and asserted to reproduce its
+  result.  The fixture pins the defined behaviour: every tagged class has a non-zero maximum, nothing is NaN, and every
+  pixel's nearest labelled prototype leads the second one by more than 1e-4 (asserted; another seed otherwise), so that
+  the last bits of another normalisation cannot move a pixel to another prototype."""
+  import linecache
+  import textwrap
+  import spml.models.embeddings.resnet_deeplab as e_dl
+  import spml.models.utils as model_utils
+  import spml.utils.general.common as g_common
+  import spml.utils.segsort.common as s_common
+  F = torch.nn.functional
+
+  def ref_lines(first, last):
+    txt = ''.join(linecache.getline(py, i) for i in range(first, last + 1))
+    assert txt.strip(), py
+    return textwrap.dedent(txt).replace('.cuda()', '')
+
+  py = os.path.join(ref, 'pyscripts', 'inference', 'pseudo_denseposerw_crf.py')
+  src_aff, src_tags, src_cam, src_walk = ref_lines(137, 142), ref_lines(145, 168), ref_lines(172, 190), ref_lines(193, 201)
+  assert src_aff.lstrip().startswith('# Create affinity matrix') and 'exp_()' in src_aff
+  assert 'generate_clusters' in src_tags and src_tags.rstrip().endswith('label_divisor=config.network.label_divisor)')
+  assert src_cam.lstrip().startswith('s_probs = common_utils.segment_mean') and 'cam_full_arr[0] = TH' in src_cam
+  assert 'aff_mat = aff ** 20' in src_walk and src_walk.rstrip().endswith('cam_rw.view(15, cam_shape[0], cam_shape[1])')
+  walk_steps = [int(linecache.getline(py, i).split('=')[1]) for i in range(20, 40)
+                if linecache.getline(py, i).startswith('WALK_STEPS')]
+  assert walk_steps == [6]
+
+  ncls, divisor = 15, 2048
+  cfg = AttrDict(dataset=AttrDict(num_classes=ncls), network=AttrDict(label_divisor=divisor))
+  StubEmbedder = stub_embedder_class(e_dl)
+  store = {}
+  cases = N12_CASES
+  orig = e_dl.segsort_common.segment_by_kmeans
+  e_dl.segsort_common.segment_by_kmeans = cpu_shimmed_segment_by_kmeans(s_common)
+  try:
+    for ci, (seed, c, image_hw, grid, tags) in enumerate(cases):
+      gen = torch.Generator().manual_seed(seed)
+      image_h, image_w = image_hw
+      h2, w2 = image_h // 2, image_w // 2
+      emb = coherent_embedding(gen, 1, c, h2, w2)
+      # a blocky class map over the three tagged classes, about 10 % of its pixels kept (the others unlabelled: 254),
+      # and an ignore strip (255) along the right edge; the instance label is the cell
+      cells = blocky_labels(gen, 1, image_h, image_w, 3, 0, 3)[0]
+      dense = torch.tensor(tags)[cells]
+      keep = torch.rand(image_h, image_w, generator=gen) < 0.10
+      semantic = torch.where(keep, dense, torch.full_like(dense, 254))
+      semantic[:, image_w - 4:] = 255
+      instance = blocky_labels(gen, 1, image_h, image_w, 3, 0, 4)[0]
+      label_tags = torch.zeros(ncls, dtype=torch.bool)
+      present = torch.unique(semantic)
+      label_tags[present[present < ncls]] = True                       # :106-110
+      assert label_tags.nonzero().view(-1).tolist() == sorted(tags)
+      lab = semantic.clone()
+      lab[lab == 255] = ncls                                           # :121-123
+      env = {'torch': torch, 'F': F, 'config': cfg, 'common_utils': g_common, 'segsort_common': s_common,
+             'model_utils': model_utils, 'embeddings': {'embedding': emb.clone()}, 'image_h': image_h, 'image_w': image_w,
+             'label_batch': {'semantic_label': lab.unsqueeze(0), 'instance_label': instance.unsqueeze(0)},
+             'embedding_model': StubEmbedder(None, list(grid)), 'label_tags': label_tags.clone(), 'TH': None,
+             'WALK_STEPS': walk_steps[0]}
+      with torch.no_grad():
+        exec(compile(src_aff, py + ':137-142', 'exec'), env)
+        exec(compile(src_tags, py + ':145-168', 'exec'), env)
+        s_labs, c_inds, s_tags = env['s_labs'], env['c_inds'], env['s_tags']
+        clusterings = env['clusterings']
+        # the retrieval of models/utils.py:198-206 again, for its index and value
+        rows, protos = clusterings['cluster_embedding'], env['protos']
+        valid = (s_labs < ncls).view(1, -1)
+        dists = torch.mm(rows, protos.t())
+        dists = torch.where(valid.expand_as(dists), dists, dists.min() - 1)
+        top2 = torch.topk(dists, 2, dim=1)
+        nn_value, nn_index = top2.values[:, 0], top2.indices[:, 0]
+        assert torch.equal(g_common.one_hot(s_labs[nn_index].view(-1, 1), ncls + 1).sum(1)[:, :ncls], s_tags)
+        lead = float((top2.values[:, 0] - top2.values[:, 1]).min())
+        exec(compile(src_cam, py + ':172-190', 'exec'), env)
+        s_probs, resampled, cam = env['s_probs'], env['semantic_probs'], env['cam_full_arr']
+        exec(compile(src_walk, py + ':193-201', 'exec'), env)
+      trans = env['aff_mat'] / torch.sum(env['aff_mat'], dim=0, keepdim=True)
+      cam_rw = env['cam_rw']
+      n, oh, ow = h2 * w2, image_h // 8, image_w // 8
+      m = int(s_labs.shape[0])
+      assert tuple(c_inds.shape) == (n,) == tuple(nn_index.shape) and int(c_inds.max()) + 1 == m
+      assert tuple(s_probs.shape) == (m, ncls) and tuple(resampled.shape) == (1, ncls, oh, ow)
+      assert tuple(cam.shape) == (1, ncls, oh, ow) and tuple(cam_rw.shape) == (ncls, oh, ow)
+      assert tuple(trans.shape) == (oh * ow, oh * ow)
+      peaks = cam[0].reshape(ncls, -1).max(1).values
+      print('n12 case %d (seed %d): %d segments (%d labelled), nearest prototype leads by %.2e, class peaks %s'
+            % (ci, seed, m, int(valid.sum()), lead, [round(float(v), 3) for v in peaks[label_tags]]))
+      assert not any(bool(torch.isnan(t).any()) for t in (s_probs, resampled, cam, cam_rw)), 'NaN -- pick another seed'
+      assert bool((peaks[label_tags] == 1).all()) and bool((peaks[~label_tags] == 0).all()), 'pick another seed'
+      assert lead > 1e-4, 'a pixel sits between two prototypes -- pick another seed'
+      assert bool(torch.equal(torch.bincount(c_inds, minlength=m) > 0, torch.ones(m, dtype=torch.bool)))
+      t = 'c%d_' % ci
+      store.update({
+          t + 'cfg': np.array([c, ncls, image_h, image_w, grid[0], grid[1], divisor, walk_steps[0]]),
+          t + 'embedding': emb[0], t + 'semantic_label': semantic.to(torch.uint8),
+          t + 'instance_label': instance.to(torch.uint8), t + 'tags': label_tags,
+          t + 'cluster_embedding': rows, t + 'cluster_semantic_label': clusterings['cluster_semantic_label'].to(torch.int16),
+          t + 'raw_cluster_index': clusterings['cluster_index'].to(torch.int16),
+          t + 'cluster_index': c_inds.to(torch.int16), t + 'proto_label': s_labs.to(torch.int16),
+          t + 'nn_index': nn_index.to(torch.int16), t + 'nn_value': nn_value, t + 's_tags': s_tags.to(torch.uint8),
+          t + 's_probs': s_probs, t + 'semantic_probs': resampled[0], t + 'cam_full_arr': cam[0], t + 'trans': trans,
+          t + 'cam_rw': cam_rw})
+  finally:
+    e_dl.segsort_common.segment_by_kmeans = orig
+  save(out, 'n12_densepose_pseudo', **store)
+  size = os.path.getsize(os.path.join(out, 'n12_densepose_pseudo.npz'))
+  assert size < 600 * 1024, 'n12_densepose_pseudo.npz is %d bytes' % size
+
+
 class AttrDict(dict):
   __getattr__ = dict.__getitem__
 
@@ -893,7 +1017,7 @@ def main():
   sys.path.insert(0, args.ref)
   torch.set_num_threads(1)       # bit-stable fp32 sums
   if ONLY is not None and ONLY <= {'n7_pseudo_labels', 'n8_softmax_msc', 'n9_knn_msc', 'n10_prototype_msc',
-                                   'n11_pseudo_knn_msc', 'n11_instance_iou'}:      # (need none of the imports and shims below)
+                                   'n11_pseudo_knn_msc', 'n11_instance_iou', 'n12_densepose_pseudo'}:      # (need none of the imports and shims below)
     if 'n7_pseudo_labels' in ONLY:
       gen_n7(args.ref, out)
     if 'n8_softmax_msc' in ONLY:
@@ -906,6 +1030,8 @@ def main():
       gen_n11(args.ref, out)
     if 'n11_instance_iou' in ONLY:
       gen_n11_instance(args.ref, out)
+    if 'n12_densepose_pseudo' in ONLY:
+      gen_n12(args.ref, out)
     return
 
   import spml.utils.general.common as g_common
@@ -1715,6 +1841,10 @@ def main():
     gen_n11(args.ref, out)
   if ONLY is None or 'n11_instance_iou' in ONLY:
     gen_n11_instance(args.ref, out)
+
+  # ======================= N12: DensePose pseudo labels (tag propagation, walk) ==============
+  if ONLY is None or 'n12_densepose_pseudo' in ONLY:
+    gen_n12(args.ref, out)
 
   # ======================= H2: two steps of the stage-2 classifier training ===============
   # pyscripts/train/train_classifier.py:139-169, the loop body exec'd as it stands on ONE device:
