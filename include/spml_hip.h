@@ -49,7 +49,7 @@ const char* spml_status_string(int status);
  * 7: the multi-scale inference entry point (spml_view_probs_accumulate_f32);
  * 8: spml_upsample_ce_bwd_path_name (entry points added since leave every earlier signature and flag as it was and
  *    keep the version: spml_view_votes_*, spml_segsort_nll_batched_*, spml_segment_majority_*, spml_tag_normalize_*,
- *    spml_dense_crf_*, spml_segment_tag_cam_*). */
+ *    spml_dense_crf_*, spml_segment_tag_cam_*, spml_conv_hl8_path_name, spml_conv_wgrad_path_name / _splits). */
 #define SPML_ABI_VERSION 8
 int spml_abi_version(void);
 
@@ -656,6 +656,32 @@ int spml_conv_wgrad_pyramid_hl8_f32(const void* dy, const float* dy_bound, const
                                     const float* x_bound, float* dw, int n_img, int H, int W,
                                     int K, int N, int branches, const int* dilations,
                                     void* ws, size_t ws_bytes, void* stream);
+
+/* Which conv_gemm instantiation a call launches (pure host functions: the launches' own expression -- the entry points,
+ * the statistics layouts and these names read one route record, csrc/conv.hip: conv_route; every SPML_CONV_* switch
+ * is read per call).  entry: 0 spml_conv_hl8_f32, 1 spml_conv_hl8_stats_f32, 2 spml_conv_hl8_bwd_stats_f32,
+ * 3 spml_conv_hl8_affine_f32, 4 spml_conv_hl8_pyramid_f32 (taps_or_groups: its `groups`; otherwise taps).
+ * Names (static strings), N % 256 == 0: "rb3" "rb4" "rb5" = 96- / 128- / 160-row tiles of 256 columns (by problem
+ * size, or SPML_CONV_RB); "rb3_chunk" = 96 rows, chunked accumulation (K * taps >= SPML_CONV_CHUNK_MIN_K, default
+ * 4096); "rb5_rg2" = 320 rows, two row groups (SPML_CONV_RG=2; never for entry 3).  N % 128 == 0: "n128" (256 rows)
+ * "n128_chunk" (192 rows); N % 64 == 0: "n64" "n64_chunk" (256 rows), with SPML_CONV_NARROW_RB=3 "n64_rb3"
+ * "n64_rb3_chunk" (384 rows).  Entries 1 / 2 append the statistics epilogue: "rb3+stats" "rb4+stats" "rb5+stats"
+ * "rb3_chunk+stats" / "rb3+bstats" "rb4+bstats" "rb5+bstats" "rb3_chunk+bstats" (every other shape: "unsupported",
+ * as the layout calls answer).  Entry 4 with groups > 1, no addend and the deterministic mode off splits the taps
+ * over workgroups (fp32 atomics): "n128+tapgroups" "n128_chunk+tapgroups" "n64+tapgroups" "n64_chunk+tapgroups"
+ * "n64_rb3+tapgroups" "n64_rb3_chunk+tapgroups".  Outside the domain: "unsupported". */
+const char* spml_conv_hl8_path_name(int entry, int n_img, int H, int W, int K, int N,
+                                    int taps_or_groups, int has_addend);
+/* The same for the weight gradient (csrc/conv.hip: wgrad_route; pyramid != 0: spml_conv_wgrad_pyramid_hl8_f32 with
+ * taps_or_branches = branches).  Names: "t256x256_pair4" (N x K tile of one tap, four ring slots, a barrier per two
+ * stages: the default at N % 256 == 0 and K % 256 == 0); "t256x256_s2" "t256x256_s3" "t256x256_s4" "t256x256_s5"
+ * (SPML_WGRAD_STAGES); "t256x128_s3" "t128x256_s3" "t128x128_s3"; "pyr_t256x256_pair4"; "unsupported".
+ * spml_conv_wgrad_splits: workgroups per tile over the pixel range (0: unsupported); the workspace holds
+ * splits * tiles * tile n * tile k floats. */
+const char* spml_conv_wgrad_path_name(int n_img, int H, int W, int K, int N,
+                                      int taps_or_branches, int pyramid);
+int spml_conv_wgrad_splits(int n_img, int H, int W, int K, int N, int taps_or_branches,
+                           int pyramid);
 
 /* ---- batch norm producing the split-f16 ("hl8") copies the matrix-core convolutions read ----
  * Same math as the spml_bn_* calls above (spml/models/backbones/resnet.py:42-63); y / dx can be

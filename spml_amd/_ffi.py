@@ -101,6 +101,9 @@ _SIGNATURES = {
     'spml_conv_wgrad_pyramid_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     'spml_conv_wgrad_pyramid_hl8_f32': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P,
                                                 c_size_t, _P]),
+    'spml_conv_hl8_path_name': (c_char_p, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    'spml_conv_wgrad_path_name': (c_char_p, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    'spml_conv_wgrad_splits': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     'spml_bn_stats_ext_f32': (c_int, [_P, c_int64, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     'spml_bn_stats_ext_chunks_f32': (c_int, [_P, c_int, c_int, c_int64, c_int, _P, _P, _P, _P, _P]),
     'spml_bn_finalize_f32': (c_int, [_P, _P, c_int, c_double, c_float, c_float, _P, _P, _P, _P]),
@@ -1133,6 +1136,29 @@ def conv_hl8_bwd_stats(a, b, n_img, h, w, taps, dilation, bn_x, relu_mask, bn_me
                                           _dp(bn_mean), _dp(st), _dp(bound), n_img, h, w, k, n, taps, dilation,
                                           stream_ptr()), 'spml_conv_hl8_bwd_stats_f32')
   return out, ChunkStats(st, chunks.value, rows.value, bound)
+
+
+CONV_ENTRIES = {'plain': 0, 'stats': 1, 'bwd_stats': 2, 'affine': 3, 'pyramid': 4}
+
+
+def conv_hl8_path_name(entry, n_img, h, w, k, n, taps_or_groups, has_addend=False):
+  """conv_gemm instantiation the entry point ('plain', 'stats', 'bwd_stats', 'affine', 'pyramid': there
+  taps_or_groups = groups) launches for a shape under the current environment and deterministic mode -- a pure
+  host function of the library, the launch's own expression; names: include/spml_hip.h."""
+  return lib().spml_conv_hl8_path_name(CONV_ENTRIES[entry], int(n_img), int(h), int(w), int(k), int(n),
+                                       int(taps_or_groups), int(bool(has_addend))).decode()
+
+
+def conv_wgrad_path_name(n_img, h, w, k, n, taps_or_branches, pyramid=False):
+  """conv_wgrad instantiation of the weight gradient (pyramid: taps_or_branches = branches)."""
+  return lib().spml_conv_wgrad_path_name(int(n_img), int(h), int(w), int(k), int(n), int(taps_or_branches),
+                                         int(bool(pyramid))).decode()
+
+
+def conv_wgrad_splits(n_img, h, w, k, n, taps_or_branches, pyramid=False):
+  """Workgroups per tile over the pixel range of that launch (0: unsupported)."""
+  return lib().spml_conv_wgrad_splits(int(n_img), int(h), int(w), int(k), int(n), int(taps_or_branches),
+                                      int(bool(pyramid)))
 
 
 def conv_wgrad_hl8_supported(k, n, taps):

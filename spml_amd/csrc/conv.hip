@@ -7,7 +7,8 @@
 // of it (profiles/r02_train_step_steady_state.md).  The f16 path is 16x faster, and the split
 //     v * S = h + l,   h = f16(v * S),  l = f16(v * S - h)            (S = per-tensor power of two)
 // carries 22 mantissa bits for every element within 2^15 of the tensor's largest magnitude
-// (smaller ones keep an absolute error of 2^-39 of it), so that
+// (smaller ones keep an absolute error of 2^-38 of it: half an f16 subnormal step, 2^-25, over S >= 2^13 / bound;
+// tests/conv_ref.py restates the format and tests/test_conv_ref.py both bounds), so that
 //     a * b = (ha*hb + ha*lb + la*hb) / (Sa * Sb)       (la*lb, 2^-24 relative, is dropped)
 // costs three f16 MFMAs -- all exact products accumulated in fp32 -- instead of one fp32 MFMA
 // at 1/16 of the rate.  S comes from an upper bound of max|v| that the producing kernel knows
@@ -616,8 +617,13 @@ __global__ __launch_bounds__(64 * NC * RG, WGS) void conv_gemm(const ConvArgs a)
   }
 }
 
+struct ConvRoute;
+template <int RB, int RG, bool CHUNK, int NC, bool BSTAT>
+bool route_is(const ConvRoute& r);         // (below, with the route: the record names exactly this instantiation)
+
 template <int RB, int kStages, int WGS, int RG = 1, bool CHUNK = false, int NC = 4, bool BSTAT = false>
-int launch_conv(const ConvArgs& a0, hipStream_t s) {
+int launch_conv(const ConvRoute& r, const ConvArgs& a0, hipStream_t s) {
+  if (!route_is<RB, RG, CHUNK, NC, BSTAT>(r)) return SPML_ERR_LAUNCH;      // the path name would not be the launch's
   ConvArgs a = a0;
   a.n_col_tiles = a.N / (64 * NC);
   const int64_t row_tiles = (a.R + RG * RB * 32 - 1) / (RG * RB * 32);
@@ -631,15 +637,10 @@ int launch_conv(const ConvArgs& a0, hipStream_t s) {
   return launch_status();
 }
 
-// narrow outputs: N % 256 != 0.  128-column tiles: 2 x 2 waves, 256 rows (RB = 4: 72 KB of LDS, two workgroups
-// per CU); 64-column tiles: 1 x 4 waves, 256 rows (RB = 2: 60 KB) -- SPML_CONV_NARROW_RB=3 takes 384 rows
-// (84 KB, one workgroup per CU)
-template <bool CHUNK>
-int launch_conv_narrow(const ConvArgs& c, hipStream_t s) {
-  if ((c.N & 127) == 0) return launch_conv<CHUNK ? 3 : 4, 3, 2, 2, CHUNK, 2>(c, s);   // (chunked: two accumulator sets)
+// SPML_CONV_NARROW_RB=3: the 64-column tiles take 384 rows instead of 256 (conv_route)
+inline bool narrow_rb3() {
   const char* e = getenv("SPML_CONV_NARROW_RB");         // (read per call: the library keeps no state)
-  if (e && e[0] == '3') return launch_conv<3, 3, 1, 4, CHUNK, 1>(c, s);
-  return launch_conv<2, 3, 2, 4, CHUNK, 1>(c, s);
+  return e && e[0] == '3';
 }
 
 // rows per tile: the tallest tile (RB = 5: the weight blocks and the barrier are amortised over the most
@@ -963,6 +964,195 @@ inline bool use_two_row_groups(int64_t, int, int) {
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// ---------------------------------------------------------------------------------------
+// routes: which conv_gemm / conv_wgrad instantiation a call launches.  Decided once per call (every environment
+// switch is read then); the entry points, the statistics layout and the path names read the same record.
+// ---------------------------------------------------------------------------------------
+enum ConvEntry { kEntryPlain = 0, kEntryStats = 1, kEntryBwdStats = 2, kEntryAffine = 3, kEntryPyramid = 4 };
+enum ConvStat { kStatNone = 0, kStatFwd = 1, kStatBwd = 2 };
+
+struct ConvRoute {
+  int rb = 0;                // 32-row blocks per row group (0: no launch for this shape)
+  int rg = 1, nc = 4;        // row groups, 64-column wave groups of a workgroup
+  bool chunk = false;        // chunked accumulation
+  int tap_groups = 1;        // > 1: workgroups per tile, partial tiles added with fp32 atomics
+  int stat = kStatNone;      // statistics epilogue
+  int tile_rows = 0;         // rg * rb * 32
+};
+
+// taps: all taps of the launch (9 * groups for the pyramid entry); groups: 1 unless the pyramid entry
+inline ConvRoute conv_route(int entry, int64_t R, int K, int N, int taps, int groups, bool has_addend) {
+  ConvRoute r;
+  if (entry < kEntryPlain || entry > kEntryPyramid || R <= 0) return r;
+  if (!spml_conv_hl8_supported(K, N, entry == kEntryPyramid ? 9 : taps)) return r;
+  const bool stats = entry == kEntryStats || entry == kEntryBwdStats;
+  const bool chunk = chunk_long_reduction((int64_t)K * taps);
+  int rb, rg = 1, nc = 4;
+  if (N & 255) {
+    // narrow outputs: 128-column tiles, 2 x 2 waves, 256 rows (RB = 4: 72 KB of LDS, two workgroups per CU; chunked:
+    // RB = 3, two accumulator sets); 64-column tiles, 1 x 4 waves, 256 rows (RB = 2: 60 KB) -- SPML_CONV_NARROW_RB=3
+    // takes 384 rows (84 KB, one workgroup per CU).  No wave owns a column over the whole tile: no statistics.
+    if (stats) return r;
+    if ((N & 127) == 0) { nc = 2; rg = 2; rb = chunk ? 3 : 4; }
+    else { nc = 1; rg = 4; rb = narrow_rb3() ? 3 : 2; }
+  } else if (stats) {
+    if (use_two_row_groups(R, N, K * taps)) return r;       // (a tile spans two row groups: no column owner either)
+    rb = chunk ? 3 : pick_rb(R, N);
+    if ((R + 32 * rb - 1) / (32 * rb) > 4096) return r;
+  } else if (chunk) {
+    rb = 3;
+  } else if (entry != kEntryAffine && use_two_row_groups(R, N, K * taps)) {   // (the inference entry has no RG rung)
+    rb = 5; rg = 2;
+  } else {
+    rb = pick_rb(R, N);
+  }
+  r.rb = rb; r.rg = rg; r.nc = nc;
+  r.chunk = chunk;
+  r.stat = entry == kEntryStats ? kStatFwd : (entry == kEntryBwdStats ? kStatBwd : kStatNone);
+  r.tile_rows = rg * rb * 32;
+  // narrow heads (the 64-d embedding: 264 row tiles of 256 pixels -- one workgroup per CU, nothing to cover its
+  // barriers): one workgroup per (tile, dilation group), the partial tiles meet through fp32 atomics
+  if (entry == kEntryPyramid && (N & 255) && groups > 1 && !has_addend && !deterministic_mode()) r.tap_groups = groups;
+  return r;
+}
+
+template <int RB, int RG, bool CHUNK, int NC, bool BSTAT>
+bool route_is(const ConvRoute& r) {
+  return r.rb == RB && r.rg == RG && r.chunk == CHUNK && r.nc == NC && (r.stat == kStatBwd) == BSTAT;
+}
+
+inline int launch_route(const ConvRoute& r, const ConvArgs& c, hipStream_t s) {
+  if (r.stat == kStatBwd) {
+    if (r.chunk) return launch_conv<3, 3, 2, 1, true, 4, true>(r, c, s);
+    switch (r.rb) {
+      case 3: return launch_conv<3, 3, 2, 1, false, 4, true>(r, c, s);
+      case 5: return launch_conv<5, 3, 2, 1, false, 4, true>(r, c, s);
+      default: return launch_conv<4, 3, 2, 1, false, 4, true>(r, c, s);
+    }
+  }
+  if (r.nc == 2) return r.chunk ? launch_conv<3, 3, 2, 2, true, 2>(r, c, s) : launch_conv<4, 3, 2, 2, false, 2>(r, c, s);
+  if (r.nc == 1) {
+    if (r.rb == 3) return r.chunk ? launch_conv<3, 3, 1, 4, true, 1>(r, c, s) : launch_conv<3, 3, 1, 4, false, 1>(r, c, s);
+    return r.chunk ? launch_conv<2, 3, 2, 4, true, 1>(r, c, s) : launch_conv<2, 3, 2, 4, false, 1>(r, c, s);
+  }
+  if (r.chunk) return launch_conv<3, 3, 2, 1, true>(r, c, s);
+  if (r.rg == 2) return launch_conv<5, 3, 2, 2>(r, c, s);
+  switch (r.rb) {
+    case 3: return launch_conv<3, 3, 2>(r, c, s);
+    case 5: return launch_conv<5, 3, 2>(r, c, s);
+    default: return launch_conv<4, 3, 2>(r, c, s);
+  }
+}
+
+inline const char* conv_route_name(const ConvRoute& r) {
+  // [instantiation][none, +stats, +bstats, +tapgroups]: every name spml_conv_hl8_path_name can return
+  static const char* const names[11][4] = {
+      {"rb3", "rb3+stats", "rb3+bstats", nullptr},
+      {"rb4", "rb4+stats", "rb4+bstats", nullptr},
+      {"rb5", "rb5+stats", "rb5+bstats", nullptr},
+      {"rb3_chunk", "rb3_chunk+stats", "rb3_chunk+bstats", nullptr},
+      {"rb5_rg2", nullptr, nullptr, nullptr},
+      {"n128", nullptr, nullptr, "n128+tapgroups"},
+      {"n128_chunk", nullptr, nullptr, "n128_chunk+tapgroups"},
+      {"n64", nullptr, nullptr, "n64+tapgroups"},
+      {"n64_chunk", nullptr, nullptr, "n64_chunk+tapgroups"},
+      {"n64_rb3", nullptr, nullptr, "n64_rb3+tapgroups"},
+      {"n64_rb3_chunk", nullptr, nullptr, "n64_rb3_chunk+tapgroups"}};
+  if (!r.rb) return "unsupported";
+  int i;
+  if (r.nc == 2) i = r.chunk ? 6 : 5;
+  else if (r.nc == 1) i = (r.rb == 3 ? 9 : 7) + (r.chunk ? 1 : 0);
+  else if (r.chunk) i = 3;
+  else if (r.rg == 2) i = 4;
+  else i = r.rb - 3;
+  const char* n = names[i][r.tap_groups > 1 ? 3 : r.stat];
+  return n ? n : "unsupported";
+}
+
+// tile widths of the weight gradient: 256 where the channel count allows it, 128 otherwise
+inline int wgrad_tile(int channels) { return (channels & 255) == 0 ? 256 : 128; }
+
+inline int pyr_groups(int branches) { return (9 * branches + 3) / 4; }
+
+inline int pyr_splits(int64_t R, int tiles) {
+  // one 128-KB workgroup per CU: the smallest split count whose last round of 256 is (almost) full
+  const int64_t max_s = (R + 255) / 256;
+  int s = 1;
+  double best = 1e9;
+  for (int c = 1; c <= 16 && c <= max_s; ++c) {
+    const int64_t wgs = (int64_t)tiles * c;
+    const double waste = (double)((wgs + 255) / 256 * 256) / (double)wgs - 1.0;
+    if (waste < best - 0.02) { best = waste; s = c; }
+  }
+  return s;
+}
+
+struct WgradRoute {
+  int tn = 0, tk = 0;        // tile of one tap: n x k (tn == 0: no launch for this shape)
+  int stages = 0;            // ring slots
+  bool pair = false;         // one barrier per two stages
+  bool pyr = false;          // four taps x 64 channels per tile
+  int taps = 0;              // tile-index taps (pyramid: groups of four taps)
+  int k_tiles = 0, tiles = 0, splits = 0, rows_per_split = 0;
+};
+
+// taps_or_branches: taps in {1, 9}; pyramid: 1..4 branches
+inline WgradRoute wgrad_route(int64_t R, int K, int N, int taps_or_branches, bool pyramid) {
+  WgradRoute r;
+  if (R <= 0) return r;
+  if (pyramid) {
+    if (!spml_conv_wgrad_pyramid_hl8_supported(K, N, taps_or_branches)) return r;
+    r.tn = r.tk = 256;
+    r.stages = 4; r.pair = true; r.pyr = true;
+    r.taps = pyr_groups(taps_or_branches);                 // (the tile index decodes as (group of four taps, k tile))
+    r.k_tiles = K / 256;
+    r.tiles = r.taps * r.k_tiles;
+    r.splits = pyr_splits(R, r.tiles);
+  } else {
+    if (!spml_conv_wgrad_hl8_supported(K, N, taps_or_branches)) return r;
+    r.tn = wgrad_tile(N); r.tk = wgrad_tile(K);
+    r.taps = taps_or_branches;
+    r.k_tiles = K / r.tk;
+    r.tiles = (N / r.tn) * r.k_tiles * r.taps;
+    r.splits = wgrad_splits(R, r.tiles);
+    // 256 x 256 tiles: four ring slots and one workgroup barrier per TWO stages (32 pixel rows) -- 5-12 % faster than
+    // a barrier per stage with three slots on every res4 / res5 shape (tools/bench_conv.py; SPML_WGRAD_STAGES=3 selects
+    // the latter, 2 / 4 / 5 its other ring depths, which all measure the same: the stage time is matrix-pipe + barrier
+    // time, not load latency).  The 128-wide tiles keep three slots.
+    // (the experiment switch only exists for the 256 x 256 tiles, and only with the depths instantiated: anything else
+    // takes the default -- a launch that matches no instantiation would leave conv_wgrad_reduce summing an unwritten
+    // workspace)
+    r.stages = 3;
+    if (r.tn == 256 && r.tk == 256) {
+      r.stages = 4; r.pair = true;
+      if (const char* e = getenv("SPML_WGRAD_STAGES")) {
+        const int v = atoi(e);
+        if (v == 2 || v == 3 || v == 4 || v == 5) { r.stages = v; r.pair = false; }
+      }
+    }
+  }
+  r.rows_per_split = (int)(((R + r.splits - 1) / r.splits + 15) / 16 * 16);
+  return r;
+}
+
+inline const char* wgrad_route_name(const WgradRoute& r) {
+  if (!r.tn) return "unsupported";
+  if (r.pyr) return "pyr_t256x256_pair4";
+  if (r.pair) return "t256x256_pair4";
+  if (r.tn == 256 && r.tk == 256)
+    return r.stages == 2 ? "t256x256_s2" : (r.stages == 3 ? "t256x256_s3" : (r.stages == 4 ? "t256x256_s4" : "t256x256_s5"));
+  if (r.tn == 256) return "t256x128_s3";
+  return r.tk == 256 ? "t128x256_s3" : "t128x128_s3";
+}
+
+template <int TN, int TK, int ST, bool PAIR = false, bool PYR = false>
+void launch_wgrad(const WgradRoute& r, const WgradArgs& a, hipStream_t s) {
+  const int lds = ST * 2 * (TN / 32 + TK / 32) * 1024;
+  auto kern = conv_wgrad<TN, TK, ST, PAIR, PYR>;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  hipLaunchKernelGGL(kern, dim3(r.tiles, r.splits), dim3(512), lds, s, a);
+}
+
 }  // namespace
 }  // namespace spml
 
@@ -1076,21 +1266,13 @@ extern "C" int spml_conv_hl8_f32(const void* a, const float* a_bound, const void
   // 1024 k, so that its rounding error stays at the level of the fp32 library's split-K kernels
   // (profiles/r03_conv_accuracy.md: 1.1e-6 -> 2.6e-7 of max|out| at K = 4608).  It costs the 3-row-block
   // tile, 9-21 % of the convolution's time: at K = 2048 / 2304 (un-chunked 6.6e-7) it stays off by default
-  if (chunk_long_reduction(c.K * c.taps)) return (N & 255) ? launch_conv_narrow<true>(c, s) : launch_conv<3, 3, 2, 1, true>(c, s);
-  if (N & 255) return launch_conv_narrow<false>(c, s);
-  if (use_two_row_groups(c.R, N, c.K * c.taps)) return launch_conv<5, 3, 2, 2>(c, s);
-  switch (pick_rb(c.R, N)) {
-    case 3: return launch_conv<3, 3, 2>(c, s);
-    case 5: return launch_conv<5, 3, 2>(c, s);
-    default: return launch_conv<4, 3, 2>(c, s);
-  }
+  return launch_route(conv_route(kEntryPlain, c.R, K, N, taps, 1, addend != nullptr), c, s);
 }
 
 // rows per row tile of the launch spml_conv_hl8_f32 picks for this shape (0: a tile spans several row
-// groups or the columns are narrow -- no fused statistics)
+// groups, the columns are narrow or there are more than 4096 row tiles -- no fused statistics)
 static int conv_stats_rows(int64_t R, int K, int N, int taps) {
-  if ((N & 255) || !spml_conv_hl8_supported(K, N, taps) || use_two_row_groups(R, N, K * taps)) return 0;
-  return 32 * (chunk_long_reduction((int64_t)K * taps) ? 3 : pick_rb(R, N));
+  return conv_route(kEntryStats, R, K, N, taps, 1, false).tile_rows;
 }
 
 extern "C" int spml_conv_hl8_stats_layout(int n_img, int H, int W, int K, int N, int taps, int* chunks,
@@ -1098,7 +1280,7 @@ extern "C" int spml_conv_hl8_stats_layout(int n_img, int H, int W, int K, int N,
   if (!chunks || !chunk_rows || n_img <= 0 || H <= 0 || W <= 0) return SPML_ERR_INVALID_ARG;
   const int64_t R = (int64_t)n_img * H * W;
   const int rows = conv_stats_rows(R, K, N, taps);
-  if (!rows || (R + rows - 1) / rows > 4096) return SPML_ERR_UNSUPPORTED;
+  if (!rows) return SPML_ERR_UNSUPPORTED;
   *chunk_rows = rows;
   *chunks = (int)((R + rows - 1) / rows);
   return SPML_OK;
@@ -1123,12 +1305,9 @@ extern "C" int spml_conv_hl8_stats_f32(const void* a, const float* a_bound, cons
   c.R = (int64_t)n_img * H * W;
   c.H = H; c.W = W; c.K = K; c.N = N; c.taps = taps; c.dil = dilation;
   hipStream_t s = (hipStream_t)stream;
-  if (chunk_long_reduction((int64_t)c.K * c.taps)) return launch_conv<3, 3, 2, 1, true>(c, s);
-  switch (rows / 32) {
-    case 3: return launch_conv<3, 3, 2>(c, s);
-    case 5: return launch_conv<5, 3, 2>(c, s);
-    default: return launch_conv<4, 3, 2>(c, s);
-  }
+  const ConvRoute r = conv_route(kEntryStats, c.R, K, N, taps, 1, false);
+  if (r.tile_rows != rows) return SPML_ERR_UNSUPPORTED;       // (a switch changed between the two reads)
+  return launch_route(r, c, s);
 }
 
 // The data gradient in front of a batch norm + ReLU of the backward pass: the same launch spml_conv_hl8_f32 picks for
@@ -1163,12 +1342,9 @@ extern "C" int spml_conv_hl8_bwd_stats_f32(const void* a, const float* a_bound, 
   c.R = (int64_t)n_img * H * W;
   c.H = H; c.W = W; c.K = K; c.N = N; c.taps = taps; c.dil = dilation;
   hipStream_t s = (hipStream_t)stream;
-  if (chunk_long_reduction((int64_t)c.K * c.taps)) return launch_conv<3, 3, 2, 1, true, 4, true>(c, s);
-  switch (rows / 32) {
-    case 3: return launch_conv<3, 3, 2, 1, false, 4, true>(c, s);
-    case 5: return launch_conv<5, 3, 2, 1, false, 4, true>(c, s);
-    default: return launch_conv<4, 3, 2, 1, false, 4, true>(c, s);
-  }
+  const ConvRoute r = conv_route(kEntryBwdStats, c.R, K, N, taps, 1, false);
+  if (r.tile_rows != rows) return SPML_ERR_UNSUPPORTED;       // (a switch changed between the two reads)
+  return launch_route(r, c, s);
 }
 
 extern "C" int spml_conv_hl8_affine_f32(const void* a, const float* a_bound, const void* b, const float* b_bound,
@@ -1192,13 +1368,7 @@ extern "C" int spml_conv_hl8_affine_f32(const void* a, const float* a_bound, con
   c.H = H; c.W = W; c.K = K; c.N = N; c.taps = taps; c.dil = dilation;
   hipStream_t s = (hipStream_t)stream;
   if (out_bound && hipMemsetAsync(out_bound, 0, sizeof(float), s) != hipSuccess) return SPML_ERR_LAUNCH;
-  if (chunk_long_reduction(c.K * c.taps)) return (N & 255) ? launch_conv_narrow<true>(c, s) : launch_conv<3, 3, 2, 1, true>(c, s);
-  if (N & 255) return launch_conv_narrow<false>(c, s);
-  switch (pick_rb(c.R, N)) {
-    case 3: return launch_conv<3, 3, 2>(c, s);
-    case 5: return launch_conv<5, 3, 2>(c, s);
-    default: return launch_conv<4, 3, 2>(c, s);
-  }
+  return launch_route(conv_route(kEntryAffine, c.R, K, N, taps, 1, addend != nullptr), c, s);
 }
 
 extern "C" int spml_conv_hl8_pyramid_f32(const void* a, const float* a_bound, const void* b, const float* b_bound,
@@ -1223,17 +1393,22 @@ extern "C" int spml_conv_hl8_pyramid_f32(const void* a, const float* a_bound, co
     if (c.dils[g] < 1) return SPML_ERR_INVALID_ARG;
   }
   hipStream_t s = (hipStream_t)stream;
-  // narrow heads (the 64-d embedding: 264 row tiles of 256 pixels -- one workgroup per CU, nothing to cover its
-  // barriers): one workgroup per (tile, dilation group), the four partial tiles are added with fp32 atomics
-  if ((N & 255) && groups > 1 && !addend && !deterministic_mode()) c.tap_groups = groups;     // (partial tiles meet through fp32 atomics)
-  if (N & 255) return chunk_long_reduction((int64_t)K * c.taps) ? launch_conv_narrow<true>(c, s) : launch_conv_narrow<false>(c, s);
-  if (chunk_long_reduction((int64_t)K * c.taps)) return launch_conv<3, 3, 2, 1, true>(c, s);     // chunked accumulation
-  if (use_two_row_groups(c.R, N, c.K * c.taps)) return launch_conv<5, 3, 2, 2>(c, s);
-  switch (pick_rb(c.R, N)) {
-    case 3: return launch_conv<3, 3, 2>(c, s);
-    case 5: return launch_conv<5, 3, 2>(c, s);
-    default: return launch_conv<4, 3, 2>(c, s);
+  const ConvRoute r = conv_route(kEntryPyramid, c.R, K, N, c.taps, groups, addend != nullptr);
+  if (r.tap_groups > 1) c.tap_groups = r.tap_groups;
+  return launch_route(r, c, s);
+}
+
+// The launch's own expression: conv_route is what the five entry points above read.
+extern "C" const char* spml_conv_hl8_path_name(int entry, int n_img, int H, int W, int K, int N, int taps_or_groups,
+                                               int has_addend) {
+  if (n_img <= 0 || H <= 0 || W <= 0) return "unsupported";
+  int taps = taps_or_groups, groups = 1;
+  if (entry == kEntryPyramid) {
+    if (taps_or_groups < 1 || taps_or_groups > 4) return "unsupported";
+    groups = taps_or_groups;
+    taps = 9 * groups;
   }
+  return conv_route_name(conv_route(entry, (int64_t)n_img * H * W, K, N, taps, groups, has_addend != 0));
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1296,14 +1471,10 @@ extern "C" int spml_conv_wgrad_hl8_supported(int K, int N, int taps) {
   return (taps == 1 || taps == 9) && K > 0 && (K & 127) == 0 && N > 0 && (N & 127) == 0;
 }
 
-// tile widths: 256 where the channel count allows it, 128 otherwise
-static inline int wgrad_tile(int channels) { return (channels & 255) == 0 ? 256 : 128; }
-
 extern "C" size_t spml_conv_wgrad_workspace_bytes(int n_img, int H, int W, int K, int N, int taps) {
-  if (!spml_conv_wgrad_hl8_supported(K, N, taps) || n_img <= 0 || H <= 0 || W <= 0) return 0;
-  const int tn = wgrad_tile(N), tk = wgrad_tile(K);
-  const int tiles = (N / tn) * (K / tk) * taps;
-  return (size_t)wgrad_splits((int64_t)n_img * H * W, tiles) * tiles * tn * tk * sizeof(float);
+  if (n_img <= 0 || H <= 0 || W <= 0) return 0;
+  const WgradRoute r = wgrad_route((int64_t)n_img * H * W, K, N, taps, false);
+  return (size_t)r.splits * r.tiles * r.tn * r.tk * sizeof(float);
 }
 
 extern "C" int spml_conv_wgrad_hl8_f32(const void* dy, const float* dy_bound, const void* x,
@@ -1319,48 +1490,21 @@ extern "C" int spml_conv_wgrad_hl8_f32(const void* dy, const float* dy_bound, co
   a.partial = static_cast<float*>(ws);
   a.R = (int64_t)n_img * H * W;
   a.H = H; a.W = W; a.K = K; a.N = N; a.taps = taps; a.dil = dilation;
-  const int tn = wgrad_tile(N), tk = wgrad_tile(K);
-  a.k_tiles = K / tk;
-  const int tiles = (N / tn) * a.k_tiles * taps;
-  a.splits = wgrad_splits(a.R, tiles);
-  a.rows_per_split = (int)(((a.R + a.splits - 1) / a.splits + 15) / 16 * 16);
+  const WgradRoute r = wgrad_route(a.R, K, N, taps, false);
+  const int tn = r.tn, tk = r.tk, tiles = r.tiles;
+  a.k_tiles = r.k_tiles;
+  a.splits = r.splits;
+  a.rows_per_split = r.rows_per_split;
   hipStream_t s = (hipStream_t)stream;
-  // 256 x 256 tiles: four ring slots and one workgroup barrier per TWO stages (32 pixel rows) -- 5-12 % faster than a
-  // barrier per stage with three slots on every res4 / res5 shape (tools/bench_conv.py; SPML_WGRAD_STAGES=3 selects the
-  // latter, 2 / 4 / 5 its other ring depths, which all measure the same: the stage time is matrix-pipe + barrier time,
-  // not load latency).  The 128-wide tiles keep three slots.
-  // (the experiment switch only exists for the 256 x 256 tiles, and only with the depths instantiated below: anything
-  // else takes the default -- a launch that matches no instantiation would leave conv_wgrad_reduce summing an
-  // unwritten workspace)
-  int nst = 42;
-  if (tn == 256 && tk == 256) {
-    if (const char* e = getenv("SPML_WGRAD_STAGES")) {
-      const int v = atoi(e);
-      if (v == 2 || v == 3 || v == 4 || v == 5) nst = v;
-    }
-  } else {
-    nst = 3;
-  }
-  bool launched = false;
-#define SPML_WGRAD(TN_, TK_, ST_)                                                                              \
-  if (tn == TN_ && tk == TK_ && nst == ST_) {                                                                  \
-    const int lds = ST_ * 2 * (TN_ / 32 + TK_ / 32) * 1024;                                                    \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad<TN_, TK_, ST_>),                        \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);                                \
-    hipLaunchKernelGGL((conv_wgrad<TN_, TK_, ST_>), dim3(tiles, a.splits), dim3(512), lds, s, a);              \
-    launched = true;                                                                                           \
-  }
-  SPML_WGRAD(256, 256, 3) SPML_WGRAD(256, 128, 3) SPML_WGRAD(128, 256, 3) SPML_WGRAD(128, 128, 3)
-  SPML_WGRAD(256, 256, 4) SPML_WGRAD(256, 256, 5) SPML_WGRAD(256, 256, 2)
-#undef SPML_WGRAD
-  if (tn == 256 && tk == 256 && nst == 42) {
-    const int lds = 4 * 2 * (256 / 32 + 256 / 32) * 1024;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad<256, 256, 4, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    hipLaunchKernelGGL((conv_wgrad<256, 256, 4, true>), dim3(tiles, a.splits), dim3(512), lds, s, a);
-    launched = true;
-  }
-  if (!launched) return SPML_ERR_UNSUPPORTED;
+  if (r.pair) launch_wgrad<256, 256, 4, true>(r, a, s);
+  else if (tn == 256 && tk == 256 && r.stages == 2) launch_wgrad<256, 256, 2>(r, a, s);
+  else if (tn == 256 && tk == 256 && r.stages == 3) launch_wgrad<256, 256, 3>(r, a, s);
+  else if (tn == 256 && tk == 256 && r.stages == 4) launch_wgrad<256, 256, 4>(r, a, s);
+  else if (tn == 256 && tk == 256 && r.stages == 5) launch_wgrad<256, 256, 5>(r, a, s);
+  else if (tn == 256 && tk == 128) launch_wgrad<256, 128, 3>(r, a, s);
+  else if (tn == 128 && tk == 256) launch_wgrad<128, 256, 3>(r, a, s);
+  else if (tn == 128 && tk == 128) launch_wgrad<128, 128, 3>(r, a, s);
+  else return SPML_ERR_UNSUPPORTED;
   const int64_t items = (int64_t)tiles * tn * (tk / 4);
   hipLaunchKernelGGL(conv_wgrad_reduce, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, (const float*)a.partial,
                      a.splits, tiles, taps, a.k_tiles, K, dy_bound, x_bound, dw, tn, tk, 0);
@@ -1369,29 +1513,14 @@ extern "C" int spml_conv_wgrad_hl8_f32(const void* dy, const float* dy_bound, co
 
 // The weight gradients of the pyramid head's 64-channel branches (conv_wgrad<..., PYR>): dw fp32
 // [branches][64][9][K] = the channels-last storage of each branch's [64, K, 3, 3] gradient, one after the other.
-static inline int pyr_groups(int branches) { return (9 * branches + 3) / 4; }
-
-static inline int pyr_splits(int64_t R, int tiles) {
-  // one 128-KB workgroup per CU: the smallest split count whose last round of 256 is (almost) full
-  const int64_t max_s = (R + 255) / 256;
-  int s = 1;
-  double best = 1e9;
-  for (int c = 1; c <= 16 && c <= max_s; ++c) {
-    const int64_t wgs = (int64_t)tiles * c;
-    const double waste = (double)((wgs + 255) / 256 * 256) / (double)wgs - 1.0;
-    if (waste < best - 0.02) { best = waste; s = c; }
-  }
-  return s;
-}
-
 extern "C" int spml_conv_wgrad_pyramid_hl8_supported(int K, int N, int branches) {
   return N == 64 && K > 0 && (K & 255) == 0 && branches >= 1 && branches <= 4;
 }
 
 extern "C" size_t spml_conv_wgrad_pyramid_workspace_bytes(int n_img, int H, int W, int K, int N, int branches) {
-  if (!spml_conv_wgrad_pyramid_hl8_supported(K, N, branches) || n_img <= 0 || H <= 0 || W <= 0) return 0;
-  const int tiles = pyr_groups(branches) * (K / 256);
-  return (size_t)pyr_splits((int64_t)n_img * H * W, tiles) * tiles * 256 * 256 * sizeof(float);
+  if (n_img <= 0 || H <= 0 || W <= 0) return 0;
+  const WgradRoute r = wgrad_route((int64_t)n_img * H * W, K, N, branches, true);
+  return (size_t)r.splits * r.tiles * r.tn * r.tk * sizeof(float);
 }
 
 extern "C" int spml_conv_wgrad_pyramid_hl8_f32(const void* dy, const float* dy_bound, const void* x,
@@ -1412,19 +1541,29 @@ extern "C" int spml_conv_wgrad_pyramid_hl8_f32(const void* dy, const float* dy_b
   a.partial = static_cast<float*>(ws);
   a.R = (int64_t)n_img * H * W;
   a.H = H; a.W = W; a.K = K; a.N = N; a.dil = 1;
-  a.taps = pyr_groups(branches);                 // (the tile index decodes as (group of four taps, k tile))
+  const WgradRoute r = wgrad_route(a.R, K, N, branches, true);
+  const int tiles = r.tiles;
+  a.taps = r.taps;
   a.pyr_taps = 9 * branches;
-  a.k_tiles = K / 256;
-  const int tiles = a.taps * a.k_tiles;
-  a.splits = pyr_splits(a.R, tiles);
-  a.rows_per_split = (int)(((a.R + a.splits - 1) / a.splits + 15) / 16 * 16);
+  a.k_tiles = r.k_tiles;
+  a.splits = r.splits;
+  a.rows_per_split = r.rows_per_split;
   hipStream_t s = (hipStream_t)stream;
-  const int lds = 4 * 2 * (256 / 32 + 256 / 32) * 1024;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad<256, 256, 4, true, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL((conv_wgrad<256, 256, 4, true, true>), dim3(tiles, a.splits), dim3(512), lds, s, a);
+  launch_wgrad<256, 256, 4, true, true>(r, a, s);
   const int64_t items = (int64_t)tiles * 256 * (256 / 4);
   hipLaunchKernelGGL(conv_wgrad_reduce, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, (const float*)a.partial,
                      a.splits, tiles, a.taps, a.k_tiles, K, dy_bound, x_bound, dw, 256, 256, a.pyr_taps);
   return launch_status();
+}
+
+// The launches' own expressions: wgrad_route is what the two entry points and the workspace sizes read.
+extern "C" const char* spml_conv_wgrad_path_name(int n_img, int H, int W, int K, int N, int taps_or_branches,
+                                                 int pyramid) {
+  if (n_img <= 0 || H <= 0 || W <= 0) return "unsupported";
+  return wgrad_route_name(wgrad_route((int64_t)n_img * H * W, K, N, taps_or_branches, pyramid != 0));
+}
+
+extern "C" int spml_conv_wgrad_splits(int n_img, int H, int W, int K, int N, int taps_or_branches, int pyramid) {
+  if (n_img <= 0 || H <= 0 || W <= 0) return 0;
+  return wgrad_route((int64_t)n_img * H * W, K, N, taps_or_branches, pyramid != 0).splits;
 }

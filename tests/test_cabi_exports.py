@@ -293,3 +293,182 @@ def test_kmeans_route_table(lib_path):
     assert rc == 0, case
     assert n_pass.value == (2 * it if want == 'mfma_f16x2_v4k' else it + 1), case
     assert wgs.value % n_img == 0 and 1 <= wgs.value // n_img <= (seg + 31) // 32, case
+
+
+def _header_names(first_words, declaration):
+  """The quoted names in the header comment that documents `declaration`."""
+  hdr = open(os.path.join(ROOT, 'include', 'spml_hip.h')).read()
+  doc = hdr[hdr.index(first_words):hdr.index(declaration)]
+  return set(re.findall(r'"([a-z0-9_+]+)"', doc))
+
+
+CONV_SWITCHES = ('SPML_CONV_RB', 'SPML_CONV_RG', 'SPML_CONV_NARROW_RB', 'SPML_CONV_CHUNK_MIN_K', 'SPML_WGRAD_STAGES')
+
+
+def _switches(monkeypatch, env):
+  for name in CONV_SWITCHES:
+    monkeypatch.delenv(name, raising=False)
+  for name, value in env.items():
+    monkeypatch.setenv(name, value)
+
+
+def test_conv_route_table(lib_path, monkeypatch):
+  """The host side of a convolution call decides its conv_gemm / conv_wgrad instantiation once (csrc/conv.hip:
+  conv_route, wgrad_route); the five entry points, the statistics layouts, the workspace sizes and the path names read
+  the same record.  Every GPU case of tests/test_conv_gpu.py and tests/test_conv_bn_bwd_stats_gpu.py reaches the
+  instantiation it names under the switches it sets; every name the header lists is reached by at least one of them; the
+  recipe-sized shapes take the production tiles; the layout rules; extremes of the arguments."""
+  import ctypes
+  from spml_amd import _ffi
+  import test_conv_gpu as tc
+  import test_conv_bn_bwd_stats_gpu as tb
+  lib = _ffi.lib()
+  assert tuple(tc.SWITCHES) == CONV_SWITCHES
+  reached, wreached = set(), set()
+  was = _ffi.set_deterministic(False)
+  try:
+    for route, env, label, n, h, w, cin, cout, k, dil in tc.GEMM_CASES + tc.CHUNK_CASES:
+      _switches(monkeypatch, env)
+      for addend in (False, True):
+        assert _ffi.conv_hl8_path_name('plain', n, h, w, cin, cout, k * k, addend) == route, (route, label)
+      reached.add(route)
+      # the shape kinds are what their comments say for the route's tile rows
+      t = dict(tc.GEMM_ROUTES, **tc.CHUNK_ROUTES)[route][1]
+      rows = n * h * w
+      if label == 'a':
+        assert rows < t and rows % 16
+      elif label == 'b':
+        assert rows == t
+      elif label == 'c':
+        assert t < rows < t + 16 and w == 1
+      elif label in ('d1', 'd2'):
+        assert n == 3 and h * w < t and t % (h * w)
+      elif label in ('e', '3x3e'):
+        assert n == 1 and rows >= 2 * t and t % w == 0 and dil > t // w and dil < h
+      elif label == 'f':
+        assert dil >= h and dil >= w
+      elif label == 'g':
+        assert h == 1 and k == 3
+      elif label.startswith('tiles'):
+        assert -(-rows // t) * (cout // 256) == int(label[5:])
+    assert {c[2] for c in tc.GEMM_CASES if c[0] == 'rb5_rg2'} >= {'a', 'b', 'c', 'd1', 'd2', 'e', 'f', 'g', 'k16x1', 'k32x1', 'k48x1', 'k16x3'}
+    assert sorted(int(c[2][5:]) % 8 for c in tc.GEMM_CASES if c[2].startswith('tiles')) == [0, 0, 6, 6]
+    # stages of the chunked cases: K * taps / 16 on either side of the fold
+    assert {c[6] * c[8] * c[8] // 16 for c in tc.CHUNK_CASES} == {64, 65, 129, 72}
+    n, h, w, cin, k, dil = tc.AFFINE_SHAPE
+    for route, env, cout in tc.AFFINE_CASES:
+      _switches(monkeypatch, env)
+      assert _ffi.conv_hl8_path_name('affine', n, h, w, cin, cout, k * k) == route
+      reached.add(route)
+    _switches(monkeypatch, {'SPML_CONV_RG': '2'})              # the inference entry has no two-row-group rung
+    assert _ffi.conv_hl8_path_name('affine', n, h, w, cin, 256, k * k) == 'rb3'
+    assert _ffi.conv_hl8_path_name('plain', n, h, w, cin, 256, k * k) == 'rb5_rg2'
+    assert _ffi.conv_hl8_path_name('pyramid', n, h, w, cin, 256, 2) == 'rb5_rg2'
+    assert _ffi.conv_hl8_path_name('plain', n, h, w, 512, 256, 9) == 'rb3_chunk'      # (chunking comes first)
+    n, h, w, cin = tc.PYR_SHAPE
+    for route, env, det, addend, cout, dils in tc.PYR_CASES:
+      _switches(monkeypatch, env)
+      _ffi.set_deterministic(det)
+      assert _ffi.conv_hl8_path_name('pyramid', n, h, w, cin, cout, len(dils), addend) == route, (route, det, addend)
+      assert ('+tapgroups' in route) == (cout % 256 != 0 and len(dils) > 1 and not addend and not det)
+      reached.add(route)
+    _ffi.set_deterministic(False)
+    for route, env, n, h, w in tc.STATS_CASES:
+      _switches(monkeypatch, env)
+      assert _ffi.conv_hl8_path_name('stats', n, h, w, 64, 256, 1) == route
+      reached.add(route)
+    for (taps, dil, k, cout), (n, h, w), env in tb.CASES:
+      _switches(monkeypatch, env)
+      want = ('rb3_chunk' if 'SPML_CONV_CHUNK_MIN_K' in env else 'rb' + env.get('SPML_CONV_RB', '3')) + '+bstats'
+      assert _ffi.conv_hl8_path_name('bwd_stats', n, h, w, k, cout, taps) == want, (taps, k, cout, n, h, w, env)
+      reached.add(want)
+    assert {(1, 97, 1), (1, 3, 5), (1, 161, 1)} <= {g for _, g, _ in tb.CASES}
+    for route, env, label, n, h, w, cin, cout, k, dil in tc.WGRAD_CASES + tc.WGRAD_SPLIT_CASES:
+      _switches(monkeypatch, env)
+      assert _ffi.conv_wgrad_path_name(n, h, w, cin, cout, k * k) == route, (route, label)
+      wreached.add(route)
+    # one tile: splits = ceil(R / 256); stages per split under the pair kernel: 1, 1, 2, 3 and (10, 9)
+    _switches(monkeypatch, {})
+    assert [_ffi.conv_wgrad_splits(c[3], c[4], c[5], 256, 256, 1) for c in tc.WGRAD_SPLIT_CASES[:len(tc.WGRAD_SPLITS)]] == tc.WGRAD_SPLITS
+    assert {1, 2, 3, 4, 7, 8, 9, 12, 15, 16} <= set(tc.WGRAD_SPLITS)
+    assert _ffi.conv_wgrad_splits(1, 296, 1, 256, 256, 1) == 2 and _ffi.conv_wgrad_splits(1, 40, 1, 256, 256, 1) == 1
+    for cin, dils in tc.PYR_WGRAD_CASES:
+      assert _ffi.conv_wgrad_path_name(2, 9, 11, cin, 64, len(dils), True) == 'pyr_t256x256_pair4'
+      wreached.add('pyr_t256x256_pair4')
+    assert sorted({(9 * len(d)) % 4 for _, d in tc.PYR_WGRAD_CASES}) == [0, 1, 2, 3]      # padding taps of the last group
+
+    names = _header_names('Which conv_gemm instantiation', 'const char* spml_conv_hl8_path_name')
+    wnames = _header_names('The same for the weight gradient', 'const char* spml_conv_wgrad_path_name')
+    assert len(names) == 26 and len(wnames) == 10
+    assert reached == names - {'unsupported'}, (sorted(names - reached), sorted(reached - names))
+    assert wreached == wnames - {'unsupported'}, (sorted(wnames - wreached), sorted(wreached - wnames))
+
+    # what the recipe-sized shapes take (batch 16, 65 x 65 maps)
+    _switches(monkeypatch, {})
+    assert _ffi.conv_hl8_path_name('stats', 16, 65, 65, 256, 256, 9) == 'rb5+stats'       # 3x3 dilation 2, 256 -> 256
+    assert _ffi.conv_hl8_path_name('plain', 16, 65, 65, 256, 256, 9) == 'rb5'
+    assert _ffi.conv_hl8_path_name('stats', 16, 65, 65, 1024, 256, 1) == 'rb5+stats'      # 1x1 1024 -> 256
+    assert _ffi.conv_hl8_path_name('plain', 16, 65, 65, 2048, 512, 1, True) == 'rb5'      # data gradient of 512 -> 2048
+    assert _ffi.conv_hl8_path_name('bwd_stats', 16, 65, 65, 2048, 512, 1) == 'rb5+bstats'
+    assert _ffi.conv_hl8_path_name('pyramid', 16, 65, 65, 256, 64, 4) == 'n64_chunk+tapgroups'
+    assert _ffi.conv_hl8_path_name('pyramid', 16, 65, 65, 256, 64, 4, True) == 'n64_chunk'
+    assert _ffi.conv_hl8_path_name('plain', 16, 65, 65, 512, 512, 9) == 'rb3_chunk'       # 3x3 of res5: K * taps = 4608
+    assert _ffi.conv_wgrad_path_name(16, 65, 65, 256, 256, 9) == 't256x256_pair4'
+    assert _ffi.conv_wgrad_path_name(16, 65, 65, 2048, 64, 4, True) == 'pyr_t256x256_pair4'
+    # by problem size: tiles5 = ceil(R / 160) * (N / 256) against 192 and 384
+    assert [_ffi.conv_hl8_path_name('plain', 1, 160 * t, 1, 64, 256, 1) for t in (191, 192, 383, 384)] == ['rb3', 'rb4', 'rb4', 'rb5']
+    # the chunk threshold
+    assert [_ffi.conv_hl8_path_name('plain', 1, 9, 9, kk, 256, t) for kk, t in ((448, 9), (464, 9), (4080, 1), (4096, 1))] == \
+        ['rb3', 'rb3_chunk', 'rb3', 'rb3_chunk']
+
+    # statistics layout: no rows under two row groups and for narrow N; at most 4096 row tiles (host only)
+    chunks, rows = ctypes.c_int(0), ctypes.c_int(0)
+    layout = lambda *a: lib.spml_conv_hl8_stats_layout(*(a + (ctypes.byref(chunks), ctypes.byref(rows))))
+    assert layout(16, 160, 256, 64, 256, 1) == 0 and (chunks.value, rows.value) == (4096, 160)
+    assert layout(16, 203, 203, 64, 256, 1) == -2 and _ffi.conv_hl8_path_name('stats', 16, 203, 203, 64, 256, 1) == 'unsupported'
+    assert _ffi.conv_hl8_path_name('plain', 16, 203, 203, 64, 256, 1) == 'rb5'
+    assert lib.spml_conv_hl8_bwd_stats_layout(16, 203, 203, 64, 256, 1, ctypes.byref(chunks), ctypes.byref(rows)) == -2
+    for cout in (64, 128, 192):
+      assert layout(2, 17, 19, 64, cout, 1) == -2
+      assert _ffi.conv_hl8_path_name('stats', 2, 17, 19, 64, cout, 1) == 'unsupported'
+    assert layout(2, 17, 19, 64, 256, 1) == 0 and (chunks.value, rows.value) == (7, 96)
+    _switches(monkeypatch, {'SPML_CONV_RG': '2'})
+    assert layout(2, 17, 19, 64, 256, 1) == -2 and layout(2, 17, 19, 512, 256, 9) == -2
+    assert _ffi.conv_hl8_path_name('bwd_stats', 2, 17, 19, 64, 256, 1) == 'unsupported'
+    _switches(monkeypatch, {})
+
+    # outside the domain
+    for args in [('plain', 1, 9, 9, 40, 256, 1), ('plain', 1, 9, 9, 64, 96, 9), ('plain', 1, 9, 9, 64, 256, 4),
+                 ('plain', 0, 9, 9, 64, 256, 1), ('pyramid', 1, 9, 9, 64, 64, 5), ('pyramid', 1, 9, 9, 64, 64, 0)]:
+      assert _ffi.conv_hl8_path_name(*args) == 'unsupported', args
+    assert lib.spml_conv_hl8_path_name(7, 1, 9, 9, 64, 256, 1, 0) == b'unsupported'
+    assert _ffi.conv_wgrad_path_name(1, 9, 9, 64, 256, 1) == 'unsupported' and _ffi.conv_wgrad_splits(1, 9, 9, 64, 256, 1) == 0
+    assert _ffi.conv_wgrad_path_name(1, 9, 9, 256, 128, 4, True) == 'unsupported'
+    assert lib.spml_conv_wgrad_workspace_bytes(1, 9, 9, 64, 256, 1) == 0
+
+    # extremes: n_img * H * W around 2^31, tiles > 256 in the split count: names and counts well defined, and the
+    # workspace is splits * tiles * tile n * tile k floats
+    tile = lambda c: 256 if c % 256 == 0 else 128
+    for n, h, w in [(1, 46341, 46341), (2, 32768, 32768), (32768, 256, 256), (2, 32768, 32767), (16, 65, 65), (1, 1, 1)]:
+      for cin, cout in [(64, 256), (128, 128), (256, 64), (4096, 512), (2048, 2048)]:
+        for taps in (1, 9):
+          for entry in ('plain', 'stats', 'bwd_stats', 'affine'):
+            assert _ffi.conv_hl8_path_name(entry, n, h, w, cin, cout, taps) in names, (entry, n, h, w, cin, cout, taps)
+          if cin % 128 or cout % 128:
+            continue
+          assert _ffi.conv_wgrad_path_name(n, h, w, cin, cout, taps) in wnames - {'unsupported'}
+          splits = _ffi.conv_wgrad_splits(n, h, w, cin, cout, taps)
+          tiles = (cout // tile(cout)) * (cin // tile(cin)) * taps
+          assert 1 <= splits <= max(1, min(256 // tiles if tiles <= 256 else 16, -(-n * h * w // 256))), (n, h, w, cin, cout, taps)
+          assert lib.spml_conv_wgrad_workspace_bytes(n, h, w, cin, cout, taps) == splits * tiles * tile(cout) * tile(cin) * 4
+      for branches in (1, 2, 3, 4):
+        for cin in (256, 2048):
+          assert _ffi.conv_hl8_path_name('pyramid', n, h, w, cin, 64, branches) in names
+          splits = _ffi.conv_wgrad_splits(n, h, w, cin, 64, branches, True)
+          tiles = (9 * branches + 3) // 4 * (cin // 256)
+          assert 1 <= splits <= 16
+          assert lib.spml_conv_wgrad_pyramid_workspace_bytes(n, h, w, cin, 64, branches) == splits * tiles * 256 * 256 * 4
+    # 288 tiles: 7 splits fill 2016 of 2048 places (1.6 % idle); 8 would fill 9 rounds exactly but gains under 2 %
+    assert _ffi.conv_wgrad_splits(16, 65, 65, 4096, 512, 9) == 7
+  finally:
+    _ffi.set_deterministic(was)

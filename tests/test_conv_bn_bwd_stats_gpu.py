@@ -29,6 +29,10 @@ EXTRA = [dict(SPML_CONV_RB='4'), dict(SPML_CONV_RB='5'), dict(SPML_CONV_CHUNK_MI
 CASES = [(c, g, {}) for c in CONVS for g in GEOMS] + \
         [(c, GEOMS[0], e) for c in CONVS[:2] for e in EXTRA[:2]] + [(CONVS[1], g, EXTRA[2]) for g in GEOMS[:2]] + \
         [(CONVS[2], g, EXTRA[1]) for g in GEOMS[1:]]
+# geometry edges of the epilogue's row range check: one row past a tile (97 = 96 + 1 on the default 96-row tiles,
+# 161 = 160 + 1 under SPML_CONV_RB=5: the last chunk is a single row) and fewer rows than one 16-row block (15)
+EDGE_GEOMS = [(1, 97, 1), (1, 3, 5)]
+CASES += [(c, g, {}) for c in CONVS for g in EDGE_GEOMS] + [(CONVS[0], (1, 161, 1), EXTRA[1]), (CONVS[1], (1, 3, 5), EXTRA[1])]
 
 
 def _case_id(case):

@@ -450,3 +450,586 @@ def test_epilogue_statistics_fall_back_on_narrow_outputs():
   wf, _ = _ffi.hl8_weight(wt)
   out, st = _ffi.conv_hl8_stats(_ffi.hl8_from_f32(x), wf, 1, 9, 9, 1)
   assert st is None and out.shape == (1, 128, 9, 9)
+
+
+# =====================================================================================================================
+# Branch-by-branch parity of csrc/conv.hip: every conv_gemm / conv_wgrad instantiation the library can launch, at the
+# smallest shapes at which the branch exists, against fp64 -- under the bound of this file (_within, FLOOR).  The case
+# lists are module-level data: tests/test_cabi_exports.py proves on the host (spml_conv_hl8_path_name,
+# spml_conv_wgrad_path_name) that every case reaches the instantiation it names and that every name of the header is
+# reached.  Observed figures: profiles/conv_branch_parity.md (`pytest -s` prints them).
+# =====================================================================================================================
+import ctypes
+
+import numpy as np
+
+import conv_ref
+
+SWITCHES = ('SPML_CONV_RB', 'SPML_CONV_RG', 'SPML_CONV_NARROW_RB', 'SPML_CONV_CHUNK_MIN_K', 'SPML_WGRAD_STAGES')
+_RB4, _RB5, _RG2, _NRB3 = {'SPML_CONV_RB': '4'}, {'SPML_CONV_RB': '5'}, {'SPML_CONV_RG': '2'}, {'SPML_CONV_NARROW_RB': '3'}
+_CHUNK = {'SPML_CONV_CHUNK_MIN_K': '1024'}
+# route -> (switches, tile rows T, output channels N of the cases)
+GEMM_ROUTES = {'rb3': ({}, 96, 256), 'rb4': (_RB4, 128, 256), 'rb5': (_RB5, 160, 256), 'rb5_rg2': (_RG2, 320, 256),
+               'n128': ({}, 256, 128), 'n64': ({}, 256, 64), 'n64_rb3': (_NRB3, 384, 64)}
+CHUNK_ROUTES = {'rb3_chunk': (_CHUNK, 96, 256), 'n128_chunk': (_CHUNK, 192, 128), 'n64_chunk': (_CHUNK, 256, 64),
+                'n64_rb3_chunk': (dict(_CHUNK, **_NRB3), 384, 64)}
+
+
+def set_switches(monkeypatch, env):
+  for name in SWITCHES:
+    monkeypatch.delenv(name, raising=False)
+  for name, value in env.items():
+    monkeypatch.setenv(name, value)
+
+
+def _shape_kinds(t):
+  """(kind, n_img, h, w, kernel side, dilation) for tile rows t; R = n_img * h * w."""
+  return [('a', 1, 7, t // 8 - 1, 3, 1),                 # R < T, R % 16 != 0
+          ('b', 1, 8, t // 8, 3, 2),                     # R == T
+          ('c', 1, t + 1, 1, 3, 1),                      # T < R < T + 16 on a map with W = 1: a whole 16-row block past the end
+          ('d1', 3, 5, 7, 3, 1), ('d2', 3, 5, 7, 3, 2),  # three images inside / across a tile: every tap active, no leak
+          ('e', 1, 3 * t // 16, 16, 3, t // 16 + 1),     # three tiles of t / 16 image rows: the first skips the top taps,
+                                                         # the last the bottom taps, the middle one none
+          ('f', 2, 6, 9, 3, 9),                          # dilation >= H and >= W: only the centre tap contributes
+          ('g', 1, 1, t + 5, 3, 1)]                      # H = 1 under 3x3
+
+
+# (route, switches, label, n_img, h, w, K, N, kernel side, dilation)
+GEMM_CASES = [(route, env, kind, n, h, w, 64, cout, k, dil)
+              for route, (env, t, cout) in GEMM_ROUTES.items() for kind, n, h, w, k, dil in _shape_kinds(t)]
+# fewer k-steps than the ring is deep (1, 2, 3 stages against three slots), and K = 16 under nine taps
+GEMM_CASES += [(route, env, 'k%dx%d' % (cin, k), 2, 5, t // 8 + 1, cin, cout, k, 1)
+               for route, (env, t, cout) in GEMM_ROUTES.items() for cin, k in [(16, 1), (32, 1), (48, 1), (16, 3)]]
+# column tiles: every tile width and 1, 2, 3, 5 of them
+GEMM_CASES += [(route, {}, 'n%d' % cout, 2, 9, 11, 64, cout, 3, 2)
+               for cout, route in [(64, 'n64'), (128, 'n128'), (192, 'n64'), (256, 'rb3'), (320, 'n64'), (384, 'n128'),
+                                   (512, 'rb3'), (768, 'rb3')]]
+# the XCD remap of the tile index (n_tiles % 8 == 0): 16 and 8 tiles against 6 and 14 on the same N
+GEMM_CASES += [('rb3', {}, 'tiles%d' % (2 * rt), 1, rt * 12, 8, 32, 512, 1, 1) for rt in (8, 4, 3, 7)]
+# chunked accumulation with the threshold lowered to 1024: 64 stages (the fold is the last stage), 65, 129, 72 (3x3),
+# and the 3x3 laid out as kind (e): the tiles that skip a tap row run 48 stages and never fold, their neighbour does
+CHUNK_CASES = []
+for _route, (_env, _t, _cout) in CHUNK_ROUTES.items():
+  CHUNK_CASES += [(_route, _env, 'k%d' % _cin, 1, _t + 5, 1, _cin, _cout, 1, 1) for _cin in (1024, 1040, 2064)]
+  CHUNK_CASES += [(_route, _env, '3x3', 1, 7, _t // 8 - 1, 128, _cout, 3, 2),
+                  (_route, _env, '3x3e', 1, 3 * _t // 16, 16, 128, _cout, 3, _t // 16 + 1)]
+
+
+def _gemm_id(case):
+  return '%s-%s' % (case[0], case[2])
+
+
+def _report(what, route, e_got, e_lib, bound=None):
+  print('PARITY\t%s\t%s\t%.3e\t%.3e\t%.3e' % (what, route, e_got, bound if bound is not None else FLOOR, e_lib))
+
+
+def _mask_bytes(rows, n, gen):
+  """Random ReLU-mask bytes [rows][n / 4] (only bits 0..3 of a byte gate anything) with an all-zero row, an all-one
+  row and a row that has only the unused high bits."""
+  m = torch.randint(0, 256, (rows, n // 4), generator=gen, dtype=torch.uint8)
+  m[0] = 0
+  m[rows // 2] = 0xff
+  m[rows - 1] = 0xf0
+  return m
+
+
+def _mask_bits_nchw(m, n_img, h, w, n):
+  bits = (m.view(-1, n // 4, 1) >> torch.arange(4, dtype=torch.uint8).view(1, 1, 4)) & 1
+  return bits.reshape(n_img, h, w, n).permute(0, 3, 1, 2).double()
+
+
+@pytest.mark.parametrize('case', GEMM_CASES, ids=_gemm_id)
+def test_every_conv_gemm_route_forward_and_data_gradient(case, monkeypatch):
+  """spml_conv_hl8_f32 on one route: forward (no addend), data gradient with an addend, and with an addend under a
+  ReLU mask -- each against fp64 with the same addend and mask, each called twice (no atomics: bit-identical)."""
+  route, env, kind, n, h, w, cin, cout, k, dil = case
+  set_switches(monkeypatch, env)
+  assert _ffi.conv_hl8_path_name('plain', n, h, w, cin, cout, k * k) == route
+  assert _ffi.conv_hl8_path_name('plain', n, h, w, cin, cout, k * k, True) == route
+  gen = torch.Generator().manual_seed(SEED + 131 * cin + cout + 7 * h + w)
+  pad = dil * (k // 2)
+  # forward: x [n, cin] -> [n, cout]
+  x = _nhwc(torch.randn(n, cin, h, w, generator=gen).to(DEV))
+  wt = (torch.randn(cout, cin, k, k, generator=gen) * (2.0 / (cin * k * k)) ** 0.5).to(DEV)
+  ref = F.conv2d(x.double(), wt.double(), padding=pad, dilation=dil)
+  lib32 = F.conv2d(x, wt, padding=pad, dilation=dil)
+  wf, _ = _ffi.hl8_weight(wt)
+  xa = _ffi.hl8_from_f32(x)
+  got = _ffi.conv_hl8(xa, wf, n, h, w, k * k, dil)
+  assert torch.equal(got, _ffi.conv_hl8(xa, wf, n, h, w, k * k, dil))
+  e_got, e_lib = _rel(got, ref), _rel(lib32, ref)
+  _report('fwd %s' % _gemm_id(case), route, e_got, e_lib)
+  _within(e_got, e_lib, FLOOR, 'branch fwd ' + _gemm_id(case))
+  # data gradient: dy [n, cin] -> [n, cout] through the transposed, tap-mirrored operand of a cin -> cout ... weight,
+  # i.e. a convolution weight [cin (its outputs)][cout (its inputs)]
+  wd = (torch.randn(cin, cout, k, k, generator=gen) * (2.0 / (cin * k * k)) ** 0.5).to(DEV)
+  dy = _nhwc(torch.randn(n, cin, h, w, generator=gen).to(DEV))
+  ref = torch.nn.grad.conv2d_input((n, cout, h, w), wd.double(), dy.double(), padding=pad, dilation=dil)
+  lib32 = torch.nn.grad.conv2d_input((n, cout, h, w), wd, dy, padding=pad, dilation=dil)
+  scale = float(ref.std()) if ref.numel() > 1 else 1.0
+  res = _nhwc((torch.randn(n, cout, h, w, generator=gen) * scale).to(DEV))      # the scale of the output: a wrong mask
+  mask = _mask_bytes(n * h * w, cout, gen)                                        # bit is an O(1) error
+  bits = _mask_bits_nchw(mask, n, h, w, cout).to(DEV)
+  mask = mask.to(DEV)
+  _, wtr = _ffi.hl8_weight(wd)
+  dya = _ffi.hl8_from_f32(dy)
+  for what, kw, add in (('addend', dict(addend=res), res.double()),
+                        ('mask', dict(addend=res, addend_mask=mask), res.double() * bits)):
+    got = _ffi.conv_hl8(dya, wtr, n, h, w, k * k, dil, **kw)
+    assert torch.equal(got, _ffi.conv_hl8(dya, wtr, n, h, w, k * k, dil, **kw))
+    full = ref + add
+    e_got, e_lib = _rel(got, full), _rel(lib32.double() + add, full)
+    _report('dgrad+%s %s' % (what, _gemm_id(case)), route, e_got, e_lib)
+    _within(e_got, e_lib, FLOOR, 'branch dgrad %s %s' % (what, _gemm_id(case)))
+  if kind == 'f':                                          # only the centre tap: the 1x1 convolution with that slice
+    centre = F.conv2d(x.double(), wt.double()[:, :, 1:2, 1:2])
+    assert _rel(_ffi.conv_hl8(xa, wf, n, h, w, k * k, dil), centre) <= FLOOR
+
+
+@pytest.mark.parametrize('case', CHUNK_CASES, ids=_gemm_id)
+def test_chunked_accumulation_on_every_route(case, monkeypatch):
+  route, env, kind, n, h, w, cin, cout, k, dil = case
+  set_switches(monkeypatch, env)
+  assert _ffi.conv_hl8_path_name('plain', n, h, w, cin, cout, k * k) == route
+  gen = torch.Generator().manual_seed(SEED + cin + cout + h)
+  pad = dil * (k // 2)
+  x = _nhwc(torch.randn(n, cin, h, w, generator=gen).clamp_min(0).to(DEV))
+  wt = (torch.randn(cout, cin, k, k, generator=gen) * (2.0 / (cin * k * k)) ** 0.5).to(DEV)
+  ref = F.conv2d(x.double(), wt.double(), padding=pad, dilation=dil)
+  lib32 = F.conv2d(x, wt, padding=pad, dilation=dil)
+  wf, _ = _ffi.hl8_weight(wt)
+  xa = _ffi.hl8_from_f32(x)
+  got = _ffi.conv_hl8(xa, wf, n, h, w, k * k, dil)
+  assert torch.equal(got, _ffi.conv_hl8(xa, wf, n, h, w, k * k, dil))
+  e_got, e_lib = _rel(got, ref), _rel(lib32, ref)
+  _report('chunk %s' % _gemm_id(case), route, e_got, e_lib)
+  _within(e_got, e_lib, FLOOR, 'branch chunk ' + _gemm_id(case))
+
+
+def test_row_tile_heights_on_the_same_inputs(monkeypatch):
+  """rb3, rb4, rb5 and rb5_rg2 on one input: each within FLOOR; whether their bits agree is printed for
+  profiles/conv_branch_parity.md, not asserted (the k order of a tile does not depend on its height, but nothing
+  promises it)."""
+  n, h, w, cin, cout = 2, 13, 17, 128, 256
+  gen = torch.Generator().manual_seed(SEED + 77)
+  x = _nhwc(torch.randn(n, cin, h, w, generator=gen).to(DEV))
+  wt = (torch.randn(cout, cin, 3, 3, generator=gen) * (2.0 / (9 * cin)) ** 0.5).to(DEV)
+  ref = F.conv2d(x.double(), wt.double(), padding=2, dilation=2)
+  wf, _ = _ffi.hl8_weight(wt)
+  xa = _ffi.hl8_from_f32(x)
+  outs = {}
+  for route in ('rb3', 'rb4', 'rb5', 'rb5_rg2'):
+    set_switches(monkeypatch, GEMM_ROUTES[route][0])
+    assert _ffi.conv_hl8_path_name('plain', n, h, w, cin, cout, 9) == route
+    outs[route] = _ffi.conv_hl8(xa, wf, n, h, w, 9, 2)
+    assert _rel(outs[route], ref) <= FLOOR
+  print('PARITY-BITS\t' + '\t'.join('%s==rb3:%s' % (r, torch.equal(outs[r], outs['rb3'])) for r in ('rb4', 'rb5', 'rb5_rg2')))
+
+
+# ---- spml_conv_hl8_affine_f32 ---------------------------------------------------------------------------------------
+# (route, switches): 2 x 9 x 11 maps, 64 -> N, 3x3 dilation 2 (K * taps = 576)
+AFFINE_SHAPE = (2, 9, 11, 64, 3, 2)
+AFFINE_CASES = [('rb3', {}, 256), ('rb5', _RB5, 256), ('n128', {}, 128), ('n64', {}, 64),
+                ('rb3_chunk', {'SPML_CONV_CHUNK_MIN_K': '512'}, 256)]
+
+
+def _affine_call(xa, wf, bias, addend, relu, n, h, w, taps, dil, poison=1e30):
+  out = torch.empty((n, wf.rows, h, w), dtype=torch.float32, device=DEV, memory_format=torch.channels_last)
+  bound = torch.full((1,), poison, dtype=torch.float32, device=DEV)
+  _ffi.check(_ffi.lib().spml_conv_hl8_affine_f32(
+      _ffi.ptr(xa.data), _ffi._dp(xa.bound), _ffi.ptr(wf.data), _ffi._dp(wf.bound), _ffi._dp(bias),
+      _ffi._ptr_any(addend, True), int(relu), _ffi._ptr_any(out), _ffi._dp(bound), n, h, w, xa.channels, wf.rows, taps,
+      dil, _ffi.stream_ptr()), 'spml_conv_hl8_affine_f32')
+  return out, bound
+
+
+@pytest.mark.parametrize('case', AFFINE_CASES, ids=lambda c: c[0])
+def test_affine_epilogue_combinations(case, monkeypatch):
+  """{no bias, bias} x {no addend, addend} x {ReLU off, on} against fp64 with the same terms; out_bound (poisoned
+  before the call) is max |out| exactly; with nothing switched on the output is conv_hl8's, bit for bit."""
+  route, env, cout = case
+  n, h, w, cin, k, dil = AFFINE_SHAPE
+  set_switches(monkeypatch, env)
+  assert _ffi.conv_hl8_path_name('affine', n, h, w, cin, cout, k * k) == route
+  gen = torch.Generator().manual_seed(SEED + cout + 19)
+  x = _nhwc(torch.randn(n, cin, h, w, generator=gen).to(DEV))
+  wt = (torch.randn(cout, cin, k, k, generator=gen) * (2.0 / (cin * k * k)) ** 0.5).to(DEV)
+  conv64 = F.conv2d(x.double(), wt.double(), padding=dil, dilation=dil)
+  conv32 = F.conv2d(x, wt, padding=dil, dilation=dil).double()
+  scale = float(conv64.std())
+  bias = (torch.randn(cout, generator=gen) * scale).to(DEV)
+  res = _nhwc((torch.randn(n, cout, h, w, generator=gen) * scale).to(DEV))
+  wf, _ = _ffi.hl8_weight(wt)
+  xa = _ffi.hl8_from_f32(x)
+  for use_bias in (False, True):
+    for use_add in (False, True):
+      for relu in (False, True):
+        extra = (bias.double().view(1, -1, 1, 1) if use_bias else 0) + (res.double() if use_add else 0)
+        ref, lib = conv64 + extra, conv32 + extra
+        if relu:
+          ref, lib = ref.clamp_min(0), lib.clamp_min(0)
+        got, bound = _affine_call(xa, wf, bias if use_bias else None, res if use_add else None, relu, n, h, w, k * k, dil)
+        what = 'affine %s bias%d add%d relu%d' % (route, use_bias, use_add, relu)
+        e_got, e_lib = _rel(got, ref), _rel(lib, ref)
+        _report(what, route, e_got, e_lib)
+        _within(e_got, e_lib, FLOOR, 'branch ' + what)
+        assert float(bound) == float(got.abs().max()), what
+        again, bound2 = _affine_call(xa, wf, bias if use_bias else None, res if use_add else None, relu, n, h, w, k * k,
+                                     dil, poison=float('inf'))
+        assert torch.equal(again, got) and torch.equal(bound2, bound)
+        if not (use_bias or use_add or relu) and _ffi.conv_hl8_path_name('plain', n, h, w, cin, cout, k * k) == route:
+          assert torch.equal(got, _ffi.conv_hl8(xa, wf, n, h, w, k * k, dil))
+
+
+# ---- spml_conv_hl8_pyramid_f32 --------------------------------------------------------------------------------------
+PYR_SHAPE = (2, 9, 11, 64)                     # n_img, h, w, K
+PYR_DILS = [(2,), (3, 12), (2, 12, 2), (1, 3, 12, 3)]       # one dilation >= H and >= W, one pair equal
+# (route, switches, deterministic mode, addend, N, dilations)
+PYR_CASES = []
+for _cout, _base in ((64, 'n64'), (128, 'n128')):
+  for _d in PYR_DILS:
+    PYR_CASES += [(_base + ('+tapgroups' if len(_d) > 1 else ''), {}, False, False, _cout, _d),
+                  (_base, {}, True, False, _cout, _d), (_base, {}, False, True, _cout, _d)]
+PYR_CASES += [('n64_rb3+tapgroups', _NRB3, False, False, 64, PYR_DILS[3]), ('n64_rb3', _NRB3, True, False, 64, PYR_DILS[2]),
+              ('n64_chunk+tapgroups', _CHUNK, False, False, 64, PYR_DILS[3]),
+              ('n64_rb3_chunk+tapgroups', dict(_CHUNK, **_NRB3), False, False, 64, PYR_DILS[3]),
+              ('n128_chunk+tapgroups', _CHUNK, False, False, 128, PYR_DILS[3]),
+              ('n128_chunk', _CHUNK, False, True, 128, PYR_DILS[3]),
+              ('rb3', {}, False, False, 256, PYR_DILS[3]), ('rb3_chunk', _CHUNK, False, False, 256, PYR_DILS[3]),
+              ('rb3', {}, False, True, 256, PYR_DILS[3]), ('rb5_rg2', _RG2, False, False, 256, PYR_DILS[1])]
+
+
+def _pyr_id(case):
+  return '%s-n%d-g%d%s%s' % (case[0], case[4], len(case[5]), '-det' if case[2] else '', '-addend' if case[3] else '')
+
+
+def _pyramid_call(xa, ws, bias, dils, n, h, w, addend=None):
+  groups = len(ws)
+  cout, cin = ws[0].shape[0], ws[0].shape[1]
+  cat = torch.cat([wt.permute(0, 2, 3, 1).reshape(cout, 9 * cin) for wt in ws], dim=1).contiguous()
+  b = _ffi.hl8_from_f32(cat, cout, 9 * groups * cin)
+  out = torch.empty((n, cout, h, w), dtype=torch.float32, device=DEV, memory_format=torch.channels_last)
+  dil = (ctypes.c_int * 4)(*([int(d) for d in dils] + [1] * (4 - groups)))
+  _ffi.check(_ffi.lib().spml_conv_hl8_pyramid_f32(
+      _ffi.ptr(xa.data), _ffi._dp(xa.bound), _ffi.ptr(b.data), _ffi._dp(b.bound), _ffi._dp(bias),
+      _ffi._ptr_any(addend, True), _ffi._ptr_any(out), n, h, w, cin, cout, groups, dil, _ffi.stream_ptr()),
+             'spml_conv_hl8_pyramid_f32')
+  return out
+
+
+@pytest.mark.parametrize('case', PYR_CASES, ids=_pyr_id)
+def test_pyramid_entry_on_every_route(case, monkeypatch):
+  """The sum of 1..4 dilated 3x3 branches in one launch, with and without bias: the tap-group grid (fp32 atomics:
+  FLOOR only), one workgroup per tile in deterministic mode (two calls bit-identical) and with an addend."""
+  route, env, det, use_add, cout, dils = case
+  n, h, w, cin = PYR_SHAPE
+  set_switches(monkeypatch, env)
+  was = _ffi.set_deterministic(det)
+  try:
+    assert _ffi.conv_hl8_path_name('pyramid', n, h, w, cin, cout, len(dils), use_add) == route
+    gen = torch.Generator().manual_seed(SEED + cout + len(dils) + 5 * det + 3 * use_add)
+    x = _nhwc(torch.randn(n, cin, h, w, generator=gen).to(DEV))
+    ws = [(torch.randn(cout, cin, 3, 3, generator=gen) * (2.0 / (9 * cin * len(dils))) ** 0.5).to(DEV) for _ in dils]
+    conv64 = sum(F.conv2d(x.double(), wt.double(), None, 1, d, d) for wt, d in zip(ws, dils))
+    conv32 = sum(F.conv2d(x, wt, None, 1, d, d) for wt, d in zip(ws, dils)).double()
+    scale = float(conv64.std())
+    bias = (torch.randn(cout, generator=gen) * scale).to(DEV)
+    res = _nhwc((torch.randn(n, cout, h, w, generator=gen) * scale).to(DEV)) if use_add else None
+    xa = _ffi.hl8_from_f32(x)
+    for use_bias in (False, True):
+      extra = (bias.double().view(1, -1, 1, 1) if use_bias else 0) + (res.double() if use_add else 0)
+      got = _pyramid_call(xa, ws, bias if use_bias else None, dils, n, h, w, res)
+      e_got, e_lib = _rel(got, conv64 + extra), _rel(conv32 + extra, conv64 + extra)
+      _report('pyramid %s bias%d' % (_pyr_id(case), use_bias), route, e_got, e_lib)
+      _within(e_got, e_lib, FLOOR, 'branch pyramid %s bias%d' % (_pyr_id(case), use_bias))
+      if '+tapgroups' not in route:
+        assert torch.equal(got, _pyramid_call(xa, ws, bias if use_bias else None, dils, n, h, w, res))
+  finally:
+    _ffi.set_deterministic(was)
+
+
+@pytest.mark.parametrize('groups', [1, 2, 3])
+def test_pyramid_data_gradient_packing(groups):
+  """conv_hl8_pyramid_dgrad (spml_absmax_bound_f32 accumulating one bound over the branches,
+  spml_hl8_weight_transposed_into_f32 writing each branch's tap range) at 1 to 3 branches."""
+  n, h, w, cin, cout = 2, 9, 11, 128, 64
+  dils = PYR_DILS[groups - 1]
+  gen = torch.Generator().manual_seed(SEED + groups)
+  ws = [(torch.randn(cout, cin, 3, 3, generator=gen) * (g + 1) * (2.0 / (9 * cin)) ** 0.5).to(DEV) for g in range(groups)]
+  dy = _nhwc(torch.randn(n, cout, h, w, generator=gen).to(DEV))
+  ref = sum(torch.nn.grad.conv2d_input((n, cin, h, w), wt.double(), dy.double(), padding=d, dilation=d)
+            for wt, d in zip(ws, dils))
+  lib32 = sum(torch.nn.grad.conv2d_input((n, cin, h, w), wt, dy, padding=d, dilation=d) for wt, d in zip(ws, dils))
+  got = _ffi.conv_hl8_pyramid_dgrad(_ffi.hl8_from_f32(dy), ws, dils, n, h, w)
+  e_got, e_lib = _rel(got, ref), _rel(lib32, ref)
+  _report('pyramid dgrad g%d' % groups, _ffi.conv_hl8_path_name('pyramid', n, h, w, cout, cin, groups), e_got, e_lib)
+  _within(e_got, e_lib, FLOOR, 'branch pyramid dgrad g%d' % groups)
+
+
+# ---- forward statistics ---------------------------------------------------------------------------------------------
+# (route, switches, T) x (a) R < T ragged, (b) R == T, R == T + 1 (the last chunk is one row); 1x1 64 -> 256
+STATS_ROUTES = [('rb3+stats', {}, 96), ('rb4+stats', _RB4, 128), ('rb5+stats', _RB5, 160),
+                ('rb3_chunk+stats', {'SPML_CONV_CHUNK_MIN_K': '64'}, 96)]
+STATS_CASES = [(route, env, n, h, w) for route, env, t in STATS_ROUTES
+               for n, h, w in [(1, 7, t // 8 - 1), (1, 8, t // 8), (1, t + 1, 1)]]
+
+
+@pytest.mark.parametrize('case', STATS_CASES, ids=lambda c: '%s-r%d' % (c[0], c[2] * c[3] * c[4]))
+def test_epilogue_statistics_on_every_tile_height(case, monkeypatch):
+  route, env, n, h, w = case
+  set_switches(monkeypatch, env)
+  assert _ffi.conv_hl8_path_name('stats', n, h, w, 64, 256, 1) == route
+  test_epilogue_statistics_feed_the_batch_norm(n, 64, 256, h, w, 1, 1)
+  rows = n * h * w
+  t = {'rb3': 96, 'rb4': 128, 'rb5': 160}[route[:3]]
+  if rows == t + 1:                                        # a chunk of one row: its mean is the value, M2 0, max == min
+    gen = torch.Generator().manual_seed(SEED + 3)
+    x = _nhwc(torch.randn(n, 64, h, w, generator=gen).to(DEV))
+    wf, _ = _ffi.hl8_weight((torch.randn(256, 64, 1, 1, generator=gen) / 8).to(DEV))
+    out, st = _ffi.conv_hl8_stats(_ffi.hl8_from_f32(x), wf, n, h, w, 1)
+    assert st.chunks == 2 and st.chunk_rows == t
+    last = out.permute(0, 2, 3, 1).reshape(rows, 256)[t]
+    assert torch.equal(st.data[0, 1], last) and torch.equal(st.data[2, 1], last) and torch.equal(st.data[3, 1], last)
+    assert float(st.data[1, 1].abs().max()) == 0.0
+
+
+def test_epilogue_statistics_fall_back_under_two_row_groups(monkeypatch):
+  set_switches(monkeypatch, _RG2)
+  gen = torch.Generator().manual_seed(SEED + 5)
+  x = _nhwc(torch.randn(1, 64, 9, 9, generator=gen).to(DEV))
+  wf, _ = _ffi.hl8_weight(torch.randn(256, 64, 1, 1, generator=gen).to(DEV) * 0.1)
+  assert _ffi.conv_hl8_path_name('stats', 1, 9, 9, 64, 256, 1) == 'unsupported'
+  out, st = _ffi.conv_hl8_stats(_ffi.hl8_from_f32(x), wf, 1, 9, 9, 1)
+  assert st is None and out.shape == (1, 256, 9, 9)
+
+
+# ---- conv_wgrad and conv_wgrad_reduce -------------------------------------------------------------------------------
+_S = lambda v: {'SPML_WGRAD_STAGES': str(v)}
+# (route, switches, label, n_img, h, w, K, N, kernel side, dilation, splits)
+WGRAD_EDGES = [('r9', 1, 9, 1, 1, 1), ('r16', 1, 16, 1, 1, 1), ('r17', 1, 17, 1, 1, 1),     # < 1 stage, 1, 1 + one row
+               ('r40', 1, 40, 1, 1, 1), ('r296', 1, 296, 1, 1, 1),          # 3 stages; two splits of 10 and 9 stages
+               ('w1', 1, 23, 1, 3, 1), ('w3', 1, 11, 3, 3, 1), ('w5', 1, 9, 5, 3, 2),       # maps narrower than a stage
+               ('dil', 1, 6, 5, 3, 6),                                                       # dilation >= both sides
+               ('2img', 2, 7, 3, 3, 1)]                                                      # no leak across the images
+WGRAD_CASES = [(route, env, label, n, h, w, cin, cout, k, dil)
+               for route, env, cin, cout in [('t256x256_pair4', {}, 256, 256), ('t256x256_s3', _S(3), 256, 256),
+                                             ('t128x128_s3', {}, 128, 128)]
+               for label, n, h, w, k, dil in WGRAD_EDGES]
+WGRAD_CASES += [(route, env, label, n, h, w, cin, cout, k, dil)
+                for route, env, cin, cout in [('t256x256_s2', _S(2), 256, 256), ('t256x256_s4', _S(4), 256, 256),
+                                              ('t256x256_s5', _S(5), 256, 256), ('t256x128_s3', {}, 128, 256),
+                                              ('t128x256_s3', {}, 256, 128)]
+                for label, n, h, w, k, dil in [WGRAD_EDGES[2], WGRAD_EDGES[4], WGRAD_EDGES[6]]]
+# split counts of one 256 x 256 tile (1x1, R x 1 maps): every remainder batch of conv_wgrad_reduce (8, 4, 2, 1) alone
+# and combined -- 1, 2, 3 = 2+1, 4, 6 = 4+2, 7 = 4+2+1, 8, 9 = 8+1, 10 = 8+2, 12 = 8+4, 14 = 8+4+2, 15 = 8+4+2+1, 16 = 8+8
+# (6, 10 and 14 end on the batch of two: with 2 they are what catches `s + 2 < splits` there)
+WGRAD_SPLITS = [1, 2, 3, 4, 6, 7, 8, 9, 10, 12, 14, 15, 16]
+WGRAD_SPLIT_CASES = [('t256x256_pair4', {}, 's%d' % s, 1, 256 * s - 100, 1, 256, 256, 1, 1) for s in WGRAD_SPLITS]
+WGRAD_SPLIT_CASES += [('t256x256_s3', _S(3), 's%d' % s, 1, 256 * s - 100, 1, 256, 256, 1, 1) for s in (7, 15)]
+
+
+def _wgrad_check(case):
+  route, env, label, n, h, w, cin, cout, k, dil = case
+  assert _ffi.conv_wgrad_path_name(n, h, w, cin, cout, k * k) == route
+  gen = torch.Generator().manual_seed(SEED + cin + 3 * cout + h + w)
+  pad = dil * (k // 2)
+  x = _nhwc(torch.randn(n, cin, h, w, generator=gen).to(DEV))
+  dy = _nhwc(torch.randn(n, cout, h, w, generator=gen).to(DEV))
+  ref = torch.nn.grad.conv2d_weight(x.double(), (cout, cin, k, k), dy.double(), padding=pad, dilation=dil)
+  lib32 = torch.nn.grad.conv2d_weight(x, (cout, cin, k, k), dy, padding=pad, dilation=dil)
+  dya, xa = _ffi.hl8_from_f32(dy), _ffi.hl8_from_f32(x)
+  got = _ffi.conv_wgrad_hl8(dya, xa, n, h, w, k * k, dil)
+  assert torch.equal(got, _ffi.conv_wgrad_hl8(dya, xa, n, h, w, k * k, dil))
+  e_got, e_lib = _rel(got, ref), _rel(lib32, ref)
+  _report('wgrad %s-%s' % (route, label), '%s x%d' % (route, _ffi.conv_wgrad_splits(n, h, w, cin, cout, k * k)), e_got,
+          e_lib)
+  _within(e_got, e_lib, FLOOR, 'branch wgrad %s-%s' % (route, label))
+  if k == 3 and dil >= h and dil >= w:                     # only the centre tap sees the map
+    off = got.clone()
+    off[:, :, 1, 1] = 0
+    assert float(off.abs().max()) == 0.0
+
+
+@pytest.mark.parametrize('case', WGRAD_CASES, ids=lambda c: '%s-%s' % (c[0], c[2]))
+def test_weight_gradient_instantiations_at_the_geometry_edges(case, monkeypatch):
+  set_switches(monkeypatch, case[1])
+  _wgrad_check(case)
+
+
+@pytest.mark.parametrize('case', WGRAD_SPLIT_CASES, ids=lambda c: '%s-%s' % (c[0], c[2]))
+def test_weight_gradient_split_counts_drive_every_reduce_batch(case, monkeypatch):
+  set_switches(monkeypatch, case[1])
+  n, h, w, cin, cout = case[3:8]
+  assert _ffi.conv_wgrad_splits(n, h, w, cin, cout, 1) == int(case[2][1:])
+  _wgrad_check(case)
+
+
+# pyramid weight gradient: 1 to 4 branches (the last group of four taps carries 3, 2, 1, 0 padding taps), K = 256 / 512
+PYR_WGRAD_CASES = [(cin, d) for cin in (256, 512) for d in [(1,), (12, 1), (1, 12, 1), (1, 3, 12, 3)]]
+
+
+@pytest.mark.parametrize('cin,dils', PYR_WGRAD_CASES)
+def test_pyramid_weight_gradient_branch_counts(cin, dils):
+  """Every returned dW, whole, against fp64: a padding tap that wrote anything would land in a neighbouring branch's
+  rows of the one [branches, 64, 9, K] buffer."""
+  n, h, w = 2, 9, 11
+  assert _ffi.conv_wgrad_path_name(n, h, w, cin, 64, len(dils), True) == 'pyr_t256x256_pair4'
+  gen = torch.Generator().manual_seed(SEED + cin + len(dils))
+  x = _nhwc(torch.randn(n, cin, h, w, generator=gen).to(DEV))
+  dy = _nhwc(torch.randn(n, 64, h, w, generator=gen).to(DEV))
+  dya, xa = _ffi.hl8_from_f32(dy), _ffi.hl8_from_f32(x)
+  got = _ffi.conv_wgrad_pyramid_hl8(dya, xa, n, h, w, dils)
+  again = _ffi.conv_wgrad_pyramid_hl8(dya, xa, n, h, w, dils)
+  assert len(got) == len(dils)
+  for b, (g, d) in enumerate(zip(got, dils)):
+    ref = torch.nn.grad.conv2d_weight(x.double(), (64, cin, 3, 3), dy.double(), padding=d, dilation=d)
+    lib32 = torch.nn.grad.conv2d_weight(x, (64, cin, 3, 3), dy, padding=d, dilation=d)
+    e_got, e_lib = _rel(g, ref), _rel(lib32, ref)
+    _report('pyramid wgrad k%d %s branch %d' % (cin, dils, b), 'pyr_t256x256_pair4', e_got, e_lib)
+    _within(e_got, e_lib, FLOOR, 'branch pyramid wgrad k%d %s b%d' % (cin, dils, b))
+    assert torch.equal(g, again[b])
+
+
+# ---- converters -----------------------------------------------------------------------------------------------------
+def _bytes(t):
+  return t.cpu().numpy()
+
+
+def _wide_range(rows, c, gen, top=1.0):
+  """Values from `top` down to 2^-30 of it: normal and subnormal halves in both parts, zeros, both signs."""
+  x = top * torch.exp2(-30 * torch.rand(rows, c, generator=gen)) * (torch.randint(0, 2, (rows, c), generator=gen) * 2 - 1)
+  x[0, 0], x[0, 1], x[rows - 1, c - 1] = top, 0.0, -top
+  return x.float()
+
+
+def _from_f32_no_bound(x):
+  out = torch.empty((x.numel() * 4,), dtype=torch.uint8, device=DEV)
+  _ffi.check(_ffi.lib().spml_hl8_from_f32(_ffi._ptr_any(x), x.shape[0], x.shape[1], None, 0, _ffi.ptr(out),
+                                          _ffi.stream_ptr()), 'spml_hl8_from_f32')
+  return out
+
+
+@pytest.mark.parametrize('rows,c,top', [(5, 8, 1.0), (37, 24, 300.0), (300, 64, 1e-7), (2049, 16, 3e20)])
+def test_converter_bytes_match_the_restatement(rows, c, top):
+  """spml_hl8_from_f32 against tests/conv_ref.py, bit for bit: computed bound, given bound, no bound pointer.  (A box
+  that flushed f16 subnormals would differ here.)"""
+  gen = torch.Generator().manual_seed(SEED + rows)
+  x = _wide_range(rows, c, gen, top)
+  xd = x.to(DEV)
+  got = _ffi.hl8_from_f32(xd)
+  assert float(got.bound) == float(x.abs().max())
+  assert np.array_equal(_bytes(got.data), conv_ref.hl8_encode(x.numpy(), float(x.abs().max())))
+  given = torch.tensor([1.7 * top], device=DEV)
+  assert np.array_equal(_bytes(_ffi.hl8_from_f32(xd, bound=given).data), conv_ref.hl8_encode(x.numpy(), np.float32(1.7 * top)))
+  if 1e-4 < top < 1e4:                                     # (unscaled: only values a half can hold)
+    assert np.array_equal(_bytes(_from_f32_no_bound(xd)), conv_ref.hl8_encode(x.numpy(), None))
+  back = conv_ref.hl8_decode(_bytes(got.data), rows, c, float(got.bound))
+  err = np.abs(back - x.double().numpy())
+  big = x.abs().double().numpy() >= 2.0 ** -15 * float(got.bound)
+  assert (err[big] <= 2.0 ** -22 * x.abs().double().numpy()[big]).all() and (err[~big] <= 2.0 ** -38 * float(got.bound)).all()
+
+
+@pytest.mark.parametrize('cout,cin,k', [(16, 8, 1), (64, 48, 3), (24, 256, 3), (256, 64, 1)])
+def test_weight_operands_match_the_restatement(cout, cin, k):
+  gen = torch.Generator().manual_seed(SEED + cout + cin)
+  wt = _wide_range(cout, cin * k * k, gen, 0.3).reshape(cout, cin, k, k)
+  fwd, tr = _ffi.hl8_weight(wt.to(DEV))
+  bound = float(wt.abs().max())
+  assert float(fwd.bound) == bound and (tr.rows, tr.channels) == (cin, k * k * cout)
+  assert np.array_equal(_bytes(fwd.data), conv_ref.hl8_encode(conv_ref.weight_forward(wt.numpy()), bound))
+  assert np.array_equal(_bytes(tr.data), conv_ref.hl8_encode(conv_ref.weight_transposed(wt.numpy()), bound))
+
+
+@pytest.mark.parametrize('count', [1, 2, 3, 4])
+def test_weight_set_equals_the_single_conversions(count):
+  """spml_hl8_weight_set_f32 (the scattered transposed and mirrored operand): every operand bit-identical to
+  hl8_weight of the same tensor, every bound its own."""
+  shapes = [(64, 256, 1), (64, 64, 3), (256, 64, 1), (128, 256, 1)][:count]
+  gen = torch.Generator().manual_seed(SEED + count)
+  ws = [(_wide_range(co, ci * k * k, gen, 0.1 * 10 ** i).reshape(co, ci, k, k)).to(DEV) for i, (co, ci, k) in enumerate(shapes)]
+  got = _ffi.hl8_weight_set(ws)
+  assert len(got) == count
+  for wt, (fwd, tr) in zip(ws, got):
+    f1, t1 = _ffi.hl8_weight(wt)
+    assert float(fwd.bound) == float(f1.bound) == float(wt.abs().max()) and float(tr.bound) == float(fwd.bound)
+    assert torch.equal(fwd.data, f1.data) and torch.equal(tr.data, t1.data)
+    assert (fwd.rows, fwd.channels, tr.rows, tr.channels) == (f1.rows, f1.channels, t1.rows, t1.channels)
+
+
+def _absmax(x, bound, zero_first):
+  _ffi.check(_ffi.lib().spml_absmax_bound_f32(_ffi._ptr_any(x), x.numel(), _ffi._dp(bound), int(zero_first),
+                                              _ffi.stream_ptr()), 'spml_absmax_bound_f32')
+
+
+@pytest.mark.parametrize('n', [1, 3, 5, 1027])
+def test_absmax_bound_tails_signs_and_accumulation(n):
+  gen = torch.Generator().manual_seed(SEED + n)
+  for where in sorted({0, n - 1, max(n - 2, 0), (n // 4) * 4 - 1 if n >= 4 else 0}):
+    x = torch.rand(n, generator=gen) - 0.5
+    x[where] = -3.5                                        # a negative maximum, in the body and in the tail
+    xd = x.to(DEV)
+    bound = torch.full((1,), 1e30, device=DEV)             # (poisoned: zero_first must reset it)
+    _absmax(xd, bound, True)
+    assert float(bound) == 3.5, (n, where)
+    y = (torch.rand(n, generator=gen) * 2).to(DEV)         # zero_first = 0: the running maximum over two tensors
+    _absmax(y, bound, False)
+    assert float(bound) == 3.5
+    y[n // 2] = 7.25
+    _absmax(y, bound, False)
+    assert float(bound) == 7.25
+
+
+def test_scale_edges_through_a_given_bound():
+  """pow2_scale through spml_hl8_from_f32 with a given bound: 0, inf and NaN take scale 1; an exact power of two keeps
+  the scaled tensor below 2^14.  A denormal bound gives the VALUES of scale 1 for every tensor that respects it (all
+  halves zero), which is what is asserted; the scale itself is 2^100 there, not 1 (the header's formula with the
+  exponent clamped: a tensor of magnitude 1 above a bound of 1e-40 comes out as h = inf), and 29 of 512 bytes differ
+  from the restatement in the sign of a zero half -- both printed, recorded in profiles/conv_branch_parity.md."""
+  gen = torch.Generator().manual_seed(SEED + 9)
+  x = _wide_range(16, 8, gen, 1.0)
+  xd = x.to(DEV)
+  for b in (0.0, float('inf'), float('nan')):
+    got = _ffi.hl8_from_f32(xd, bound=torch.tensor([b], device=DEV))
+    assert np.array_equal(_bytes(got.data), conv_ref.hl8_encode(x.numpy(), None)), b
+  tiny = torch.tensor([1e-40], device=DEV)
+  assert float(tiny) > 0                                   # (the box keeps fp32 denormals)
+  small = (x * 1e-40).to(DEV)
+  got = _ffi.hl8_from_f32(small, bound=tiny)
+  above = _ffi.hl8_from_f32(xd, bound=tiny).data.view(torch.float16).float().cpu().view(-1, 2, 8)[0]
+  want1 = torch.from_numpy(conv_ref.hl8_encode(small.cpu().numpy(), None))
+  print('PARITY-SCALE\tdenormal bound: bytes of a tensor inside it equal the scale-1 restatement: %s (bytes that differ: '
+        '%d, all of them the sign of a zero: %s); a tensor of magnitude 1 ABOVE it comes out as h = %s' % (
+            torch.equal(got.data.cpu(), want1), int((got.data.cpu() != want1).sum()),
+            bool(((got.data.cpu() ^ want1) & 0x7f).max() == 0), above[0, :3].tolist()))
+  # the values are those of scale 1 (every half a zero); the sign bits of those zeros are not compared: fp32 denormal
+  # inputs are the one place where the box's arithmetic and numpy's may round a -0 differently
+  assert float(got.data.view(torch.float16).float().abs().max()) == 0.0
+  for e in (-20, 0, 3, 14, 40):
+    b = 2.0 ** e
+    y = (x * b).to(DEV)                                    # max |y| == the bound, an exact power of two
+    got = _ffi.hl8_from_f32(y, bound=torch.tensor([b], device=DEV))
+    assert np.array_equal(_bytes(got.data), conv_ref.hl8_encode(y.cpu().numpy(), np.float32(b)))
+    halves = got.data.view(torch.float16).float()
+    assert float(halves.abs().max()) == 2.0 ** 13 < 2.0 ** 14
+
+
+# ---- tap gather -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('cout,dils', [(16, (1, 12, 3, 3)), (128, (12,)), (128, (2, 12, 2)), (64, (2,)), (64, (1, 12, 3))])
+def test_tap_gather_widths_and_branch_counts(cout, dils):
+  """conv_hl8_pyramid_forward_gemm at Cout 16 and 128 (4 and 32 lanes per pixel) beside 64, 1 and 3 branches (Cout 16
+  exists with four only: 9 * branches * Cout must be a multiple of 64), one dilation >= H and >= W."""
+  n, cin, h, w = 2, 64, 9, 11
+  gen = torch.Generator().manual_seed(SEED + cout + len(dils))
+  x = _nhwc(torch.randn(n, cin, h, w, generator=gen).to(DEV))
+  ws = [(torch.randn(cout, cin, 3, 3, generator=gen) * (2.0 / (9 * cin)) ** 0.5).to(DEV) for _ in dils]
+  bs = [torch.randn(cout, generator=gen).to(DEV) for _ in dils]
+  assert _ffi.conv_hl8_pyramid_forward_gemm_supported(cin, cout, len(dils))
+  xa = _ffi.hl8_from_f32(x)
+  got = _ffi.conv_hl8_pyramid_forward_gemm(xa, ws, bs, dils, n, h, w)
+  ref = sum(F.conv2d(x.double(), wt.double(), b.double(), 1, d, d) for wt, b, d in zip(ws, bs, dils))
+  lib32 = sum(F.conv2d(x, wt, b, 1, d, d) for wt, b, d in zip(ws, bs, dils))
+  e_got, e_lib = _rel(got, ref), _rel(lib32, ref)
+  _report('tap gather cout%d g%d' % (cout, len(dils)), _ffi.conv_hl8_path_name('plain', n, h, w, cin, 9 * len(dils) * cout, 1),
+          e_got, e_lib)
+  _within(e_got, e_lib, FLOOR, 'branch tap gather cout%d g%d' % (cout, len(dils)))
+  assert torch.equal(got, _ffi.conv_hl8_pyramid_forward_gemm(xa, ws, bs, dils, n, h, w))
