@@ -619,6 +619,16 @@ int spml_conv_hl8_bwd_stats_f32(const void* a, const float* a_bound, const void*
                                 const unsigned char* relu_mask, const float* bn_mean,
                                 float* chunk_stats, float* zero_me, int n_img, int H, int W,
                                 int K, int N, int taps, int dilation, void* stream);
+/* ... whose output also takes an addend, as spml_conv_hl8_f32 applies it (out = conv + addend where addend_mask is
+ * NULL or its bit is set; `out` bit-identical to that call's): the last data gradient of a bottleneck unit, whose
+ * output is the dy of the bn3 + ReLU of the unit below (bn_x, relu_mask, bn_mean: that batch norm's).  Same layout
+ * call, same route as spml_conv_hl8_bwd_stats_f32; launches with the chunked accumulation are not supported. */
+int spml_conv_hl8_bwd_stats_addend_f32(const void* a, const float* a_bound, const void* b,
+                                       const float* b_bound, float* out, const float* bn_x,
+                                       const unsigned char* relu_mask, const float* bn_mean,
+                                       float* chunk_stats, float* zero_me, int n_img, int H, int W,
+                                       int K, int N, int taps, int dilation, const float* addend,
+                                       const unsigned char* addend_mask, void* stream);
 
 /* Weight gradient of the same convolutions:
  *   dw[n][tap][k] = sum_r dy[r][n] * x[r + shift(tap)][k]      (dw fp32 [N][taps][K] = the

@@ -89,6 +89,8 @@ _SIGNATURES = {
     'spml_conv_hl8_bwd_stats_layout': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     'spml_conv_hl8_bwd_stats_f32': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
                                             c_int, c_int, _P]),
+    'spml_conv_hl8_bwd_stats_addend_f32': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int,
+                                                   c_int, c_int, c_int, _P, _P, _P]),
     'spml_bn_bwd_hl8_chunks_f32': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P,
                                            _P, _P, _P, _P, _P]),
     'spml_bn_act_bwd_reduce_ext_chunks_f32': (c_int, [_P, c_int, c_int, c_int64, c_int, _P, _P, _P, _P, _P]),
@@ -1113,28 +1115,38 @@ def conv_hl8_stats(a, b, n_img, h, w, taps, dilation=1):
   return out, ChunkStats(st, chunks.value, rows.value, bound)
 
 
-def conv_hl8_bwd_stats(a, b, n_img, h, w, taps, dilation, bn_x, relu_mask, bn_mean):
+def conv_hl8_bwd_stats(a, b, n_img, h, w, taps, dilation, bn_x, relu_mask, bn_mean, addend=None, addend_mask=None):
   """conv_hl8 as the data gradient in front of a batch norm + ReLU (saved input bn_x, mask bytes, batch mean): the
   epilogue also leaves that batch norm's backward chunk sums -> (out, ChunkStats [3, chunks, N]), or (out, None)
   where the launch has no per-tile column owner (narrow outputs) or there is no mask.  SPML_CONV_BN_BWD_STATS=0:
-  never."""
+  never.  addend (+ addend_mask): added to the result as conv_hl8 does, before the sums are taken (a unit's last data
+  gradient in front of the bn3 of the unit below); launches with the chunked accumulation take the plain route."""
   import ctypes
   k, n = a.channels, b.rows
   chunks, rows = ctypes.c_int(0), ctypes.c_int(0)
   if relu_mask is None or os.environ.get('SPML_CONV_BN_BWD_STATS') == '0' or lib().spml_conv_hl8_bwd_stats_layout(
-      n_img, h, w, k, n, taps, ctypes.byref(chunks), ctypes.byref(rows)) != 0:
-    return conv_hl8(a, b, n_img, h, w, taps, dilation), None
+      n_img, h, w, k, n, taps, ctypes.byref(chunks), ctypes.byref(rows)) != 0 or \
+      (addend is not None and 'chunk' in conv_hl8_path_name('bwd_stats', n_img, h, w, k, n, taps)):
+    return conv_hl8(a, b, n_img, h, w, taps, dilation, addend, addend_mask), None
   if a.rows != n_img * h * w or b.channels != taps * k or bn_x.numel() != a.rows * n or \
-      relu_mask.numel() != a.rows * (n // 4) or bn_mean.numel() != n:
+      relu_mask.numel() != a.rows * (n // 4) or bn_mean.numel() != n or \
+      (addend is not None and addend.numel() != a.rows * n) or (addend is None and addend_mask is not None) or \
+      (addend_mask is not None and addend_mask.numel() != a.rows * (n // 4)):
     raise SpmlHipError('conv_hl8_bwd_stats: operand shapes do not match')
   dev = a.data.device
   out = torch.empty((n_img, n, h, w), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
   st = torch.empty((3, chunks.value, n), dtype=torch.float32, device=dev)
   bound = _f32(1, dev)
-  check(lib().spml_conv_hl8_bwd_stats_f32(ptr(a.data), c_void_p(a.bound.data_ptr()), ptr(b.data),
-                                          c_void_p(b.bound.data_ptr()), _ptr_any(out), _ptr_any(bn_x), _dp(relu_mask),
-                                          _dp(bn_mean), _dp(st), _dp(bound), n_img, h, w, k, n, taps, dilation,
-                                          stream_ptr()), 'spml_conv_hl8_bwd_stats_f32')
+  if addend is None:
+    check(lib().spml_conv_hl8_bwd_stats_f32(ptr(a.data), c_void_p(a.bound.data_ptr()), ptr(b.data),
+                                            c_void_p(b.bound.data_ptr()), _ptr_any(out), _ptr_any(bn_x), _dp(relu_mask),
+                                            _dp(bn_mean), _dp(st), _dp(bound), n_img, h, w, k, n, taps, dilation,
+                                            stream_ptr()), 'spml_conv_hl8_bwd_stats_f32')
+  else:
+    check(lib().spml_conv_hl8_bwd_stats_addend_f32(
+        ptr(a.data), c_void_p(a.bound.data_ptr()), ptr(b.data), c_void_p(b.bound.data_ptr()), _ptr_any(out),
+        _ptr_any(bn_x), _dp(relu_mask), _dp(bn_mean), _dp(st), _dp(bound), n_img, h, w, k, n, taps, dilation,
+        _ptr_any(addend), _dp(addend_mask), stream_ptr()), 'spml_conv_hl8_bwd_stats_addend_f32')
   return out, ChunkStats(st, chunks.value, rows.value, bound)
 
 

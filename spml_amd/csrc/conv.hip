@@ -237,9 +237,13 @@ struct ConvArgs {
 // BSTAT (RG == 1, NC == 4, gridDim.y == 1, no addend / bias / ReLU: the data gradients in front of bn2 and bn1 of a
 // bottleneck unit): the epilogue also reads the tile of the batch norm's saved input and ReLU mask and leaves the three
 // backward partial statistics per column (ConvArgs::bstats).
-template <int RB, int kStages, int WGS, int RG, bool CHUNK = false, int NC = 4, bool BSTAT = false>
+// BADD (a BSTAT launch with an addend: the last data gradient of a unit, whose output -- conv1's data gradient plus
+// the gradient of the residual branch -- is the d_out of the unit below, i.e. the dy of THAT unit's bn3 + ReLU): the
+// same epilogue on v = acc * mult + addend (the addend gated by its own mask bytes, if any).
+template <int RB, int kStages, int WGS, int RG, bool CHUNK = false, int NC = 4, bool BSTAT = false, bool BADD = false>
 __global__ __launch_bounds__(64 * NC * RG, WGS) void conv_gemm(const ConvArgs a) {
   static_assert(!BSTAT || (RG == 1 && NC == 4), "backward statistics: a wave owns its 64 columns over the whole tile");
+  static_assert(!BADD || (BSTAT && !CHUNK), "the addend form exists for the un-chunked backward statistics only");
   // CHUNK (very long reductions, e.g. the 36-tap forward of a wide ASPP head, K = 73 728): the MFMA chain
   // is cut every 1024 k -- the running accumulator is added to a second register set and restarted -- so
   // that the fp32 accumulation error stays at the level of a K = 1024 convolution
@@ -448,7 +452,9 @@ __global__ __launch_bounds__(64 * NC * RG, WGS) void conv_gemm(const ConvArgs a)
     // drops the stores and zeroes the loads of rows past R (whose accumulators are zero anyway: their A rows came from
     // the zero page), so the epilogue is one basic block -- with a branch per row the compiler sinks every sum to the
     // end of the kernel and spills the values it keeps for them.
-    constexpr int kB = BSTAT_BATCH, kBatches = RB * 16 / kB;
+    // BADD: the addend and its mask byte join each batch's fetch; half the batch keeps the register count (two batches
+    // in flight: 2 x 4 x kB registers without, 2 x 8 x kB with the addend)
+    constexpr int kB = BADD ? BSTAT_BATCH / 2 : BSTAT_BATCH, kBatches = RB * 16 / kB;
     const unsigned N = (unsigned)a.N;
     const unsigned rows_here = (unsigned)(m0 + RB * 32 < a.R ? (int64_t)RB * 32 : a.R - m0);
     const unsigned tile_bytes = rows_here * N * 4u;
@@ -457,6 +463,13 @@ __global__ __launch_bounds__(64 * NC * RG, WGS) void conv_gemm(const ConvArgs a)
     const auto rm = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.bstat_mask + (t0e >> 2)), 0,
                                                       (int)(tile_bytes >> 4), 0x00020000);
     const auto ro = __builtin_amdgcn_make_buffer_rsrc(a.out + t0e, 0, (int)tile_bytes, 0x00020000);
+    // BADD: no addend mask = an empty range (every byte reads 0) and all four bits forced on
+    const auto ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(BADD ? a.addend + t0e : a.bstat_x), 0,
+                                                      BADD ? (int)tile_bytes : 0, 0x00020000);
+    const auto ram = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<unsigned char*>(BADD && a.addend_mask ? a.addend_mask + (t0e >> 2) : a.bstat_mask), 0,
+        BADD && a.addend_mask ? (int)(tile_bytes >> 4) : 0, 0x00020000);
+    const unsigned ungated = BADD && !a.addend_mask ? 0xfu : 0u;
     // (lane constants from an opaque copy of the thread index: derived from `lane` they are computed before the main
     // loop and spilled across it)
     unsigned tid = threadIdx.x;
@@ -466,9 +479,10 @@ __global__ __launch_bounds__(64 * NC * RG, WGS) void conv_gemm(const ConvArgs a)
     const unsigned lo = (up * 4u * N + col) * 4u;                         // byte offset of the lane in the fp32 tile
     const unsigned lm = up * N + (col >> 2);                              // ... in the mask tile
     const unsigned bit = 1u << (tid & 3u);
-    float xv[2][kB][2];
-    unsigned mv[2][kB][2];
-    auto fetch = [&](int b, float (&x)[kB][2], unsigned (&m)[kB][2]) {
+    constexpr int kA = BADD ? kB : 1;
+    float xv[2][kB][2], av[2][kA][2];
+    unsigned mv[2][kB][2], amv[2][kA][2];
+    auto fetch = [&](int b, float (&x)[kB][2], unsigned (&m)[kB][2], float (&ad)[kA][2], unsigned (&am)[kA][2]) {
 #pragma unroll
       for (int e = 0; e < kB; ++e) {
         const int idx = b * kB + e;
@@ -478,9 +492,15 @@ __global__ __launch_bounds__(64 * NC * RG, WGS) void conv_gemm(const ConvArgs a)
         x[e][1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, vo + 128u, 0, 0));
         m[e][0] = __builtin_amdgcn_raw_buffer_load_b8(rm, vm, 0, 0);
         m[e][1] = __builtin_amdgcn_raw_buffer_load_b8(rm, vm + 8u, 0, 0);
+        if constexpr (BADD) {
+          ad[e][0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ra, vo, 0, 0));
+          ad[e][1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ra, vo + 128u, 0, 0));
+          am[e][0] = __builtin_amdgcn_raw_buffer_load_b8(ram, vm, 0, 0);
+          am[e][1] = __builtin_amdgcn_raw_buffer_load_b8(ram, vm + 8u, 0, 0);
+        }
       }
     };
-    fetch(0, xv[0], mv[0]);
+    fetch(0, xv[0], mv[0], av[0], amv[0]);
     __builtin_amdgcn_sched_barrier(0);
     if (a.stats_zero && blockIdx.x == 0 && threadIdx.x == 0) *a.stats_zero = 0.f;
     const float mu[2] = {a.bstat_mean[col], a.bstat_mean[col + 32]};
@@ -488,7 +508,7 @@ __global__ __launch_bounds__(64 * NC * RG, WGS) void conv_gemm(const ConvArgs a)
     float s0[2] = {0.f, 0.f}, s1[2] = {0.f, 0.f}, mx[2] = {0.f, 0.f};
 #pragma unroll
     for (int b = 0; b < kBatches; ++b) {
-      if (b + 1 < kBatches) fetch(b + 1, xv[(b + 1) & 1], mv[(b + 1) & 1]);
+      if (b + 1 < kBatches) fetch(b + 1, xv[(b + 1) & 1], mv[(b + 1) & 1], av[(b + 1) & 1], amv[(b + 1) & 1]);
       __builtin_amdgcn_sched_barrier(0);                  // (the scheduler would hoist every batch's loads and spill)
       float t0[2] = {0.f, 0.f}, t1[2] = {0.f, 0.f};      // the batch's own sums: a fixed, shallower summation tree
 #pragma unroll
@@ -497,7 +517,11 @@ __global__ __launch_bounds__(64 * NC * RG, WGS) void conv_gemm(const ConvArgs a)
         const unsigned vo = lo + (unsigned)(i * 32 + acc_row(r, 0)) * N * 4u;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          const float v = acc[i][j][r] * mult;
+          float v = acc[i][j][r] * mult;
+          if constexpr (BADD) {
+#pragma clang fp contract(off)             // (the product is rounded before the addend joins it, as in the plain epilogue)
+            v += ((amv[b & 1][e][j] | ungated) & bit) ? av[b & 1][e][j] : 0.f;
+          }
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ro, vo + 128u * j, 0, 0);
           const float dz = (mv[b & 1][e][j] & bit) ? v : 0.f;
           t0[j] += dz;
@@ -621,14 +645,14 @@ struct ConvRoute;
 template <int RB, int RG, bool CHUNK, int NC, bool BSTAT>
 bool route_is(const ConvRoute& r);         // (below, with the route: the record names exactly this instantiation)
 
-template <int RB, int kStages, int WGS, int RG = 1, bool CHUNK = false, int NC = 4, bool BSTAT = false>
+template <int RB, int kStages, int WGS, int RG = 1, bool CHUNK = false, int NC = 4, bool BSTAT = false, bool BADD = false>
 int launch_conv(const ConvRoute& r, const ConvArgs& a0, hipStream_t s) {
   if (!route_is<RB, RG, CHUNK, NC, BSTAT>(r)) return SPML_ERR_LAUNCH;      // the path name would not be the launch's
   ConvArgs a = a0;
   a.n_col_tiles = a.N / (64 * NC);
   const int64_t row_tiles = (a.R + RG * RB * 32 - 1) / (RG * RB * 32);
   a.n_tiles = (int)(row_tiles * a.n_col_tiles);
-  auto kern = conv_gemm<RB, kStages, WGS, RG, CHUNK, NC, BSTAT>;
+  auto kern = conv_gemm<RB, kStages, WGS, RG, CHUNK, NC, BSTAT, BADD>;
   const int lds = kStages * (2 * RB * RG + 4 * NC) * 1024;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   const int groups = a.tap_groups > 1 ? a.tap_groups : 1;
@@ -1022,6 +1046,14 @@ bool route_is(const ConvRoute& r) {
 }
 
 inline int launch_route(const ConvRoute& r, const ConvArgs& c, hipStream_t s) {
+  if (r.stat == kStatBwd && c.addend) {            // (the same route record: the addend only selects the epilogue)
+    if (r.chunk) return SPML_ERR_UNSUPPORTED;
+    switch (r.rb) {
+      case 3: return launch_conv<3, 3, 2, 1, false, 4, true, true>(r, c, s);
+      case 5: return launch_conv<5, 3, 2, 1, false, 4, true, true>(r, c, s);
+      default: return launch_conv<4, 3, 2, 1, false, 4, true, true>(r, c, s);
+    }
+  }
   if (r.stat == kStatBwd) {
     if (r.chunk) return launch_conv<3, 3, 2, 1, true, 4, true>(r, c, s);
     switch (r.rb) {
@@ -1344,6 +1376,42 @@ extern "C" int spml_conv_hl8_bwd_stats_f32(const void* a, const float* a_bound, 
   hipStream_t s = (hipStream_t)stream;
   const ConvRoute r = conv_route(kEntryBwdStats, c.R, K, N, taps, 1, false);
   if (r.tile_rows != rows) return SPML_ERR_UNSUPPORTED;       // (a switch changed between the two reads)
+  return launch_route(r, c, s);
+}
+
+// ... with an addend (optionally gated by its own ReLU mask bytes), as spml_conv_hl8_f32 applies it: the last data
+// gradient of a bottleneck unit, whose output is the dy of the bn3 + ReLU of the unit below.  Un-chunked launches only.
+extern "C" int spml_conv_hl8_bwd_stats_addend_f32(const void* a, const float* a_bound, const void* b,
+                                                  const float* b_bound, float* out, const float* bn_x,
+                                                  const unsigned char* relu_mask, const float* bn_mean,
+                                                  float* chunk_stats, float* zero_me, int n_img, int H, int W, int K,
+                                                  int N, int taps, int dilation, const float* addend,
+                                                  const unsigned char* addend_mask, void* stream) {
+  if (!a || !b || !out || !bn_x || !relu_mask || !bn_mean || !chunk_stats || !addend || n_img <= 0 || H <= 0 ||
+      W <= 0 || dilation < 1)
+    return SPML_ERR_INVALID_ARG;
+  int chunks = 0, rows = 0;
+  if (spml_conv_hl8_bwd_stats_layout(n_img, H, W, K, N, taps, &chunks, &rows) != SPML_OK || !al16(a) || !al16(b) ||
+      !al16(out) || !al16(bn_x) || !al16(addend))
+    return SPML_ERR_UNSUPPORTED;
+  ConvArgs c{};
+  c.a = static_cast<const uint4*>(a);
+  c.b = static_cast<const uint4*>(b);
+  c.a_bound = a_bound;
+  c.b_bound = b_bound;
+  c.addend = addend;
+  c.addend_mask = addend_mask;
+  c.out = out;
+  c.bstat_x = bn_x;
+  c.bstat_mask = relu_mask;
+  c.bstat_mean = bn_mean;
+  c.bstats = chunk_stats;
+  c.stats_zero = zero_me;
+  c.R = (int64_t)n_img * H * W;
+  c.H = H; c.W = W; c.K = K; c.N = N; c.taps = taps; c.dil = dilation;
+  hipStream_t s = (hipStream_t)stream;
+  const ConvRoute r = conv_route(kEntryBwdStats, c.R, K, N, taps, 1, false);
+  if (r.tile_rows != rows || r.chunk) return SPML_ERR_UNSUPPORTED;
   return launch_route(r, c, s);
 }
 

@@ -266,10 +266,47 @@ def _wgrad(side, dy, x, n, h, w, taps, dil=1):
   return dw
 
 
+def handover_mode():
+  """SPML_BN3_HANDOVER: 0 = every unit's bn3 backward reduces (d_out, a3, mask3) in a pass of its own; 1 (default) =
+  the unit above leaves those sums in the epilogue of its last data gradient, whose output IS that d_out.  (Mode 2 of
+  the plan -- the unit above also runs that bn3 backward before it joins its weight gradients -- did not separate from
+  the run-to-run noise and is not built: profiles/bn3_handover.md.)"""
+  return 0 if os.environ.get('SPML_BN3_HANDOVER') == '0' else 1
+
+
+class _Handover(object):
+  """What travels from a unit (the producer of an activation) to the unit that consumes it, and back in the backward
+  pass.  Forward: references to the producer's bn3 operands (a3, mask3, the batch mean; the producer saves the same
+  tensor objects, so no memory is added).  Backward: the consumer's last data gradient -- the producer's d_out -- with
+  the chunk sums of the producer's bn3 backward its epilogue left.  The sums are only good for that very tensor:
+  `take` hands them out once, and only if the gradient autograd delivers is the tensor `put` saw, unmodified (a second
+  consumer of the activation makes autograd deliver a sum, i.e. another tensor)."""
+  taken = 0                              # (class-wide: how many times handed sums were used)
+
+  def __init__(self):
+    self.bn3 = None                      # (a3, mask3, mean) of the producer
+    self.dx = self.stats = self.version = None
+
+  def put(self, dx, stats):
+    self.dx, self.stats, self.version = dx, stats, dx._version
+
+  def take(self, d_out):
+    dx, stats, version = self.dx, self.stats, self.version
+    self.dx = self.stats = self.version = None
+    if dx is None or d_out._version != version or d_out.data_ptr() != dx.data_ptr() or d_out.shape != dx.shape or \
+        d_out.stride() != dx.stride() or d_out.dtype != dx.dtype:
+      return None
+    _Handover.taken += 1
+    return stats
+
+
 class _Unit(torch.autograd.Function):
 
   @staticmethod
-  def forward(ctx, block, x, xh_data, xh_bound, w1, g1, b1, w2, g2, b2, w3, g3, b3, wd, gd, bd):
+  def forward(ctx, block, x, xh_data, xh_bound, w1, g1, b1, w2, g2, b2, w3, g3, b3, wd, gd, bd, hand_out=None,
+              hand_in=None, *p_bn3):
+    # hand_out: this unit's _Handover (filled here); hand_in + p_bn3 (its three tensors): the one of the unit that
+    # produced x, if any
     n, cin, h, w = x.shape
     rows = n * h * w
     dil = block.conv2.dilation[0]
@@ -310,6 +347,14 @@ class _Unit(torch.autograd.Function):
     tensors += list(n1.saved) + list(n2.saved) + list(n3.saved)
     if nd is not None:
       tensors += [ad, wdt.data, wdt.bound, gd] + list(nd.saved)
+    ctx.hand_in = ctx.hand_out = None
+    if hand_in is not None and len(p_bn3) == 3 and p_bn3[0] is not None and n3.world == 1 and \
+        tuple(p_bn3[0].shape) == tuple(x.shape):
+      ctx.hand_in = hand_in
+      tensors += list(p_bn3)
+    if hand_out is not None and n3.world == 1 and n3.mask is not None:
+      hand_out.bn3 = (a3, n3.mask, n3.saved[0])
+      ctx.hand_out = hand_out
     ctx.save_for_backward(*tensors)
     ctx.mark_non_differentiable(n3.yh.data, n3.yh.bound)
     ctx.set_materialize_grads(False)       # no zero-filled 0.3-0.5 GB "gradients" for the hl8 side outputs
@@ -318,8 +363,17 @@ class _Unit(torch.autograd.Function):
   @staticmethod
   def backward(ctx, d_out, _unused_data, _unused_bound):
     if d_out is None:
-      return (None,) * 16
+      return (None,) * 21
     t = ctx.saved_tensors
+    # the chunk sums of bn3's backward, if the unit above left them with this very d_out (checked before any copy);
+    # the forward references have served
+    handed = None
+    if ctx.hand_out is not None:
+      handed = ctx.hand_out.take(d_out)
+      ctx.hand_out.bn3 = None
+    p_bn3 = None                           # bn3 of the unit below: what this unit's dx feeds
+    if ctx.hand_in is not None:
+      p_bn3, t = t[-3:], t[:-3]
     n, cin, h, w, dil, width, cout = ctx.geom
     rows = n * h * w
     (xh_d, xh_b, a1, y1_d, y1_b, a2, y2_d, y2_b, a3, m3, m1, m2, w1t_d, w1t_b, w2t_d, w2t_b, w3t_d, w3t_b, g1, g2,
@@ -344,7 +398,7 @@ class _Unit(torch.autograd.Function):
       dres = None
     else:
       _, da3, dres, dg3, db3 = _bn_backward(d_out, a3, rows, cout, g3, s3, m[2][0], m[2][1], m[2][2], m3,
-                                            want_dres=has_ds)
+                                            want_dres=has_ds, chunk_stats=handed)
     side = _side_stream(d_out.device)
     dw3 = _wgrad(side, da3, y2h, n, h, w, 1)
     # dy2 / dy1 are the dy of bn2 / bn1: where the tiling allows it (256-column tiles) the data gradient's epilogue
@@ -358,6 +412,15 @@ class _Unit(torch.autograd.Function):
     _, da1, _, dg1, db1 = _bn_backward(dy1, a1, rows, width, g1, s1, m[0][0], m[0][1], m[0][2], m1, chunk_stats=c1)
     dw1 = _wgrad(side, da1, xh, n, h, w, 1)
     dx = None
+    # the last data gradient (conv1's + the masked d_out of the identity branch; with a downsample branch the second
+    # launch, which adds the first one's result unmasked) is the d_out of the unit below: its epilogue leaves the chunk
+    # sums of that unit's bn3 backward (dz = dx * mask3 of that unit), which then skips its reduction pass over
+    # (d_out, a3, mask3)
+    if p_bn3 is not None and need_x and handover_mode():
+      last = lambda dy, wt, **kw: _ffi.conv_hl8_bwd_stats(dy, wt, n, h, w, 1, 1, p_bn3[0], p_bn3[1], p_bn3[2], **kw)
+    else:
+      last = lambda dy, wt, **kw: (_ffi.conv_hl8(dy, wt, n, h, w, 1, **kw), None)
+    cx = None
     if has_ds:
       ad, wdt_d, wdt_b, gd = t[33:37]
       sd = t[37:41]
@@ -366,12 +429,14 @@ class _Unit(torch.autograd.Function):
       dwd = _wgrad(side, dad, xh, n, h, w, 1)
       if need_x:
         dx = _ffi.conv_hl8(da1, w1t, n, h, w, 1)
-        dx = _ffi.conv_hl8(dad, H(wdt_d, wdt_b, cin, cout), n, h, w, 1, addend=dx)
+        dx, cx = last(dad, H(wdt_d, wdt_b, cin, cout), addend=dx)
     elif need_x:
-      dx = _ffi.conv_hl8(da1, w1t, n, h, w, 1, addend=d_out, addend_mask=m3)
+      dx, cx = last(da1, w1t, addend=d_out, addend_mask=m3)
+    if cx is not None:
+      ctx.hand_in.put(dx, cx)
     if side is not None:
       torch.cuda.current_stream().wait_stream(side)      # the weight gradients are consumed on this stream
-    return (None, dx, None, None, dw1, dg1, db1, dw2, dg2, db2, dw3, dg3, db3, dwd, dgd, dbd)
+    return (None, dx, None, None, dw1, dg1, db1, dw2, dg2, db2, dw3, dg3, db3, dwd, dgd, dbd) + (None,) * 5
 
 
 class _ConvBnAct(torch.autograd.Function):
@@ -439,10 +504,15 @@ def bottleneck_forward(block, x):
   copy (attribute `_spml_hl8`) for the next unit."""
   xh = getattr(x, '_spml_hl8', None)
   ds = block.downsample
+  hand_in = getattr(x, '_spml_handover', None) if torch.is_grad_enabled() and handover_mode() else None
+  hand_out = _Handover() if torch.is_grad_enabled() and handover_mode() else None
   out, oh, ob = _Unit.apply(
       block, x, None if xh is None else xh.data, None if xh is None else xh.bound,
       block.conv1.weight, block.bn1.weight, block.bn1.bias, block.conv2.weight, block.bn2.weight, block.bn2.bias,
       block.conv3.weight, block.bn3.weight, block.bn3.bias,
-      None if ds is None else ds[0].weight, None if ds is None else ds[1].weight, None if ds is None else ds[1].bias)
+      None if ds is None else ds[0].weight, None if ds is None else ds[1].weight, None if ds is None else ds[1].bias,
+      hand_out, hand_in, *(hand_in.bn3 if hand_in is not None and hand_in.bn3 is not None else (None,) * 3))
   out._spml_hl8 = _ffi.Hl8(oh, ob, out.shape[0] * out.shape[2] * out.shape[3], out.shape[1])
+  if hand_out is not None and hand_out.bn3 is not None:
+    out._spml_handover = hand_out          # (on the tensor object, like the hl8 copy: any op on `out` drops both)
   return out
