@@ -49,7 +49,8 @@ const char* spml_status_string(int status);
  * 7: the multi-scale inference entry point (spml_view_probs_accumulate_f32);
  * 8: spml_upsample_ce_bwd_path_name (entry points added since leave every earlier signature and flag as it was and
  *    keep the version: spml_view_votes_*, spml_segsort_nll_batched_*, spml_segment_majority_*, spml_tag_normalize_*,
- *    spml_dense_crf_*, spml_segment_tag_cam_*, spml_conv_hl8_path_name, spml_conv_wgrad_path_name / _splits). */
+ *    spml_dense_crf_*, spml_segment_tag_cam_*, spml_conv_hl8_path_name, spml_conv_wgrad_path_name / _splits,
+ *    spml_augment_*). */
 #define SPML_ABI_VERSION 8
 int spml_abi_version(void);
 
@@ -1157,6 +1158,61 @@ int spml_segment_tag_cam_f32(const int64_t* nn_index, const float* nn_value, con
                              float threshold, const int64_t* cluster_index, int S, int ncls, int h2, int w2, int oh,
                              int ow, float* acc, int* counts, float* probs, void* ws, size_t ws_bytes, void* stream);
 const char* spml_segment_tag_cam_path_name(int64_t N, int S, int ncls);
+
+/* ------------------------------------------------------------------------
+ * Training batches from decoded files: one fused augmentation launch (csrc/augment.hip)
+ * replaces: spml/data/datasets/base_dataset.py:135-155,183-186 (mirror, random_resize, random_crop_with_pad, mean / std,
+ *           transpose), list_tag_dataset.py:75-78 (image tags), :179-218 (+ grayscale, 5x5 blur),
+ *           densepose_dataset.py:78-103,157-198 (+ the left/right remap of the part labels), spml/data/transforms.py
+ *           :26-37,76-78,134-151,179-191 and the collate of base_dataset.py:192-223 -- all of it host numpy / cv2 per
+ *           image there, followed by the upload of the finished fp32 image and two int64 maps.
+ *
+ * packed: uint8, device: for every image its RGB bytes (h x w x 3, as PIL decodes them) and its two label planes
+ * (semantic, instance; h x w), anywhere in the buffer.  One spml_augment_params record per image says where, and what was
+ * drawn for it.  Output pixel (y, x) of image b, with (Y, X) = (y + start_h, x + start_w) in the padded plane of
+ * max(new_h, S_h) x max(new_w, S_w) whose top-left corner holds the resized image:
+ *   outside new_h x new_w: the pixel is mean[c], both labels are 255;
+ *   image, cv2.resize(INTER_LINEAR) on uint8 / 255 in fp32: per axis scale = 1.0 / ((double)new / src),
+ *     f = (X + 0.5) * scale - 0.5, s = floor(f), f -= s; s < 0 -> s = 0, f = 0; s >= src - 1 -> s = src - 1, f = 0;
+ *     the fraction rounded to fp32; value = b0 * (a0 * v00 + a1 * v01) + b1 * (a0 * v10 + a1 * v11);
+ *   labels, INTER_NEAREST: s = min(floor(X * scale), src - 1), the same double scale;
+ *   flip: source column w - 1 - s, and the semantic label (only it, only then) goes through remap[256];
+ *   gray: (r * 0.3f + g * 0.59f) + b * 0.11f into all three channels, the padded area included;
+ *   blur: 5 x 5 correlation of that S_h x S_w image with weights[25] (row-major, anchor at the centre), reflect-101 at the
+ *     crop's own edges (cv2.filter2D's default border);
+ *   then (v - mean[c]) / std[c].
+ * The coordinates are formed in fp64 in the kernel with the operations above, unfused: the label maps equal the host
+ * chain's bit for bit.  image fp32 [B][3][S_h][S_w]; semantic_label, instance_label int64 [B][S_h][S_w]; mean, std fp32
+ * [3] and remap uint8 [256] are device pointers.  params_host and params_dev hold the same B records: the host copy is
+ * checked before anything is launched, the device copy is what the kernel reads (and checks again: a record that fails
+ * writes nothing and forms no address).  SPML_ERR_UNSUPPORTED, with nothing launched and no output touched: a side of a
+ * source, a resized image or the crop outside [1, 16384] (new_h or new_w of 0 included), a crop start outside
+ * [0, padded - S], an offset whose plane does not lie inside packed_bytes, blur with a crop side below 3, B > 65535.
+ * SPML_ERR_INVALID_ARG: a null or misaligned pointer, B < 1, an output that overlaps an input or another output.
+ * One launch, no workspace, no atomics, no host read of device memory: bit-identical from call to call.
+ * spml_augment_tags_u8: semantic_tag int64 [B][256], 1 where the value occurs in the un-augmented semantic plane (np.unique
+ * + a scatter of ones on the host there): a memset on `stream` and one launch; same record checks for h, w and sem_off.
+ * spml_augment_path_name (host only; the expression the launch itself evaluates per record): "plain", "blur" (the tile
+ * staged in LDS) or "unsupported".  spml_augment_params_bytes: sizeof(spml_augment_params), for bindings. */
+typedef struct spml_augment_params {
+  int64_t image_off, sem_off, inst_off;     /* byte offsets into `packed` */
+  int32_t h, w;                             /* source size */
+  int32_t new_h, new_w;                     /* int(ratio * h), int(ratio * w); = h, w without scaling */
+  int32_t start_h, start_w;                 /* crop start in the padded plane */
+  int32_t flip, gray, blur;                 /* 0 / non-zero */
+  int32_t reserved0;
+  float weights[25];                        /* of the blur; read only when blur is set */
+  float reserved1;
+} spml_augment_params;
+
+size_t spml_augment_params_bytes(void);
+const char* spml_augment_path_name(const spml_augment_params* record, int64_t packed_bytes, int S_h, int S_w);
+int spml_augment_batch_u8(const unsigned char* packed, int64_t packed_bytes, const spml_augment_params* params_host,
+                          const spml_augment_params* params_dev, int B, const float* mean, const float* std,
+                          const unsigned char* remap, int S_h, int S_w, float* image, int64_t* semantic_label,
+                          int64_t* instance_label, void* stream);
+int spml_augment_tags_u8(const unsigned char* packed, int64_t packed_bytes, const spml_augment_params* params_host,
+                         const spml_augment_params* params_dev, int B, int64_t* semantic_tag, void* stream);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,7 @@ config surface (`pyscripts/inference/inference.py:35-255` of twke18/SPML):
 Loads `model-{max_iteration-1}.pth` from the snapshot directory and the prototype memory bank from
 `--semantic_memory_dir` (the ignore class dropped: :99-111).  Every image is zero-padded to the crop size and goes through
 `spml_amd.inference.predict_full_resolution` (:136-237: sliding-window embedding, k-means over the whole image with the
-padding ignored, top-20 retrieval per segment, majority vote, scatter to the pixels).  As in the training entry points the
+padding ignored, top-20 retrieval per segment, majority vote, scatter to the pixels).  The evaluation
 file-list loader is outside this repository: `--data_list synthetic` feeds seeded synthetic images of `test.image_size`
 (made at the network's size: the reference's resize to `test.image_size` and the nearest-neighbour resize of the label map
 back, :124-133 and :238-241, are file plumbing and not built).  Without `--semantic_memory_dir` the synthetic mode builds

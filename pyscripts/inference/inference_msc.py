@@ -11,7 +11,7 @@ Loads `model-{max_iteration-1}.pth` from the snapshot directory (:83-89) and the
 the ten views of `spml_amd.inference.flip_scale_views` (scales 0.5, 0.75, 1, 1.25, 1.5, each flipped and plain,
 zero-padded to the crop size: :123-137) and goes through `spml_amd.inference.predict_knn_multiscale` (per view the
 sliding-window embedding, k-means over the un-padded view, top-20 retrieval per segment and one HIP launch pair for
-votes, resize, un-flip and sum; then the mean over the views and one arg-max).  As in the training entry points the
+votes, resize, un-flip and sum; then the mean over the views and one arg-max).  The evaluation
 file-list loader is outside this repository: `--data_list synthetic` feeds seeded synthetic images of
 `test.image_size`.  Without `--semantic_memory_dir` the synthetic mode builds the bank itself: the prototypes of the
 synthetic images (`full_resolution_prototypes`, what `prototype.py` does) are written with `save_image_memory` to

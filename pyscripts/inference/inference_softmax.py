@@ -8,7 +8,7 @@ Loads `model-{max_iteration-1}.pth` from the snapshot directory (:70-76): `embed
 name mapping (`resume=True`), `prediction_model` non-strictly -- a stage-1 `SegsortSoftmax` snapshot carries the same
 `semantic_classifier.*` names next to entries this model does not have.  Every image goes through
 `spml_amd.inference.predict_softmax_full_resolution` (sliding windows, HIP classifier head, summed logits, arg-max).
-As in the training entry points the file-list loader is outside this repository: `--data_list synthetic` feeds seeded
+The evaluation file-list loader is outside this repository: `--data_list synthetic` feeds seeded
 synthetic images of `test.image_size`, padded to the crop size (:97-103).  Label maps are written as
 `semantic_gray/<name>.npy` (uint8; no image library is needed); one JSON line reports images/s and, where labels
 exist, mIoU and pixel accuracy (`pyscripts/benchmark/benchmark_by_mIoU.py`)."""

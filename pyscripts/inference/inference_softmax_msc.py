@@ -10,8 +10,8 @@ name mapping (`resume=True`), `prediction_model` non-strictly -- a stage-1 `Segs
 `semantic_classifier.*` names next to entries this model does not have.  Every image becomes the ten views of
 `spml_amd.inference.flip_scale_views` (scales 0.5, 0.75, 1, 1.25, 1.5, each flipped and plain, zero-padded to the crop
 size: :90-103) and goes through `spml_amd.inference.predict_softmax_multiscale` (sliding windows and the HIP classifier
-head per view, one HIP kernel per view for counts, crop, resize, softmax, un-flip and sum, one arg-max).  As in the
-training entry points the file-list loader is outside this repository: `--data_list synthetic` feeds seeded synthetic
+head per view, one HIP kernel per view for counts, crop, resize, softmax, un-flip and sum, one arg-max).  The
+evaluation file-list loader is outside this repository: `--data_list synthetic` feeds seeded synthetic
 images of `test.image_size`.  Label maps are written as `semantic_gray/<name>.npy` (uint8; no image library is needed);
 one JSON line reports images/s, mIoU and pixel accuracy (`pyscripts/benchmark/benchmark_by_mIoU.py`), the number of
 views and the paths taken by the classifier head and by the per-view tail."""

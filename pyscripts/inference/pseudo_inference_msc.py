@@ -12,7 +12,7 @@ eight views of `spml_amd.inference.flip_scale_views` (scales 0.5, 1, 1.5, 2, eac
 crop size: :133-153) and goes through `spml_amd.inference.pseudo_labels_knn_multiscale`: per view the work of
 `inference_msc.py`, then one HIP launch pair that takes the mean over the views, normalises every class the image
 carries by its maximum over the image (floored at 0.15) and takes the arg-max (:252-263, :275).  The image's tags are
-the classes of its label map (:138-141).  As in the other entry points the file-list loader is outside this repository:
+the classes of its label map (:138-141).  As in the other inference programs the file-list loader is outside this repository:
 `--data_list synthetic` feeds seeded synthetic images of `test.image_size`, and without `--semantic_memory_dir` the bank
 is built from those images first, written with `save_image_memory` to `<save_dir>/semantic_prototype` and read back.
 Label maps are written as `semantic_gray/<name>.npy` (uint8); one JSON line reports images/s, mIoU and pixel accuracy

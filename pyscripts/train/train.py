@@ -11,11 +11,12 @@ memory bank and step order (spml_amd/train.py::Trainer.step), same snapshot file
 (`model-{iter}.pth` with `embedding_model` / `prediction_model`, `model-{iter}.state.pth`).
 Differences: one process per GPU under torch.distributed instead of nn.DataParallel over
 `config.gpus` (the global batch is `train.batch_size` per process x world size, as the
-reference's per-GPU batch), no tensorboard, and the data source: the reference's
-ListTagDataset (cv2 augmentation, file lists) is outside the scope of this repository --
-`--data_list synthetic` (the default when none is given) feeds seeded synthetic batches of
-the loader's shape (spml_amd/synth.py); a real loader only has to yield the same
-`(datas, targets)` dicts."""
+reference's per-GPU batch), no tensorboard, and where the augmentation runs: `--data_dir` /
+`--data_list` (or `dataset.data_dir` / `dataset.train_data_list` of the config) name a file list
+as the reference's ListTagDataset reads it (DenseposeDataset under the DensePose recipe); the host
+decodes the files and draws the augmentation, one launch per batch makes the pixels on the GPU
+(spml_amd/data, csrc/augment.hip).  `--data_list synthetic` (the default when no list is given
+anywhere) feeds seeded synthetic batches of the same shape (spml_amd/synth.py)."""
 import os
 import sys
 import time
@@ -49,6 +50,8 @@ def main(argv=None, default_recipe='voc', description='Training for pixel-wise e
   args = parse_args(description, argv)
   if not torch.cuda.is_available():
     raise SystemExit('training needs an MI355X (the HIP path has no CPU fallback)')
+  from spml_amd.data.batcher import resolve_data_list, training_batcher
+  source = resolve_data_list(args, config)  # (a list that does not exist ends the program here, by name)
   world = int(os.environ.get('WORLD_SIZE', '1'))
   rank = int(os.environ.get('RANK', '0'))
   local = int(os.environ.get('LOCAL_RANK', '0'))
@@ -92,11 +95,13 @@ def main(argv=None, default_recipe='voc', description='Training for pixel-wise e
   else:
     print('Training from scratch')
 
-  if args.data_list in (None, 'synthetic'):
+  if recipe == 'densepose':                 # train_densepose.py:27,60-69
+    from spml_amd.data.datasets.densepose_dataset import DenseposeDataset as dataset_class
+  else:                                     # train.py:27,63-72
+    from spml_amd.data.datasets.list_tag_dataset import ListTagDataset as dataset_class
+  batches = training_batcher(dataset_class, source, config, device, rank, world, first_iteration=trainer.curr_iter)
+  if batches is None:
     batches = synthetic_batches(config, device, rank, args.supervision, first=trainer.curr_iter)
-  else:
-    raise SystemExit('file-list data loading (ListTagDataset) is outside the scope of this repository; '
-                     'use --data_list synthetic or plug a loader that yields (datas, targets) dicts')
 
   t0 = time.time()
   for curr_iter in range(trainer.curr_iter, config.train.max_iteration):
@@ -116,6 +121,8 @@ def main(argv=None, default_recipe='voc', description='Training for pixel-wise e
       extra['spml_iteration'] = state['iteration']
       extra['spml_rng'] = {'cpu': torch.get_rng_state(), 'cuda': torch.cuda.get_rng_state(device)}
       torch.save(extra, state_path.format(curr_iter))
+  if hasattr(batches, 'close'):
+    batches.close()
   if world > 1:
     dist.destroy_process_group()
 

@@ -2,8 +2,10 @@
 """DensePose training entry point (`pyscripts/train/train_densepose.py` of twke18/SPML): the same
 loop as train.py with the DensePose embedding network (colour + location local features) and
 predictor (tags propagated from the nearest labelled segment) bound -- the reference's script
-differs from train.py only in those imports (train_densepose.py:27-29) and in its dataset class.
+differs from train.py only in those imports (train_densepose.py:27-29) and in its dataset class,
+DenseposeDataset (mirrored part labels swap left and right; spml_amd/data), which a file list is read with.
 
+  python3 pyscripts/train/train_densepose.py --data_dir D --data_list L --snapshot_dir S --cfg_path C.yaml
   python3 pyscripts/train/train_densepose.py --snapshot_dir S --cfg_path C.yaml [--data_list synthetic]"""
 import os
 import sys

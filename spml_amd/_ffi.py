@@ -176,6 +176,10 @@ _SIGNATURES = {
     'spml_segment_tag_cam_f32': (c_int, [_P, _P, _P, c_int64, c_float, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P,
                                          _P, _P, c_size_t, _P]),
     'spml_segment_tag_cam_path_name': (c_char_p, [c_int64, c_int, c_int]),
+    'spml_augment_params_bytes': (c_size_t, []),
+    'spml_augment_path_name': (c_char_p, [_P, c_int64, c_int, c_int]),
+    'spml_augment_batch_u8': (c_int, [_P, c_int64, _P, _P, c_int, _P, _P, _P, c_int, c_int, _P, _P, _P, _P]),
+    'spml_augment_tags_u8': (c_int, [_P, c_int64, _P, _P, c_int, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -1700,3 +1704,79 @@ def segment_tag_cam(nn_index, nn_value, proto_label, threshold, cluster_index, n
                                        ptr(counts, torch.int32, True), ptr(probs, torch.float32, True), ptr(ws),
                                        ws.numel(), stream_ptr()), 'spml_segment_tag_cam_f32')
   return (acc, counts, probs) if want_tables else acc
+
+
+# ---------------------------------------------------------------------------
+# Training batches from decoded files: the fused augmentation launch (csrc/augment.hip)
+def _augment_params_dtype():
+  import numpy as np
+  return np.dtype([('image_off', '<i8'), ('sem_off', '<i8'), ('inst_off', '<i8'), ('h', '<i4'), ('w', '<i4'),
+                   ('new_h', '<i4'), ('new_w', '<i4'), ('start_h', '<i4'), ('start_w', '<i4'), ('flip', '<i4'),
+                   ('gray', '<i4'), ('blur', '<i4'), ('reserved0', '<i4'), ('weights', '<f4', (25,)),
+                   ('reserved1', '<f4')])
+
+
+AUGMENT_PARAMS = _augment_params_dtype()      # spml_augment_params of include/spml_hip.h, field for field (168 bytes)
+
+
+def _augment_records(params):
+  """(host pointer, count) of a C-contiguous array of AUGMENT_PARAMS records whose size the library agrees with."""
+  import numpy as np
+  if not isinstance(params, np.ndarray) or params.dtype != AUGMENT_PARAMS or not params.flags['C_CONTIGUOUS']:
+    raise SpmlHipError('augment: the records must be a contiguous numpy array of _ffi.AUGMENT_PARAMS')
+  if lib().spml_augment_params_bytes() != AUGMENT_PARAMS.itemsize:
+    raise SpmlHipError('augment: spml_augment_params is %d bytes in the library, %d here'
+                       % (lib().spml_augment_params_bytes(), AUGMENT_PARAMS.itemsize))
+  return c_void_p(params.ctypes.data), int(params.size)
+
+
+def augment_path_name(record, packed_bytes, size):
+  """'plain', 'blur' or 'unsupported' for one record (a host function of the library: the expression its launch
+  evaluates for that record)."""
+  host, n = _augment_records(record.reshape(1) if getattr(record, 'ndim', 1) == 0 else record)
+  if n != 1:
+    raise SpmlHipError('augment_path_name takes one record')
+  return lib().spml_augment_path_name(host, int(packed_bytes), int(size[0]), int(size[1])).decode()
+
+
+def _augment_params_dev(params_dev, n):
+  if params_dev.dtype != torch.uint8 or params_dev.numel() != n * AUGMENT_PARAMS.itemsize:
+    raise SpmlHipError('augment: params_dev must hold the %d records as %d bytes of uint8' % (n, n * AUGMENT_PARAMS.itemsize))
+  return ptr(params_dev, torch.uint8)
+
+
+def augment_batch(packed, params, params_dev, mean, std, remap, size, out=None):
+  """One launch: `packed` uint8 (device; raw RGB + label planes) and `params` (host records; `params_dev` the same
+  bytes on the device) -> image fp32 `[B, 3, S_h, S_w]`, semantic_label, instance_label int64 `[B, S_h, S_w]`.
+  `out`: the three tensors to write into."""
+  host, n = _augment_records(params)
+  s_h, s_w = int(size[0]), int(size[1])
+  dev_ptr = _augment_params_dev(params_dev, n)
+  if out is None:
+    dev = packed.device
+    out = (torch.empty((n, 3, s_h, s_w), dtype=torch.float32, device=dev),
+           torch.empty((n, s_h, s_w), dtype=torch.int64, device=dev),
+           torch.empty((n, s_h, s_w), dtype=torch.int64, device=dev))
+  image, sem, inst = out
+  if tuple(image.shape) != (n, 3, s_h, s_w) or tuple(sem.shape) != (n, s_h, s_w) or tuple(inst.shape) != (n, s_h, s_w):
+    raise SpmlHipError('augment_batch: outputs do not have the shapes of %d images at %d x %d' % (n, s_h, s_w))
+  if mean.numel() != 3 or std.numel() != 3 or remap.numel() != 256:
+    raise SpmlHipError('augment_batch: mean and std hold 3 values, the remap table 256')
+  check(lib().spml_augment_batch_u8(ptr(packed, torch.uint8), packed.numel(), host, dev_ptr, n, ptr(mean, torch.float32),
+                                    ptr(std, torch.float32), ptr(remap, torch.uint8), s_h, s_w,
+                                    ptr(image, torch.float32), ptr(sem, torch.int64), ptr(inst, torch.int64),
+                                    stream_ptr()), 'spml_augment_batch_u8')
+  return image, sem, inst
+
+
+def augment_tags(packed, params, params_dev, out=None):
+  """semantic_tag int64 `[B, 256]`: the multi-hot of the values in the un-augmented semantic planes of `packed`."""
+  host, n = _augment_records(params)
+  dev_ptr = _augment_params_dev(params_dev, n)
+  if out is None:
+    out = torch.empty((n, 256), dtype=torch.int64, device=packed.device)
+  if tuple(out.shape) != (n, 256):
+    raise SpmlHipError('augment_tags: the output must be [%d, 256]' % n)
+  check(lib().spml_augment_tags_u8(ptr(packed, torch.uint8), packed.numel(), host, dev_ptr, n, ptr(out, torch.int64),
+                                   stream_ptr()), 'spml_augment_tags_u8')
+  return out

@@ -375,3 +375,38 @@ def upsample_bilinear(x, size=None, scale_factor=None):
   if x.is_cuda and x.requires_grad and _ffi.deterministic():
     return _UpsampleBilinearDetBwd.apply(x, tuple(size))
   return F.interpolate(x, size=size, mode='bilinear')
+
+
+# ---------------------------------------------------------------------------
+# Training batches from decoded files (csrc/augment.hip; spml_amd/data)
+# ---------------------------------------------------------------------------
+AUGMENT_PARAMS = _ffi.AUGMENT_PARAMS
+
+
+def augment_path_name(record, packed_bytes, size):
+  """'plain', 'blur' or 'unsupported': what one parameter record runs as (host only)."""
+  return _ffi.augment_path_name(record, packed_bytes, size)
+
+
+def augment_batch(packed, params, mean, std, remap, size, params_dev=None, out=None):
+  """The reference's per-image augmentation chain (base_dataset.py:135-155,183-186, list_tag_dataset.py:179-218,
+  densepose_dataset.py:157-198) as one launch over a packed batch of decoded files: `packed` uint8 on the GPU, `params` a
+  numpy array of `AUGMENT_PARAMS` records (one per image; `params_dev`: the same bytes on the GPU, uploaded here when
+  not given), `mean` / `std` fp32 `[3]` and `remap` uint8 `[256]` on the GPU, `size = (S_h, S_w)`.
+  -> image fp32 `[B, 3, S_h, S_w]`, semantic_label, instance_label int64 `[B, S_h, S_w]`.  No CPU path."""
+  if not packed.is_cuda:
+    raise _ffi.SpmlHipError('the HIP path needs GPU tensors (got %s); there is no CPU fallback' % packed.device)
+  if params_dev is None:
+    params_dev = torch.from_numpy(params.view('uint8').reshape(-1).copy()).to(packed.device)
+  with torch.no_grad():
+    return _ffi.augment_batch(packed, params, params_dev, mean, std, remap, size, out)
+
+
+def augment_tags(packed, params, params_dev=None, out=None):
+  """semantic_tag int64 `[B, 256]` (list_tag_dataset.py:75-78) from the semantic planes of the same packed buffer."""
+  if not packed.is_cuda:
+    raise _ffi.SpmlHipError('the HIP path needs GPU tensors (got %s); there is no CPU fallback' % packed.device)
+  if params_dev is None:
+    params_dev = torch.from_numpy(params.view('uint8').reshape(-1).copy()).to(packed.device)
+  with torch.no_grad():
+    return _ffi.augment_tags(packed, params, params_dev, out)

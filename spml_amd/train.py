@@ -134,8 +134,9 @@ class Trainer:
     (targets['prototype'], targets['prototype_with_loc'], targets['prototype_semantic_label'],
      targets['prototype_instance_label'], targets['prototype_batch_index'],
      emb['cluster_index']) = parallel.gather_prototypes(*protos)
-    targets['semantic_tag'] = parallel.gather_tags(targets['semantic_tag'])
-    targets['prototype_semantic_tag'] = targets['semantic_tag'][targets['prototype_batch_index']]
+    if targets.get('semantic_tag', None) is not None:      # (the DensePose datasets carry none: train_densepose.py:187-195)
+      targets['semantic_tag'] = parallel.gather_tags(targets['semantic_tag'])
+      targets['prototype_semantic_tag'] = targets['semantic_tag'][targets['prototype_batch_index']]
     for k, bank in self.memory_banks.items():
       assert targets.get(k, None) is None
       targets[k] = list(bank)

@@ -998,6 +998,70 @@ def gen_n12(ref, out):
   assert size < 600 * 1024, 'n12_densepose_pseudo.npz is %d bytes' % size
 
 
+def gen_n13(ref, out):
+  """N13: the numpy-only stages of the training augmentation.  `spml/data/transforms.py` imports cv2, which is not
+  installed: an empty module stands in for it in memory while the file is imported (none of the functions called here
+  touches it).  `transforms.mirror`, `resize_with_pad` and `random_crop_with_pad` (with `return_bbox`, under a seeded
+  `np.random`) are the reference's own functions; the grayscale lines (list_tag_dataset.py:202-205), the blur-weight lines
+  (:210-212) and the tag lines (:76-78) are exec'd from the reference's file.  `cv2.resize` and `cv2.filter2D` themselves
+  cannot be run: tests/augment_ref.py restates them and tests/test_augment.py holds those two to ATen on the CPU."""
+  import linecache
+  import textwrap
+  had = sys.modules.get('cv2')
+  sys.modules['cv2'] = types.ModuleType('cv2')
+  try:
+    import spml.data.transforms as transforms
+  finally:
+    if had is None:
+      del sys.modules['cv2']
+    else:
+      sys.modules['cv2'] = had
+  py = os.path.join(ref, 'spml', 'data', 'datasets', 'list_tag_dataset.py')
+
+  def ref_lines(first, last):
+    txt = ''.join(linecache.getline(py, i) for i in range(first, last + 1))
+    assert txt.strip(), py
+    return textwrap.dedent(txt)
+
+  src_gray, src_weight, src_tags = ref_lines(202, 205), ref_lines(210, 212), ref_lines(76, 78)
+  assert src_gray.startswith('rgb2gray = np.array([0.3, 0.59, 0.11]') and 'np.tile(image, (1,1,3))' in src_gray
+  assert src_weight.startswith('w_x, w_y = np.meshgrid') and src_weight.rstrip().endswith('weight / weight.sum()')
+  assert src_tags.startswith('cats = np.unique(semantic_label)') and src_tags.rstrip().endswith('semantic_tags[cats] = 1')
+
+  rng = np.random.RandomState(235)
+  mean = (0.485, 0.456, 0.406)
+  store = {'mean': np.array(mean)}
+  # (h, w, crop): both sides below the crop, one above and one below, both above, equal to the crop
+  for ci, (h, w, crop) in enumerate([(5, 7, (9, 11)), (13, 6, (9, 11)), (17, 19, (9, 11)), (9, 11, (9, 11))]):
+    image = (rng.randint(0, 256, (h, w, 3)).astype(np.float32) / 255).astype(np.float32)
+    label = np.stack([rng.choice(np.array([0, 3, 14, 254, 255], np.uint8), (h, w)),
+                      rng.randint(0, 256, (h, w)).astype(np.uint8)], axis=2)
+    m_image, m_label = transforms.mirror(image, label)
+    p_image = transforms.resize_with_pad(image, crop, mean)
+    p_label = transforms.resize_with_pad(label, crop, 255)
+    np.random.seed(1000 + ci)
+    c_image, c_label, bbox = transforms.random_crop_with_pad(image, label, crop, mean, 255, return_bbox=True)
+    env = {'np': np, 'image': c_image}
+    exec(compile(src_gray, py + ':202-205', 'exec'), env)
+    env_t = {'np': np, 'semantic_label': label[..., 0]}
+    exec(compile(src_tags, py + ':76-78', 'exec'), env_t)
+    t = 'c%d_' % ci
+    store.update({t + 'image': image, t + 'label': label, t + 'crop': np.array(crop), t + 'mirror_image': m_image,
+                  t + 'mirror_label': m_label, t + 'pad_image': p_image, t + 'pad_label': p_label,
+                  t + 'crop_image': c_image, t + 'crop_label': c_label, t + 'bbox': np.array(bbox),
+                  t + 'gray': env['image'], t + 'tags': env_t['semantic_tags']})
+  sigmas = np.array([0.1, 0.7, 2.5, 5.0])
+  weights = []
+  for sigma in sigmas:
+    env = {'np': np, 'sigma': float(sigma)}
+    exec(compile(src_weight, py + ':210-212', 'exec'), env)
+    weights.append(env['weight'])
+  store.update({'sigmas': sigmas, 'weights': np.stack(weights)})
+  save(out, 'n13_augment', **store)
+  size = os.path.getsize(os.path.join(out, 'n13_augment.npz'))
+  assert size < 100 * 1024, 'n13_augment.npz is %d bytes' % size
+
+
 class AttrDict(dict):
   __getattr__ = dict.__getitem__
 
@@ -1017,7 +1081,8 @@ def main():
   sys.path.insert(0, args.ref)
   torch.set_num_threads(1)       # bit-stable fp32 sums
   if ONLY is not None and ONLY <= {'n7_pseudo_labels', 'n8_softmax_msc', 'n9_knn_msc', 'n10_prototype_msc',
-                                   'n11_pseudo_knn_msc', 'n11_instance_iou', 'n12_densepose_pseudo'}:      # (need none of the imports and shims below)
+                                   'n11_pseudo_knn_msc', 'n11_instance_iou', 'n12_densepose_pseudo',
+                                   'n13_augment'}:      # (need none of the imports and shims below)
     if 'n7_pseudo_labels' in ONLY:
       gen_n7(args.ref, out)
     if 'n8_softmax_msc' in ONLY:
@@ -1032,6 +1097,8 @@ def main():
       gen_n11_instance(args.ref, out)
     if 'n12_densepose_pseudo' in ONLY:
       gen_n12(args.ref, out)
+    if 'n13_augment' in ONLY:
+      gen_n13(args.ref, out)
     return
 
   import spml.utils.general.common as g_common
@@ -1845,6 +1912,10 @@ def main():
   # ======================= N12: DensePose pseudo labels (tag propagation, walk) ==============
   if ONLY is None or 'n12_densepose_pseudo' in ONLY:
     gen_n12(args.ref, out)
+
+  # ======================= N13: the numpy-only stages of the training augmentation ===========
+  if ONLY is None or 'n13_augment' in ONLY:
+    gen_n13(args.ref, out)
 
   # ======================= H2: two steps of the stage-2 classifier training ===============
   # pyscripts/train/train_classifier.py:139-169, the loop body exec'd as it stands on ONE device:
