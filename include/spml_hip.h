@@ -50,7 +50,7 @@ const char* spml_status_string(int status);
  * 8: spml_upsample_ce_bwd_path_name (entry points added since leave every earlier signature and flag as it was and
  *    keep the version: spml_view_votes_*, spml_segsort_nll_batched_*, spml_segment_majority_*, spml_tag_normalize_*,
  *    spml_dense_crf_*, spml_segment_tag_cam_*, spml_conv_hl8_path_name, spml_conv_wgrad_path_name / _splits,
- *    spml_augment_*). */
+ *    spml_augment_*, spml_image_views_*, spml_label_export_*). */
 #define SPML_ABI_VERSION 8
 int spml_abi_version(void);
 
@@ -1213,6 +1213,64 @@ int spml_augment_batch_u8(const unsigned char* packed, int64_t packed_bytes, con
                           int64_t* instance_label, void* stream);
 int spml_augment_tags_u8(const unsigned char* packed, int64_t packed_bytes, const spml_augment_params* params_host,
                          const spml_augment_params* params_dev, int B, int64_t* semantic_tag, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Inference from decoded files: the view pyramid and the label export, one launch each (csrc/inference_io.hip;
+ * DESIGN.md 8o)
+ * replaces: spml/data/datasets/base_dataset.py:105-119,157-171 (uint8 / 255, mean / std), spml/utils/general/others.py
+ *           :10-47 (create_image_pyramid) with spml/data/transforms.py:26-37 (resize), :110-119
+ *           (resize_with_interpolation), :134-151 (resize_with_pad) and the upload of every finished fp32 view;
+ *           pyscripts/inference/inference_softmax.py:142-160 (the padded prediction copied to the host, cropped, resized
+ *           with cv2.INTER_NEAREST and coloured there).
+ *
+ * spml_image_views_u8: rgb uint8 [h][w][3] (as PIL decodes it) and, optionally, semantic uint8 [h][w] -> all V views of
+ * the image.  One spml_view_params record per view.  View v is the contiguous plane set fp32 [3][pad_h][pad_w] at byte
+ * image_off of `images` and, when `semantic` is given, its label int64 [new_h][new_w] (unpadded) at byte label_off of
+ * `labels`.  Output pixel (y, x) of view v:
+ *   outside new_h x new_w: exactly 0.0f in all three channels (the reference pads the normalised image with 0);
+ *   inside: X = x, or new_w - 1 - x under flip (the reference resizes first and mirrors the resized image);
+ *   image, cv2.resize(INTER_LINEAR) on the normalised fp32 image: per axis scale = 1.0 / ((double)new / src),
+ *     f = (X + 0.5) * scale - 0.5, s = floor(f), f -= s; s < 0 -> s = 0, f = 0; s >= src - 1 -> s = src - 1, f = 0;
+ *     the fraction rounded to fp32; every tap is normalised first, v = (u8 / 255.0f - mean[c]) / std[c], then
+ *     value = b0 * (a0 * v00 + a1 * v01) + b1 * (a0 * v10 + a1 * v11); new == src gives the normalised byte exactly;
+ *   label, INTER_NEAREST: s = min(floor(X * scale), src - 1), the same double scale and the same mirror; no remap.
+ * The coordinates are formed in fp64 in the kernel with the operations above, unfused: the labels equal the host
+ * chain's bit for bit.  rgb, semantic, mean, std (fp32 [3]) and params_dev are device pointers; params_host and
+ * params_dev hold the same V records: the host copy is checked before anything is launched, the device copy is what the
+ * kernel reads (and checks again: a record that fails writes nothing and forms no address).  image_bytes / label_bytes:
+ * the sizes of the two output buffers.  Every element of every plane is written: the buffers need no memset.
+ * SPML_ERR_UNSUPPORTED, with nothing launched and no output touched: a side of the source, of a view or of its padded
+ * plane outside [1, 16384], pad < new, V outside [1, 64], an offset that is negative, not a multiple of the element size
+ * or whose plane leaves its buffer, two planes of one buffer that overlap.  SPML_ERR_INVALID_ARG: a null or misaligned
+ * pointer (labels without semantic or the reverse included), an output that overlaps an input or the other output.
+ * One launch, no workspace, no atomics, no host read of device memory: bit-identical from call to call.
+ * spml_image_views_path_name (host only; the expression the entry itself evaluates): "views", "views+labels" or
+ * "unsupported".  spml_view_params_bytes: sizeof(spml_view_params), for bindings.
+ *
+ * spml_label_export_u8: prediction int64 [pred_h][pred_w] (contiguous), its valid rectangle valid_h x valid_w at the top
+ * left, color_map uint8 [256][3] -> gray uint8 [out_h][out_w] and rgb uint8 [out_h][out_w][3]: source pixel by
+ * INTER_NEAREST from the valid rectangle to the output size (the index rule above; out == valid is the identity),
+ * gray = (uint8)label, rgb = color_map[gray].  One launch; the table is read through the cache.  SPML_ERR_UNSUPPORTED:
+ * a side outside [1, 16384], a valid rectangle larger than the prediction.  SPML_ERR_INVALID_ARG: a null or misaligned
+ * pointer, an output that overlaps an input or the other output.  spml_label_export_path_name: "export" or
+ * "unsupported". */
+typedef struct spml_view_params {
+  int64_t image_off, label_off;             /* byte offsets into `images` / `labels` */
+  int32_t new_h, new_w;                     /* int(scale * h), int(scale * w) */
+  int32_t pad_h, pad_w;                     /* max(new, crop) */
+  int32_t flip;                             /* 0 / non-zero */
+  int32_t reserved0;
+} spml_view_params;
+
+size_t spml_view_params_bytes(void);
+const char* spml_image_views_path_name(const spml_view_params* records, int V, int h, int w, int64_t image_bytes,
+                                       int64_t label_bytes, int with_labels);
+int spml_image_views_u8(const unsigned char* rgb, const unsigned char* semantic, int h, int w, const float* mean,
+                        const float* std, const spml_view_params* params_host, const spml_view_params* params_dev, int V,
+                        float* images, int64_t image_bytes, int64_t* labels, int64_t label_bytes, void* stream);
+const char* spml_label_export_path_name(int pred_h, int pred_w, int valid_h, int valid_w, int out_h, int out_w);
+int spml_label_export_u8(const int64_t* prediction, int pred_h, int pred_w, int valid_h, int valid_w, int out_h, int out_w,
+                         const unsigned char* color_map, unsigned char* gray, unsigned char* rgb, void* stream);
 
 #ifdef __cplusplus
 }

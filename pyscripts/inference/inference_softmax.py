@@ -8,10 +8,13 @@ Loads `model-{max_iteration-1}.pth` from the snapshot directory (:70-76): `embed
 name mapping (`resume=True`), `prediction_model` non-strictly -- a stage-1 `SegsortSoftmax` snapshot carries the same
 `semantic_classifier.*` names next to entries this model does not have.  Every image goes through
 `spml_amd.inference.predict_softmax_full_resolution` (sliding windows, HIP classifier head, summed logits, arg-max).
-The evaluation file-list loader is outside this repository: `--data_list synthetic` feeds seeded
-synthetic images of `test.image_size`, padded to the crop size (:97-103).  Label maps are written as
-`semantic_gray/<name>.npy` (uint8; no image library is needed); one JSON line reports images/s and, where labels
-exist, mIoU and pixel accuracy (`pyscripts/benchmark/benchmark_by_mIoU.py`)."""
+`--data_dir D --data_list L` reads the reference's file list (`ListDataset`): the view of every file is made on the GPU
+from its decoded bytes (`spml_amd.inference.device_views`: normalised, resized to `test.image_size`, padded to the crop
+size, :89-103) and the label map goes back to the file's own size (:148-152) as `semantic_gray/<name>.png` and
+`semantic_color/<name>.png` (`spml_amd.inference.export_label_map`), the folders `benchmark_by_mIoU.py` scores.
+`--data_list synthetic` feeds seeded synthetic images of `test.image_size` and writes `semantic_gray/<name>.npy` (uint8).
+One JSON line reports images/s and, where labels exist, mIoU and pixel accuracy
+(`pyscripts/benchmark/benchmark_by_mIoU.py`)."""
 import os
 import sys
 
@@ -20,24 +23,23 @@ sys.path.insert(0, ROOT)
 
 def main(argv=None):
   from spml_amd import inference, inference_cli as cli
-  from spml_amd.utils.general import metrics
-  config, args, device = cli.parse('Inference for semantic segmentation.', argv, 'predict_softmax_full_resolution')
+  api = 'predict_softmax_full_resolution'
+  config, args, device = cli.parse('Inference for semantic segmentation.', argv, api, file_lists='images')
   semantic_dir = cli.output_dir(args, 'semantic_gray')
+  source = cli.ImageSource.for_program(config, args, device, [1], False, api, single_view=True)   # :89-103
   embedding_model, prediction_model, path = cli.load_models(config, args, device, 'softmax_classifier')   # :63-76
-  num_classes, crop_size, stride, size = cli.geometry(config)
-  counts, out = None, None
+  _, crop_size, stride, _ = cli.geometry(config)
+  out = None
 
-  def one(index):
-    nonlocal counts, out
-    image, label, _ = cli.synthetic_image(index, size, num_classes, device)
-    padded = inference.flip_scale_views(image, [1], False, crop_size)[0][0]                   # resize_with_pad, :97-103
-    out = inference.predict_softmax_full_resolution(embedding_model, prediction_model, padded, (size, size), crop_size,
-                                                    stride)
-    counts = metrics.iou_stats(out['semantic_prediction'], label, num_classes, counts)
-    cli.save_label_map(semantic_dir, index, out['semantic_prediction'])
+  def one(image):
+    nonlocal out
+    padded, valid_hw, _ = image.views[0]
+    out = inference.predict_softmax_full_resolution(embedding_model, prediction_model, padded, valid_hw, crop_size, stride)
+    source.emit(image, out['semantic_prediction'], semantic_dir)
 
-  done, seconds = cli.timed_images(one)
-  cli.report(done, seconds, **cli.scores(counts), head_path=out['head_path'], snapshot=path, save_dir=semantic_dir)
+  done, seconds = source.timed(one)
+  cli.report(done, seconds, **source.scores(), head_path=out['head_path'], snapshot=path, save_dir=semantic_dir,
+             **source.fields())
 
 
 if __name__ == '__main__':

@@ -6,7 +6,9 @@
       --kmeans_num_clusters 12,12 --label_divisor 2048
 
 One view per image at its own size: the pass of `prototype_msc.py` with the scales `[1]`; the bank of every image goes
-to `<save_dir>/semantic_prototype/<name>.npy`; see `run_prototypes` of spml_amd/inference_cli.py."""
+to `<save_dir>/semantic_prototype/<name>.npy`; see `run_prototypes` of spml_amd/inference_cli.py.  `--data_dir D
+--data_list L` reads the reference's file list with its label columns (image and label go to `test.image_size` first,
+:96-105); `--data_list synthetic` feeds seeded synthetic images."""
 import os
 import sys
 
@@ -18,7 +20,7 @@ SCALES = [1]
 
 def main(argv=None):
   from spml_amd.inference_cli import run_prototypes
-  run_prototypes('Inference for generating memory banks.', SCALES, argv)
+  run_prototypes('Inference for generating memory banks.', SCALES, argv, single_view=True)
 
 
 if __name__ == '__main__':

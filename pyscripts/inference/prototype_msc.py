@@ -7,7 +7,9 @@
 
 Three views per image (scales 0.5, 1, 1.5, no flip: :92-95); per view the sliding-window embedding, k-means that ignores
 the padding, prototypes and their majority labels; the views' banks concatenated into
-`<save_dir>/semantic_prototype/<name>.npy`; see `run_prototypes` of spml_amd/inference_cli.py."""
+`<save_dir>/semantic_prototype/<name>.npy`; see `run_prototypes` of spml_amd/inference_cli.py.  `--data_dir D
+--data_list L` reads the reference's file list with its label columns; `--data_list synthetic` feeds seeded synthetic
+images."""
 import os
 import sys
 

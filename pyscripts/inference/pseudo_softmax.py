@@ -6,8 +6,10 @@
 
 Flip pairs at scales 0.75 and 1, mean of the views' logits and one softmax, WALK_STEPS = 0: the class maps go once
 through the transition matrix, without squarings (:29, :108-111, :144-150).  The script's CRF lines are commented out,
-so the labels written as `semantic_gray/<name>.npy` are its output; see `run_pseudo_softmax` of
-spml_amd/inference_cli.py."""
+so the labels written are its output: `semantic_gray/<name>.png` and `semantic_color/<name>.png` at the file's own size
+under `--data_dir D --data_list L` (the reference's file list with its label columns, which give the image tags; the
+folder `train_classifier.py --data_list` reads back), `semantic_gray/<name>.npy` under `--data_list synthetic`; see
+`run_pseudo_softmax` of spml_amd/inference_cli.py."""
 import os
 import sys
 

@@ -7,7 +7,9 @@ box recipes run it between stage 1 and stage 2):
 
 Flip pair at scale 1, softmax per view and mean of the probabilities, WALK_STEPS = 6 squarings of the transition
 matrix (:29, :109-112, :143-147).  Writes the labels of :176 (before the denseCRF refinement, which is outside this
-repository) as `semantic_gray/<name>.npy`; see `run_pseudo_softmax` of spml_amd/inference_cli.py."""
+repository): `semantic_gray/<name>.png` and `semantic_color/<name>.png` at the file's own size under `--data_dir D
+--data_list L` (the reference's file list with its label columns, which give the image tags), `semantic_gray/<name>.npy`
+under `--data_list synthetic`; see `run_pseudo_softmax` of spml_amd/inference_cli.py."""
 import os
 import sys
 

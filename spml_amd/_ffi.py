@@ -180,6 +180,11 @@ _SIGNATURES = {
     'spml_augment_path_name': (c_char_p, [_P, c_int64, c_int, c_int]),
     'spml_augment_batch_u8': (c_int, [_P, c_int64, _P, _P, c_int, _P, _P, _P, c_int, c_int, _P, _P, _P, _P]),
     'spml_augment_tags_u8': (c_int, [_P, c_int64, _P, _P, c_int, _P, _P]),
+    'spml_view_params_bytes': (c_size_t, []),
+    'spml_image_views_path_name': (c_char_p, [_P, c_int, c_int, c_int, c_int64, c_int64, c_int]),
+    'spml_image_views_u8': (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P, c_int, _P, c_int64, _P, c_int64, _P]),
+    'spml_label_export_path_name': (c_char_p, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    'spml_label_export_u8': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -1780,3 +1785,83 @@ def augment_tags(packed, params, params_dev, out=None):
   check(lib().spml_augment_tags_u8(ptr(packed, torch.uint8), packed.numel(), host, dev_ptr, n, ptr(out, torch.int64),
                                    stream_ptr()), 'spml_augment_tags_u8')
   return out
+
+
+# ---------------------------------------------------------------------------
+# Inference from decoded files: the view pyramid and the label export (csrc/inference_io.hip)
+def _view_params_dtype():
+  import numpy as np
+  return np.dtype([('image_off', '<i8'), ('label_off', '<i8'), ('new_h', '<i4'), ('new_w', '<i4'), ('pad_h', '<i4'),
+                   ('pad_w', '<i4'), ('flip', '<i4'), ('reserved0', '<i4')])
+
+
+VIEW_PARAMS = _view_params_dtype()            # spml_view_params of include/spml_hip.h, field for field (40 bytes)
+
+
+def _view_records(params):
+  """(host pointer, count) of a C-contiguous array of VIEW_PARAMS records whose size the library agrees with."""
+  import numpy as np
+  if not isinstance(params, np.ndarray) or params.dtype != VIEW_PARAMS or not params.flags['C_CONTIGUOUS']:
+    raise SpmlHipError('image_views: the records must be a contiguous numpy array of _ffi.VIEW_PARAMS')
+  if lib().spml_view_params_bytes() != VIEW_PARAMS.itemsize:
+    raise SpmlHipError('image_views: spml_view_params is %d bytes in the library, %d here'
+                       % (lib().spml_view_params_bytes(), VIEW_PARAMS.itemsize))
+  return c_void_p(params.ctypes.data), int(params.size)
+
+
+def image_views_path_name(params, source_hw, image_bytes, label_bytes=0, with_labels=False):
+  """'views', 'views+labels' or 'unsupported' for the records of one image (a host function of the library: the
+  expression its entry evaluates before the launch)."""
+  host, n = _view_records(params)
+  return lib().spml_image_views_path_name(host, n, int(source_hw[0]), int(source_hw[1]), int(image_bytes),
+                                          int(label_bytes), int(bool(with_labels))).decode()
+
+
+def image_views(rgb, semantic, params, params_dev, mean, std, images, labels=None):
+  """One launch: `rgb` uint8 `[h, w, 3]` (+ `semantic` uint8 `[h, w]`), both on the device, and `params` (host records;
+  `params_dev` the same bytes on the device) -> every view into `images` (fp32, flat) at its `image_off` and, with a
+  label, into `labels` (int64, flat) at its `label_off`."""
+  host, n = _view_records(params)
+  if rgb.dim() != 3 or rgb.shape[2] != 3:
+    raise SpmlHipError('image_views: rgb must be uint8 [h, w, 3]')
+  h, w = int(rgb.shape[0]), int(rgb.shape[1])
+  if (semantic is None) != (labels is None):
+    raise SpmlHipError('image_views: the label buffer goes with the semantic plane')
+  if semantic is not None and tuple(semantic.shape) != (h, w):
+    raise SpmlHipError('image_views: the semantic plane must be uint8 [%d, %d]' % (h, w))
+  if params_dev.dtype != torch.uint8 or params_dev.numel() != n * VIEW_PARAMS.itemsize:
+    raise SpmlHipError('image_views: params_dev must hold the %d records as %d bytes of uint8' % (n, n * VIEW_PARAMS.itemsize))
+  if mean.numel() != 3 or std.numel() != 3:
+    raise SpmlHipError('image_views: mean and std hold 3 values')
+  check(lib().spml_image_views_u8(ptr(rgb, torch.uint8), ptr(semantic, torch.uint8, allow_none=True), h, w,
+                                  ptr(mean, torch.float32), ptr(std, torch.float32), host, ptr(params_dev, torch.uint8), n,
+                                  ptr(images, torch.float32), images.numel() * 4, ptr(labels, torch.int64, allow_none=True),
+                                  0 if labels is None else labels.numel() * 8, stream_ptr()), 'spml_image_views_u8')
+  return images, labels
+
+
+def label_export_path_name(pred_hw, valid_hw, out_hw):
+  return lib().spml_label_export_path_name(int(pred_hw[0]), int(pred_hw[1]), int(valid_hw[0]), int(valid_hw[1]),
+                                           int(out_hw[0]), int(out_hw[1])).decode()
+
+
+def label_export(prediction, valid_hw, out_hw, color_map, out=None):
+  """One launch: `prediction` int64 `[pred_h, pred_w]`, its valid top-left rectangle, `color_map` uint8 `[256, 3]`
+  -> (gray uint8 `[out_h, out_w]`, rgb uint8 `[out_h, out_w, 3]`).  `out`: the two tensors to write into."""
+  if prediction.dim() != 2:
+    raise SpmlHipError('label_export: the prediction must be int64 [pred_h, pred_w]')
+  if tuple(color_map.shape) != (256, 3):
+    raise SpmlHipError('label_export: the colour map must be uint8 [256, 3]')
+  oh, ow = int(out_hw[0]), int(out_hw[1])
+  if out is None:
+    if oh < 1 or ow < 1:
+      raise SpmlHipError('label_export: an output of %d x %d' % (oh, ow))
+    out = (torch.empty((oh, ow), dtype=torch.uint8, device=prediction.device),
+           torch.empty((oh, ow, 3), dtype=torch.uint8, device=prediction.device))
+  gray, rgb = out
+  if tuple(gray.shape) != (oh, ow) or tuple(rgb.shape) != (oh, ow, 3):
+    raise SpmlHipError('label_export: outputs do not have the shapes of a %d x %d map' % (oh, ow))
+  check(lib().spml_label_export_u8(ptr(prediction, torch.int64), int(prediction.shape[0]), int(prediction.shape[1]),
+                                   int(valid_hw[0]), int(valid_hw[1]), oh, ow, ptr(color_map, torch.uint8),
+                                   ptr(gray, torch.uint8), ptr(rgb, torch.uint8), stream_ptr()), 'spml_label_export_u8')
+  return gray, rgb

@@ -83,6 +83,12 @@ class ListDataset:
     instance_label = self._read_label(self.instance_label_paths[idx]) if self.instance_label_paths else None
     return image, semantic_label, instance_label
 
+  def read(self, idx):
+    """-> (rgb uint8 [h, w, 3], semantic_label, instance_label uint8 [h, w] or None): the decoded files of entry `idx`,
+    in either mode.  What the inference programs take (`spml_amd.inference_cli.ImageSource`): their views are made on
+    the GPU from these bytes (csrc/inference_io.hip)."""
+    return self._get_datas_by_index(idx)
+
   def plan(self, idx, h, w, epoch=0):
     """The parameter record of sample `idx` in `epoch` for an `h x w` file."""
     return transforms.plan_training(

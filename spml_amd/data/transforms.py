@@ -1,7 +1,8 @@
 """The *plan* of the reference's augmentation (`spml/data/transforms.py`, the `_training_preprocess` of its dataset
 classes): what it draws, in its order and from its distributions -- and nothing else.  The functions return the
 parameter record of `spml_augment_batch_u8` (include/spml_hip.h) instead of pixels; the pixels are made on the GPU by one
-launch per batch (csrc/augment.hip).
+launch per batch (csrc/augment.hip).  `plan_views` is the same for the inference programs: the views of one file in the
+reference's order and sizes, as the records of `spml_image_views_u8` (csrc/inference_io.hip).
 
 The draws come from a `numpy.random.Generator` seeded by `(seed, epoch, index)`, never from global state: a sample's
 augmentation is a function of those three numbers, whichever thread decodes it and whenever."""
@@ -69,3 +70,44 @@ def plan_training(rng, h, w, size, random_mirror, random_scale, random_crop, sca
   return {'h': int(h), 'w': int(w), 'new_h': new_h, 'new_w': new_w, 'flip': flip, 'start_h': start_h,
           'start_w': start_w, 'gray': gray, 'blur': blur,
           'weights': np.zeros((25,), np.float32) if weights is None else weights.reshape(25).astype(np.float32)}
+
+
+def _align16(n):
+  return (int(n) + 15) // 16 * 16
+
+
+def plan_views(h, w, scales, is_flip, crop_size, image_size=0, name=''):
+  """The views of one `h x w` file at inference, in the reference's order and arithmetic: per scale the flipped view
+  first, then the plain one (`create_image_pyramid`, spml/utils/general/others.py:29-32); `new = int(scale * side)` in
+  Python doubles (transforms.py:26-27); with `image_size > 0` (the single-view programs; only with `scales == [1]`) the
+  larger side goes to `image_size`: `ratio = min(S / h, S / w)`, `new = int(ratio * side)` (transforms.py:110-113; the
+  truncation can leave the larger side one short of S); `pad = max(new, crop)` per axis (transforms.py:134-137).
+  -> list of dicts with the fields of `spml_view_params`; `image_off` / `label_off` are byte offsets into one fp32 and
+  one int64 buffer, packed in view order with 16-byte alignment (`view_buffer_bytes`: the sizes of the two)."""
+  h, w = int(h), int(w)
+  scales = list(scales)
+  if image_size and image_size > 0:
+    if scales != [1]:
+      raise ValueError('plan_views: image_size goes with scales == [1] (the single-view programs), not %r' % (scales,))
+    new_size = float(image_size)
+    ratio = min(new_size / h, new_size / w)
+    sizes = [(int(ratio * h), int(ratio * w))]
+  else:
+    sizes = [(int(scale * h), int(scale * w)) for scale in scales]
+  views, image_off, label_off = [], 0, 0
+  for (new_h, new_w), scale in zip(sizes, scales):
+    if new_h < 1 or new_w < 1:
+      raise ValueError('%s: %d x %d at scale %s has no pixel left' % (name or 'image', h, w, scale))
+    pad_h, pad_w = max(new_h, int(crop_size[0])), max(new_w, int(crop_size[1]))
+    for flip in ((True, False) if is_flip else (False,)):
+      views.append({'new_h': new_h, 'new_w': new_w, 'pad_h': pad_h, 'pad_w': pad_w, 'flip': flip,
+                    'image_off': image_off, 'label_off': label_off})
+      image_off = _align16(image_off + 3 * pad_h * pad_w * 4)
+      label_off = _align16(label_off + new_h * new_w * 8)
+  return views
+
+
+def view_buffer_bytes(views):
+  """-> (bytes of the fp32 buffer, bytes of the int64 buffer) that hold every plane of `plan_views`' records."""
+  return (max(v['image_off'] + 3 * v['pad_h'] * v['pad_w'] * 4 for v in views),
+          max(v['label_off'] + v['new_h'] * v['new_w'] * 8 for v in views))

@@ -127,7 +127,8 @@ def label_views(label, view_sizes):
   neighbour to each `(rh, rw)` of `view_sizes` -- the second entries of `flip_scale_views`' views, so that the image and
   the label of a view always have one size.  -> list of int64 `[rh, rw]` maps on the label's device.  A host-side
   stand-in for the loader (cv2's INTER_NEAREST there, torch's `nearest` here): not parity-pinned; for views that
-  `flip_scale_views` mirrored the caller mirrors the label too (the memory-bank pass makes none)."""
+  `flip_scale_views` mirrored the caller mirrors the label too (the memory-bank pass makes none).  The label views of a
+  decoded file come from `device_views(..., semantic_label=...)`."""
   label = torch.as_tensor(label)
   if label.dim() != 2:
     raise ValueError('label_views expects one label map [h,w]')
@@ -494,7 +495,9 @@ def flip_scale_views(image, scales, is_flip, crop_size):
   spml/utils/general/others.py + `resize_with_pad`, pseudo_softmaxrw_crf.py:109-125): per scale the flipped view first
   (when `is_flip`), then the plain one; each resized bilinearly to `round(h * scale) x round(w * scale)` and
   zero-padded at the bottom / right to at least `crop_size`.  -> list of `(image [1,3,Hp,Wp], (rh, rw), is_flip)`,
-  the `views` of `pseudo_labels_softmax`.  A host-side stand-in for the loader (cv2 there): not parity-pinned."""
+  the `views` of `pseudo_labels_softmax`.  A host-side stand-in for the loader (cv2 there): not parity-pinned -- the
+  synthetic mode's and for callers with float images; a decoded file goes through `device_views`, which is pinned
+  (sizes `int(scale * side)`, not `round`)."""
   if image.dim() != 4 or image.shape[0] != 1:
     raise ValueError('flip_scale_views expects one image [1,3,H,W]')
   h, w = image.shape[-2:]
@@ -512,6 +515,78 @@ def flip_scale_views(image, scales, is_flip, crop_size):
       view[:, :, :rh, :rw] = torch.flip(scaled, dims=[3]) if flip else scaled
       views.append((view, (rh, rw), flip))
   return views
+
+
+def view_records(plan):
+  """`spml_amd.data.transforms.plan_views`' dicts -> the numpy array of `_ffi.VIEW_PARAMS` records the launch reads."""
+  records = np.zeros((len(plan),), dtype=_ffi.VIEW_PARAMS)
+  for k, view in enumerate(plan):
+    for name in ('image_off', 'label_off', 'new_h', 'new_w', 'pad_h', 'pad_w', 'flip'):
+      records[name][k] = int(view[name])
+  return records
+
+
+_NORMALISATION = {}       # (device, means, stds) -> the two fp32 [3] tensors on that device
+
+
+def _normalisation(device, pixel_means, pixel_stds):
+  key = (str(device), tuple(float(v) for v in pixel_means), tuple(float(v) for v in pixel_stds))
+  if key not in _NORMALISATION:
+    _NORMALISATION[key] = (torch.tensor(key[1], dtype=torch.float32, device=device),
+                           torch.tensor(key[2], dtype=torch.float32, device=device))
+  return _NORMALISATION[key]
+
+
+def views_from_records(rgb_u8, records, params_dev, mean, std, semantic_label=None):
+  """The launch behind `device_views`, for a caller that planned the views itself and already has the records on the
+  device (`params_dev`: the same bytes as uint8 -- `inference_cli.ImageSource` sends them up with the image in one
+  copy).  -> (views, label views or None)."""
+  from spml_amd.data import transforms
+  plan = [{name: int(r[name]) for name in ('image_off', 'label_off', 'new_h', 'new_w', 'pad_h', 'pad_w')} for r in records]
+  image_bytes, label_bytes = transforms.view_buffer_bytes(plan)
+  with torch.no_grad():
+    images = torch.empty((image_bytes // 4,), dtype=torch.float32, device=rgb_u8.device)
+    labels = None if semantic_label is None else torch.empty((label_bytes // 8,), dtype=torch.int64, device=rgb_u8.device)
+    _ffi.image_views(rgb_u8, semantic_label, records, params_dev, mean, std, images, labels)
+  views, label_views_ = [], []
+  for r, p in zip(records, plan):
+    at, n = p['image_off'] // 4, 3 * p['pad_h'] * p['pad_w']
+    views.append((images[at:at + n].view(1, 3, p['pad_h'], p['pad_w']), (p['new_h'], p['new_w']), bool(r['flip'])))
+    if labels is not None:
+      at, n = p['label_off'] // 8, p['new_h'] * p['new_w']
+      label_views_.append(labels[at:at + n].view(p['new_h'], p['new_w']))
+  return views, (label_views_ if labels is not None else None)
+
+
+def device_views(rgb_u8, scales, is_flip, crop_size, pixel_means, pixel_stds, image_size=0, semantic_label=None):
+  """The views of one decoded file, made on the GPU from its bytes by ONE launch (`spml_image_views_u8`): `rgb_u8` uint8
+  `[h,w,3]` on the device -> what the reference's loader and programs make on the host per view (normalise,
+  `create_image_pyramid` / `resize_with_interpolation` with cv2.INTER_LINEAR, mirror, `resize_with_pad` with zeros:
+  inference_softmax_msc.py:90-103, inference_softmax.py:89-103) in the reference's order, sizes
+  (`spml_amd.data.transforms.plan_views`: `int(scale * side)`) and arithmetic.  -> the `views` every `predict_*` /
+  `pseudo_*` function takes, `(image [1,3,Hp,Wp], (rh, rw), is_flip)`, as slices of one allocation.  With
+  `semantic_label` (uint8 `[h,w]` on the device) -> `(views, label views)`: the label of every view `[rh, rw]` int64
+  (cv2.INTER_NEAREST, mirrored with its view), the `label_views` of `multiscale_prototypes`.  No CPU path."""
+  from spml_amd.data import transforms
+  if not rgb_u8.is_cuda:
+    raise _ffi.SpmlHipError('the HIP path needs GPU tensors (got %s); there is no CPU fallback' % rgb_u8.device)
+  if rgb_u8.dim() != 3 or rgb_u8.shape[2] != 3 or rgb_u8.dtype != torch.uint8:
+    raise ValueError('device_views expects one decoded image, uint8 [h,w,3]')
+  records = view_records(transforms.plan_views(rgb_u8.shape[0], rgb_u8.shape[1], scales, is_flip, crop_size, image_size))
+  params_dev = torch.from_numpy(records.view(np.uint8).reshape(-1).copy()).to(rgb_u8.device)
+  mean, std = _normalisation(rgb_u8.device, pixel_means, pixel_stds)
+  views, labels = views_from_records(rgb_u8, records, params_dev, mean, std, semantic_label)
+  return views if semantic_label is None else (views, labels)
+
+
+def export_label_map(prediction, valid_hw, out_hw, color_map, out=None):
+  """The tail of a label-inference program (inference_softmax.py:142-160) as ONE launch (`spml_label_export_u8`):
+  `prediction` int64 `[pred_h,pred_w]` on the device, its valid top-left `valid_hw` rectangle resized with
+  cv2.INTER_NEAREST's rule to `out_hw` (the file's own size) -> `(gray uint8 [out_h,out_w], rgb uint8 [out_h,out_w,3])`
+  on the device, `rgb = color_map[gray]` (`color_map`: uint8 `[256,3]` on the device).  `out`: the two tensors to write
+  into (slices of one buffer come down in one copy)."""
+  with torch.no_grad():
+    return _ffi.label_export(prediction, valid_hw, out_hw, color_map, out)
 
 
 def _walked_cams_softmax(name, embedding_model, prediction_model, views, image_hw, label_tags, combine, walk_steps,

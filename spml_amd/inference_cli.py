@@ -1,7 +1,8 @@
 """Shared body of the seventeen inference programs under `pyscripts/inference/`: the reference's command line and config
-surface (`parse_args`), the argument guards, snapshot loading, the seeded synthetic images that stand in for the
-file-list loader (outside this repository, DESIGN 9: `--data_list synthetic`), the self-built memory bank of the kNN
-programs, the timed loop over the images and the JSON line.  A program's `main` holds what is specific to its recipe:
+surface (`parse_args`), the argument guards, snapshot loading, where the images come from and the label maps go
+(`ImageSource`: the seeded synthetic images of `--data_list synthetic`, or the reference's file list with the views made
+and the label images finished on the GPU, DESIGN 8o -- eight programs so far, the other nine still refuse a list), the
+self-built memory bank of the kNN programs, the timed loop over the images and the JSON line.  A program's `main` holds what is specific to its recipe:
 which `spml_amd.inference` function it calls, with which extra inputs, and which fields it adds to the report.  The two
 memory-bank programs (`prototype.py`, `prototype_msc.py`) and the two softmax pseudo-label programs (`pseudo_softmax.py`,
 `pseudo_softmaxrw.py`) differ in constants only; their bodies are `run_prototypes` and `run_pseudo_softmax` below."""
@@ -16,10 +17,37 @@ NUM_SYNTHETIC_IMAGES = 4          # read at call time: the tests shorten the pro
 NUM_LABEL_VALUES = 256            # label maps hold classes and the ignore value 255 (prototype_msc.py:189-192)
 
 
-def parse(description, argv, api_function, what='inference'):
+def reads_file_list(args):
+  return args.data_list not in (None, 'synthetic')
+
+
+def list_dataset(config, args, api_function, need_labels=False):
+  """The reference's evaluation dataset (inference_softmax.py:45-54) over `--data_dir` (or `dataset.data_dir`) and
+  `--data_list`.  A list that does not exist, or one without label columns under a program that needs them, ends the
+  program."""
+  from spml_amd.data.datasets import ListDataset
+  if not os.path.isfile(args.data_list):
+    raise SystemExit("data list '%s' does not exist (ListDataset reads 'image [semantic_label instance_label]' per "
+                     'line); use --data_list synthetic or call spml_amd.inference.%s on your own images'
+                     % (args.data_list, api_function))
+  data_dir = args.data_dir if args.data_dir is not None else (config.dataset.data_dir or '')
+  dataset = ListDataset(data_dir=data_dir, data_list=args.data_list, img_mean=config.network.pixel_means,
+                        img_std=config.network.pixel_stds, size=None, random_crop=False, random_scale=False,
+                        random_mirror=False, training=False)
+  if len(dataset) < 1:
+    raise SystemExit("data list '%s' is empty" % args.data_list)
+  if need_labels and not dataset.semantic_label_paths:
+    raise SystemExit("data list '%s' has no label columns: this program reads the semantic label of every image "
+                     "('image semantic_label instance_label' per line)" % args.data_list)
+  return dataset
+
+
+def parse(description, argv, api_function, what='inference', file_lists=None):
   """`parse_args`, the reference's `--kmeans_num_clusters` / `--label_divisor` overrides (inference_msc.py:40-41; the
   softmax programs read neither), then the guards, in one order for every program: a file list, a missing `--save_dir`,
-  a machine without a GPU.  -> (config, args, device), with `device` made the current one."""
+  a machine without a GPU.  `file_lists`: None for a program that does not read file lists yet (it refuses one),
+  'images' for one that does, 'labels' for one that also needs the list's label columns.
+  -> (config, args, device), with `device` made the current one."""
   from spml_amd.config.default import config
   from spml_amd.config.parse_args import parse_args
   args = parse_args(description, argv)
@@ -27,9 +55,11 @@ def parse(description, argv, api_function, what='inference'):
     config.network.kmeans_num_clusters = [int(i) for i in args.kmeans_num_clusters.split(',')]
   if args.label_divisor:
     config.network.label_divisor = args.label_divisor
-  if args.data_list not in (None, 'synthetic'):
-    raise SystemExit('file-list data loading (ListDataset) is outside the scope of this repository; '
-                     'use --data_list synthetic or call spml_amd.inference.%s on your own images' % api_function)
+  if reads_file_list(args):
+    if file_lists is None:
+      raise SystemExit('file-list data loading (ListDataset) is outside the scope of this repository; '
+                       'use --data_list synthetic or call spml_amd.inference.%s on your own images' % api_function)
+    list_dataset(config, args, api_function, need_labels=file_lists == 'labels')
   if not args.save_dir:
     raise SystemExit('--save_dir is required')
   if not torch.cuda.is_available():
@@ -172,62 +202,292 @@ def report(done, seconds, **fields):
   print(json.dumps({'images': done, 'images_per_s': round(done / seconds, 3), **fields}))
 
 
-def run_prototypes(description, scales, argv=None):
+class SourceImage(object):
+  """One image of an `ImageSource`: `index`, `name` (of its output files, without a directory), `image_hw` (the size the
+  label map is scored and written at), `views` (`(image [1,3,Hp,Wp], (rh, rw), is_flip)`, what the `predict_*` /
+  `pseudo_*` functions take), `label_views` (the label `[rh, rw]` of every view; a source with labels only) and `label`
+  (the semantic label `[h, w]` on the device, or None)."""
+
+  def __init__(self, index, name, image_hw, views, label_views, label):
+    self.index, self.name, self.image_hw = index, name, image_hw
+    self.views, self.label_views, self.label = views, label_views, label
+
+
+class ImageSource(object):
+  """Where a program's images come from and where its label maps go: one interface, two implementations, so that a
+  program's `main` does not branch.  `scales` / `is_flip`: the views of every image; `single_view`: the program resizes
+  to `test.image_size` first (inference_softmax.py:89-94) and its label map goes back to the file's size; `with_labels`:
+  every view comes with its label map (the memory-bank pass).
+
+    for_program(...)        the implementation `--data_list` selects
+    timed(per_image)        `per_image(SourceImage)` for every image, between two synchronisations -> (done, seconds)
+    emit(image, prediction, directory)
+                            scores the label map `[h, w]` against the image's label and writes it
+    bank_name(image)        file name of the image's memory bank
+    scores()                the `mIoU` / `pixel_acc` fields of the report
+    fields()                further fields of the report"""
+
+  def __init__(self, config, args, device, scales, is_flip, single_view=False, with_labels=False):
+    self.config, self.args, self.device = config, args, device
+    self.scales, self.is_flip, self.single_view, self.with_labels = list(scales), bool(is_flip), single_view, with_labels
+    self.num_classes, self.crop_size, self.stride, self.size = geometry(config)
+    self.counts = None
+
+  @staticmethod
+  def for_program(config, args, device, scales, is_flip, api_function, **kind):
+    if reads_file_list(args):
+      return ListImageSource(config, args, device, scales, is_flip, api_function, **kind)
+    return SyntheticImageSource(config, args, device, scales, is_flip, **kind)
+
+  def tags(self, image):
+    """The image tags of the pseudo-label programs (pseudo_softmaxrw_crf.py:102-106)."""
+    from spml_amd import inference
+    return inference.label_tags_from_map(image.label, self.num_classes)
+
+  def score(self, prediction, label):
+    from spml_amd.utils.general import metrics
+    self.counts = metrics.iou_stats(prediction, label, self.num_classes, self.counts)
+
+  def scores(self):
+    return {'mIoU': None, 'pixel_acc': None} if self.counts is None else scores(self.counts)
+
+  def fields(self):
+    return {}
+
+
+class SyntheticImageSource(ImageSource):
+  """`--data_list synthetic` (or none): `synthetic_image` + `flip_scale_views` (+ `label_views` of the densified label),
+  label maps as `.npy` (`save_label_map`)."""
+
+  def image(self, index):
+    from spml_amd import inference
+    image, label, _ = synthetic_image(index, self.size, self.num_classes, self.device)
+    views = inference.flip_scale_views(image, self.scales, self.is_flip, self.crop_size)
+    labels = None
+    if self.with_labels:
+      dense = dense_label(label, self.num_classes, self.config.dataset.semantic_ignore_index)
+      labels = inference.label_views(dense, [hw for _, hw, _ in views])
+    return SourceImage(index, 'synthetic_{:04d}'.format(index), (self.size, self.size), views, labels, label)
+
+  def timed(self, per_image):
+    return timed_images(lambda index: per_image(self.image(index)))
+
+  def emit(self, image, prediction, directory):
+    self.score(prediction, image.label)
+    save_label_map(directory, image.index, prediction)
+
+  def bank_name(self, image):
+    return image.name + '.npy'
+
+
+def output_name(image_path):
+  """inference.py:117: the base name of the image, `.jpg` -> `.png`."""
+  return os.path.basename(image_path).replace('.jpg', '.png')
+
+
+def write_label_pngs(gray_path, color_path, gray, color):
+  """inference.py:243-255."""
+  import PIL.Image as Image
+  for path, array, mode in ((gray_path, gray, 'L'), (color_path, color, 'RGB')):
+    if not os.path.isdir(os.path.dirname(path)):
+      os.makedirs(os.path.dirname(path), exist_ok=True)
+    Image.fromarray(array, mode=mode).save(path)
+
+
+class ListImageSource(ImageSource):
+  """`--data_dir D --data_list L`: the files of `ListDataset(training=False)`, decoded ahead on a thread pool (threads,
+  never processes: a forked child of a process that holds the GPU is not safe); the raw bytes and the view records go
+  up from pinned memory in ONE `non_blocking` copy and `spml_image_views_u8` makes every view from them
+  (`spml_amd.inference.views_from_records`); `spml_label_export_u8` writes the finished gray and colour bytes at the
+  file's own size, one copy brings them into pinned memory and a writer pool saves `semantic_gray/<name>.png` (mode L)
+  and `semantic_color/<name>.png` (mode RGB)."""
+
+  AHEAD = 4         # images decoded ahead of the one on the GPU
+
+  def __init__(self, config, args, device, scales, is_flip, api_function, **kind):
+    from concurrent.futures import ThreadPoolExecutor
+    from spml_amd import inference
+    from spml_amd.utils.general import vis
+    ImageSource.__init__(self, config, args, device, scales, is_flip, **kind)
+    self.dataset = list_dataset(config, args, api_function, need_labels=self.with_labels)
+    self.has_labels = bool(self.dataset.semantic_label_paths)
+    self.image_size = config.test.image_size if self.single_view else 0
+    threads = max(1, min(int(config.num_threads), 4))
+    self.readers, self.writers = ThreadPoolExecutor(max_workers=threads), ThreadPoolExecutor(max_workers=threads)
+    self.pending = []
+    path = config.dataset.color_map_path
+    self.color_map = torch.from_numpy(vis.load_color_map(path) if path else vis.voc_color_map()).to(device)
+    self.mean, self.std = inference._normalisation(device, config.network.pixel_means, config.network.pixel_stds)
+    self.staging = [None, None]         # pinned upload buffers, used in turn: [tensor, event of its last copy]
+    self.turn = 0
+
+  def __len__(self):
+    return len(self.dataset)
+
+  def decode(self, index):
+    """On a reader thread: the decoded files and the view records of image `index`."""
+    from spml_amd import inference
+    from spml_amd.data import transforms
+    rgb, semantic, _ = self.dataset.read(index)
+    plan = transforms.plan_views(rgb.shape[0], rgb.shape[1], self.scales, self.is_flip, self.crop_size, self.image_size,
+                                 name=self.dataset.image_paths[index])
+    return rgb, semantic, inference.view_records(plan)
+
+  def _stage(self, nbytes):
+    slot = self.staging[self.turn]
+    if slot is not None:
+      slot[1].synchronize()             # the copy that last read this buffer has finished
+    if slot is None or slot[0].numel() < nbytes:
+      slot = [torch.empty((nbytes + nbytes // 4,), dtype=torch.uint8, pin_memory=True), torch.cuda.Event()]
+      self.staging[self.turn] = slot
+    self.turn ^= 1
+    return slot
+
+  def image(self, index, decoded):
+    """On the main thread: pack (records, RGB, semantic plane), one copy, one launch."""
+    from spml_amd import inference
+    rgb, semantic, records = decoded
+    h, w = rgb.shape[:2]
+    rec_bytes = (records.nbytes + 15) // 16 * 16
+    sem_at = rec_bytes + (3 * h * w + 15) // 16 * 16
+    total = sem_at + (h * w if semantic is not None else 0)
+    stage, event = self._stage(total)
+    host = stage.numpy()
+    host[:records.nbytes] = records.view(np.uint8).reshape(-1)
+    host[rec_bytes:rec_bytes + 3 * h * w] = rgb.reshape(-1)
+    if semantic is not None:
+      host[sem_at:total] = semantic.reshape(-1)
+    packed = torch.empty((total,), dtype=torch.uint8, device=self.device)
+    packed.copy_(stage[:total], non_blocking=True)
+    event.record()
+    rgb_dev = packed[rec_bytes:rec_bytes + 3 * h * w].view(h, w, 3)
+    sem_dev = packed[sem_at:total].view(h, w) if semantic is not None else None
+    views, labels = inference.views_from_records(rgb_dev, records, packed[:records.nbytes], self.mean, self.std,
+                                                 sem_dev if self.with_labels else None)
+    return SourceImage(index, output_name(self.dataset.image_paths[index]), (h, w), views, labels, sem_dev)
+
+  def timed(self, per_image):
+    n, done = len(self), 0
+    torch.cuda.synchronize()
+    t0 = time.time()
+    ahead = [self.readers.submit(self.decode, i) for i in range(min(self.AHEAD, n))]
+    try:
+      for index in range(n):
+        decoded = ahead.pop(0).result()
+        if index + self.AHEAD < n:
+          ahead.append(self.readers.submit(self.decode, index + self.AHEAD))
+        per_image(self.image(index, decoded))
+        done += 1
+      self.drain()
+    finally:
+      for future in ahead:
+        future.cancel()
+      self.readers.shutdown(wait=True)
+      self.writers.shutdown(wait=True)
+    torch.cuda.synchronize()
+    return done, time.time() - t0
+
+  def emit(self, image, prediction, directory):
+    """`prediction` `[rh, rw]` (the un-padded view of a single-view program, else the file's size) -> the file's size
+    (INTER_NEAREST; the identity where the sizes agree), scored there, written by the writer pool."""
+    from spml_amd import inference
+    h, w = image.image_hw
+    out = torch.empty((4 * h * w,), dtype=torch.uint8, device=self.device)
+    gray, color = out[:h * w].view(h, w), out[h * w:].view(h, w, 3)
+    inference.export_label_map(prediction.contiguous(), tuple(prediction.shape), (h, w), self.color_map, out=(gray, color))
+    if image.label is not None:
+      self.score(gray, image.label)
+    host = torch.empty((4 * h * w,), dtype=torch.uint8, pin_memory=True)
+    host.copy_(out, non_blocking=True)
+    event = torch.cuda.Event()
+    event.record()
+    color_dir = os.path.join(os.path.dirname(os.path.normpath(directory)), 'semantic_color')
+    self.pending.append(self.writers.submit(self._write, host, event, (h, w), os.path.join(directory, image.name),
+                                            os.path.join(color_dir, image.name)))
+
+  @staticmethod
+  def _write(host, event, hw, gray_path, color_path):
+    event.synchronize()
+    h, w = hw
+    array = host.numpy()
+    write_label_pngs(gray_path, color_path, array[:h * w].reshape(h, w), array[h * w:].reshape(h, w, 3))
+
+  def drain(self):
+    """Waits for every file handed to the writer pool (a failed write raises here)."""
+    pending, self.pending = self.pending, []
+    for future in pending:
+      future.result()
+
+  def bank_name(self, image):
+    return image.name.replace('.png', '.npy')                                                    # prototype.py:195-197
+
+  def fields(self):
+    return {'data_list': self.args.data_list, 'has_labels': self.has_labels}
+
+
+def memory_bank_dir(embedding_model, config, args, device):
+  """`--semantic_memory_dir`; without it the synthetic mode builds its own bank, a data list needs one."""
+  if args.semantic_memory_dir is not None:
+    return args.semantic_memory_dir
+  if reads_file_list(args):
+    raise SystemExit('--semantic_memory_dir is required with a data list (prototype.py / prototype_msc.py write one)')
+  return build_synthetic_bank(embedding_model, config, args, device)
+
+
+def run_prototypes(description, scales, argv=None, single_view=False):
   """`prototype.py` and `prototype_msc.py` (`prototype_msc.py:34-207` of twke18/SPML): every image through
-  `spml_amd.inference.multiscale_prototypes`; the programs differ in the scales of the image pyramid only (`[1]` against
-  `[0.5, 1, 1.5]`, no flip in either).  The bank of every image is written to `<save_dir>/semantic_prototype/<name>.npy`
-  in the reference's on-disk format, where `inference.py` / `inference_msc.py --semantic_memory_dir` read it."""
+  `spml_amd.inference.multiscale_prototypes`; the programs differ in the scales of the image pyramid (`[1]` against
+  `[0.5, 1, 1.5]`, no flip in either) and in `single_view`: `prototype.py` resizes image and label to `test.image_size`
+  first (prototype.py:96-105).  The bank of every image is written to `<save_dir>/semantic_prototype/<name>.npy` in the
+  reference's on-disk format, where `inference.py` / `inference_msc.py --semantic_memory_dir` read it.  A data list
+  needs its label columns."""
   from spml_amd import inference
-  config, args, device = parse(description, argv, 'multiscale_prototypes', 'memory-bank generation')
+  config, args, device = parse(description, argv, 'multiscale_prototypes', 'memory-bank generation', file_lists='labels')
   prototype_dir = output_dir(args, 'semantic_prototype')                                          # :43-44
+  source = ImageSource.for_program(config, args, device, scales, False, 'multiscale_prototypes', single_view=single_view,
+                                   with_labels=True)                                              # :92-95
   embedding_model, _, path = load_models(config, args, device, None)                              # :69-79
-  num_classes, crop_size, stride, size = geometry(config)
+  _, crop_size, stride, _ = geometry(config)
   ignore_index = config.dataset.semantic_ignore_index
   per_image, out, views = [], None, []
 
-  def one(index):
+  def one(image):
     nonlocal out, views
-    image, label, _ = synthetic_image(index, size, num_classes, device)
-    views = inference.flip_scale_views(image, scales, False, crop_size)                           # :92-95
-    labels = inference.label_views(dense_label(label, num_classes, ignore_index), [hw for _, hw, _ in views])
-    out = inference.multiscale_prototypes(embedding_model, views, labels, crop_size, stride, ignore_index,
+    views = image.views
+    out = inference.multiscale_prototypes(embedding_model, views, image.label_views, crop_size, stride, ignore_index,
                                           NUM_LABEL_VALUES)
-    inference.save_image_memory(os.path.join(prototype_dir, 'synthetic_{:04d}.npy'.format(index)), out['prototype'],
+    inference.save_image_memory(os.path.join(prototype_dir, source.bank_name(image)), out['prototype'],
                                 out['prototype_label'])                                           # :200-207
     per_image.append(int(out['prototype'].shape[0]))
 
-  done, seconds = timed_images(one)
+  done, seconds = source.timed(one)
   report(done, seconds, prototypes_per_image=per_image, views=len(views), scales=list(scales),
-         majority_path=out['majority_path'], snapshot=path, save_dir=prototype_dir)
+         majority_path=out['majority_path'], snapshot=path, save_dir=prototype_dir, **source.fields())
 
 
 def run_pseudo_softmax(description, scales, combine, walk_steps, argv=None):
   """`pseudo_softmax.py` and `pseudo_softmaxrw.py` (`pseudo_softmaxrw_crf.py:33-204` of twke18/SPML): every image through
   `spml_amd.inference.pseudo_labels_softmax`; the programs differ in three constants only (scales of the image pyramid,
-  how the views' class scores are combined, squarings of the transition matrix).  The label maps of the synthetic images
-  give the image tags (:102-106) and the mIoU of the JSON line; the labels written are those of :176, before the denseCRF
-  refinement (built for other programs; for these two it is the follow-up named there)."""
+  how the views' class scores are combined, squarings of the transition matrix).  The label map of an image (synthetic,
+  or the file's own: a data list needs its label columns) gives the image tags (:102-106) and the mIoU of the JSON line;
+  the labels written are those of :176, before the denseCRF refinement (built for other programs; for these
+  two it is the follow-up named there)."""
   from spml_amd import inference
-  from spml_amd.utils.general import metrics
-  config, args, device = parse(description, argv, 'pseudo_labels_softmax')
+  config, args, device = parse(description, argv, 'pseudo_labels_softmax', file_lists='labels')
   semantic_dir = output_dir(args, 'semantic_gray')
+  source = ImageSource.for_program(config, args, device, scales, True, 'pseudo_labels_softmax')   # :109-125
   embedding_model, prediction_model, path = load_models(config, args, device, 'softmax_classifier')
-  num_classes, crop_size, _, size = geometry(config)
-  counts, out = None, None
+  out = None
 
-  def one(index):
-    nonlocal counts, out
-    image, label, _ = synthetic_image(index, size, num_classes, device)
-    views = inference.flip_scale_views(image, scales, True, crop_size)                            # :109-125
-    out = inference.pseudo_labels_softmax(embedding_model, prediction_model, views, (size, size),
-                                          inference.label_tags_from_map(label, num_classes), combine=combine,
-                                          walk_steps=walk_steps)
-    counts = metrics.iou_stats(out['semantic_prediction'], label, num_classes, counts)
-    save_label_map(semantic_dir, index, out['semantic_prediction'])
+  def one(image):
+    nonlocal out
+    out = inference.pseudo_labels_softmax(embedding_model, prediction_model, image.views, image.image_hw,
+                                          source.tags(image), combine=combine, walk_steps=walk_steps)
+    source.emit(image, out['semantic_prediction'], semantic_dir)
 
-  done, seconds = timed_images(one)
-  report(done, seconds, **scores(counts), scales=list(scales), is_flip=True, combine=combine, walk_steps=walk_steps,
-         head_path=out['head_path'], snapshot=path, save_dir=semantic_dir)
+  done, seconds = source.timed(one)
+  report(done, seconds, **source.scores(), scales=list(scales), is_flip=True, combine=combine, walk_steps=walk_steps,
+         head_path=out['head_path'], snapshot=path, save_dir=semantic_dir, **source.fields())
 
 
 class CrfStage(object):

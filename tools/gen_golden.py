@@ -1062,6 +1062,99 @@ def gen_n13(ref, out):
   assert size < 100 * 1024, 'n13_augment.npz is %d bytes' % size
 
 
+def gen_n14(ref, out):
+  """N14: what the reference's inference programs ask of cv2 and do around it.  `spml/data/transforms.py` and
+  `spml/utils/general/others.py` are imported with a RECORDING stand-in for cv2 in memory: its `resize` notes
+  `(dsize, interpolation)` and returns an array of that size whose every pixel holds its own column index, so that a
+  mirror of the resized array shows.  Recorded: the sizes `resize_with_interpolation` and `resize` request for a table
+  of `(h, w, image_size)` and `(h, w, scale)` cases; the order, sizes, interpolation modes and flip flags of
+  `create_image_pyramid`; `resize_with_pad` with 0; the uint8 table of `load_color_map` on `misc/colormapvoc.mat`
+  (vis.py imports torchvision, which is not installed: an empty module stands in for it, none of it is called).
+  cv2's pixels themselves cannot be run: tests/augment_ref.py restates them."""
+  calls = []
+  cv2 = types.ModuleType('cv2')
+  cv2.INTER_NEAREST, cv2.INTER_LINEAR = 0, 1
+
+  def resize(src, dsize, interpolation=1):
+    calls.append((int(dsize[0]), int(dsize[1]), int(interpolation)))
+    shape = (int(dsize[1]), int(dsize[0])) + tuple(src.shape[2:])
+    ramp = np.arange(shape[1]).reshape((1, shape[1]) + (1,) * (len(shape) - 2))
+    return np.broadcast_to(ramp, shape).astype(src.dtype)
+  cv2.resize = resize
+  stand_ins = {'cv2': cv2, 'torchvision': types.ModuleType('torchvision'), 'torchvision.utils': types.ModuleType('torchvision.utils')}
+  stand_ins['torchvision'].utils = stand_ins['torchvision.utils']
+  had = {name: sys.modules.get(name) for name in stand_ins}
+  for name in ('spml.data.transforms', 'spml.utils.general.others'):      # (n13 may have imported them with its own cv2)
+    sys.modules.pop(name, None)
+  sys.modules.update(stand_ins)
+  try:
+    import spml.data.transforms as transforms
+    import spml.utils.general.others as others
+    import spml.utils.general.vis as vis
+  finally:
+    for name, module in had.items():
+      if module is None:
+        del sys.modules[name]
+      else:
+        sys.modules[name] = module
+  assert transforms.cv2 is cv2
+
+  store = {}
+  interp_cases = [(23, 43, 23), (43, 23, 23), (375, 500, 513), (500, 375, 513), (41, 29, 33), (366, 500, 512),
+                  (333, 500, 320), (17, 17, 40), (1, 9, 4)]
+  sizes = []
+  for h, w, size in interp_cases:
+    del calls[:]
+    got = transforms.resize_with_interpolation(np.zeros((h, w, 3), np.float32), size, method='bilinear')
+    (new_w, new_h, inter), = calls
+    assert inter == cv2.INTER_LINEAR and got.shape == (new_h, new_w, 3)
+    sizes.append((new_h, new_w))
+  store.update({'interp_cases': np.array(interp_cases), 'interp_sizes': np.array(sizes)})
+  assert sizes[0] == (12, 22)
+
+  scale_cases = [(375, 500, s) for s in (0.5, 0.75, 1, 1.25, 1.5)] + \
+                [(23, 37, s) for s in (0.5, 1, 1.75)] + [(41, 29, s) for s in (0.5, 1, 1.75)] + \
+                [(333, 500, 0.75), (281, 500, 1.25), (500, 334, 1.5), (3, 5, 0.5), (97, 113, 0.7)]
+  sizes = []
+  for h, w, scale in scale_cases:
+    del calls[:]
+    transforms.resize(np.zeros((h, w, 3), np.float32), np.zeros((h, w, 2), np.uint8), scale)
+    (iw, ih, ii), (lw, lh, li) = calls
+    assert (ii, li) == (cv2.INTER_LINEAR, cv2.INTER_NEAREST) and (iw, ih) == (lw, lh)
+    sizes.append((ih, iw))
+  store.update({'scale_cases': np.array(scale_cases, dtype=np.float64), 'scale_sizes': np.array(sizes)})
+
+  # create_image_pyramid: order, sizes, flags; the first pixel of a mirrored view holds the last column's index
+  for tag, (h, w), scales, is_flip in [('msc', (375, 500), [0.5, 0.75, 1, 1.25, 1.5], True),
+                                       ('bank', (41, 29), [0.5, 1, 1.5], False),
+                                       ('small', (23, 37), [0.5, 1, 1.75], True)]:
+    del calls[:]
+    batches = others.create_image_pyramid(
+        {'image': np.zeros((3, h, w), np.float32)},
+        {'semantic_label': np.zeros((h, w), np.uint8), 'instance_label': np.zeros((h, w), np.uint8)}, scales, is_flip)
+    assert len(calls) == 2 * len(batches) and all(c[2] == (cv2.INTER_LINEAR, cv2.INTER_NEAREST)[i % 2] for i, c in enumerate(calls))
+    store.update({
+        tag + '_hw': np.array([h, w]), tag + '_scales': np.array(scales, dtype=np.float64), tag + '_is_flip': np.array(is_flip),
+        tag + '_sizes': np.array([b[0]['image'].shape[-2:] for b in batches]),
+        tag + '_label_sizes': np.array([b[1]['semantic_label'].shape for b in batches]),
+        tag + '_flips': np.array([b[2]['is_flip'] for b in batches]),
+        tag + '_first_column': np.array([int(b[0]['image'][0, 0, 0]) for b in batches]),
+        tag + '_first_label_column': np.array([int(b[1]['semantic_label'][0, 0]) for b in batches])})
+
+  rng = np.random.RandomState(914)
+  for ci, (h, w, crop) in enumerate([(5, 7, (9, 11)), (13, 6, (9, 11)), (17, 19, (9, 11)), (9, 11, (9, 11))]):
+    image = rng.standard_normal((h, w, 3)).astype(np.float32)
+    store.update({'pad%d_image' % ci: image, 'pad%d_crop' % ci: np.array(crop),
+                  'pad%d_out' % ci: transforms.resize_with_pad(image, crop, image_pad_value=0)})
+
+  table = vis.load_color_map(os.path.join(ref, 'misc', 'colormapvoc.mat')).numpy()
+  assert table.shape == (256, 3) and table.dtype == np.uint8
+  store['color_map'] = table
+  save(out, 'n14_inference_io', **store)
+  size = os.path.getsize(os.path.join(out, 'n14_inference_io.npz'))
+  assert size < 100 * 1024, 'n14_inference_io.npz is %d bytes' % size
+
+
 class AttrDict(dict):
   __getattr__ = dict.__getitem__
 
@@ -1082,7 +1175,7 @@ def main():
   torch.set_num_threads(1)       # bit-stable fp32 sums
   if ONLY is not None and ONLY <= {'n7_pseudo_labels', 'n8_softmax_msc', 'n9_knn_msc', 'n10_prototype_msc',
                                    'n11_pseudo_knn_msc', 'n11_instance_iou', 'n12_densepose_pseudo',
-                                   'n13_augment'}:      # (need none of the imports and shims below)
+                                   'n13_augment', 'n14_inference_io'}:      # (need none of the imports and shims below)
     if 'n7_pseudo_labels' in ONLY:
       gen_n7(args.ref, out)
     if 'n8_softmax_msc' in ONLY:
@@ -1099,6 +1192,8 @@ def main():
       gen_n12(args.ref, out)
     if 'n13_augment' in ONLY:
       gen_n13(args.ref, out)
+    if 'n14_inference_io' in ONLY:
+      gen_n14(args.ref, out)
     return
 
   import spml.utils.general.common as g_common
@@ -1916,6 +2011,10 @@ def main():
   # ======================= N13: the numpy-only stages of the training augmentation ===========
   if ONLY is None or 'n13_augment' in ONLY:
     gen_n13(args.ref, out)
+
+  # ======================= N14: sizes, order and flags of the inference programs' image chain ====
+  if ONLY is None or 'n14_inference_io' in ONLY:
+    gen_n14(args.ref, out)
 
   # ======================= H2: two steps of the stage-2 classifier training ===============
   # pyscripts/train/train_classifier.py:139-169, the loop body exec'd as it stands on ONE device:
