@@ -50,7 +50,7 @@ const char* spml_status_string(int status);
  * 8: spml_upsample_ce_bwd_path_name (entry points added since leave every earlier signature and flag as it was and
  *    keep the version: spml_view_votes_*, spml_segsort_nll_batched_*, spml_segment_majority_*, spml_tag_normalize_*,
  *    spml_dense_crf_*, spml_segment_tag_cam_*, spml_conv_hl8_path_name, spml_conv_wgrad_path_name / _splits,
- *    spml_augment_*, spml_image_views_*, spml_label_export_*). */
+ *    spml_augment_*, spml_image_views_*, spml_label_export_*, spml_score_*). */
 #define SPML_ABI_VERSION 8
 int spml_abi_version(void);
 
@@ -1271,6 +1271,53 @@ int spml_image_views_u8(const unsigned char* rgb, const unsigned char* semantic,
 const char* spml_label_export_path_name(int pred_h, int pred_w, int valid_h, int valid_w, int out_h, int out_w);
 int spml_label_export_u8(const int64_t* prediction, int pred_h, int pred_w, int valid_h, int valid_w, int out_h, int out_w,
                          const unsigned char* color_map, unsigned char* gray, unsigned char* rgb, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Scoring label files against ground truth, a batch of decoded files per call (csrc/score_batch.hip)
+ * replaces: pyscripts/benchmark/benchmark_by_mIoU.py:25-53 (iou_stats, three np.histogram per file on the host) and
+ *           pyscripts/benchmark/benchmark_by_instance.py:97-108 (np.unique, one mask and one np.histogram per instance).
+ *
+ * packed: uint8, device, 16-byte aligned: for every file its prediction and ground-truth planes and, optionally, its
+ * instance plane, n = h * w bytes each, anywhere in the buffer.  One spml_score_params record per file says where.
+ * Every plane offset is a multiple of 16 and every plane is padded inside `packed` to a multiple of 16 bytes (the kernel
+ * loads 16-byte vectors); the padding bytes are never counted and their content does not matter.
+ * stats: int64 [B][4][ncls], rows TP+FN, TP+FP, TP and the number of instances per class.  Every element is written: the
+ * output needs no memset.  For file b and pixel i, with g = gt[i], p = pred[i], s = inst[i]:
+ *   the pixel counts only if g < ncls; then TP+FN[g] += 1; TP+FP[p] += 1 if p < ncls, TP+FP[ncls-1] += 1 if p == ncls
+ *     (np.histogram closes its last bin on the right; spml_iou_counts_i64 leaves this out because an arg-max never
+ *     yields that value, a PNG of unknown origin can hold it), nothing for a larger p; TP[g] += 1 if p == g (a
+ *     prediction of ncls over g = ncls - 1 is no true positive);
+ *   instances (inst_off >= 0): an id occurs if any pixel carries it, pixels with g >= ncls included; its class is the
+ *     lowest class with the largest count among its pixels with g < ncls, class 0 for an id with no such pixel; row 3
+ *     counts the occurring ids per class; when all 256 ids occur, id 255 is dropped (`if i < 255` over the sorted unique
+ *     ids); row 3 is all zero when inst_off = -1.
+ * params_host and params_dev hold the same B records: the host copy is checked before anything is launched, the device
+ * copy is what the kernels read (and check again: a record that fails counts nothing and forms no address).
+ * ws: 4-byte aligned, at least spml_score_batch_workspace_bytes(B, ncls) bytes (the per-file tables; that call returns 0
+ * outside the limits), else SPML_ERR_WORKSPACE; the call zeroes it on `stream` itself, its previous content does not
+ * matter.  A memset and two launches on `stream`: the count (each workgroup owns one run of 8192 contiguous pixels of
+ * one file; the grid is the SUM of the files' runs, found per workgroup by a prefix over the records) and the pass that
+ * turns the tables into stats.  Only integer atomics on 32-bit counters: bit-identical from call to call, in either
+ * deterministic mode.  No host read of device memory, no allocation.
+ * SPML_ERR_UNSUPPORTED, with nothing launched and stats untouched: B outside [1, 256], ncls outside [1, 64], n outside
+ * [1, 2^31), an offset that is negative (other than inst_off = -1), not a multiple of 16 or whose padded plane leaves
+ * packed_bytes, two planes that overlap.  SPML_ERR_INVALID_ARG: a null or misaligned pointer, stats or ws overlapping an
+ * input or each other.
+ * spml_score_batch_path_name (host only; the expression the entry itself evaluates): "lds_table" (the tables of a file,
+ * ncls * (ncls + 2) + 256 * (ncls + 1) counters, fit the 8192 entries a workgroup keeps in LDS: ncls <= 27),
+ * "global_table" or
+ * "unsupported".  spml_score_params_bytes: sizeof(spml_score_params), for bindings. */
+typedef struct spml_score_params {
+  int64_t pred_off, gt_off, inst_off;       /* byte offsets of the uint8 planes in `packed`; inst_off = -1: no instance plane */
+  int64_t n;                                /* pixels of this file (h * w) */
+} spml_score_params;
+
+size_t spml_score_params_bytes(void);
+size_t spml_score_batch_workspace_bytes(int B, int ncls);
+const char* spml_score_batch_path_name(const spml_score_params* records, int B, int64_t packed_bytes, int ncls);
+int spml_score_batch_u8(const unsigned char* packed, int64_t packed_bytes, const spml_score_params* params_host,
+                        const spml_score_params* params_dev, int B, int ncls, int64_t* stats, void* ws, size_t ws_bytes,
+                        void* stream);
 
 #ifdef __cplusplus
 }

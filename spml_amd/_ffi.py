@@ -185,6 +185,10 @@ _SIGNATURES = {
     'spml_image_views_u8': (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P, c_int, _P, c_int64, _P, c_int64, _P]),
     'spml_label_export_path_name': (c_char_p, [c_int, c_int, c_int, c_int, c_int, c_int]),
     'spml_label_export_u8': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
+    'spml_score_params_bytes': (c_size_t, []),
+    'spml_score_batch_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'spml_score_batch_path_name': (c_char_p, [_P, c_int, c_int64, c_int]),
+    'spml_score_batch_u8': (c_int, [_P, c_int64, _P, _P, c_int, c_int, _P, _P, c_size_t, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -1865,3 +1869,59 @@ def label_export(prediction, valid_hw, out_hw, color_map, out=None):
                                    int(valid_hw[0]), int(valid_hw[1]), oh, ow, ptr(color_map, torch.uint8),
                                    ptr(gray, torch.uint8), ptr(rgb, torch.uint8), stream_ptr()), 'spml_label_export_u8')
   return gray, rgb
+
+
+# ---------------------------------------------------------------------------
+# Scoring label files against ground truth, a batch of decoded files per call (csrc/score_batch.hip)
+MAX_SCORE_FILES = 256                  # the limits of spml_score_batch_u8 (include/spml_hip.h)
+MAX_SCORE_CLASSES = 64
+SCORE_PLANE_ALIGN = 16                 # plane offsets and padded plane sizes are multiples of this
+
+
+def _score_params_dtype():
+  import numpy as np
+  return np.dtype([('pred_off', '<i8'), ('gt_off', '<i8'), ('inst_off', '<i8'), ('n', '<i8')])
+
+
+SCORE_PARAMS = _score_params_dtype()          # spml_score_params of include/spml_hip.h, field for field (32 bytes)
+
+
+def _score_records(records):
+  """(host pointer, count) of a C-contiguous array of SCORE_PARAMS records whose size the library agrees with."""
+  import numpy as np
+  if not isinstance(records, np.ndarray) or records.dtype != SCORE_PARAMS or not records.flags['C_CONTIGUOUS']:
+    raise SpmlHipError('score_batch: the records must be a contiguous numpy array of _ffi.SCORE_PARAMS')
+  if lib().spml_score_params_bytes() != SCORE_PARAMS.itemsize:
+    raise SpmlHipError('score_batch: spml_score_params is %d bytes in the library, %d here'
+                       % (lib().spml_score_params_bytes(), SCORE_PARAMS.itemsize))
+  return c_void_p(records.ctypes.data), int(records.size)
+
+
+def score_batch_path_name(records, packed_bytes, ncls):
+  """'lds_table', 'global_table' or 'unsupported' for the records of one batch (a host function of the library: the
+  expression its entry evaluates before the launch)."""
+  host, n = _score_records(records)
+  return lib().spml_score_batch_path_name(host, n, int(packed_bytes), int(ncls)).decode()
+
+
+def score_batch(packed, records, ncls, params_dev=None, out=None):
+  """stats int64 `[B, 4, ncls]` (TP+FN, TP+FP, TP, instances per class) of the B files whose uint8 planes lie in
+  `packed` (uint8, on the device) where `records` (host, SCORE_PARAMS) say.  `params_dev`: the same records as bytes of
+  uint8 on the device, for a caller that uploaded them with the planes; copied up here otherwise.  No host read."""
+  host, n = _score_records(records)
+  ncls = int(ncls)
+  ptr(packed, torch.uint8)                                   # (CPU tensors are refused before anything is allocated)
+  if params_dev is None:
+    params_dev = torch.from_numpy(records.view('u1').reshape(-1).copy()).to(packed.device)
+  if params_dev.dtype != torch.uint8 or params_dev.numel() != n * SCORE_PARAMS.itemsize:
+    raise SpmlHipError('score_batch: params_dev must hold the %d records as %d bytes of uint8' % (n, n * SCORE_PARAMS.itemsize))
+  if out is None:
+    if n < 1 or ncls < 1:
+      raise SpmlHipError('score_batch: needs at least one file and one class (got %d, %d)' % (n, ncls))
+    out = torch.empty((n, 4, ncls), dtype=torch.int64, device=packed.device)
+  if tuple(out.shape) != (n, 4, ncls):
+    raise SpmlHipError('score_batch: the output must be [%d, 4, %d]' % (n, ncls))
+  ws = workspace(lib().spml_score_batch_workspace_bytes(n, ncls), packed.device)
+  check(lib().spml_score_batch_u8(ptr(packed, torch.uint8), packed.numel(), host, ptr(params_dev, torch.uint8), n, ncls,
+                                  ptr(out, torch.int64), ptr(ws), ws.numel(), stream_ptr()), 'spml_score_batch_u8')
+  return out

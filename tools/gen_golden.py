@@ -1155,6 +1155,128 @@ def gen_n14(ref, out):
   assert size < 100 * 1024, 'n14_inference_io.npz is %d bytes' % size
 
 
+def gen_n15(ref, out):
+  """N15: scoring directories.  pyscripts/benchmark/benchmark_by_mIoU.py: its own `iou_stats` (:25-53), the per-file lines
+  :80-88 and the final lines :90, :113, :116; pyscripts/benchmark/benchmark_by_instance.py: `iou_stats` (:27-55), the
+  per-file lines :88-113 and the final lines :115-116, :139 -- exec'd as they stand on seeded uint8 triples, five files
+  of different sizes for 21 classes and four for 15.  Between them: predictions equal to the class count (the
+  histogram's last bin is closed on the right; over the last class they are still no true positive), above it and 255,
+  all at counted pixels; ground truth between the class
+  count and 254 and at 255; a file without a counted pixel; an instance all of whose pixels are uncounted (class 0); an
+  instance tied between two classes (the lower one); a file with all 256 ids (`if i < 255` drops the largest); a file
+  with one id; a 1 x 1 file.  Stored per file: `pred`, `gt`, `inst` (uint8) and `rows` int64 [4, ncls] (TP+FN, TP+FP,
+  TP, instances per class); per class count the final `iou`, `mean_iou`, `pixel_acc` of the first program and
+  `inst_iou`, `inst_mean_iou` of the second."""
+  import linecache
+  import textwrap
+  py_m = os.path.join(ref, 'pyscripts', 'benchmark', 'benchmark_by_mIoU.py')
+  py_i = os.path.join(ref, 'pyscripts', 'benchmark', 'benchmark_by_instance.py')
+
+  def ref_lines(py, first, last):
+    txt = ''.join(linecache.getline(py, i) for i in range(first, last + 1))
+    assert txt.strip(), py
+    return textwrap.dedent(txt)
+
+  m_stats, m_file = ref_lines(py_m, 25, 53), ref_lines(py_m, 80, 88)
+  m_final = ref_lines(py_m, 90, 90) + ref_lines(py_m, 113, 113) + ref_lines(py_m, 116, 116)
+  i_stats, i_file = ref_lines(py_i, 27, 55), ref_lines(py_i, 88, 113)
+  i_final = ref_lines(py_i, 115, 116) + ref_lines(py_i, 139, 139)
+  assert m_stats.startswith('def iou_stats(') and i_stats.startswith('def iou_stats(')
+  assert m_file.startswith('_tp_fn, _tp_fp, _tp = iou_stats(') and m_file.rstrip().endswith('tp += _tp')
+  assert 'iou = tp / (tp_fn + tp_fp - tp + 1e-12) * 100.0' in m_final and 'mean_pixel_acc = ' in m_final
+  assert 'if i < 255:' in i_file and 'ninst += ninst_' in i_file and 'iou /= ninst+1e-12' in i_final
+
+  def blocky(rng, h, w, cells_y, cells_x, values):
+    grid = rng.choice(values, size=(cells_y, cells_x))
+    return np.ascontiguousarray(grid[np.arange(h) * cells_y // h][:, np.arange(w) * cells_x // w].astype(np.uint8))
+
+  def triple(rng, nc, kind):
+    if kind == 'blocky':
+      h, w = 40, 52
+      inst = blocky(rng, h, w, 4, 4, np.array([0, 3, 5, 9, 200, 255]))
+      inst[:10, :13], inst[10:20, :13], inst[:10, 13:26] = 3, 5, 0
+      gt = blocky(rng, h, w, 5, 6, np.arange(nc))
+      gt[30:34, 40:46] = nc - 1
+      gt[rng.random((h, w)) < 0.1] = 255
+      gt[rng.random((h, w)) < 0.03] = nc + 2
+      gt[rng.random((h, w)) < 0.02] = nc
+      gt[inst == 3] = 255
+      five = np.flatnonzero(inst.reshape(-1) == 5)
+      a, b = sorted(rng.choice(np.arange(1, nc), size=2, replace=False).tolist())
+      flat = gt.reshape(-1)
+      flat[five[:five.size // 2]], flat[five[five.size // 2:]] = b, a
+      pred = np.where(rng.random((h, w)) < 0.7, np.minimum(gt, nc - 1), rng.integers(0, nc, size=(h, w))).astype(np.uint8)
+      for value, share in ((nc, 0.04), (nc + 3, 0.03), (255, 0.03)):
+        pred[rng.random((h, w)) < share] = value
+      last = np.flatnonzero(gt.reshape(-1) == nc - 1)
+      pred.reshape(-1)[last[:3]], pred.reshape(-1)[last[3:6]] = nc, nc - 1     # the class count over the last class: no TP
+      counted = gt < nc
+      assert last.size >= 6 and five.size % 2 == 0 and (gt[inst == 3] >= nc).all()
+      counts5 = np.bincount(gt[inst == 5], minlength=256)
+      assert counts5[a] == counts5[b] == counts5[:nc].max() and a < b
+      for value in (nc, nc + 3, 255):
+        assert (pred[counted] == value).any(), value
+      assert ((gt >= nc) & (gt < 255)).any() and (gt == 255).any()
+    elif kind == 'all_ids':
+      h, w = 24, 32
+      inst = rng.permutation(np.arange(h * w) % 256).reshape(h, w).astype(np.uint8)
+      gt = rng.integers(0, nc, size=(h, w)).astype(np.uint8)
+      gt[rng.random((h, w)) < 0.2] = 255
+      pred = rng.integers(0, nc + 2, size=(h, w)).astype(np.uint8)
+    elif kind == 'one_id':
+      h, w = 17, 23
+      inst = np.full((h, w), 7, dtype=np.uint8)
+      gt = blocky(rng, h, w, 3, 3, np.arange(nc))
+      pred = np.where(rng.random((h, w)) < 0.6, gt, rng.integers(0, 256, size=(h, w))).astype(np.uint8)
+    elif kind == 'no_counted':
+      h, w = 9, 11
+      inst = blocky(rng, h, w, 2, 2, np.array([1, 2, 254]))
+      gt = rng.choice(np.array([nc, 254, 255]), size=(h, w)).astype(np.uint8)
+      pred = rng.integers(0, 256, size=(h, w)).astype(np.uint8)
+    else:
+      inst, gt, pred = (np.array([[v]], dtype=np.uint8) for v in (255, 3, 3))
+    return pred, gt, inst
+
+  store = {}
+  for nc, kinds in ((21, ('blocky', 'all_ids', 'one_id', 'one_pixel', 'no_counted')),
+                    (15, ('blocky', 'all_ids', 'no_counted', 'one_pixel'))):
+    rng = np.random.default_rng(1500 + nc)
+    env_m, env_i = {'np': np}, {'np': np}
+    exec(compile(m_stats, py_m + ':25-53', 'exec'), env_m)
+    exec(compile(i_stats, py_i + ':27-55', 'exec'), env_i)
+    env_m.update(args=AttrDict(num_classes=nc), **{k: np.zeros(nc, dtype=np.float64) for k in ('tp_fn', 'tp_fp', 'tp')})
+    env_i.update(args=AttrDict(num_classes=nc), iou=np.zeros(nc, dtype=np.float64), ninst=np.zeros(nc, dtype=np.float64))
+    for fi, kind in enumerate(kinds):
+      pred, gt, inst = triple(rng, nc, kind)
+      env_m.update(pred=pred, gt=gt)
+      env_i.update(pred=pred, gt=gt, inst=inst)
+      exec(compile(m_file, py_m + ':80-88', 'exec'), env_m)
+      exec(compile(i_file, py_i + ':88-113', 'exec'), env_i)
+      for name in ('_tp_fn', '_tp_fp', '_tp'):
+        assert (env_m[name] == env_i[name]).all()
+      ninst_ = env_i['ninst_']
+      ids = np.unique(inst)
+      assert ninst_.sum() == min(ids.size, 255) and (ninst_ == np.round(ninst_)).all()
+      if kind == 'all_ids':
+        assert ids.size == 256
+      if kind == 'no_counted':
+        assert env_m['_tp_fn'].sum() == 0 and ninst_[0] == ids.size
+      rows = np.stack([env_m['_tp_fn'], env_m['_tp_fp'], env_m['_tp'], ninst_.astype(np.int64)]).astype(np.int64)
+      t = 'n%d_f%d_' % (nc, fi)
+      store.update({t + 'pred': pred, t + 'gt': gt, t + 'inst': inst, t + 'rows': rows})
+    exec(compile(m_final, py_m + ':90,113,116', 'exec'), env_m)
+    exec(compile(i_final, py_i + ':115-116,139', 'exec'), env_i)
+    assert np.isfinite(env_m['iou']).all() and 0.0 < env_m['mean_iou'] < 100.0 and 0.0 < env_i['mean_iou'] < 100.0
+    store.update({'n%d_files' % nc: np.array(len(kinds)), 'n%d_iou' % nc: env_m['iou'],
+                  'n%d_mean_iou' % nc: np.array(env_m['mean_iou']), 'n%d_pixel_acc' % nc: np.array(env_m['mean_pixel_acc']),
+                  'n%d_inst_iou' % nc: env_i['iou'], 'n%d_inst_mean_iou' % nc: np.array(env_i['mean_iou'])})
+    print('n15 score dirs, %d classes: %d files, mIoU %.4f, instance mIoU %.4f'
+          % (nc, len(kinds), env_m['mean_iou'], env_i['mean_iou']))
+  save(out, 'n15_score_dirs', **store)
+  size = os.path.getsize(os.path.join(out, 'n15_score_dirs.npz'))
+  assert size <= 100 * 1024, 'n15_score_dirs.npz is %d bytes' % size
+
+
 class AttrDict(dict):
   __getattr__ = dict.__getitem__
 
@@ -1175,7 +1297,7 @@ def main():
   torch.set_num_threads(1)       # bit-stable fp32 sums
   if ONLY is not None and ONLY <= {'n7_pseudo_labels', 'n8_softmax_msc', 'n9_knn_msc', 'n10_prototype_msc',
                                    'n11_pseudo_knn_msc', 'n11_instance_iou', 'n12_densepose_pseudo',
-                                   'n13_augment', 'n14_inference_io'}:      # (need none of the imports and shims below)
+                                   'n13_augment', 'n14_inference_io', 'n15_score_dirs'}:      # (need none of the imports and shims below)
     if 'n7_pseudo_labels' in ONLY:
       gen_n7(args.ref, out)
     if 'n8_softmax_msc' in ONLY:
@@ -1194,6 +1316,8 @@ def main():
       gen_n13(args.ref, out)
     if 'n14_inference_io' in ONLY:
       gen_n14(args.ref, out)
+    if 'n15_score_dirs' in ONLY:
+      gen_n15(args.ref, out)
     return
 
   import spml.utils.general.common as g_common
@@ -2015,6 +2139,10 @@ def main():
   # ======================= N14: sizes, order and flags of the inference programs' image chain ====
   if ONLY is None or 'n14_inference_io' in ONLY:
     gen_n14(args.ref, out)
+
+  # ======================= N15: scoring directories (mIoU and instance-weighted IoU per file) ====
+  if ONLY is None or 'n15_score_dirs' in ONLY:
+    gen_n15(args.ref, out)
 
   # ======================= H2: two steps of the stage-2 classifier training ===============
   # pyscripts/train/train_classifier.py:139-169, the loop body exec'd as it stands on ONE device:
