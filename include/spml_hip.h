@@ -50,7 +50,8 @@ const char* spml_status_string(int status);
  * 8: spml_upsample_ce_bwd_path_name (entry points added since leave every earlier signature and flag as it was and
  *    keep the version: spml_view_votes_*, spml_segsort_nll_batched_*, spml_segment_majority_*, spml_tag_normalize_*,
  *    spml_dense_crf_*, spml_segment_tag_cam_*, spml_conv_hl8_path_name, spml_conv_wgrad_path_name / _splits,
- *    spml_augment_*, spml_image_views_*, spml_label_export_*, spml_score_*). */
+ *    spml_augment_*, spml_image_views_*, spml_label_export_*, spml_score_*, spml_pca_*, spml_summary_panels_u8,
+ *    spml_train_summary_workspace_bytes). */
 #define SPML_ABI_VERSION 8
 int spml_abi_version(void);
 
@@ -1318,6 +1319,56 @@ const char* spml_score_batch_path_name(const spml_score_params* records, int B, 
 int spml_score_batch_u8(const unsigned char* packed, int64_t packed_bytes, const spml_score_params* params_host,
                         const spml_score_params* params_dev, int B, int ncls, int64_t* stats, void* ws, size_t ws_bytes,
                         void* stream);
+
+/* ------------------------------------------------------------------------
+ * The picture of a training summary (csrc/train_summary.hip)
+ * replaces: pyscripts/train/train.py:222-258 with spml/utils/general/vis.py:23-31 (write_image_to_tensorboard), :41-48
+ *           (convert_label_to_color), :62-101 (embedding_to_rgb) and spml/utils/general/common.py:29-73 (pca through
+ *           torch.svd of the gathered P x C matrix on the host), :101-120 (normalize_embedding).
+ *
+ * emb: fp32 [N, C, H, W], device, 16-byte aligned, in one of two storages named by its element strides: channels-last
+ * (pixel_stride == C, channel_stride == 1) or NCHW-contiguous (pixel_stride == 1, channel_stride == H * W).  C is 32 or
+ * 64 and P = N * H * W < 2^31, else SPML_ERR_UNSUPPORTED (as for any other pair of strides).  Every pixel is
+ * L2-normalised first, x / max(||x||, 1e-12) in fp32; an all-zero pixel stays zero.
+ *
+ * spml_pca_moments_f32: mean fp64 [C] and cov fp64 [C][C] of the normalised pixels, cov = sum (x - mean)(x - mean)^T /
+ * max(P - 1, 1): DIVIDED by P - 1.  Pass 1 takes the column sums, pass 2 the Gram matrix of the rows centred with the
+ * mean rounded to fp32, on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulation per workgroup); each pass
+ * leaves one partial per workgroup in ws and a finishing kernel adds them in index order in fp64.  Four launches.  cov is
+ * exactly symmetric.
+ * spml_pca_project_minmax_f32: V fp32 [C][3] -> proj fp32 [N, H, W, 3] = normalised row . V (NOT centred, as
+ * common.py:68) and minmax fp32 [N][3][2] = (minimum, maximum) of proj per image and channel, exactly the extrema of
+ * the values written.  Two launches (per-workgroup partial extrema in ws, a finishing kernel).  N <= 65535.
+ * ws: 16-byte aligned (else SPML_ERR_INVALID_ARG), at least spml_train_summary_workspace_bytes(N, C, H, W) bytes (0
+ * outside the limits), else SPML_ERR_WORKSPACE; its previous content does not matter and nothing is kept in it between
+ * the calls.  No float atomics, no ticket: bit-identical from call to call, in either deterministic mode.
+ * spml_pca_path_name (host only; the expression the entries evaluate): "gram_mfma_f32_c32", "gram_mfma_f32_c64", the
+ * same with "_nchw" where the transposing LDS tile is taken ("gram_mfma_f32_c32_nchw", "gram_mfma_f32_c64_nchw"), or
+ * "unsupported".
+ *
+ * spml_summary_panels_u8: one launch writes the finished picture.  With the label maps semantic and instance, int64
+ * [N, Hl, Wl] (both or neither), out is uint8 [3][out_h][out_w], the reference's rows stacked as
+ * torchvision.utils.make_grid(nrow=1, padding=2, pad_value=0) stacks them: per image, side by side, semantic colour,
+ * instance colour and embedding RGB, each h x w (the embedding's size), image i at row pad + i * (h + pad), column pad,
+ * out_h = N * (h + pad) + pad, out_w = 3 * w + 2 * pad with pad = 2 (pad = 0 is allowed for N = 1: make_grid returns
+ * a single image as it is); anything else is SPML_ERR_UNSUPPORTED.  Labels are resized as F.interpolate(mode='nearest'):
+ * source = min((int)floorf(dst * ((float)in / out)), in - 1), and coloured with color_map uint8 [256][3] at label & 255
+ * (the reference's index_select raises outside 0..255).  Embedding bytes: (uint8)(((v - min) / (max - min)) * 255) in
+ * fp32, in that order, truncated (vis.py:92-95), from proj and minmax as the projection writes them; a channel with
+ * max == min gives 0 where the reference divides 0 by 0.  Every byte of out is written.  Without label maps (both
+ * NULL; Hl, Wl, pad, out_h, out_w and color_map are ignored) out is uint8 [N][3][h][w], the embedding panel alone.
+ * Sides in [1, 16384], N * h * w < 2^31, 3 * out_h * out_w < 2^31, else SPML_ERR_UNSUPPORTED; a null or misaligned
+ * pointer (proj 16 bytes, labels 8) is SPML_ERR_INVALID_ARG. */
+size_t spml_train_summary_workspace_bytes(int N, int C, int H, int W);
+const char* spml_pca_path_name(int C, int64_t pixel_stride, int64_t channel_stride);
+int spml_pca_moments_f32(const float* emb, int N, int C, int H, int W, int64_t pixel_stride, int64_t channel_stride,
+                         double* mean, double* cov, void* ws, size_t ws_bytes, void* stream);
+int spml_pca_project_minmax_f32(const float* emb, int N, int C, int H, int W, int64_t pixel_stride,
+                                int64_t channel_stride, const float* V, float* proj, float* minmax, void* ws,
+                                size_t ws_bytes, void* stream);
+int spml_summary_panels_u8(const int64_t* semantic, const int64_t* instance, int N, int Hl, int Wl, const float* proj,
+                           const float* minmax, int h, int w, const unsigned char* color_map, int pad, int out_h,
+                           int out_w, unsigned char* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,9 @@ memory bank and step order (spml_amd/train.py::Trainer.step), same snapshot file
 (`model-{iter}.pth` with `embedding_model` / `prediction_model`, `model-{iter}.state.pth`).
 Differences: one process per GPU under torch.distributed instead of nn.DataParallel over
 `config.gpus` (the global batch is `train.batch_size` per process x world size, as the
-reference's per-GPU batch), no tensorboard, and where the augmentation runs: `--data_dir` /
+reference's per-GPU batch), summaries as files instead of tensorboard events (`train.tensorboard_step: K` writes
+`<snapshot_dir>/summary/image-{iter}.png` and a line of `scalars.jsonl` every K iterations on rank 0, from
+rank 0's batch: spml_amd/summary.py), and where the augmentation runs: `--data_dir` /
 `--data_list` (or `dataset.data_dir` / `dataset.train_data_list` of the config) name a file list
 as the reference's ListTagDataset reads it (DenseposeDataset under the DensePose recipe); the host
 decodes the files and draws the augmentation, one launch per batch makes the pixels on the GPU
@@ -103,10 +105,22 @@ def main(argv=None, default_recipe='voc', description='Training for pixel-wise e
   if batches is None:
     batches = synthetic_batches(config, device, rank, args.supervision, first=trainer.curr_iter)
 
+  summary = None
+  if rank == 0 and config.train.tensorboard_step > 0:      # train.py:54-55 (the reference's SummaryWriter and colour map)
+    from spml_amd.summary import TrainingSummary
+    from spml_amd.utils.general import vis
+    path = config.dataset.color_map_path
+    if path and not os.path.exists(path):      # (the recipes name misc/colormapvoc.mat of the reference's tree)
+      print('Colour map {:s} not found: the summaries use the PASCAL VOC table'.format(path))
+      path = ''
+    summary = TrainingSummary(os.path.join(args.snapshot_dir, 'summary'),
+                              vis.load_color_map(path) if path else vis.voc_color_map(),
+                              config.train.batch_size * world)
+
   t0 = time.time()
   for curr_iter in range(trainer.curr_iter, config.train.max_iteration):
     datas, targets = next(batches)
-    out = trainer.step(datas, targets)
+    out = trainer.step(datas, targets, summary) if summary is not None else trainer.step(datas, targets)
     if rank == 0 and (curr_iter % 10 == 0 or curr_iter == config.train.max_iteration - 1):
       print('iter {:d}: loss = {:.3f}, acc = {:.3f}, lr = {:.6f}  ({:.2f} s)'.format(
           curr_iter, float(out['loss']), float(out.get('accuracy', 0.0)), out['lr'], time.time() - t0),
@@ -121,6 +135,8 @@ def main(argv=None, default_recipe='voc', description='Training for pixel-wise e
       extra['spml_iteration'] = state['iteration']
       extra['spml_rng'] = {'cpu': torch.get_rng_state(), 'cuda': torch.cuda.get_rng_state(device)}
       torch.save(extra, state_path.format(curr_iter))
+  if summary is not None:
+    summary.close()
   if hasattr(batches, 'close'):
     batches.close()
   if world > 1:

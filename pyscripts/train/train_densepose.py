@@ -4,6 +4,7 @@ loop as train.py with the DensePose embedding network (colour + location local f
 predictor (tags propagated from the nearest labelled segment) bound -- the reference's script
 differs from train.py only in those imports (train_densepose.py:27-29) and in its dataset class,
 DenseposeDataset (mirrored part labels swap left and right; spml_amd/data), which a file list is read with.
+`train.tensorboard_step` writes the same summaries as train.py does (spml_amd/summary.py), as :215-251 there.
 
   python3 pyscripts/train/train_densepose.py --data_dir D --data_list L --snapshot_dir S --cfg_path C.yaml
   python3 pyscripts/train/train_densepose.py --snapshot_dir S --cfg_path C.yaml [--data_list synthetic]"""

@@ -189,6 +189,13 @@ _SIGNATURES = {
     'spml_score_batch_workspace_bytes': (c_size_t, [c_int, c_int]),
     'spml_score_batch_path_name': (c_char_p, [_P, c_int, c_int64, c_int]),
     'spml_score_batch_u8': (c_int, [_P, c_int64, _P, _P, c_int, c_int, _P, _P, c_size_t, _P]),
+    'spml_train_summary_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'spml_pca_path_name': (c_char_p, [c_int, c_int64, c_int64]),
+    'spml_pca_moments_f32': (c_int, [_P, c_int, c_int, c_int, c_int, c_int64, c_int64, _P, _P, _P, c_size_t, _P]),
+    'spml_pca_project_minmax_f32': (c_int, [_P, c_int, c_int, c_int, c_int, c_int64, c_int64, _P, _P, _P, _P, c_size_t,
+                                            _P]),
+    'spml_summary_panels_u8': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_int, c_int, _P, c_int, c_int, c_int, _P,
+                                       _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -1924,4 +1931,92 @@ def score_batch(packed, records, ncls, params_dev=None, out=None):
   ws = workspace(lib().spml_score_batch_workspace_bytes(n, ncls), packed.device)
   check(lib().spml_score_batch_u8(ptr(packed, torch.uint8), packed.numel(), host, ptr(params_dev, torch.uint8), n, ncls,
                                   ptr(out, torch.int64), ptr(ws), ws.numel(), stream_ptr()), 'spml_score_batch_u8')
+  return out
+
+
+# ---------------------------------------------------------------------------
+# The picture of a training summary (csrc/train_summary.hip)
+def pca_path_name(c, pixel_stride, channel_stride):
+  """'gram_mfma_f32_c32', 'gram_mfma_f32_c64', the same with '_nchw', or 'unsupported' (a host function of the library:
+  the expression its entries evaluate before the launch)."""
+  return lib().spml_pca_path_name(int(c), int(pixel_stride), int(channel_stride)).decode()
+
+
+def embedding_strides(emb):
+  """(pixel_stride, channel_stride) in elements of a dense fp32 `[N, C, H, W]` GPU tensor: `(C, 1)` for channels-last
+  storage, `(1, H * W)` for NCHW-contiguous."""
+  _ptr_any(emb)
+  if emb.dim() != 4:
+    raise SpmlHipError('the embedding must be [N, C, H, W] (got %s)' % (tuple(emb.shape),))
+  n, c, h, w = emb.shape
+  if emb.is_contiguous(memory_format=torch.channels_last):
+    return c, 1
+  if emb.is_contiguous():
+    return 1, h * w
+  raise SpmlHipError('the embedding must be channels-last or NCHW-contiguous')
+
+
+def _summary_workspace(emb, ws):
+  n, c, h, w = emb.shape
+  need = lib().spml_train_summary_workspace_bytes(n, c, h, w)
+  return workspace(need, emb.device) if ws is None else ws
+
+
+def pca_moments(emb, ws=None):
+  """mean fp64 `[C]` and covariance fp64 `[C, C]` (divided by P - 1) of the L2-normalised pixels of `emb`."""
+  ps, cs = embedding_strides(emb)
+  n, c, h, w = emb.shape
+  ws = _summary_workspace(emb, ws)
+  mean = torch.empty((c,), dtype=torch.float64, device=emb.device)
+  cov = torch.empty((c, c), dtype=torch.float64, device=emb.device)
+  check(lib().spml_pca_moments_f32(_ptr_any(emb), n, c, h, w, ps, cs, ptr(mean), ptr(cov), ptr(ws), ws.numel(),
+                                   stream_ptr()), 'spml_pca_moments_f32')
+  return mean, cov
+
+
+def pca_project_minmax(emb, basis, ws=None):
+  """proj fp32 `[N, H, W, 3]` = normalised pixel . `basis` (fp32 `[C, 3]`, un-centred) and minmax fp32 `[N, 3, 2]`, the
+  (minimum, maximum) of proj per image and channel."""
+  ps, cs = embedding_strides(emb)
+  n, c, h, w = emb.shape
+  if tuple(basis.shape) != (c, 3):
+    raise SpmlHipError('pca_project_minmax: the basis must be fp32 [%d, 3]' % c)
+  ws = _summary_workspace(emb, ws)
+  proj = torch.empty((n, h, w, 3), dtype=torch.float32, device=emb.device)
+  minmax = torch.empty((n, 3, 2), dtype=torch.float32, device=emb.device)
+  check(lib().spml_pca_project_minmax_f32(_ptr_any(emb), n, c, h, w, ps, cs, ptr(basis, torch.float32), ptr(proj),
+                                          ptr(minmax), ptr(ws), ws.numel(), stream_ptr()), 'spml_pca_project_minmax_f32')
+  return proj, minmax
+
+
+def summary_panels(semantic, instance, proj, minmax, color_map, out=None):
+  """One launch: the label maps int64 `[N, Hl, Wl]`, proj fp32 `[N, h, w, 3]` and minmax fp32 `[N, 3, 2]` of
+  `pca_project_minmax`, `color_map` uint8 `[256, 3]` -> the picture uint8 `[3, Htot, Wtot]` of
+  `vis.summary_grid_shape(N, h, w)`.  Without label maps (both None): the embedding panel alone, uint8 `[N, 3, h, w]`."""
+  from .utils.general.vis import summary_grid_padding, summary_grid_shape
+  if proj.dim() != 4 or proj.shape[3] != 3:
+    raise SpmlHipError('summary_panels: proj must be fp32 [N, h, w, 3]')
+  n, h, w = int(proj.shape[0]), int(proj.shape[1]), int(proj.shape[2])
+  if tuple(minmax.shape) != (n, 3, 2):
+    raise SpmlHipError('summary_panels: minmax must be fp32 [%d, 3, 2]' % n)
+  if (semantic is None) != (instance is None):
+    raise SpmlHipError('summary_panels: the two label maps go together')
+  if semantic is None:
+    shape, pad, hl, wl, out_h, out_w = (n, 3, h, w), 0, 0, 0, 0, 0
+  else:
+    if semantic.dim() != 3 or semantic.shape[0] != n or semantic.shape != instance.shape:
+      raise SpmlHipError('summary_panels: the label maps must be int64 [%d, Hl, Wl], both of one size' % n)
+    if tuple(color_map.shape) != (256, 3):
+      raise SpmlHipError('summary_panels: the colour map must be uint8 [256, 3]')
+    hl, wl = int(semantic.shape[1]), int(semantic.shape[2])
+    out_h, out_w = summary_grid_shape(n, h, w)
+    shape, pad = (3, out_h, out_w), summary_grid_padding(n)
+  if out is None:
+    out = torch.empty(shape, dtype=torch.uint8, device=proj.device)
+  if tuple(out.shape) != shape:
+    raise SpmlHipError('summary_panels: the output must be uint8 %s' % (shape,))
+  check(lib().spml_summary_panels_u8(ptr(semantic, torch.int64, allow_none=True), ptr(instance, torch.int64, allow_none=True),
+                                     n, hl, wl, ptr(proj, torch.float32), ptr(minmax, torch.float32), h, w,
+                                     ptr(color_map, torch.uint8, allow_none=semantic is None), pad, out_h, out_w,
+                                     ptr(out, torch.uint8), stream_ptr()), 'spml_summary_panels_u8')
   return out

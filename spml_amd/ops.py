@@ -410,3 +410,30 @@ def augment_tags(packed, params, params_dev=None, out=None):
     params_dev = torch.from_numpy(params.view('uint8').reshape(-1).copy()).to(packed.device)
   with torch.no_grad():
     return _ffi.augment_tags(packed, params, params_dev, out)
+
+
+def pca_path_name(c, pixel_stride, channel_stride):
+  """Which Gram kernel an embedding of `c` channels with these element strides takes, or 'unsupported' (host only)."""
+  return _ffi.pca_path_name(c, pixel_stride, channel_stride)
+
+
+def pca_moments(emb, ws=None):
+  """mean fp64 `[C]`, covariance fp64 `[C, C]` (divided by P - 1) of the L2-normalised pixels of `emb` fp32
+  `[N, C, H, W]`, channels-last or NCHW-contiguous (common.normalize_embedding + the centring of
+  common.calculate_principal_components, on the f32-input matrix instruction).  No CPU path."""
+  with torch.no_grad():
+    return _ffi.pca_moments(emb.detach(), ws)
+
+
+def pca_project_minmax(emb, basis, ws=None):
+  """proj fp32 `[N, H, W, 3]` = normalised pixel . `basis` fp32 `[C, 3]` (common.py:68: not centred) and its per-image,
+  per-channel (minimum, maximum) fp32 `[N, 3, 2]`.  No CPU path."""
+  with torch.no_grad():
+    return _ffi.pca_project_minmax(emb.detach(), basis, ws)
+
+
+def summary_panels(semantic, instance, proj, minmax, color_map, out=None):
+  """The finished summary picture uint8 `[3, Htot, Wtot]` in one launch (vis.write_image_to_tensorboard's rows as
+  make_grid(nrow=1) stacks them); without label maps the embedding panel alone, uint8 `[N, 3, h, w]`.  No CPU path."""
+  with torch.no_grad():
+    return _ffi.summary_panels(semantic, instance, proj, minmax, color_map, out)

@@ -124,10 +124,13 @@ class Trainer:
       return train_utils.lr_step(t.base_lr, it, t.decay_iterations, t.warmup_iteration)
     return train_utils.lr_poly(t.base_lr, it, t.max_iteration, t.warmup_iteration)
 
-  def forward_losses(self, datas, targets):
-    """Embeddings -> prototypes -> losses for this rank's images (train.py:167-220)."""
+  def forward_losses(self, datas, targets, keep=None):
+    """Embeddings -> prototypes -> losses for this rank's images (train.py:167-220).  `keep`: a dict that receives
+    the detached embedding map of this rank (for a summary); nothing is kept without it."""
     targets = dict(targets)
     emb = self.emb_fwd(datas, targets)
+    if keep is not None:
+      keep['embedding'] = emb['embedding'].detach()
     protos = model_utils.local_prototypes(
         emb['cluster_embedding'], emb['cluster_embedding_with_loc'], emb['cluster_index'],
         emb['cluster_batch_index'], emb['cluster_semantic_label'], emb['cluster_instance_label'])
@@ -157,14 +160,25 @@ class Trainer:
       for mem in self.memory_banks.get('memory_prototype_batch_index', []):
         mem += self.config.train.batch_size * self.world
 
-  def step(self, datas, targets):
+  def step(self, datas, targets, summary=None):
+    """One iteration.  `summary`: a spml_amd.summary.TrainingSummary; when it is due (`config.train.tensorboard_step`)
+    the detached embedding and the two label maps of THIS rank go to its `write` after the losses and before the
+    backward, as in the reference (train.py:222-258; the reference gathers every GPU's batch, here the caller hands a
+    summary to rank 0 alone and it shows rank 0's batch).  Otherwise nothing is kept and nothing else runs."""
     self.embedding_model.train()
     self.prediction_model.train()
     # (grads are dropped before the forward: the loop over the parameters then runs while the GPU is
     # busy with the backbone instead of right after the loss assembly's host syncs, when it is idle)
     self.optimizer.zero_grad()
-    loss, outputs, targets = self.forward_losses(datas, targets)
+    due = summary is not None and summary.due(self.curr_iter, self.config.train.tensorboard_step)
+    keep = {} if due else None
+    labels = targets
+    loss, outputs, targets = self.forward_losses(datas, targets, keep) if due else self.forward_losses(datas, targets)
     lr = self.lr(self.curr_iter)
+    if due:
+      scalars = {k: outputs[k].detach() for k in LOSS_KEYS + ('accuracy',) if outputs.get(k, None) is not None}
+      scalars['loss'], scalars['lr'] = loss.detach(), lr
+      summary.write(self.curr_iter, labels['semantic_label'], labels['instance_label'], keep['embedding'], scalars)
     loss.backward()
     self.optimizer.step(lr)
     self.update_memory(targets)

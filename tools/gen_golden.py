@@ -45,10 +45,13 @@ def save(out_dir, name, **arrays):
   print('wrote %-40s %7.1f KB' % (path, os.path.getsize(path) / 1024.0))
 
 
-def coherent_embedding(gen, n, c, h, w, blobs=5, noise=0.35):
+def coherent_embedding(gen, n, c, h, w, blobs=5, noise=0.35, strengths=None):
   """Spatially coherent embedding map: a few random directions blended by
-  smooth spatial weights plus noise (so k-means has structure to find)."""
+  smooth spatial weights plus noise (so k-means has structure to find).
+  `strengths`: one factor per blob direction (the same random draws without it)."""
   dirs = torch.randn(blobs, c, generator=gen)
+  if strengths is not None:
+    dirs = dirs * torch.tensor(strengths, dtype=dirs.dtype).view(blobs, 1)
   cy = torch.rand(n, blobs, generator=gen)
   cx = torch.rand(n, blobs, generator=gen)
   yy = torch.linspace(0, 1, h).view(1, 1, h, 1)
@@ -1277,6 +1280,89 @@ def gen_n15(ref, out):
   assert size <= 100 * 1024, 'n15_score_dirs.npz is %d bytes' % size
 
 
+def gen_n16(ref, out):
+  """N16: the picture of a training summary.  `spml/utils/general/vis.py` is imported with empty stand-ins for
+  torchvision (not installed; `make_grid` is not part of the fixture) and, where it is missing, scipy.io; its
+  `embedding_to_rgb`, `convert_label_to_color` and `load_color_map`, `common.pca` / `calculate_principal_components`
+  / `normalize_embedding` run as they stand on the CPU in fp32, and lines 23-29 of `write_image_to_tensorboard` (the
+  nearest resize of the panels and their concatenation) are exec'd from the file.  The floats before `.byte()`
+  (vis.py:95) are taken by exec'ing :74-94 of the same function next to the whole call.  Two cases: N = 2, C = 64, a
+  9 x 11 embedding with 33 x 41 labels; N = 1, C = 32, 8 x 8 with 8 x 8 labels.  The embeddings are `coherent_embedding`
+  with graded blob strengths; a seed is taken only if the four leading eigenvalues of the covariance of the normalised
+  pixels are separated by a factor of at least 1.5 each (a degenerate pair would make the components arbitrary)."""
+  import linecache
+  import textwrap
+  import torch.nn.functional as F
+  stand_ins = {'torchvision': types.ModuleType('torchvision'), 'torchvision.utils': types.ModuleType('torchvision.utils')}
+  stand_ins['torchvision'].utils = stand_ins['torchvision.utils']
+  try:
+    import scipy.io                                        # noqa: F401
+  except ImportError:
+    stand_ins.update({'scipy': types.ModuleType('scipy'), 'scipy.io': types.ModuleType('scipy.io')})
+    stand_ins['scipy'].io = stand_ins['scipy.io']
+  had = {name: sys.modules.get(name) for name in stand_ins}
+  sys.modules.pop('spml.utils.general.vis', None)          # (n14 may have imported it with its own stand-ins)
+  sys.modules.update(stand_ins)
+  try:
+    import spml.utils.general.vis as vis
+    import spml.utils.general.common as common
+  finally:
+    for name, module in had.items():
+      if module is None:
+        del sys.modules[name]
+      else:
+        sys.modules[name] = module
+  vis_py = os.path.join(ref, 'spml', 'utils', 'general', 'vis.py')
+
+  def ref_lines(first, last):
+    return textwrap.dedent(''.join(linecache.getline(vis_py, i) for i in range(first, last + 1)))
+  floats_src, panels_src = ref_lines(74, 94), ref_lines(23, 29)
+  assert floats_src.startswith('embeddings = embeddings.permute(0, 2, 3, 1)') and floats_src.rstrip().endswith('rgb *= 255')
+  assert panels_src.startswith('for ind, image in enumerate(images):') and panels_src.rstrip().endswith('images = torch.cat(images, dim=3)')
+  assert "mode='nearest'" in panels_src
+  table = vis.load_color_map(os.path.join(ref, 'misc', 'colormapvoc.mat'))
+  assert table.shape == (256, 3) and table.dtype == torch.uint8
+
+  store = {'color_map': table.numpy()}
+  cases = [(2, 64, 9, 11, 33, 41, (3.0, 2.2, 1.6, 1.2, 0.8)), (1, 32, 8, 8, 8, 8, (3.0, 2.2, 1.6, 1.2, 0.8))]
+  for ci, (n, c, h, w, hl, wl, strengths) in enumerate(cases):
+    for seed in range(1600 + 100 * ci, 1700 + 100 * ci):
+      gen = torch.Generator().manual_seed(seed)
+      emb = coherent_embedding(gen, n, c, h, w, blobs=5, noise=0.15, strengths=strengths)
+      rows = common.normalize_embedding(emb.permute(0, 2, 3, 1).contiguous()).view(-1, c).double()
+      rows = rows - rows.mean(0, keepdim=True)
+      lam = torch.linalg.eigvalsh(rows.t() @ rows).flip(0)[:4]
+      if bool((lam[:-1] >= 1.5 * lam[1:]).all()):
+        break
+    else:
+      raise AssertionError('case %d: no seed separates the four leading eigenvalues by 1.5' % ci)
+    sem = blocky_labels(gen, n, hl, wl, 4, 0, 21)
+    sem[torch.rand(n, hl, wl, generator=gen) < 0.05] = 255
+    ins = blocky_labels(gen, n, hl, wl, 5, 0, 12)
+    # the whole function, and its lines up to `.byte()` for the floats
+    rgb = vis.embedding_to_rgb(emb.clone(), 'pca')
+    env = {'embeddings': emb.clone(), 'common_utils': common, 'torch': torch, 'project_type': 'pca'}
+    exec(compile(floats_src, vis_py + ':74-94', 'exec'), env)
+    floats = env['rgb'].clone()                            # [N, H W, 3], 0 .. 255
+    assert torch.equal(floats.byte().view(n, h, w, 3).permute(0, 3, 1, 2), rgb)
+    normed = common.normalize_embedding(emb.permute(0, 2, 3, 1).contiguous())
+    basis = common.calculate_principal_components(normed.view(-1, c), 3)
+    assert torch.equal(common.pca(normed, 3), torch.mm(normed.view(-1, c), basis).view(n, h, w, 3))
+    env = {'images': [vis.convert_label_to_color(sem, table), vis.convert_label_to_color(ins, table), rgb],
+           'size': (h, w), 'F': F, 'torch': torch}
+    exec(compile(panels_src, vis_py + ':23-29', 'exec'), env)
+    panels = env['images']
+    assert panels.shape == (n, 3, h, 3 * w) and panels.dtype == torch.uint8
+    t = 'c%d_' % ci
+    store.update({t + 'embedding': emb, t + 'semantic': sem.to(torch.uint8), t + 'instance': ins.to(torch.uint8),
+                  t + 'basis': basis, t + 'floats': floats.view(n, h, w, 3), t + 'bytes': rgb, t + 'panels': panels,
+                  t + 'eigenvalues': lam, t + 'seed': np.array(seed)})
+    print('n16 case %d: seed %d, leading eigenvalues %s' % (ci, seed, ['%.4f' % v for v in lam.tolist()]))
+  save(out, 'n16_train_summary', **store)
+  size = os.path.getsize(os.path.join(out, 'n16_train_summary.npz'))
+  assert size <= 100 * 1024, 'n16_train_summary.npz is %d bytes' % size
+
+
 class AttrDict(dict):
   __getattr__ = dict.__getitem__
 
@@ -1297,7 +1383,7 @@ def main():
   torch.set_num_threads(1)       # bit-stable fp32 sums
   if ONLY is not None and ONLY <= {'n7_pseudo_labels', 'n8_softmax_msc', 'n9_knn_msc', 'n10_prototype_msc',
                                    'n11_pseudo_knn_msc', 'n11_instance_iou', 'n12_densepose_pseudo',
-                                   'n13_augment', 'n14_inference_io', 'n15_score_dirs'}:      # (need none of the imports and shims below)
+                                   'n13_augment', 'n14_inference_io', 'n15_score_dirs', 'n16_train_summary'}:      # (need none of the imports and shims below)
     if 'n7_pseudo_labels' in ONLY:
       gen_n7(args.ref, out)
     if 'n8_softmax_msc' in ONLY:
@@ -1318,6 +1404,8 @@ def main():
       gen_n14(args.ref, out)
     if 'n15_score_dirs' in ONLY:
       gen_n15(args.ref, out)
+    if 'n16_train_summary' in ONLY:
+      gen_n16(args.ref, out)
     return
 
   import spml.utils.general.common as g_common
@@ -2143,6 +2231,10 @@ def main():
   # ======================= N15: scoring directories (mIoU and instance-weighted IoU per file) ====
   if ONLY is None or 'n15_score_dirs' in ONLY:
     gen_n15(args.ref, out)
+
+  # ======================= N16: the picture of a training summary (PCA embedding panels, label panels) ====
+  if ONLY is None or 'n16_train_summary' in ONLY:
+    gen_n16(args.ref, out)
 
   # ======================= H2: two steps of the stage-2 classifier training ===============
   # pyscripts/train/train_classifier.py:139-169, the loop body exec'd as it stands on ONE device:
