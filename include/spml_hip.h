@@ -51,7 +51,7 @@ const char* spml_status_string(int status);
  *    keep the version: spml_view_votes_*, spml_segsort_nll_batched_*, spml_segment_majority_*, spml_tag_normalize_*,
  *    spml_dense_crf_*, spml_segment_tag_cam_*, spml_conv_hl8_path_name, spml_conv_wgrad_path_name / _splits,
  *    spml_augment_*, spml_image_views_*, spml_label_export_*, spml_score_*, spml_pca_*, spml_summary_panels_u8,
- *    spml_train_summary_workspace_bytes). */
+ *    spml_train_summary_workspace_bytes, spml_crf_guide_*, spml_export_scores_bytes, spml_label_export_scored_u8). */
 #define SPML_ABI_VERSION 8
 int spml_abi_version(void);
 
@@ -1272,6 +1272,48 @@ int spml_image_views_u8(const unsigned char* rgb, const unsigned char* semantic,
 const char* spml_label_export_path_name(int pred_h, int pred_w, int valid_h, int valid_w, int out_h, int out_w);
 int spml_label_export_u8(const int64_t* prediction, int pred_h, int pred_w, int valid_h, int valid_w, int out_h, int out_w,
                          const unsigned char* color_map, unsigned char* gray, unsigned char* rgb, void* stream);
+
+/* ------------------------------------------------------------------------
+ * The dense CRF on decoded files: the guide image and the scored export, one launch each (csrc/inference_io.hip;
+ * DESIGN.md 8r)
+ * replaces: pyscripts/inference/inference_softmax_crf_msc.py:159-164 = inference_crf.py:247-252 (the uint8 image
+ *           rebuilt on the host from the normalised fp32 input: image *= std, image += mean, * 255, astype(uint8));
+ *           inference_crf.py:257-261 (the refined labels cropped and resized back with cv2.INTER_NEAREST) with
+ *           pyscripts/benchmark/benchmark_by_mIoU.py:25-53 (iou_stats) for the labels after and before the CRF.
+ *
+ * spml_crf_guide_u8: rgb uint8 [h][w][3] -> guide uint8 [new_h][new_w][3].  Per output value: v = what
+ * spml_image_views_u8 writes at that pixel of an un-flipped new_h x new_w view (the same device function and the same
+ * unfused fp64 coordinates; new == src: (u8 / 255.0f - mean[c]) / std[c]), then numpy's steps on a float32 array and
+ * float64 statistics: t = (float)((double)v * std64[c]); t = (float)((double)t + mean64[c]); t = t * 255.0f;
+ * out = (uint8)((int32)t & 255).  No contraction anywhere.  The round trip is lossy (with the VOC statistics 129 of the
+ * 768 (byte, channel) pairs come back one lower), which is why the file's bytes are not passed through.  mean / std:
+ * device fp32 [3], as for spml_image_views_u8; mean64_host / std64_host: the same statistics as doubles on the host
+ * (passed to the kernel by value).  Paths (spml_crf_guide_path_name, host only): "guide_table" when new == src in both
+ * axes -- the guide is a function of (byte, channel), every workgroup evaluates the 768 pairs into LDS and streams the
+ * image through the table in 12-byte spans (four pixels per lane, a fixed channel phase), no fp64 per pixel;
+ * "guide_resized" otherwise, four taps per channel and the chain per pixel; "unsupported".  One launch, no workspace, no
+ * atomics; every byte of guide is written.  SPML_ERR_UNSUPPORTED: a side outside [1, 16384].  SPML_ERR_INVALID_ARG: a
+ * null pointer, rgb / guide / mean / std not 4-byte aligned, guide overlapping an input.  Both before any launch.
+ *
+ * spml_label_export_scored_u8: gray and rgb exactly as spml_label_export_u8 writes them for `refined`; `before` (int64
+ * [pred_h][pred_w], or NULL) is resampled with the same source index and cast the same way; truth: uint8
+ * [out_h][out_w] or NULL.  scores: int64 [2][3][ncls] followed by one counter (spml_export_scores_bytes(ncls) =
+ * (2 * 3 * ncls + 1) * 8 bytes; 0 outside 1 <= ncls <= 256), accumulated INTO: scores[0] += the (TP+FN, TP+FP, TP)
+ * counts of gray against truth by the rule of spml_iou_counts_i64 (only pixels with truth < ncls count, a prediction
+ * >= ncls falls into no bin); scores[1] += the same for `before`; the counter += the output pixels whose two bytes
+ * differ.  before == NULL leaves scores[1] and the counter alone, truth == NULL both tables.  Every workgroup counts
+ * into an int32 LDS table and adds its non-zero bins with 64-bit integer atomics: bit-identical from run to run.
+ * SPML_ERR_UNSUPPORTED: the cases of spml_label_export_u8, ncls outside [1, 256].  SPML_ERR_INVALID_ARG: a null or
+ * misaligned pointer, an output that overlaps an input or another output. */
+const char* spml_crf_guide_path_name(int h, int w, int new_h, int new_w);
+int spml_crf_guide_u8(const unsigned char* rgb, int h, int w, const float* mean, const float* std,
+                      const double* mean64_host, const double* std64_host, int new_h, int new_w, unsigned char* guide,
+                      void* stream);
+size_t spml_export_scores_bytes(int ncls);
+int spml_label_export_scored_u8(const int64_t* refined, const int64_t* before, int pred_h, int pred_w, int valid_h,
+                                int valid_w, int out_h, int out_w, const unsigned char* color_map,
+                                const unsigned char* truth, int ncls, unsigned char* gray, unsigned char* rgb,
+                                int64_t* scores, void* stream);
 
 /* ------------------------------------------------------------------------
  * Scoring label files against ground truth, a batch of decoded files per call (csrc/score_batch.hip)

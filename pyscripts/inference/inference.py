@@ -15,7 +15,8 @@ to the file's own size (:238-241) as `semantic_gray/<name>.png` and `semantic_co
 (`spml_amd.inference.export_label_map`), and `--semantic_memory_dir` is required.  `--data_list synthetic` feeds seeded
 synthetic images of `test.image_size` (made at the network's size) and writes `semantic_gray/<name>.npy` (uint8); without
 `--semantic_memory_dir` it builds the bank itself, as `inference_msc.py` does.  One JSON line
-reports images/s, mIoU and pixel accuracy (`pyscripts/benchmark/benchmark_by_mIoU.py`)."""
+reports images/s, mIoU and pixel accuracy (`pyscripts/benchmark/benchmark_by_mIoU.py`).
+`--crf` (off by default) adds the denseCRF tail of `inference_crf.py`, on either kind of `--data_list`: the per-segment votes and the guide image at the un-padded `test.image_size` view through `spml_amd.inference.predict_knn_full_resolution_crf`, the label map going back to the file's size afterwards; the labels written and scored are the refined ones and the JSON line gains `crf_path`, `crf_share`, `mIoU_before_crf` and `changed_by_crf` (see `run_knn` of spml_amd/inference_cli.py)."""
 import os
 import sys
 
@@ -24,25 +25,8 @@ sys.path.insert(0, ROOT)
 
 
 def main(argv=None):
-  from spml_amd import inference, inference_cli as cli
-  api = 'predict_full_resolution'
-  config, args, device = cli.parse('Inference for semantic segmentation.', argv, api, file_lists='images')
-  semantic_dir = cli.output_dir(args, 'semantic_gray')
-  source = cli.ImageSource.for_program(config, args, device, [1], False, api, single_view=True)   # :124-142
-  embedding_model, prediction_model, path = cli.load_models(config, args, device, 'segsort')   # :70-90
-  _, crop_size, stride, _ = cli.geometry(config)
-  memory_dir = cli.memory_bank_dir(embedding_model, config, args, device)
-  prototypes, prototype_labels = cli.load_bank(memory_dir, config, device)                    # :93-111
-
-  def one(image):
-    padded, valid_hw, _ = image.views[0]
-    out = inference.predict_full_resolution(embedding_model, prediction_model, padded, valid_hw, crop_size, stride,
-                                            prototypes, prototype_labels, config.dataset.semantic_ignore_index)
-    source.emit(image, out['semantic_prediction'], semantic_dir)
-
-  done, seconds = source.timed(one)
-  cli.report(done, seconds, **source.scores(), memory_prototypes=int(prototypes.shape[0]), snapshot=path,
-             semantic_memory_dir=memory_dir, save_dir=semantic_dir, **source.fields())
+  from spml_amd.inference_cli import run_knn
+  run_knn('Inference for semantic segmentation.', [1], False, argv, single_view=True)          # :124-142
 
 
 if __name__ == '__main__':

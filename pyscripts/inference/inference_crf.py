@@ -15,8 +15,8 @@ CRF's first kernel gathers them per pixel, writes the label before the CRF and s
 `semantic_gray/<name>.npy`; the JSON line carries what `inference.py` reports, scored on the refined labels, plus
 `mIoU_before_crf`, `changed_by_crf` (the share of pixels whose label the CRF changed), `crf_path`, `votes_path` and
 `crf_share`, the CRF's share of the image time.  The reference's resize to `test.image_size` and the nearest-neighbour
-resize of the label map back (:133-142, :258-261) are file plumbing and not built: synthetic images are made at the
-network's size."""
+resize of the label map back (:133-142, :258-261) are built where files are read: the body is `run_knn` of
+spml_amd/inference_cli.py with the CRF on and file lists refused, and `inference.py --crf` runs the same on a list."""
 import os
 import sys
 
@@ -25,40 +25,8 @@ sys.path.insert(0, ROOT)
 
 
 def main(argv=None):
-  import torch
-  from spml_amd import inference, inference_cli as cli
-  from spml_amd.utils.general import metrics
-  config, args, device = cli.parse('Inference for semantic segmentation.', argv, 'predict_knn_full_resolution_crf')
-  semantic_dir = cli.output_dir(args, 'semantic_gray')
-  embedding_model, prediction_model, path = cli.load_models(config, args, device, 'segsort')   # :71-90
-  num_classes, crop_size, stride, size = cli.geometry(config)
-  crf = cli.CrfStage(config, args)                                                            # :92-99
-  memory_dir = args.semantic_memory_dir
-  if memory_dir is None:
-    memory_dir = cli.build_synthetic_bank(embedding_model, config, args, device)
-  prototypes, prototype_labels = cli.load_bank(memory_dir, config, device)                    # :102-120
-  counts, counts_before, out = None, None, None
-  changed = torch.zeros((), dtype=torch.int64, device=device)
-
-  def one(index):
-    nonlocal counts, counts_before, out
-    image, label, _ = cli.synthetic_image(index, size, num_classes, device)
-    padded = inference.flip_scale_views(image, [1], False, crop_size)[0][0]                   # :145-152
-    out = inference.predict_knn_full_resolution_crf(embedding_model, prediction_model, padded, (size, size), crop_size,
-                                                    stride, prototypes, prototype_labels, num_classes,
-                                                    crf.image_u8(padded, (size, size)), crf,
-                                                    config.dataset.semantic_ignore_index)     # :154-257
-    refined, before = out['semantic_prediction'], out['semantic_prediction_before_crf']
-    counts = metrics.iou_stats(refined, label, num_classes, counts)
-    counts_before = metrics.iou_stats(before, label, num_classes, counts_before)
-    changed.add_((refined != before).sum())
-    cli.save_label_map(semantic_dir, index, refined)
-
-  done, seconds = cli.timed_images(one)
-  cli.report(done, seconds, **cli.scores(counts), mIoU_before_crf=cli.scores(counts_before)['mIoU'],
-             changed_by_crf=round(int(changed) / float(max(done, 1) * size * size), 4), votes_path=out['votes_path'],
-             **crf.fields(seconds), memory_prototypes=int(prototypes.shape[0]), snapshot=path,
-             semantic_memory_dir=memory_dir, save_dir=semantic_dir)
+  from spml_amd.inference_cli import run_knn
+  run_knn('Inference for semantic segmentation.', [1], False, argv, single_view=True, file_lists=None, crf=True)
 
 
 if __name__ == '__main__':

@@ -19,7 +19,8 @@ one launch (`spml_amd.inference.device_views`), the label map is written as `sem
 and writes `semantic_gray/<name>.npy` (uint8).  Without `--semantic_memory_dir` the synthetic mode builds the bank
 itself: the prototypes of the synthetic images (`full_resolution_prototypes`, what `prototype.py` does) are written with
 `save_image_memory` to `<save_dir>/semantic_prototype` and read back from those files.  One JSON line reports images/s, mIoU and pixel accuracy
-(`pyscripts/benchmark/benchmark_by_mIoU.py`), the number of views and the path taken by the per-view tail."""
+(`pyscripts/benchmark/benchmark_by_mIoU.py`), the number of views and the path taken by the per-view tail.
+`--crf` (off by default) adds the denseCRF tail of `inference_crf_msc.py`, on either kind of `--data_list`: the view mean of the vote maps and the guide image at the file's own size through `spml_amd.inference.dense_crf_refine`; the labels written and scored are the refined ones and the JSON line gains `crf_path`, `crf_share`, `mIoU_before_crf` and `changed_by_crf` (see `run_knn` of spml_amd/inference_cli.py)."""
 import os
 import sys
 
@@ -30,28 +31,8 @@ SCALES = [0.5, 0.75, 1, 1.25, 1.5]                                              
 
 
 def main(argv=None):
-  from spml_amd import inference, inference_cli as cli
-  api = 'predict_knn_multiscale'
-  config, args, device = cli.parse('Inference for semantic segmentation.', argv, api, file_lists='images')
-  semantic_dir = cli.output_dir(args, 'semantic_gray')
-  source = cli.ImageSource.for_program(config, args, device, SCALES, True, api)                   # :123-137
-  embedding_model, prediction_model, path = cli.load_models(config, args, device, 'segsort')   # :70-89
-  num_classes, crop_size, stride, _ = cli.geometry(config)
-  memory_dir = cli.memory_bank_dir(embedding_model, config, args, device)
-  prototypes, prototype_labels = cli.load_bank(memory_dir, config, device)                    # :94-111
-  out, views = None, []
-
-  def one(image):
-    nonlocal out, views
-    views = image.views
-    out = inference.predict_knn_multiscale(embedding_model, prediction_model, views, image.image_hw, crop_size, stride,
-                                           prototypes, prototype_labels, num_classes)
-    source.emit(image, out['semantic_prediction'], semantic_dir)
-
-  done, seconds = source.timed(one)
-  cli.report(done, seconds, **source.scores(), views=len(views), combine_path=out['combine_path'],
-             memory_prototypes=int(prototypes.shape[0]), snapshot=path, semantic_memory_dir=memory_dir,
-             save_dir=semantic_dir, **source.fields())
+  from spml_amd.inference_cli import run_knn
+  run_knn('Inference for semantic segmentation.', SCALES, True, argv)                          # :123-137
 
 
 if __name__ == '__main__':

@@ -14,7 +14,8 @@ size, :89-103) and the label map goes back to the file's own size (:148-152) as 
 `semantic_color/<name>.png` (`spml_amd.inference.export_label_map`), the folders `benchmark_by_mIoU.py` scores.
 `--data_list synthetic` feeds seeded synthetic images of `test.image_size` and writes `semantic_gray/<name>.npy` (uint8).
 One JSON line reports images/s and, where labels exist, mIoU and pixel accuracy
-(`pyscripts/benchmark/benchmark_by_mIoU.py`)."""
+(`pyscripts/benchmark/benchmark_by_mIoU.py`).
+`--crf` (off by default) adds the denseCRF tail of `inference_softmax_crf.py`, on either kind of `--data_list`: the soft-max of the summed logits and the guide image at the un-padded `test.image_size` view through `spml_amd.inference.dense_crf_refine`; the labels written and scored are the refined ones and the JSON line gains `crf_path`, `crf_share`, `mIoU_before_crf` and `changed_by_crf` (see `run_softmax` of spml_amd/inference_cli.py)."""
 import os
 import sys
 
@@ -22,24 +23,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 
 def main(argv=None):
-  from spml_amd import inference, inference_cli as cli
-  api = 'predict_softmax_full_resolution'
-  config, args, device = cli.parse('Inference for semantic segmentation.', argv, api, file_lists='images')
-  semantic_dir = cli.output_dir(args, 'semantic_gray')
-  source = cli.ImageSource.for_program(config, args, device, [1], False, api, single_view=True)   # :89-103
-  embedding_model, prediction_model, path = cli.load_models(config, args, device, 'softmax_classifier')   # :63-76
-  _, crop_size, stride, _ = cli.geometry(config)
-  out = None
-
-  def one(image):
-    nonlocal out
-    padded, valid_hw, _ = image.views[0]
-    out = inference.predict_softmax_full_resolution(embedding_model, prediction_model, padded, valid_hw, crop_size, stride)
-    source.emit(image, out['semantic_prediction'], semantic_dir)
-
-  done, seconds = source.timed(one)
-  cli.report(done, seconds, **source.scores(), head_path=out['head_path'], snapshot=path, save_dir=semantic_dir,
-             **source.fields())
+  from spml_amd.inference_cli import run_softmax
+  run_softmax('Inference for semantic segmentation.', [1], False, argv, single_view=True)      # :89-103
 
 
 if __name__ == '__main__':

@@ -10,8 +10,8 @@ Everything up to the sum of the ten views' class probabilities is `inference_sof
 (`spml_amd.inference.predict_softmax_multiscale`).  Then the mean over the views (:156), the uint8 image rebuilt from
 the network's input (:159-164, `denormalized_uint8`) and `spml_amd.inference.dense_crf_refine`: the exact mean-field
 filter as HIP kernels (`spml_amd.models.crf.DenseCRF`).  Label maps are the arg-max of the refined marginals
-(:168); the JSON line carries what `inference_softmax_msc.py` reports plus `crf_path` and `crf_share`, the CRF's share of
-the image time."""
+(:168); the JSON line carries what `inference_softmax_msc.py --crf` reports: the body is that program's, `run_softmax` of
+spml_amd/inference_cli.py, with the CRF on and file lists refused (`inference_softmax_msc.py --crf` reads them)."""
 import os
 import sys
 
@@ -22,29 +22,8 @@ SCALES = [0.5, 0.75, 1, 1.25, 1.5]                                              
 
 
 def main(argv=None):
-  import torch
-  from spml_amd import inference, inference_cli as cli
-  from spml_amd.utils.general import metrics
-  config, args, device = cli.parse('Inference for semantic segmentation.', argv, 'dense_crf_refine')
-  semantic_dir = cli.output_dir(args, 'semantic_gray')
-  embedding_model, prediction_model, path = cli.load_models(config, args, device, 'softmax_classifier')   # :60-78
-  num_classes, crop_size, stride, size = cli.geometry(config)
-  crf = cli.CrfStage(config, args)                                                            # :81-87
-  counts, out, views = None, None, []
-
-  def one(index):
-    nonlocal counts, out, views
-    image, label, _ = cli.synthetic_image(index, size, num_classes, device)
-    views = inference.flip_scale_views(image, SCALES, True, crop_size)                        # :100-112
-    out = inference.predict_softmax_multiscale(embedding_model, prediction_model, views, (size, size), crop_size, stride)
-    prob = out['semantic_prob'] / torch.full((), float(len(views)), device=device)            # the mean of :156
-    refined = crf(crf.image_u8(image, (size, size)), prob)                                    # :159-166
-    counts = metrics.iou_stats(refined['semantic_prediction'], label, num_classes, counts)
-    cli.save_label_map(semantic_dir, index, refined['semantic_prediction'])
-
-  done, seconds = cli.timed_images(one)
-  cli.report(done, seconds, **cli.scores(counts), views=len(views), head_path=out['head_path'],
-             combine_path=out['combine_path'], **crf.fields(seconds), snapshot=path, save_dir=semantic_dir)
+  from spml_amd.inference_cli import run_softmax
+  run_softmax('Inference for semantic segmentation.', SCALES, True, argv, file_lists=None, crf=True)
 
 
 if __name__ == '__main__':

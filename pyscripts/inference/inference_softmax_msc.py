@@ -15,7 +15,8 @@ from its decoded bytes by one launch (`spml_amd.inference.device_views`) and the
 `semantic_gray/<name>.png` and `semantic_color/<name>.png` (`spml_amd.inference.export_label_map`), the folders
 `benchmark_by_mIoU.py` scores.  `--data_list synthetic` feeds seeded synthetic images of `test.image_size` through
 `spml_amd.inference.flip_scale_views` and writes `semantic_gray/<name>.npy` (uint8).  One JSON line reports images/s, mIoU and pixel accuracy (`pyscripts/benchmark/benchmark_by_mIoU.py`), the number of
-views and the paths taken by the classifier head and by the per-view tail."""
+views and the paths taken by the classifier head and by the per-view tail.
+`--crf` (off by default) adds the denseCRF tail of `inference_softmax_crf_msc.py`, on either kind of `--data_list`: the mean of the views' class probabilities and the guide image at the file's own size through `spml_amd.inference.dense_crf_refine`; the labels written and scored are the refined ones and the JSON line gains `crf_path`, `crf_share`, `mIoU_before_crf` and `changed_by_crf` (see `run_softmax` of spml_amd/inference_cli.py)."""
 import os
 import sys
 
@@ -26,24 +27,8 @@ SCALES = [0.5, 0.75, 1, 1.25, 1.5]                                              
 
 
 def main(argv=None):
-  from spml_amd import inference, inference_cli as cli
-  api = 'predict_softmax_multiscale'
-  config, args, device = cli.parse('Inference for semantic segmentation.', argv, api, file_lists='images')
-  semantic_dir = cli.output_dir(args, 'semantic_gray')
-  source = cli.ImageSource.for_program(config, args, device, SCALES, True, api)                   # :90-103
-  embedding_model, prediction_model, path = cli.load_models(config, args, device, 'softmax_classifier')   # :63-76
-  _, crop_size, stride, _ = cli.geometry(config)
-  out, views = None, []
-
-  def one(image):
-    nonlocal out, views
-    views = image.views
-    out = inference.predict_softmax_multiscale(embedding_model, prediction_model, views, image.image_hw, crop_size, stride)
-    source.emit(image, out['semantic_prediction'], semantic_dir)
-
-  done, seconds = source.timed(one)
-  cli.report(done, seconds, **source.scores(), views=len(views), head_path=out['head_path'],
-             combine_path=out['combine_path'], snapshot=path, save_dir=semantic_dir, **source.fields())
+  from spml_amd.inference_cli import run_softmax
+  run_softmax('Inference for semantic segmentation.', SCALES, True, argv)                      # :90-103
 
 
 if __name__ == '__main__':

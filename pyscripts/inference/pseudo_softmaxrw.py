@@ -6,8 +6,9 @@ box recipes run it between stage 1 and stage 2):
   python3 pyscripts/inference/pseudo_softmaxrw.py --snapshot_dir S --cfg_path C.yaml --save_dir OUT --data_list L
 
 Flip pair at scale 1, softmax per view and mean of the probabilities, WALK_STEPS = 6 squarings of the transition
-matrix (:29, :109-112, :143-147).  Writes the labels of :176 (before the denseCRF refinement, which is outside this
-repository): `semantic_gray/<name>.png` and `semantic_color/<name>.png` at the file's own size under `--data_dir D
+matrix (:29, :109-112, :143-147).  Writes the labels of :176, or with `--crf` (off by default) the labels of :187 after the denseCRF refinement
+of `pseudo_softmaxrw_crf.py` (`spml_amd.inference.pseudo_labels_softmax_crf` on the guide image of the file, DESIGN 8r;
+the JSON line gains `crf_path`, `crf_share`, `mIoU_before_crf` and `changed_by_crf`): `semantic_gray/<name>.png` and `semantic_color/<name>.png` at the file's own size under `--data_dir D
 --data_list L` (the reference's file list with its label columns, which give the image tags), `semantic_gray/<name>.npy`
 under `--data_list synthetic`; see `run_pseudo_softmax` of spml_amd/inference_cli.py."""
 import os
@@ -21,7 +22,8 @@ SCALES, COMBINE, WALK_STEPS = (1,), 'prob_mean', 6
 
 def main(argv=None):
   from spml_amd.inference_cli import run_pseudo_softmax
-  run_pseudo_softmax('Generate pseudo labels by softmax classifier and random walk.', SCALES, COMBINE, WALK_STEPS, argv)
+  run_pseudo_softmax('Generate pseudo labels by softmax classifier and random walk.', SCALES, COMBINE, WALK_STEPS, argv,
+                     crf=None)
 
 
 if __name__ == '__main__':

@@ -13,7 +13,9 @@ one fused call (`spml_amd.inference.pseudo_labels_softmax_crf`): the 
 (:173-175), writes the label before the CRF (:176) and starts the exact mean-field filter (`spml_amd.models.crf.DenseCRF`,
 DESIGN 8j).  Label maps are the arg-max of the refined marginals (:187), written as `semantic_gray/<name>.npy`; the JSON
 line carries what `pseudo_softmaxrw.py` reports, scored on the refined labels, plus `mIoU_before_crf`, `changed_by_crf`
-(the share of pixels whose label the CRF changed), `crf_path` and `crf_share`, the CRF's share of the image time."""
+(the share of pixels whose label the CRF changed), `crf_path` and `crf_share`, the CRF's share of the image time.  The
+body is `run_pseudo_softmax` of spml_amd/inference_cli.py with the CRF on and file lists refused;
+`pseudo_softmaxrw.py --crf` runs the same on a list."""
 import os
 import sys
 
@@ -24,37 +26,9 @@ SCALES, COMBINE, WALK_STEPS = (1,), 'prob_mean', 6                              
 
 
 def main(argv=None):
-  import torch
-  from spml_amd import inference, inference_cli as cli
-  from spml_amd.utils.general import metrics
-  config, args, device = cli.parse('Generate pseudo labels by softmax classifier, random walk and CRF.', argv,
-                                   'pseudo_labels_softmax_crf')
-  semantic_dir = cli.output_dir(args, 'semantic_gray')
-  embedding_model, prediction_model, path = cli.load_models(config, args, device, 'softmax_classifier')
-  num_classes, crop_size, _, size = cli.geometry(config)
-  crf = cli.CrfStage(config, args)                                                            # :66-73
-  counts, counts_before, out = None, None, None
-  changed = torch.zeros((), dtype=torch.int64, device=device)
-
-  def one(index):
-    nonlocal counts, counts_before, out
-    image, label, _ = cli.synthetic_image(index, size, num_classes, device)
-    views = inference.flip_scale_views(image, SCALES, True, crop_size)                        # :109-125
-    out = inference.pseudo_labels_softmax_crf(embedding_model, prediction_model, views, (size, size),
-                                              inference.label_tags_from_map(label, num_classes),
-                                              crf.image_u8(image, (size, size)), crf, combine=COMBINE,
-                                              walk_steps=WALK_STEPS)                          # :126-187
-    refined, before = out['semantic_prediction'], out['semantic_prediction_before_crf']
-    counts = metrics.iou_stats(refined, label, num_classes, counts)
-    counts_before = metrics.iou_stats(before, label, num_classes, counts_before)
-    changed.add_((refined != before).sum())
-    cli.save_label_map(semantic_dir, index, refined)
-
-  done, seconds = cli.timed_images(one)
-  cli.report(done, seconds, **cli.scores(counts), mIoU_before_crf=cli.scores(counts_before)['mIoU'],
-             changed_by_crf=round(int(changed) / float(max(done, 1) * size * size), 4), scales=list(SCALES),
-             is_flip=True, combine=COMBINE, walk_steps=WALK_STEPS, head_path=out['head_path'], **crf.fields(seconds),
-             snapshot=path, save_dir=semantic_dir)
+  from spml_amd.inference_cli import run_pseudo_softmax
+  run_pseudo_softmax('Generate pseudo labels by softmax classifier, random walk and CRF.', SCALES, COMBINE, WALK_STEPS,
+                     argv, file_lists=None, crf=True)
 
 
 if __name__ == '__main__':

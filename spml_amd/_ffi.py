@@ -185,6 +185,10 @@ _SIGNATURES = {
     'spml_image_views_u8': (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P, c_int, _P, c_int64, _P, c_int64, _P]),
     'spml_label_export_path_name': (c_char_p, [c_int, c_int, c_int, c_int, c_int, c_int]),
     'spml_label_export_u8': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
+    'spml_crf_guide_path_name': (c_char_p, [c_int, c_int, c_int, c_int]),
+    'spml_crf_guide_u8': (c_int, [_P, c_int, c_int, _P, _P, _P, _P, c_int, c_int, _P, _P]),
+    'spml_export_scores_bytes': (c_size_t, [c_int]),
+    'spml_label_export_scored_u8': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P, _P]),
     'spml_score_params_bytes': (c_size_t, []),
     'spml_score_batch_workspace_bytes': (c_size_t, [c_int, c_int]),
     'spml_score_batch_path_name': (c_char_p, [_P, c_int, c_int64, c_int]),
@@ -1875,6 +1879,74 @@ def label_export(prediction, valid_hw, out_hw, color_map, out=None):
   check(lib().spml_label_export_u8(ptr(prediction, torch.int64), int(prediction.shape[0]), int(prediction.shape[1]),
                                    int(valid_hw[0]), int(valid_hw[1]), oh, ow, ptr(color_map, torch.uint8),
                                    ptr(gray, torch.uint8), ptr(rgb, torch.uint8), stream_ptr()), 'spml_label_export_u8')
+  return gray, rgb
+
+
+MAX_EXPORT_SCORE_CLASSES = 256         # the limit of spml_label_export_scored_u8 (include/spml_hip.h)
+
+
+def crf_guide_path_name(source_hw, out_hw=None):
+  """'guide_table', 'guide_resized' or 'unsupported' (a host function of the library)."""
+  out_hw = source_hw if out_hw is None else out_hw
+  return lib().spml_crf_guide_path_name(int(source_hw[0]), int(source_hw[1]), int(out_hw[0]), int(out_hw[1])).decode()
+
+
+def crf_guide(rgb, mean, std, pixel_means, pixel_stds, out_hw=None, out=None):
+  """One launch: `rgb` uint8 `[h, w, 3]` on the device -> the dense CRF's guide uint8 `[new_h, new_w, 3]` (`out_hw`; the
+  source's own size when None).  `mean` / `std`: the fp32 `[3]` device tensors of `image_views`; `pixel_means` /
+  `pixel_stds`: the same statistics as Python numbers (they go to the library as doubles)."""
+  import ctypes
+  if rgb.dim() != 3 or rgb.shape[2] != 3:
+    raise SpmlHipError('crf_guide: rgb must be uint8 [h, w, 3]')
+  if mean.numel() != 3 or std.numel() != 3 or len(pixel_means) != 3 or len(pixel_stds) != 3:
+    raise SpmlHipError('crf_guide: mean and std hold 3 values')
+  h, w = int(rgb.shape[0]), int(rgb.shape[1])
+  new_h, new_w = (h, w) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+  if out is None:
+    if new_h < 1 or new_w < 1:
+      raise SpmlHipError('crf_guide: an output of %d x %d' % (new_h, new_w))
+    out = torch.empty((new_h, new_w, 3), dtype=torch.uint8, device=rgb.device)
+  elif tuple(out.shape) != (new_h, new_w, 3):
+    raise SpmlHipError('crf_guide: the output must be uint8 [%d, %d, 3]' % (new_h, new_w))
+  mean64 = (ctypes.c_double * 3)(*(float(v) for v in pixel_means))
+  std64 = (ctypes.c_double * 3)(*(float(v) for v in pixel_stds))
+  check(lib().spml_crf_guide_u8(ptr(rgb, torch.uint8), h, w, ptr(mean, torch.float32), ptr(std, torch.float32), mean64,
+                                std64, new_h, new_w, ptr(out, torch.uint8), stream_ptr()), 'spml_crf_guide_u8')
+  return out
+
+
+def export_scores_bytes(ncls):
+  return int(lib().spml_export_scores_bytes(int(ncls)))
+
+
+def label_export_scored(refined, before, valid_hw, out_hw, color_map, truth, ncls, scores, out=None):
+  """One launch: `label_export` of `refined` + the same resampling of `before` (int64 `[pred_h, pred_w]` or None), both
+  counted against `truth` (uint8 `[out_h, out_w]` or None) INTO `scores` (int64 `[2 * 3 * ncls + 1]`: the two
+  `[3, ncls]` tables of `iou_counts`, then the number of output pixels the two maps differ at).
+  -> (gray uint8 `[out_h, out_w]`, rgb uint8 `[out_h, out_w, 3]`)."""
+  if refined.dim() != 2 or (before is not None and tuple(before.shape) != tuple(refined.shape)):
+    raise SpmlHipError('label_export_scored: the two predictions must be int64 [pred_h, pred_w]')
+  if tuple(color_map.shape) != (256, 3):
+    raise SpmlHipError('label_export_scored: the colour map must be uint8 [256, 3]')
+  oh, ow = int(out_hw[0]), int(out_hw[1])
+  if truth is not None and tuple(truth.shape) != (oh, ow):
+    raise SpmlHipError('label_export_scored: the ground truth must be uint8 [%d, %d]' % (oh, ow))
+  nbytes = export_scores_bytes(ncls)
+  if nbytes and scores.numel() * 8 != nbytes:
+    raise SpmlHipError('label_export_scored: scores must hold 2 * 3 * %d + 1 int64 values' % int(ncls))
+  if out is None:
+    if oh < 1 or ow < 1:
+      raise SpmlHipError('label_export_scored: an output of %d x %d' % (oh, ow))
+    out = (torch.empty((oh, ow), dtype=torch.uint8, device=refined.device),
+           torch.empty((oh, ow, 3), dtype=torch.uint8, device=refined.device))
+  gray, rgb = out
+  if tuple(gray.shape) != (oh, ow) or tuple(rgb.shape) != (oh, ow, 3):
+    raise SpmlHipError('label_export_scored: outputs do not have the shapes of a %d x %d map' % (oh, ow))
+  check(lib().spml_label_export_scored_u8(
+      ptr(refined, torch.int64), ptr(before, torch.int64, allow_none=True), int(refined.shape[0]), int(refined.shape[1]),
+      int(valid_hw[0]), int(valid_hw[1]), oh, ow, ptr(color_map, torch.uint8), ptr(truth, torch.uint8, allow_none=True),
+      int(ncls), ptr(gray, torch.uint8), ptr(rgb, torch.uint8), ptr(scores, torch.int64), stream_ptr()),
+        'spml_label_export_scored_u8')
   return gray, rgb
 
 

@@ -4,7 +4,7 @@ import argparse
 from spml_amd.config.default import config, update_config
 
 
-def build_parser(description=''):
+def build_parser(description='', crf_option=False):
   p = argparse.ArgumentParser(description=description)
   p.add_argument('--snapshot_dir', required=True, type=str, help='/path/to/snapshot/dir.')
   p.add_argument('--save_dir', type=str, help='/path/to/save/dir.')
@@ -22,12 +22,17 @@ def build_parser(description=''):
   for name, default in (('crf_iter_max', 10), ('crf_pos_xy_std', 1), ('crf_pos_w', 3),
                         ('crf_bi_xy_std', 67), ('crf_bi_w', 4), ('crf_bi_rgb_std', 3)):
     p.add_argument('--' + name, type=int, default=default)
+  # not in the reference's CLI either (it has one script with and one without the CRF): the five programs that have a
+  # `*_crf*` sibling take the sibling's denseCRF tail as an option, off by default
+  if crf_option:
+    p.add_argument('--crf', action='store_true', help='refine the labels with the dense CRF (the --crf_* options).')
   return p
 
 
-def parse_args(description='', argv=None):
-  """parse_known_args -> update_config(cfg_path) -> parse_args (parse_args.py:46-53)."""
-  parser = build_parser(description)
+def parse_args(description='', argv=None, crf_option=False):
+  """parse_known_args -> update_config(cfg_path) -> parse_args (parse_args.py:46-53).  `crf_option`: the program takes
+  `--crf`."""
+  parser = build_parser(description, crf_option)
   args, _ = parser.parse_known_args(argv)
   update_config(args.cfg_path)
   return parser.parse_args(argv)

@@ -589,6 +589,39 @@ def export_label_map(prediction, valid_hw, out_hw, color_map, out=None):
     return _ffi.label_export(prediction, valid_hw, out_hw, color_map, out)
 
 
+def crf_guide(rgb_u8, pixel_means, pixel_stds, out_hw=None):
+  """The uint8 image the reference hands to its CRF (`inference_softmax_crf_msc.py:159-164`), from a decoded file's
+  bytes by ONE launch (`spml_crf_guide_u8`): `rgb_u8` uint8 `[h,w,3]` on the device -> uint8 `[rh,rw,3]`, bit for bit
+  `denormalized_uint8` of the un-flipped `out_hw` view `device_views` makes of the same bytes (`out_hw` None: the
+  file's own size, the multi-view programs; the un-padded `test.image_size` view for the single-view ones,
+  `inference_crf.py:247-252`).  Not the bytes themselves: the reference rebuilds the image from the normalised fp32
+  input and that round trip lowers some (byte, channel) pairs by one.  No CPU path."""
+  if not rgb_u8.is_cuda:
+    raise _ffi.SpmlHipError('the HIP path needs GPU tensors (got %s); there is no CPU fallback' % rgb_u8.device)
+  if rgb_u8.dim() != 3 or rgb_u8.shape[2] != 3 or rgb_u8.dtype != torch.uint8:
+    raise ValueError('crf_guide expects one decoded image, uint8 [h,w,3]')
+  mean, std = _normalisation(rgb_u8.device, pixel_means, pixel_stds)
+  with torch.no_grad():
+    return _ffi.crf_guide(rgb_u8, mean, std, pixel_means, pixel_stds, out_hw)
+
+
+def export_scored_label_map(refined, before, valid_hw, out_hw, color_map, truth, num_classes, scores=None, out=None):
+  """The tail of a program that ends in the dense CRF (`inference_crf.py:257-261` + `benchmark_by_mIoU.py:25-53`) as ONE
+  launch (`spml_label_export_scored_u8`): `export_label_map` of `refined`, the same resampling of `before` (the labels
+  before the CRF, int64 `[pred_h,pred_w]`, or None), both scored at `out_hw` against `truth` (uint8 `[out_h,out_w]` on
+  the device, or None), and the count of output pixels the CRF changed.  `scores`: int64 `[2 * 3 * num_classes + 1]` on
+  the device, accumulated INTO over the images of a list (a fresh zero tensor when None): `scores[:-1].view(2, 3, -1)`
+  are the `iou_stats` tables after and before the CRF, `scores[-1]` the changed pixels.
+  -> `(gray, rgb, scores)`."""
+  if not refined.is_cuda:
+    raise _ffi.SpmlHipError('the HIP path needs GPU tensors (got %s); there is no CPU fallback' % refined.device)
+  with torch.no_grad():
+    if scores is None:
+      scores = torch.zeros((2 * 3 * int(num_classes) + 1,), dtype=torch.int64, device=refined.device)
+    gray, rgb = _ffi.label_export_scored(refined, before, valid_hw, out_hw, color_map, truth, num_classes, scores, out)
+  return gray, rgb, scores
+
+
 def _walked_cams_softmax(name, embedding_model, prediction_model, views, image_hw, label_tags, combine, walk_steps,
                          background_threshold, scale, power):
   """`pseudo_labels_softmax` up to the walked maps, shared with `pseudo_labels_softmax_crf`: the argument checks (under

@@ -4,8 +4,14 @@ surface (`parse_args`), the argument guards, snapshot loading, where the images 
 and the label images finished on the GPU, DESIGN 8o -- eight programs so far, the other nine still refuse a list), the
 self-built memory bank of the kNN programs, the timed loop over the images and the JSON line.  A program's `main` holds what is specific to its recipe:
 which `spml_amd.inference` function it calls, with which extra inputs, and which fields it adds to the report.  The two
-memory-bank programs (`prototype.py`, `prototype_msc.py`) and the two softmax pseudo-label programs (`pseudo_softmax.py`,
-`pseudo_softmaxrw.py`) differ in constants only; their bodies are `run_prototypes` and `run_pseudo_softmax` below."""
+memory-bank programs (`prototype.py`, `prototype_msc.py`) differ in constants only; their body is `run_prototypes`.
+The label-inference and softmax pseudo-label programs come in pairs, `X.py` and `X_crf.py`: the pair shares one body
+(`run_softmax`, `run_knn`, `run_pseudo_softmax`) with the denseCRF stage (`CrfStage`) on or off.  `X.py` reads file
+lists and takes `--crf`; `X_crf.py` runs the same body with the CRF always on and refuses a list, so the CRF of those five
+programs reaches image files through `X.py --crf`: the source then adds the CRF's guide image to every
+`SourceImage` (`spml_crf_guide_u8` from the bytes already on the device) and `emit_refined` finishes, scores (after and
+before the CRF) and compares the label maps in one launch (`spml_label_export_scored_u8`).  `pseudo_softmax.py` runs
+`run_pseudo_softmax` too; it has no CRF sibling in the reference and takes no `--crf`."""
 import json
 import os
 import time
@@ -42,15 +48,16 @@ def list_dataset(config, args, api_function, need_labels=False):
   return dataset
 
 
-def parse(description, argv, api_function, what='inference', file_lists=None):
+def parse(description, argv, api_function, what='inference', file_lists=None, crf_option=False):
   """`parse_args`, the reference's `--kmeans_num_clusters` / `--label_divisor` overrides (inference_msc.py:40-41; the
   softmax programs read neither), then the guards, in one order for every program: a file list, a missing `--save_dir`,
   a machine without a GPU.  `file_lists`: None for a program that does not read file lists yet (it refuses one),
-  'images' for one that does, 'labels' for one that also needs the list's label columns.
+  'images' for one that does, 'labels' for one that also needs the list's label columns.  `crf_option`: the program
+  takes `--crf` (the denseCRF tail of its `*_crf*` sibling).
   -> (config, args, device), with `device` made the current one."""
   from spml_amd.config.default import config
   from spml_amd.config.parse_args import parse_args
-  args = parse_args(description, argv)
+  args = parse_args(description, argv, crf_option)
   if args.kmeans_num_clusters:
     config.network.kmeans_num_clusters = [int(i) for i in args.kmeans_num_clusters.split(',')]
   if args.label_divisor:
@@ -206,32 +213,40 @@ class SourceImage(object):
   """One image of an `ImageSource`: `index`, `name` (of its output files, without a directory), `image_hw` (the size the
   label map is scored and written at), `views` (`(image [1,3,Hp,Wp], (rh, rw), is_flip)`, what the `predict_*` /
   `pseudo_*` functions take), `label_views` (the label `[rh, rw]` of every view; a source with labels only) and `label`
-  (the semantic label `[h, w]` on the device, or None)."""
+  (the semantic label `[h, w]` on the device, or None).  A source made `with_guide` adds `guide`, the uint8 image
+  `[rh, rw, 3]` the denseCRF takes, at the resolution the CRF runs at: the file's own size for the multi-view programs
+  (inference_softmax_crf_msc.py:159-164 uses the original image), the un-padded `test.image_size` view for a
+  `single_view` one (inference_crf.py:247-252)."""
 
-  def __init__(self, index, name, image_hw, views, label_views, label):
+  def __init__(self, index, name, image_hw, views, label_views, label, guide=None):
     self.index, self.name, self.image_hw = index, name, image_hw
-    self.views, self.label_views, self.label = views, label_views, label
+    self.views, self.label_views, self.label, self.guide = views, label_views, label, guide
 
 
 class ImageSource(object):
   """Where a program's images come from and where its label maps go: one interface, two implementations, so that a
   program's `main` does not branch.  `scales` / `is_flip`: the views of every image; `single_view`: the program resizes
   to `test.image_size` first (inference_softmax.py:89-94) and its label map goes back to the file's size; `with_labels`:
-  every view comes with its label map (the memory-bank pass).
+  every view comes with its label map (the memory-bank pass); `with_guide`: every image comes with the denseCRF's guide.
 
     for_program(...)        the implementation `--data_list` selects
     timed(per_image)        `per_image(SourceImage)` for every image, between two synchronisations -> (done, seconds)
     emit(image, prediction, directory)
                             scores the label map `[h, w]` against the image's label and writes it
+    emit_refined(image, refined, before, directory)
+                            the same for the labels after the denseCRF; the labels before it are scored too and the
+                            pixels the CRF changed are counted, all at the size `emit` scores at
     bank_name(image)        file name of the image's memory bank
     scores()                the `mIoU` / `pixel_acc` fields of the report
+    crf_fields()            `mIoU_before_crf` and `changed_by_crf` of the report, after `emit_refined`
     fields()                further fields of the report"""
 
-  def __init__(self, config, args, device, scales, is_flip, single_view=False, with_labels=False):
+  def __init__(self, config, args, device, scales, is_flip, single_view=False, with_labels=False, with_guide=False):
     self.config, self.args, self.device = config, args, device
     self.scales, self.is_flip, self.single_view, self.with_labels = list(scales), bool(is_flip), single_view, with_labels
+    self.with_guide = with_guide
     self.num_classes, self.crop_size, self.stride, self.size = geometry(config)
-    self.counts = None
+    self.counts, self.counts_before, self.changed, self.pixels = None, None, None, 0
 
   @staticmethod
   def for_program(config, args, device, scales, is_flip, api_function, **kind):
@@ -251,6 +266,12 @@ class ImageSource(object):
   def scores(self):
     return {'mIoU': None, 'pixel_acc': None} if self.counts is None else scores(self.counts)
 
+  def crf_fields(self):
+    """Read after the loop's closing synchronisation."""
+    before = None if self.counts_before is None else scores(self.counts_before)['mIoU']
+    changed = 0 if self.changed is None else int(self.changed)
+    return {'mIoU_before_crf': before, 'changed_by_crf': round(changed / float(max(self.pixels, 1)), 4)}
+
   def fields(self):
     return {}
 
@@ -267,7 +288,10 @@ class SyntheticImageSource(ImageSource):
     if self.with_labels:
       dense = dense_label(label, self.num_classes, self.config.dataset.semantic_ignore_index)
       labels = inference.label_views(dense, [hw for _, hw, _ in views])
-    return SourceImage(index, 'synthetic_{:04d}'.format(index), (self.size, self.size), views, labels, label)
+    guide = None
+    if self.with_guide:         # (a single view's padded image holds `image` in its top-left corner: one guide for both)
+      guide = inference.denormalized_uint8(image, self.config.network.pixel_means, self.config.network.pixel_stds)
+    return SourceImage(index, 'synthetic_{:04d}'.format(index), (self.size, self.size), views, labels, label, guide)
 
   def timed(self, per_image):
     return timed_images(lambda index: per_image(self.image(index)))
@@ -275,6 +299,16 @@ class SyntheticImageSource(ImageSource):
   def emit(self, image, prediction, directory):
     self.score(prediction, image.label)
     save_label_map(directory, image.index, prediction)
+
+  def emit_refined(self, image, refined, before, directory):
+    from spml_amd.utils.general import metrics
+    if self.changed is None:
+      self.changed = torch.zeros((), dtype=torch.int64, device=self.device)
+    self.score(refined, image.label)
+    self.counts_before = metrics.iou_stats(before, image.label, self.num_classes, self.counts_before)
+    self.changed.add_((refined != before).sum())
+    self.pixels += refined.numel()
+    save_label_map(directory, image.index, refined)
 
   def bank_name(self, image):
     return image.name + '.npy'
@@ -300,9 +334,11 @@ class ListImageSource(ImageSource):
   up from pinned memory in ONE `non_blocking` copy and `spml_image_views_u8` makes every view from them
   (`spml_amd.inference.views_from_records`); `spml_label_export_u8` writes the finished gray and colour bytes at the
   file's own size, one copy brings them into pinned memory and a writer pool saves `semantic_gray/<name>.png` (mode L)
-  and `semantic_color/<name>.png` (mode RGB)."""
+  and `semantic_color/<name>.png` (mode RGB).  `with_guide`: `spml_crf_guide_u8` forms the denseCRF's guide from the
+  bytes already on the device, and `emit_refined` finishes, scores (after and before the CRF) and compares in one launch
+  (`spml_label_export_scored_u8`); the counts of the whole list stay in one device tensor."""
 
-  AHEAD = 4         # images decoded ahead of the one on the GPU
+  AHEAD = 4        # images decoded ahead of the one on the GPU
 
   def __init__(self, config, args, device, scales, is_flip, api_function, **kind):
     from concurrent.futures import ThreadPoolExecutor
@@ -364,7 +400,11 @@ class ListImageSource(ImageSource):
     sem_dev = packed[sem_at:total].view(h, w) if semantic is not None else None
     views, labels = inference.views_from_records(rgb_dev, records, packed[:records.nbytes], self.mean, self.std,
                                                  sem_dev if self.with_labels else None)
-    return SourceImage(index, output_name(self.dataset.image_paths[index]), (h, w), views, labels, sem_dev)
+    guide = None
+    if self.with_guide:
+      guide = inference.crf_guide(rgb_dev, self.config.network.pixel_means, self.config.network.pixel_stds,
+                                  views[0][1] if self.single_view else None)
+    return SourceImage(index, output_name(self.dataset.image_paths[index]), (h, w), views, labels, sem_dev, guide)
 
   def timed(self, per_image):
     n, done = len(self), 0
@@ -397,6 +437,29 @@ class ListImageSource(ImageSource):
     inference.export_label_map(prediction.contiguous(), tuple(prediction.shape), (h, w), self.color_map, out=(gray, color))
     if image.label is not None:
       self.score(gray, image.label)
+    self._queue(image, out, directory)
+
+  def emit_refined(self, image, refined, before, directory):
+    """`emit` for the labels after the denseCRF (`refined`, `before`: `[rh, rw]` as there): one launch writes the bytes
+    and adds both score tables and the changed pixels into `self.crf_scores`."""
+    from spml_amd import inference
+    h, w = image.image_hw
+    n = self.num_classes
+    out = torch.empty((4 * h * w,), dtype=torch.uint8, device=self.device)
+    gray, color = out[:h * w].view(h, w), out[h * w:].view(h, w, 3)
+    if self.changed is None:
+      self.crf_scores = torch.zeros((2 * 3 * n + 1,), dtype=torch.int64, device=self.device)
+      self.changed = self.crf_scores[-1]
+    inference.export_scored_label_map(refined.contiguous(), before.contiguous(), tuple(refined.shape), (h, w),
+                                      self.color_map, image.label, n, self.crf_scores, out=(gray, color))
+    if image.label is not None:
+      self.counts, self.counts_before = self.crf_scores[:3 * n].view(3, n), self.crf_scores[3 * n:-1].view(3, n)
+    self.pixels += h * w
+    self._queue(image, out, directory)
+
+  def _queue(self, image, out, directory):
+    """The finished bytes `[gray | colour]` of an image: one copy into pinned memory, then the writer pool."""
+    h, w = image.image_hw
     host = torch.empty((4 * h * w,), dtype=torch.uint8, pin_memory=True)
     host.copy_(out, non_blocking=True)
     event = torch.cuda.Event()
@@ -465,29 +528,149 @@ def run_prototypes(description, scales, argv=None, single_view=False):
          majority_path=out['majority_path'], snapshot=path, save_dir=prototype_dir, **source.fields())
 
 
-def run_pseudo_softmax(description, scales, combine, walk_steps, argv=None):
-  """`pseudo_softmax.py` and `pseudo_softmaxrw.py` (`pseudo_softmaxrw_crf.py:33-204` of twke18/SPML): every image through
-  `spml_amd.inference.pseudo_labels_softmax`; the programs differ in three constants only (scales of the image pyramid,
-  how the views' class scores are combined, squarings of the transition matrix).  The label map of an image (synthetic,
-  or the file's own: a data list needs its label columns) gives the image tags (:102-106) and the mIoU of the JSON line;
-  the labels written are those of :176, before the denseCRF refinement (built for other programs; for these
-  two it is the follow-up named there)."""
+def crf_stage(config, args, crf):
+  """The `CrfStage` of a run, or None.  `crf`: True in a `*_crf*.py` program, None in its list-reading sibling, where
+  `--crf` decides, False in a program without the option."""
+  return CrfStage(config, args) if crf or (crf is None and args.crf) else None
+
+
+def run_pseudo_softmax(description, scales, combine, walk_steps, argv=None, file_lists='labels', crf=False):
+  """`pseudo_softmax.py`, `pseudo_softmaxrw.py` and `pseudo_softmaxrw_crf.py` (`pseudo_softmaxrw_crf.py:33-204` of
+  twke18/SPML): every image through `spml_amd.inference.pseudo_labels_softmax`; the programs differ in three constants
+  (scales of the image pyramid, how the views' class scores are combined, squarings of the transition matrix) and in
+  `crf` (see `crf_stage`).  The label map of an image (synthetic, or the file's own: a data list needs its label columns)
+  gives the image tags (:102-106) and the mIoU of the JSON line.  Without the CRF the labels written are those of :176;
+  with it every image goes through `pseudo_labels_softmax_crf` on the source's guide image (:172-187) and the
+  refined labels of :187 are written, the labels of :176 scored next to them."""
   from spml_amd import inference
-  config, args, device = parse(description, argv, 'pseudo_labels_softmax', file_lists='labels')
+  api = 'pseudo_labels_softmax_crf' if crf else 'pseudo_labels_softmax'
+  config, args, device = parse(description, argv, api, file_lists=file_lists, crf_option=crf is None)
   semantic_dir = output_dir(args, 'semantic_gray')
-  source = ImageSource.for_program(config, args, device, scales, True, 'pseudo_labels_softmax')   # :109-125
+  stage = crf_stage(config, args, crf)                                                            # :66-73
+  source = ImageSource.for_program(config, args, device, scales, True, api, with_guide=stage is not None)   # :109-125
   embedding_model, prediction_model, path = load_models(config, args, device, 'softmax_classifier')
   out = None
 
   def one(image):
     nonlocal out
-    out = inference.pseudo_labels_softmax(embedding_model, prediction_model, image.views, image.image_hw,
-                                          source.tags(image), combine=combine, walk_steps=walk_steps)
-    source.emit(image, out['semantic_prediction'], semantic_dir)
+    if stage is None:
+      out = inference.pseudo_labels_softmax(embedding_model, prediction_model, image.views, image.image_hw,
+                                            source.tags(image), combine=combine, walk_steps=walk_steps)
+      source.emit(image, out['semantic_prediction'], semantic_dir)
+    else:
+      out = inference.pseudo_labels_softmax_crf(embedding_model, prediction_model, image.views, image.image_hw,
+                                                source.tags(image), image.guide, stage, combine=combine,
+                                                walk_steps=walk_steps)                            # :126-187
+      source.emit_refined(image, out['semantic_prediction'], out['semantic_prediction_before_crf'], semantic_dir)
 
   done, seconds = source.timed(one)
-  report(done, seconds, **source.scores(), scales=list(scales), is_flip=True, combine=combine, walk_steps=walk_steps,
-         head_path=out['head_path'], snapshot=path, save_dir=semantic_dir, **source.fields())
+  report(done, seconds, **source.scores(), **crf_report(stage, source, seconds), scales=list(scales), is_flip=True,
+         combine=combine, walk_steps=walk_steps, head_path=out['head_path'], snapshot=path, save_dir=semantic_dir,
+         **source.fields())
+
+
+def crf_report(stage, source, seconds):
+  """The fields a run with the denseCRF adds to its report: `mIoU_before_crf`, `changed_by_crf` (the share of output
+  pixels whose label the CRF changed), `crf_path` and `crf_share`; none without the stage."""
+  return {} if stage is None else dict(source.crf_fields(), **stage.fields(seconds))
+
+
+def run_softmax(description, scales, is_flip, argv=None, single_view=False, file_lists='images', crf=None):
+  """The four softmax label-inference programs: `inference_softmax.py` / `inference_softmax_crf.py` (`single_view`: one
+  view at `test.image_size` through `predict_softmax_full_resolution`, inference_softmax_crf.py:27-176) and
+  `inference_softmax_msc.py` / `inference_softmax_crf_msc.py` (the flip pairs of `scales` through
+  `predict_softmax_multiscale`, inference_softmax_crf_msc.py:30-177).  `crf`: see `crf_stage`.  With the CRF the class
+  probabilities -- the soft-max of the summed logits cropped to the view (:153-154), or the mean over the views
+  (:156) -- go with the source's guide image through `dense_crf_refine` (:158-168) and the arg-max of the
+  refined marginals is written; the labels before the CRF are the plain program's."""
+  from spml_amd import inference
+  api = 'dense_crf_refine' if crf else ('predict_softmax_full_resolution' if single_view else 'predict_softmax_multiscale')
+  config, args, device = parse(description, argv, api, file_lists=file_lists, crf_option=crf is None)
+  semantic_dir = output_dir(args, 'semantic_gray')
+  embedding_model, prediction_model, path = load_models(config, args, device, 'softmax_classifier')
+  _, crop_size, stride, _ = geometry(config)
+  stage = crf_stage(config, args, crf)
+  source = ImageSource.for_program(config, args, device, scales, is_flip, api, single_view=single_view,
+                                   with_guide=stage is not None)
+  out, views = None, []
+
+  def one(image):
+    nonlocal out, views
+    views = image.views
+    if single_view:
+      padded, (h, w), _ = views[0]
+      out = inference.predict_softmax_full_resolution(embedding_model, prediction_model, padded, (h, w), crop_size, stride)
+    else:
+      out = inference.predict_softmax_multiscale(embedding_model, prediction_model, views, image.image_hw, crop_size, stride)
+    if stage is None:
+      source.emit(image, out['semantic_prediction'], semantic_dir)
+      return
+    if single_view:
+      prob = torch.softmax(out['semantic_logit'], dim=1)[0, :, :h, :w].contiguous()
+    else:
+      prob = out['semantic_prob'] / torch.full((), float(len(views)), device=device)
+    refined = stage(image.guide, prob)
+    source.emit_refined(image, refined['semantic_prediction'], out['semantic_prediction'], semantic_dir)
+
+  done, seconds = source.timed(one)
+  more = {} if single_view else {'views': len(views), 'combine_path': out['combine_path']}
+  report(done, seconds, **source.scores(), **more, head_path=out['head_path'], **crf_report(stage, source, seconds),
+         snapshot=path, save_dir=semantic_dir, **source.fields())
+
+
+def run_knn(description, scales, is_flip, argv=None, single_view=False, file_lists='images', crf=None):
+  """The four kNN label-inference programs: `inference.py` / `inference_crf.py` (`single_view`: one view at
+  `test.image_size`, inference_crf.py:35-280) and `inference_msc.py` / `inference_crf_msc.py` (the flip pairs of `scales`
+  through `predict_knn_multiscale`, inference_crf_msc.py:35-283), against the memory bank of `--semantic_memory_dir`
+  (`memory_bank_dir`).  `crf`: see `crf_stage`.  With the CRF a single view goes through the fused
+  `predict_knn_full_resolution_crf` (votes gathered inside the CRF's first kernel), the view mean of the
+  votes of a multi-view program through `dense_crf_refine` (:251-260), on the source's guide image."""
+  from spml_amd import inference
+  api = 'predict_full_resolution' if single_view else 'predict_knn_multiscale'
+  if crf and single_view:
+    api = 'predict_knn_full_resolution_crf'
+  config, args, device = parse(description, argv, api, file_lists=file_lists, crf_option=crf is None)
+  semantic_dir = output_dir(args, 'semantic_gray')
+  embedding_model, prediction_model, path = load_models(config, args, device, 'segsort')
+  num_classes, crop_size, stride, _ = geometry(config)
+  stage = crf_stage(config, args, crf)
+  source = ImageSource.for_program(config, args, device, scales, is_flip, api, single_view=single_view,
+                                   with_guide=stage is not None)
+  memory_dir = memory_bank_dir(embedding_model, config, args, device)
+  prototypes, prototype_labels = load_bank(memory_dir, config, device)
+  ignore_index = config.dataset.semantic_ignore_index
+  out, views = None, []
+
+  def one(image):
+    nonlocal out, views
+    views = image.views
+    if not single_view:
+      out = inference.predict_knn_multiscale(embedding_model, prediction_model, views, image.image_hw, crop_size, stride,
+                                             prototypes, prototype_labels, num_classes)
+      if stage is None:
+        source.emit(image, out['semantic_prediction'], semantic_dir)
+      else:
+        refined = stage(image.guide, out['semantic_prob'])
+        source.emit_refined(image, refined['semantic_prediction'], out['semantic_prediction'], semantic_dir)
+      return
+    padded, valid_hw, _ = views[0]
+    if stage is None:
+      out = inference.predict_full_resolution(embedding_model, prediction_model, padded, valid_hw, crop_size, stride,
+                                              prototypes, prototype_labels, ignore_index)
+      source.emit(image, out['semantic_prediction'], semantic_dir)
+    else:
+      out = inference.predict_knn_full_resolution_crf(embedding_model, prediction_model, padded, valid_hw, crop_size,
+                                                      stride, prototypes, prototype_labels, num_classes, image.guide,
+                                                      stage, ignore_index)
+      source.emit_refined(image, out['semantic_prediction'], out['semantic_prediction_before_crf'], semantic_dir)
+
+  done, seconds = source.timed(one)
+  more = {} if single_view else {'views': len(views), 'combine_path': out['combine_path']}
+  if single_view and stage is not None:
+    more['votes_path'] = out['votes_path']
+  report(done, seconds, **source.scores(), **more, **crf_report(stage, source, seconds),
+         memory_prototypes=int(prototypes.shape[0]), snapshot=path, semantic_memory_dir=memory_dir, save_dir=semantic_dir,
+         **source.fields())
 
 
 class CrfStage(object):
