@@ -9,12 +9,21 @@
 // normalise + scale/shift (+ residual) (+ ReLU), and the backward is one reduction pass + one
 // apply pass that also yields the gradient of the residual branch.  HBM-bound, float4 accesses.
 //
-//   spml_bn_stats_f32          per-channel mean and sum of squared deviations (chunked, merged
-//                              with Chan's formula: no E[x^2] - E[x]^2 cancellation)
-//   spml_bn_act_apply_f32      y = act((x - mean) * invstd * gamma + beta [+ residual])
-//   spml_bn_act_bwd_reduce_f32 sum(dz), sum(dz * xhat)   with dz = dy * (y > 0)
-//   spml_bn_act_bwd_apply_f32  dx = gamma * invstd * (dz - sum_dz/n - xhat * sum_dz_xhat/n); dres = dz
-// Cross-rank statistics (SyncBatchNorm) are combined by the caller between the two halves.
+// Four kernels carry every pass:
+//   bn_partial<MODE, MASK>  per chunk of rows and channel: MODE 0 mean and sum of squared deviations (+ max / min),
+//                           MODE 1 sum(dz), sum(dz * (x - mean)) (+ max |dz|)   with dz = dy * (y > 0)
+//   bn_merge<MODE>          the chunks pooled in a fixed order (Chan's formula: no E[x^2] - E[x]^2 cancellation);
+//                           single-rank calls finalise (invstd, running statistics) and bound the output tensor here
+//   bn_apply<HAS_RES>       y = act((x - mean) * invstd * gamma + beta [+ residual]) as fp32, hl8 and / or ReLU mask
+//   bn_bwd_apply<MASK>      dx = gamma * invstd * (dz - sum_dz/n - xhat * sum_dz_xhat/n) as fp32 and / or hl8; dres = dz
+// Entry points (the host side at the end of the file; include/spml_hip.h has the contracts):
+//   spml_bn_stats_f32 / _act_apply_f32 / _act_bwd_reduce_f32 / _act_bwd_apply_f32   one pass each: SyncBatchNorm
+//       combines the ranks' statistics between the halves (spml_bn_finalize_f32, spml_bn_finalize_ranks_f32)
+//   spml_bn_act_fwd_f32 / _act_bwd_f32                                              single rank: one call per direction
+//   spml_bn_stats_ext_f32 / _act_apply_hl8_f32 / _act_bwd_reduce_ext_f32 / _act_bwd_apply_hl8_f32, spml_bn_fwd_hl8_f32 /
+//       _bwd_hl8_f32                the same two families with the split-f16 (hl8) copies, bounds and mask bytes that
+//                                   the matrix-core convolutions consume (C % 8 == 0)
+//   spml_bn_*_chunks_f32            ... pooled from the chunk statistics a convolution's epilogue left: no partial pass
 #include "common.hpp"
 
 namespace spml {
@@ -376,7 +385,7 @@ __global__ __launch_bounds__(kMergeCh * kMergeLanes) void bn_merge(
 
 // apply kernels: block = cq channel quads x (256 / cq) row lanes, grid (C / (4*cq), row tiles);
 // a thread keeps its channel quad's coefficients in registers and walks down the rows of its
-// tile (bn_apply_rows: ~4096 blocks per launch, at most 256 rows each)
+// tile (BnGeom::apply_rows: ~4096 blocks per launch, at most 256 rows each)
 
 template <bool HAS_RES>
 __global__ __launch_bounds__(256) void bn_apply(const float* __restrict__ x, const float* __restrict__ res,
@@ -557,151 +566,229 @@ __global__ __launch_bounds__(256) void bn_finalize_ranks(int C, int world, const
   }
 }
 
-inline int bn_cq(int C);
-inline int bn_apply_rows(int64_t R, int C);
-inline int bn_cq(int C) { const int q = C >> 2; return q >= 64 ? 64 : (q >= 32 ? 32 : (q >= 16 ? 16 : (q >= 8 ? 8 : 4))); }
-// rows per partial-statistics chunk: enough chunks to fill the chip (~1024 blocks), at most 1024
-// of them (merge depth), never fewer than 128 rows each
-inline int bn_chunk_rows(int64_t R, int C) {
-  const int cq = bn_cq(C), col_blocks = ((C >> 2) + cq - 1) / cq;
-  const int64_t target = std::min<int64_t>(1024, std::max<int64_t>(1, 1024 / col_blocks));
-  return (int)std::max<int64_t>(128, (R + target - 1) / target);
+// ---- Host side.  bn_geom fixes the launch geometry of an [R, C] tensor once per call: the workspace size, every grid
+// and every kernel argument read it.  One launcher per kernel takes the geometry, the stream, R and C, and a record of
+// the kernel's pointers in which what a call does not pass stays null; a function returns the template variant.
+// cq channel quads per 256-thread block (256 / cq row lanes), col_blocks = grid.x of the partial and apply kernels;
+// chunks of chunk_rows rows for the partial statistics (grid.y of bn_partial, depth of the merge): enough to fill the
+// chip (~1024 blocks), at most 1024, at least 128 rows each; apply_rows per block of the apply kernels (~4096 blocks)
+struct BnGeom { int cq, col_blocks, chunks, chunk_rows, apply_rows; };
+inline BnGeom bn_geom(int64_t R, int C) {
+  BnGeom g;
+  const int q = C >> 2;
+  g.cq = q >= 64 ? 64 : (q >= 32 ? 32 : (q >= 16 ? 16 : (q >= 8 ? 8 : 4)));
+  g.col_blocks = (q + g.cq - 1) / g.cq;
+  const int64_t target = std::min<int64_t>(1024, std::max<int64_t>(1, 1024 / std::max(g.col_blocks, 1)));
+  g.chunk_rows = (int)std::max<int64_t>(128, (R + target - 1) / target);
+  g.chunks = (int)((R + g.chunk_rows - 1) / g.chunk_rows);
+  const int nty = 256 / g.cq;
+  const int64_t rows = (R * g.col_blocks + 4095) / 4096;
+  g.apply_rows = (int)std::min<int64_t>(256, std::max<int64_t>(nty, (rows + nty - 1) / nty * nty));
+  return g;
 }
-inline int bn_chunks(int64_t R, int C) { const int cr = bn_chunk_rows(R, C); return (int)((R + cr - 1) / cr); }
-inline int bn_apply_rows(int64_t R, int C) {
-  const int cq = bn_cq(C), col_blocks = ((C >> 2) + cq - 1) / cq, nty = 256 / cq;
-  const int64_t rows = (R * col_blocks + 4095) / 4096;
-  return (int)std::min<int64_t>(256, std::max<int64_t>(nty, (rows + nty - 1) / nty * nty));
+// ... with the chunks a producer left (the epilogue of a convolution, csrc/conv.hip) in place of its own
+inline BnGeom with_chunks(BnGeom g, int chunks, int rows) { g.chunks = chunks; g.chunk_rows = rows; return g; }
+// such chunks cover the R rows exactly: the last one holds at least one row
+inline bool chunks_cover(int chunks, int chunk_rows, int64_t R) {
+  return chunks > 0 && chunk_rows > 0 && (int64_t)chunks * chunk_rows >= R && (int64_t)(chunks - 1) * chunk_rows < R;
 }
-inline bool bn_ok(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// The [chunks][C] planes of a workspace (four) or of a producer's chunk_stats (four forward, three backward).
+// MODE 0: a = chunk mean, b = chunk M2, c = max, d = min.  MODE 1: a = sum dz, b = sum dz * (x - mean), c = max |dz|;
+// no kernel takes d there, and spml_bn_bwd_hl8_f32 keeps the merged max_dz [C] in that quarter of the workspace.
+template <typename T>
+struct BnPlanes {
+  T *a, *b, *c, *d;
+  // the first n of them: what the kernels are handed by a call that has no use for the rest
+  BnPlanes first(int n) const { return {a, b, n > 2 ? c : nullptr, n > 3 ? d : nullptr}; }
+};
+template <typename T>
+inline BnPlanes<T> bn_planes(T* base, const BnGeom& g, int C) {
+  const size_t n = (size_t)g.chunks * C;
+  return {base, base + n, base + 2 * n, base + 3 * n};
+}
+inline size_t bn_ws_bytes(const BnGeom& g, int C) { return (size_t)4 * g.chunks * C * 4 + 256; }
+
+// the kernel variant by where dz = dy * (y > 0) comes from (1 an fp32 y, 2 the mask bytes, 0 no ReLU): no test per row
+inline int mask_kind(const float* y, const unsigned char* relu_mask) { return y ? 1 : (relu_mask ? 2 : 0); }
+inline dim3 apply_grid(const BnGeom& g, int64_t R) {
+  return dim3(g.col_blocks, (unsigned)((R + g.apply_rows - 1) / g.apply_rows));
+}
+
+struct PartialArgs {
+  const float* x;
+  const float *dy = nullptr, *mean = nullptr, *y = nullptr;      // MODE 1: dy, batch mean; y or the mask bytes if ReLU
+  const unsigned char* relu_mask = nullptr;
+  float* zero_me = nullptr;                                      // the bound slot the next merge max-reduces into
+};
+template <int MODE>
+inline auto partial_kernel(int mask) {
+  using K = decltype(&bn_partial<0, 0>);
+  if (MODE == 0) return K(bn_partial<0, 0>);
+  return select_int<0, 1, 2>(mask, K(nullptr), [](auto M_) -> K { return bn_partial<1, decltype(M_)::value>; });
+}
+template <int MODE>
+inline void launch_partial(const BnGeom& g, hipStream_t s, int64_t R, int C, const PartialArgs& a, BnPlanes<float> p) {
+  hipLaunchKernelGGL(partial_kernel<MODE>(mask_kind(a.y, a.relu_mask)), dim3(g.col_blocks, g.chunks), dim3(256), 0, s,
+                     a.x, a.dy, a.y, a.mean, R, C, g.cq, g.chunk_rows, p.a, p.b, a.relu_mask, p.c, p.d, a.zero_me);
+}
+
+struct MergeArgs {
+  float *out_a, *out_b;                  // MODE 0: mean, M2 (invstd where fin.fin);  MODE 1: sum dz, sum dz * xhat
+  const float* invstd = nullptr;         // MODE 1
+  float *out_c = nullptr, *out_d = nullptr;      // merged extremes of p.c / p.d: max and min of x, or max |dz| alone
+  BnBound bound = {};
+  BnFinal fin = {0, 0.f, 0.f, nullptr, nullptr};
+};
+template <int MODE, typename T>
+inline void launch_merge(const BnGeom& g, hipStream_t s, int64_t R, int C, BnPlanes<T> p, const MergeArgs& a) {
+  hipLaunchKernelGGL(bn_merge<MODE>, dim3((C + kMergeCh - 1) / kMergeCh), dim3(kMergeCh * kMergeLanes), 0, s, p.a, p.b,
+                     R, C, g.chunks, g.chunk_rows, a.invstd, a.out_a, a.out_b, a.fin, p.c, p.d, a.out_c, a.out_d,
+                     a.bound);
+}
+
+struct ApplyArgs {
+  const float *x, *residual, *mean, *invstd, *gamma, *beta;      // residual may be null
+  int relu;
+  float *y = nullptr, *y_bound = nullptr;      // y_bound fixes the scale of y_hl8 (a single-rank merge writes it)
+  uint2* y_hl8 = nullptr;
+  unsigned char* relu_mask = nullptr;
+};
+inline auto apply_kernel(bool has_res) { return has_res ? bn_apply<true> : bn_apply<false>; }
+inline void launch_apply(const BnGeom& g, hipStream_t s, int64_t R, int C, const ApplyArgs& a) {
+  hipLaunchKernelGGL(apply_kernel(a.residual != nullptr), apply_grid(g, R), dim3(256), 0, s, a.x, a.residual, R, C,
+                     g.cq, g.apply_rows, a.mean, a.invstd, a.gamma, a.beta, a.relu, a.y, a.y_hl8, a.y_bound,
+                     a.relu_mask);
+}
+
+struct BwdApplyArgs {
+  const float *dy, *y;                   // y or relu_mask or neither (mask_kind)
+  const unsigned char* relu_mask;
+  const float *x, *mean, *invstd, *gamma, *sum_dz, *sum_dz_xhat;      // read for dx / dx_hl8 only
+  const float* count_dev;                // the row count of all ranks on the device, or null: 1 / count in inv_count
+  float inv_count;
+  float *dx, *d_residual;
+  uint2* dx_hl8 = nullptr;               // with dx_bound, which fixes its scale (and which a single-rank merge writes)
+  float* dx_bound = nullptr;
+};
+inline auto bwd_apply_kernel(int mask) {
+  using K = decltype(&bn_bwd_apply<0>);
+  return select_int<0, 1, 2>(mask, K(nullptr), [](auto M_) -> K { return bn_bwd_apply<decltype(M_)::value>; });
+}
+inline void launch_bwd_apply(const BnGeom& g, hipStream_t s, int64_t R, int C, const BwdApplyArgs& a) {
+  hipLaunchKernelGGL(bwd_apply_kernel(mask_kind(a.y, a.relu_mask)), apply_grid(g, R), dim3(256), 0, s, a.dy, a.y, a.x,
+                     R, C, g.cq, g.apply_rows, a.mean, a.invstd, a.gamma, a.sum_dz, a.sum_dz_xhat, a.inv_count,
+                     a.count_dev, a.dx, a.d_residual, a.relu_mask, a.dx_hl8, a.dx_bound);
+}
+
+// statistics of x: the chunk partials into the planes p of the workspace, then their merge
+inline void stats_pass(const BnGeom& g, hipStream_t s, const float* x, int64_t R, int C, BnPlanes<float> p,
+                       const MergeArgs& m) {
+  launch_partial<0>(g, s, R, C, {x}, p);
+  launch_merge<0>(g, s, R, C, p, m);
+}
+// tail of the two single-rank hl8 forwards: merge with finalisation and the bound of y (reset with p), then the apply
+template <typename T>
+inline void merge_final_apply(const BnGeom& g, hipStream_t s, int64_t R, int C, BnPlanes<T> p, const BnFinal& fin,
+                              const float* residual_bound, float* mean, float* invstd, float* cmax, float* cmin,
+                              const ApplyArgs& ap) {
+  const BnBound bound{ap.y_bound, ap.residual ? residual_bound : nullptr, ap.gamma, ap.beta};
+  launch_merge<0>(g, s, R, C, p, {mean, invstd, nullptr, cmax, cmin, bound, fin});
+  launch_apply(g, s, R, C, ap);
+}
+// tail of the two single-rank hl8 backwards: merge with the bound of dx (if dx_hl8), then the apply if it has an output
+template <typename T>
+inline void merge_bound_bwd_apply(const BnGeom& g, hipStream_t s, int64_t R, int C, BnPlanes<T> p, float* d_beta,
+                                  float* d_gamma, float* max_dz, const float* cmax, const float* cmin,
+                                  const BwdApplyArgs& ba) {
+  const BnBound bound{ba.dx_hl8 ? ba.dx_bound : nullptr, nullptr, ba.gamma, nullptr, ba.mean, cmax, cmin, ba.inv_count};
+  launch_merge<1>(g, s, R, C, p, {d_beta, d_gamma, ba.invstd, max_dz, nullptr, bound});
+  if (!ba.dx && !ba.dx_hl8 && !ba.d_residual) return;
+  launch_bwd_apply(g, s, R, C, ba);
+}
+// the pointers every forward entry point reads or writes with float4 accesses (absent outputs pass)
+inline bool fwd_aligned(const float* x, const float* residual, const float* mean, const float* invstd,
+                        const float* gamma, const float* beta, const float* y, const void* y_hl8) {
+  return al16(x) && (!y || al16(y)) && (!y_hl8 || al16(y_hl8)) && (!residual || al16(residual)) && al16(mean) &&
+         al16(invstd) && al16(gamma) && al16(beta);
+}
 
 }  // namespace
 }  // namespace spml
 
 using namespace spml;
 
-// kernel variant dispatch on the (uniform) optional inputs: no pointer tests inside the row loops
-#define SPML_BN_BY_MASK(KERNEL, MASK, ...)                                        \
-  do {                                                                            \
-    if ((MASK) == 1) hipLaunchKernelGGL((KERNEL<1>), __VA_ARGS__);                \
-    else if ((MASK) == 2) hipLaunchKernelGGL((KERNEL<2>), __VA_ARGS__);           \
-    else hipLaunchKernelGGL((KERNEL<0>), __VA_ARGS__);                            \
-  } while (0)
-#define SPML_BN_PARTIAL1(MASK, ...)                                               \
-  do {                                                                            \
-    if ((MASK) == 1) hipLaunchKernelGGL((bn_partial<1, 1>), __VA_ARGS__);         \
-    else if ((MASK) == 2) hipLaunchKernelGGL((bn_partial<1, 2>), __VA_ARGS__);    \
-    else hipLaunchKernelGGL((bn_partial<1, 0>), __VA_ARGS__);                     \
-  } while (0)
-#define SPML_BN_APPLY(HAS_RES, ...)                                               \
-  do {                                                                            \
-    if (HAS_RES) hipLaunchKernelGGL((bn_apply<true>), __VA_ARGS__);               \
-    else hipLaunchKernelGGL((bn_apply<false>), __VA_ARGS__);                      \
-  } while (0)
-
 extern "C" size_t spml_bn_workspace_bytes(int64_t R, int C) {
-  if (R <= 0 || C <= 0) return 0;
-  return (size_t)4 * bn_chunks(R, C) * C * 4 + 256;
+  return R <= 0 || C <= 0 ? 0 : bn_ws_bytes(bn_geom(R, C), C);
 }
 
-extern "C" int spml_bn_stats_f32(const float* x, int64_t R, int C, float* mean, float* m2, void* ws,
-                                 size_t ws_bytes, void* stream) {
+extern "C" int spml_bn_stats_f32(const float* x, int64_t R, int C, float* mean, float* m2, void* ws, size_t ws_bytes,
+                                 void* stream) {
   if (!x || !mean || !m2 || R <= 0 || C <= 0) return SPML_ERR_INVALID_ARG;
-  if ((C & 3) || !bn_ok(x) || !bn_ok(mean) || !bn_ok(m2)) return SPML_ERR_UNSUPPORTED;
-  if (!ws || ws_bytes < spml_bn_workspace_bytes(R, C)) return SPML_ERR_WORKSPACE;
-  const int chunks = bn_chunks(R, C), cq = bn_cq(C), crows = bn_chunk_rows(R, C);
-  float* pa = static_cast<float*>(ws);
-  float* pb = pa + (size_t)chunks * C;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL((bn_partial<0, 0>), dim3(((C >> 2) + cq - 1) / cq, chunks), dim3(256), 0, s, x,
-                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, R, C, cq, crows, pa, pb, (const unsigned char*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
-  hipLaunchKernelGGL(bn_merge<0>, dim3((C + kMergeCh - 1) / kMergeCh), dim3(kMergeCh * kMergeLanes), 0, s, pa, pb, R, C, chunks, crows,
-                     (const float*)nullptr, mean, m2, BnFinal{0, 0.f, 0.f, nullptr, nullptr}, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr, BnBound{});
+  if ((C & 3) || !al16(x) || !al16(mean) || !al16(m2)) return SPML_ERR_UNSUPPORTED;
+  const BnGeom g = bn_geom(R, C);
+  if (!ws || ws_bytes < bn_ws_bytes(g, C)) return SPML_ERR_WORKSPACE;
+  stats_pass(g, (hipStream_t)stream, x, R, C, bn_planes(static_cast<float*>(ws), g, C).first(2), {mean, m2});
   return launch_status();
 }
 
-extern "C" int spml_bn_act_apply_f32(const float* x, const float* residual, int64_t R, int C,
-                                     const float* mean, const float* invstd, const float* gamma,
-                                     const float* beta, int relu, float* y, void* stream) {
+extern "C" int spml_bn_act_apply_f32(const float* x, const float* residual, int64_t R, int C, const float* mean,
+                                     const float* invstd, const float* gamma, const float* beta, int relu, float* y,
+                                     void* stream) {
   if (!x || !mean || !invstd || !gamma || !beta || !y || R <= 0 || C <= 0) return SPML_ERR_INVALID_ARG;
-  if ((C & 3) || !bn_ok(x) || !bn_ok(y) || (residual && !bn_ok(residual)) || !bn_ok(mean) ||
-      !bn_ok(invstd) || !bn_ok(gamma) || !bn_ok(beta))
-    return SPML_ERR_UNSUPPORTED;
-  const int cq = bn_cq(C), arows = bn_apply_rows(R, C);
-  const dim3 grid(((C >> 2) + cq - 1) / cq, (unsigned)((R + arows - 1) / arows));
-  SPML_BN_APPLY(residual != nullptr, grid, dim3(256), 0, (hipStream_t)stream, x, residual, R, C, cq, arows, mean, invstd,
-                     gamma, beta, relu, y, (uint2*)nullptr, (const float*)nullptr, (unsigned char*)nullptr);
+  if ((C & 3) || !fwd_aligned(x, residual, mean, invstd, gamma, beta, y, nullptr)) return SPML_ERR_UNSUPPORTED;
+  launch_apply(bn_geom(R, C), (hipStream_t)stream, R, C, {x, residual, mean, invstd, gamma, beta, relu, y});
   return launch_status();
 }
 
-extern "C" int spml_bn_act_bwd_reduce_f32(const float* dy, const float* y, const float* x, int64_t R,
-                                          int C, const float* mean, const float* invstd,
-                                          float* sum_dz, float* sum_dz_xhat, void* ws, size_t ws_bytes,
-                                          void* stream) {
-  if (!dy || !x || !mean || !invstd || !sum_dz || !sum_dz_xhat || R <= 0 || C <= 0)
-    return SPML_ERR_INVALID_ARG;
-  if ((C & 3) || !bn_ok(dy) || !bn_ok(x) || (y && !bn_ok(y)) || !bn_ok(mean)) return SPML_ERR_UNSUPPORTED;
-  if (!ws || ws_bytes < spml_bn_workspace_bytes(R, C)) return SPML_ERR_WORKSPACE;
-  const int chunks = bn_chunks(R, C), cq = bn_cq(C), crows = bn_chunk_rows(R, C);
-  float* pa = static_cast<float*>(ws);
-  float* pb = pa + (size_t)chunks * C;
-  hipStream_t s = (hipStream_t)stream;
-  SPML_BN_PARTIAL1(y ? 1 : 0, dim3(((C >> 2) + cq - 1) / cq, chunks), dim3(256), 0, s, x, dy, y, mean, R, C, cq, crows,
-                   pa, pb, (const unsigned char*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
-  hipLaunchKernelGGL(bn_merge<1>, dim3((C + kMergeCh - 1) / kMergeCh), dim3(kMergeCh * kMergeLanes), 0, s, pa, pb, R, C, chunks, crows, invstd, sum_dz,
-                     sum_dz_xhat, BnFinal{0, 0.f, 0.f, nullptr, nullptr}, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr, BnBound{});
+extern "C" int spml_bn_act_bwd_reduce_f32(const float* dy, const float* y, const float* x, int64_t R, int C,
+                                          const float* mean, const float* invstd, float* sum_dz, float* sum_dz_xhat,
+                                          void* ws, size_t ws_bytes, void* stream) {
+  if (!dy || !x || !mean || !invstd || !sum_dz || !sum_dz_xhat || R <= 0 || C <= 0) return SPML_ERR_INVALID_ARG;
+  if ((C & 3) || !al16(dy) || !al16(x) || (y && !al16(y)) || !al16(mean)) return SPML_ERR_UNSUPPORTED;
+  const BnGeom g = bn_geom(R, C);
+  if (!ws || ws_bytes < bn_ws_bytes(g, C)) return SPML_ERR_WORKSPACE;
+  const BnPlanes<float> p = bn_planes(static_cast<float*>(ws), g, C).first(2);
+  launch_partial<1>(g, (hipStream_t)stream, R, C, {x, dy, mean, y}, p);
+  launch_merge<1>(g, (hipStream_t)stream, R, C, p, {sum_dz, sum_dz_xhat, invstd});
   return launch_status();
 }
 
-extern "C" int spml_bn_act_bwd_apply_f32(const float* dy, const float* y, const float* x, int64_t R,
-                                         int C, const float* mean, const float* invstd,
-                                         const float* gamma, const float* sum_dz,
-                                         const float* sum_dz_xhat, double count,
-                                         const float* count_dev, float* dx,
-                                         float* d_residual, void* stream) {
+extern "C" int spml_bn_act_bwd_apply_f32(const float* dy, const float* y, const float* x, int64_t R, int C,
+                                         const float* mean, const float* invstd, const float* gamma,
+                                         const float* sum_dz, const float* sum_dz_xhat, double count,
+                                         const float* count_dev, float* dx, float* d_residual, void* stream) {
   if (!dy || R <= 0 || C <= 0 || (!dx && !d_residual) || (count <= 0 && !count_dev)) return SPML_ERR_INVALID_ARG;
   if (dx && (!x || !mean || !invstd || !gamma || !sum_dz || !sum_dz_xhat)) return SPML_ERR_INVALID_ARG;
-  if ((C & 3) || !bn_ok(dy) || (y && !bn_ok(y)) || (dx && !bn_ok(dx)) || (d_residual && !bn_ok(d_residual)))
+  if ((C & 3) || !al16(dy) || (y && !al16(y)) || (dx && !al16(dx)) || (d_residual && !al16(d_residual)))
     return SPML_ERR_UNSUPPORTED;
-  const int cq = bn_cq(C), arows = bn_apply_rows(R, C);
-  const dim3 grid(((C >> 2) + cq - 1) / cq, (unsigned)((R + arows - 1) / arows));
-  SPML_BN_BY_MASK(bn_bwd_apply, y ? 1 : 0, grid, dim3(256), 0, (hipStream_t)stream, dy, y, x, R, C, cq, arows, mean, invstd,
-                     gamma, sum_dz, sum_dz_xhat, count > 0 ? (float)(1.0 / count) : 0.f, count_dev, dx, d_residual,
-                     (const unsigned char*)nullptr, (uint2*)nullptr, (const float*)nullptr);
+  launch_bwd_apply(bn_geom(R, C), (hipStream_t)stream, R, C,
+                   {dy, y, nullptr, x, mean, invstd, gamma, sum_dz, sum_dz_xhat, count_dev,
+                    count > 0 ? (float)(1.0 / count) : 0.f, dx, d_residual});
   return launch_status();
 }
 
 // Single-rank batch norm: the whole forward / backward in one call each (three launches, no
 // framework ops in between).
-extern "C" int spml_bn_act_fwd_f32(const float* x, const float* residual, int64_t R, int C,
-                                   const float* gamma, const float* beta, float* running_mean,
-                                   float* running_var, float momentum, float eps, int relu, float* y,
-                                   float* mean, float* invstd, void* ws, size_t ws_bytes,
-                                   void* stream) {
+extern "C" int spml_bn_act_fwd_f32(const float* x, const float* residual, int64_t R, int C, const float* gamma,
+                                   const float* beta, float* running_mean, float* running_var, float momentum,
+                                   float eps, int relu, float* y, float* mean, float* invstd, void* ws,
+                                   size_t ws_bytes, void* stream) {
   if (!x || !gamma || !beta || !y || !mean || !invstd || R <= 0 || C <= 0) return SPML_ERR_INVALID_ARG;
-  if ((C & 3) || !bn_ok(x) || !bn_ok(y) || (residual && !bn_ok(residual)) || !bn_ok(mean) ||
-      !bn_ok(invstd) || !bn_ok(gamma) || !bn_ok(beta))
-    return SPML_ERR_UNSUPPORTED;
-  if (!ws || ws_bytes < spml_bn_workspace_bytes(R, C)) return SPML_ERR_WORKSPACE;
-  const int chunks = bn_chunks(R, C), cq = bn_cq(C), crows = bn_chunk_rows(R, C), arows = bn_apply_rows(R, C);
-  float* pa = static_cast<float*>(ws);
-  float* pb = pa + (size_t)chunks * C;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL((bn_partial<0, 0>), dim3(((C >> 2) + cq - 1) / cq, chunks), dim3(256), 0, s, x,
-                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, R, C, cq, crows, pa, pb, (const unsigned char*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
-  hipLaunchKernelGGL(bn_merge<0>, dim3((C + kMergeCh - 1) / kMergeCh), dim3(kMergeCh * kMergeLanes), 0, s, pa, pb, R, C, chunks, crows,
-                     (const float*)nullptr, mean, invstd, BnFinal{1, eps, momentum, running_mean, running_var}, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr, BnBound{});
-  const dim3 grid(((C >> 2) + cq - 1) / cq, (unsigned)((R + arows - 1) / arows));
-  SPML_BN_APPLY(residual != nullptr, grid, dim3(256), 0, s, x, residual, R, C, cq, arows, mean, invstd, gamma, beta, relu, y, (uint2*)nullptr, (const float*)nullptr, (unsigned char*)nullptr);
+  if ((C & 3) || !fwd_aligned(x, residual, mean, invstd, gamma, beta, y, nullptr)) return SPML_ERR_UNSUPPORTED;
+  const BnGeom g = bn_geom(R, C);
+  if (!ws || ws_bytes < bn_ws_bytes(g, C)) return SPML_ERR_WORKSPACE;
+  stats_pass(g, (hipStream_t)stream, x, R, C, bn_planes(static_cast<float*>(ws), g, C).first(2),
+             {mean, invstd, nullptr, nullptr, nullptr, {}, BnFinal{1, eps, momentum, running_mean, running_var}});
+  launch_apply(g, (hipStream_t)stream, R, C, {x, residual, mean, invstd, gamma, beta, relu, y});
   return launch_status();
 }
 
 extern "C" int spml_bn_act_bwd_f32(const float* dy, const float* y, const float* x, int64_t R, int C,
-                                   const float* mean, const float* invstd, const float* gamma,
-                                   float* d_gamma, float* d_beta, float* dx, float* d_residual,
-                                   void* ws, size_t ws_bytes, void* stream) {
-  if (!dy || !x || !mean || !invstd || !gamma || !d_gamma || !d_beta || R <= 0 || C <= 0)
-    return SPML_ERR_INVALID_ARG;
+                                   const float* mean, const float* invstd, const float* gamma, float* d_gamma,
+                                   float* d_beta, float* dx, float* d_residual, void* ws, size_t ws_bytes,
+                                   void* stream) {
+  if (!dy || !x || !mean || !invstd || !gamma || !d_gamma || !d_beta || R <= 0 || C <= 0) return SPML_ERR_INVALID_ARG;
   int rc = spml_bn_act_bwd_reduce_f32(dy, y, x, R, C, mean, invstd, d_beta, d_gamma, ws, ws_bytes, stream);
   if (rc != SPML_OK) return rc;
   if (!dx && !d_residual) return SPML_OK;
@@ -714,37 +801,22 @@ extern "C" int spml_bn_act_bwd_f32(const float* dy, const float* y, const float*
 extern "C" int spml_bn_stats_ext_f32(const float* x, int64_t R, int C, float* mean, float* m2, float* cmax,
                                      float* cmin, void* ws, size_t ws_bytes, void* stream) {
   if (!x || !mean || !m2 || !cmax || !cmin || R <= 0 || C <= 0) return SPML_ERR_INVALID_ARG;
-  if ((C & 3) || !bn_ok(x) || !bn_ok(mean) || !bn_ok(m2)) return SPML_ERR_UNSUPPORTED;
-  if (!ws || ws_bytes < spml_bn_workspace_bytes(R, C)) return SPML_ERR_WORKSPACE;
-  const int chunks = bn_chunks(R, C), cq = bn_cq(C), crows = bn_chunk_rows(R, C);
-  float* pa = static_cast<float*>(ws);
-  float* pb = pa + (size_t)chunks * C;
-  float* pc = pb + (size_t)chunks * C;
-  float* pd = pc + (size_t)chunks * C;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL((bn_partial<0, 0>), dim3(((C >> 2) + cq - 1) / cq, chunks), dim3(256), 0, s, x,
-                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, R, C, cq, crows, pa, pb,
-                     (const unsigned char*)nullptr, pc, pd, (float*)nullptr);
-  hipLaunchKernelGGL(bn_merge<0>, dim3((C + kMergeCh - 1) / kMergeCh), dim3(kMergeCh * kMergeLanes), 0, s, pa, pb, R, C, chunks, crows,
-                     (const float*)nullptr, mean, m2, BnFinal{0, 0.f, 0.f, nullptr, nullptr}, (const float*)pc,
-                     (const float*)pd, cmax, cmin, BnBound{});
+  if ((C & 3) || !al16(x) || !al16(mean) || !al16(m2)) return SPML_ERR_UNSUPPORTED;
+  const BnGeom g = bn_geom(R, C);
+  if (!ws || ws_bytes < bn_ws_bytes(g, C)) return SPML_ERR_WORKSPACE;
+  stats_pass(g, (hipStream_t)stream, x, R, C, bn_planes(static_cast<float*>(ws), g, C),
+             {mean, m2, nullptr, cmax, cmin});
   return launch_status();
 }
 
 // The same statistics pooled from the chunk statistics a convolution's epilogue left
-// (spml_conv_hl8_stats_f32): one launch, x is not read.
+// (spml_conv_hl8_stats_f32): one launch, x is not read.  Any C: only the chunk members of the geometry are used.
 extern "C" int spml_bn_stats_ext_chunks_f32(const float* chunk_stats, int chunks, int chunk_rows, int64_t R, int C,
                                             float* mean, float* m2, float* cmax, float* cmin, void* stream) {
-  if (!chunk_stats || !mean || !m2 || !cmax || !cmin || R <= 0 || C <= 0 || chunks <= 0 || chunk_rows <= 0 ||
-      (int64_t)chunks * chunk_rows < R || (int64_t)(chunks - 1) * chunk_rows >= R)
+  if (!chunk_stats || !mean || !m2 || !cmax || !cmin || R <= 0 || C <= 0 || !chunks_cover(chunks, chunk_rows, R))
     return SPML_ERR_INVALID_ARG;
-  const float* pa = chunk_stats;
-  const float* pb = pa + (size_t)chunks * C;
-  const float* pc = pb + (size_t)chunks * C;
-  const float* pd = pc + (size_t)chunks * C;
-  hipLaunchKernelGGL(bn_merge<0>, dim3((C + kMergeCh - 1) / kMergeCh), dim3(kMergeCh * kMergeLanes), 0,
-                     (hipStream_t)stream, pa, pb, R, C, chunks, chunk_rows, (const float*)nullptr, mean, m2,
-                     BnFinal{0, 0.f, 0.f, nullptr, nullptr}, pc, pd, cmax, cmin, BnBound{});
+  const BnGeom g = with_chunks(BnGeom{}, chunks, chunk_rows);
+  launch_merge<0>(g, (hipStream_t)stream, R, C, bn_planes(chunk_stats, g, C), {mean, m2, nullptr, cmax, cmin});
   return launch_status();
 }
 
@@ -764,66 +836,50 @@ extern "C" int spml_bn_act_apply_hl8_f32(const float* x, const float* residual, 
                                          unsigned char* relu_mask, void* stream) {
   if (!x || !mean || !invstd || !gamma || !beta || (!y && !y_hl8) || R <= 0 || C <= 0) return SPML_ERR_INVALID_ARG;
   if ((y_hl8 || y_bound) && (!cmax || !cmin || !y_bound || (residual && !residual_bound))) return SPML_ERR_INVALID_ARG;
-  if ((C & 7) || !bn_ok(x) || (y && !bn_ok(y)) || (y_hl8 && !bn_ok(y_hl8)) || (residual && !bn_ok(residual)) ||
-      !bn_ok(mean) || !bn_ok(invstd) || !bn_ok(gamma) || !bn_ok(beta))
-    return SPML_ERR_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
+  if ((C & 7) || !fwd_aligned(x, residual, mean, invstd, gamma, beta, y, y_hl8)) return SPML_ERR_UNSUPPORTED;
   if (y_bound)
-    hipLaunchKernelGGL(bn_bound_fwd, dim3(1), dim3(256), 0, s, C, cmax, cmin, mean, invstd, gamma, beta,
-                       residual ? residual_bound : (const float*)nullptr, y_bound);
-  const int cq = bn_cq(C), arows = bn_apply_rows(R, C);
-  const dim3 grid(((C >> 2) + cq - 1) / cq, (unsigned)((R + arows - 1) / arows));
-  SPML_BN_APPLY(residual != nullptr, grid, dim3(256), 0, s, x, residual, R, C, cq, arows, mean, invstd, gamma, beta, relu, y,
-                static_cast<uint2*>(y_hl8), (const float*)y_bound, relu_mask);
+    hipLaunchKernelGGL(bn_bound_fwd, dim3(1), dim3(256), 0, (hipStream_t)stream, C, cmax, cmin, mean, invstd, gamma,
+                       beta, residual ? residual_bound : (const float*)nullptr, y_bound);
+  launch_apply(bn_geom(R, C), (hipStream_t)stream, R, C,
+               {x, residual, mean, invstd, gamma, beta, relu, y, y_bound, static_cast<uint2*>(y_hl8), relu_mask});
   return launch_status();
 }
 
 extern "C" int spml_bn_act_bwd_reduce_ext_f32(const float* dy, const float* y, const unsigned char* relu_mask,
-                                              const float* x,
-                                              int64_t R, int C, const float* mean, const float* invstd,
-                                              float* sum_dz, float* sum_dz_xhat, float* max_dz, void* ws,
-                                              size_t ws_bytes, void* stream) {
+                                              const float* x, int64_t R, int C, const float* mean,
+                                              const float* invstd, float* sum_dz, float* sum_dz_xhat, float* max_dz,
+                                              void* ws, size_t ws_bytes, void* stream) {
   if (!dy || !x || !mean || !invstd || !sum_dz || !sum_dz_xhat || !max_dz || R <= 0 || C <= 0)
     return SPML_ERR_INVALID_ARG;
-  if ((C & 7) || !bn_ok(dy) || !bn_ok(x) || (y && !bn_ok(y)) || !bn_ok(mean)) return SPML_ERR_UNSUPPORTED;
-  if (!ws || ws_bytes < spml_bn_workspace_bytes(R, C)) return SPML_ERR_WORKSPACE;
-  const int chunks = bn_chunks(R, C), cq = bn_cq(C), crows = bn_chunk_rows(R, C);
-  float* pa = static_cast<float*>(ws);
-  float* pb = pa + (size_t)chunks * C;
-  float* pc = pb + (size_t)chunks * C;
-  hipStream_t s = (hipStream_t)stream;
-  SPML_BN_PARTIAL1(y ? 1 : (relu_mask ? 2 : 0), dim3(((C >> 2) + cq - 1) / cq, chunks), dim3(256), 0, s, x, dy, y, mean,
-                   R, C, cq, crows, pa, pb, relu_mask, pc, (float*)nullptr, (float*)nullptr);
-  hipLaunchKernelGGL(bn_merge<1>, dim3((C + kMergeCh - 1) / kMergeCh), dim3(kMergeCh * kMergeLanes), 0, s, pa, pb, R, C, chunks, crows,
-                     invstd, sum_dz, sum_dz_xhat, BnFinal{0, 0.f, 0.f, nullptr, nullptr}, (const float*)pc,
-                     (const float*)nullptr, max_dz, (float*)nullptr, BnBound{});
+  if ((C & 7) || !al16(dy) || !al16(x) || (y && !al16(y)) || !al16(mean)) return SPML_ERR_UNSUPPORTED;
+  const BnGeom g = bn_geom(R, C);
+  if (!ws || ws_bytes < bn_ws_bytes(g, C)) return SPML_ERR_WORKSPACE;
+  const BnPlanes<float> p = bn_planes(static_cast<float*>(ws), g, C).first(3);
+  launch_partial<1>(g, (hipStream_t)stream, R, C, {x, dy, mean, y, relu_mask}, p);
+  launch_merge<1>(g, (hipStream_t)stream, R, C, p, {sum_dz, sum_dz_xhat, invstd, max_dz});
   return launch_status();
 }
 
 extern "C" int spml_bn_act_bwd_apply_hl8_f32(const float* dy, const float* y, const unsigned char* relu_mask,
-                                             const float* x,
-                                             int64_t R, int C, const float* mean, const float* invstd,
-                                             const float* gamma, const float* sum_dz, const float* sum_dz_xhat,
-                                             const float* max_dz, const float* cmax, const float* cmin,
-                                             double count, const float* count_dev, float* dx, void* dx_hl8,
-                                             float* dx_bound, float* d_residual, void* stream) {
+                                             const float* x, int64_t R, int C, const float* mean,
+                                             const float* invstd, const float* gamma, const float* sum_dz,
+                                             const float* sum_dz_xhat, const float* max_dz, const float* cmax,
+                                             const float* cmin, double count, const float* count_dev, float* dx,
+                                             void* dx_hl8, float* dx_bound, float* d_residual, void* stream) {
   if (!dy || R <= 0 || C <= 0 || (!dx && !dx_hl8 && !d_residual) || (count <= 0 && !count_dev))
     return SPML_ERR_INVALID_ARG;
   const float inv_count = count > 0 ? (float)(1.0 / count) : 0.f;
   if ((dx || dx_hl8) && (!x || !mean || !invstd || !gamma || !sum_dz || !sum_dz_xhat)) return SPML_ERR_INVALID_ARG;
   if (dx_hl8 && (!max_dz || !cmax || !cmin || !dx_bound)) return SPML_ERR_INVALID_ARG;
-  if ((C & 7) || !bn_ok(dy) || (y && !bn_ok(y)) || (dx && !bn_ok(dx)) ||
-      (dx_hl8 && !bn_ok(dx_hl8)) || (d_residual && !bn_ok(d_residual)))
+  if ((C & 7) || !al16(dy) || (y && !al16(y)) || (dx && !al16(dx)) || (dx_hl8 && !al16(dx_hl8)) ||
+      (d_residual && !al16(d_residual)))
     return SPML_ERR_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
   if (dx_hl8)
-    hipLaunchKernelGGL(bn_bound_bwd, dim3(1), dim3(256), 0, s, C, max_dz, cmax, cmin, mean, invstd, gamma, sum_dz,
-                       sum_dz_xhat, inv_count, count_dev, dx_bound);
-  const int cq = bn_cq(C), arows = bn_apply_rows(R, C);
-  const dim3 grid(((C >> 2) + cq - 1) / cq, (unsigned)((R + arows - 1) / arows));
-  SPML_BN_BY_MASK(bn_bwd_apply, y ? 1 : (relu_mask ? 2 : 0), grid, dim3(256), 0, s, dy, y, x, R, C, cq, arows, mean, invstd, gamma, sum_dz,
-                     sum_dz_xhat, inv_count, count_dev, dx, d_residual, relu_mask,
-                  static_cast<uint2*>(dx_hl8), (const float*)dx_bound);
+    hipLaunchKernelGGL(bn_bound_bwd, dim3(1), dim3(256), 0, (hipStream_t)stream, C, max_dz, cmax, cmin, mean, invstd,
+                       gamma, sum_dz, sum_dz_xhat, inv_count, count_dev, dx_bound);
+  launch_bwd_apply(bn_geom(R, C), (hipStream_t)stream, R, C,
+                   {dy, y, relu_mask, x, mean, invstd, gamma, sum_dz, sum_dz_xhat, count_dev, inv_count, dx, d_residual,
+                    static_cast<uint2*>(dx_hl8), dx_bound});
   return launch_status();
 }
 
@@ -837,26 +893,14 @@ extern "C" int spml_bn_fwd_hl8_f32(const float* x, const float* residual, const 
   if (!x || !gamma || !beta || (!y && !y_hl8) || !y_bound || !mean || !invstd || !cmax || !cmin || R <= 0 || C <= 0 ||
       (residual && !residual_bound))
     return SPML_ERR_INVALID_ARG;
-  if ((C & 7) || !bn_ok(x) || (y && !bn_ok(y)) || (y_hl8 && !bn_ok(y_hl8)) || (residual && !bn_ok(residual)) ||
-      !bn_ok(mean) || !bn_ok(invstd) || !bn_ok(gamma) || !bn_ok(beta))
-    return SPML_ERR_UNSUPPORTED;
-  if (!ws || ws_bytes < spml_bn_workspace_bytes(R, C)) return SPML_ERR_WORKSPACE;
-  const int chunks = bn_chunks(R, C), cq = bn_cq(C), crows = bn_chunk_rows(R, C), arows = bn_apply_rows(R, C);
-  float* pa = static_cast<float*>(ws);
-  float* pb = pa + (size_t)chunks * C;
-  float* pc = pb + (size_t)chunks * C;
-  float* pd = pc + (size_t)chunks * C;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL((bn_partial<0, 0>), dim3(((C >> 2) + cq - 1) / cq, chunks), dim3(256), 0, s, x,
-                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, R, C, cq, crows, pa, pb,
-                     (const unsigned char*)nullptr, pc, pd, y_bound);
-  hipLaunchKernelGGL(bn_merge<0>, dim3((C + kMergeCh - 1) / kMergeCh), dim3(kMergeCh * kMergeLanes), 0, s, pa, pb, R,
-                     C, chunks, crows, (const float*)nullptr, mean, invstd,
-                     BnFinal{1, eps, momentum, running_mean, running_var}, (const float*)pc, (const float*)pd, cmax,
-                     cmin, BnBound{y_bound, residual ? residual_bound : nullptr, gamma, beta, nullptr, nullptr, nullptr, 0.f});
-  const dim3 grid(((C >> 2) + cq - 1) / cq, (unsigned)((R + arows - 1) / arows));
-  SPML_BN_APPLY(residual != nullptr, grid, dim3(256), 0, s, x, residual, R, C, cq, arows, mean, invstd, gamma, beta,
-                relu, y, static_cast<uint2*>(y_hl8), (const float*)y_bound, relu_mask);
+  if ((C & 7) || !fwd_aligned(x, residual, mean, invstd, gamma, beta, y, y_hl8)) return SPML_ERR_UNSUPPORTED;
+  const BnGeom g = bn_geom(R, C);
+  if (!ws || ws_bytes < bn_ws_bytes(g, C)) return SPML_ERR_WORKSPACE;
+  const BnPlanes<float> p = bn_planes(static_cast<float*>(ws), g, C);
+  launch_partial<0>(g, (hipStream_t)stream, R, C, {x, nullptr, nullptr, nullptr, nullptr, y_bound}, p);
+  merge_final_apply(g, (hipStream_t)stream, R, C, p, BnFinal{1, eps, momentum, running_mean, running_var},
+                    residual_bound, mean, invstd, cmax, cmin,
+                    {x, residual, mean, invstd, gamma, beta, relu, y, y_bound, static_cast<uint2*>(y_hl8), relu_mask});
   return launch_status();
 }
 
@@ -870,25 +914,13 @@ extern "C" int spml_bn_fwd_hl8_chunks_f32(const float* x, const float* chunk_sta
                                           void* y_hl8, float* y_bound, unsigned char* relu_mask, float* mean,
                                           float* invstd, float* cmax, float* cmin, void* stream) {
   if (!x || !chunk_stats || !gamma || !beta || (!y && !y_hl8) || !y_bound || !mean || !invstd || !cmax || !cmin ||
-      R <= 0 || C <= 0 || chunks <= 0 || chunk_rows <= 0 || (int64_t)chunks * chunk_rows < R ||
-      (int64_t)(chunks - 1) * chunk_rows >= R || (residual && !residual_bound))
+      R <= 0 || C <= 0 || !chunks_cover(chunks, chunk_rows, R) || (residual && !residual_bound))
     return SPML_ERR_INVALID_ARG;
-  if ((C & 7) || !bn_ok(x) || (y && !bn_ok(y)) || (y_hl8 && !bn_ok(y_hl8)) || (residual && !bn_ok(residual)) ||
-      !bn_ok(mean) || !bn_ok(invstd) || !bn_ok(gamma) || !bn_ok(beta))
-    return SPML_ERR_UNSUPPORTED;
-  const int cq = bn_cq(C), arows = bn_apply_rows(R, C);
-  const float* pa = chunk_stats;
-  const float* pb = pa + (size_t)chunks * C;
-  const float* pc = pb + (size_t)chunks * C;
-  const float* pd = pc + (size_t)chunks * C;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(bn_merge<0>, dim3((C + kMergeCh - 1) / kMergeCh), dim3(kMergeCh * kMergeLanes), 0, s, pa, pb, R,
-                     C, chunks, chunk_rows, (const float*)nullptr, mean, invstd,
-                     BnFinal{1, eps, momentum, running_mean, running_var}, pc, pd, cmax, cmin,
-                     BnBound{y_bound, residual ? residual_bound : nullptr, gamma, beta, nullptr, nullptr, nullptr, 0.f});
-  const dim3 grid(((C >> 2) + cq - 1) / cq, (unsigned)((R + arows - 1) / arows));
-  SPML_BN_APPLY(residual != nullptr, grid, dim3(256), 0, s, x, residual, R, C, cq, arows, mean, invstd, gamma, beta,
-                relu, y, static_cast<uint2*>(y_hl8), (const float*)y_bound, relu_mask);
+  if ((C & 7) || !fwd_aligned(x, residual, mean, invstd, gamma, beta, y, y_hl8)) return SPML_ERR_UNSUPPORTED;
+  const BnGeom g = with_chunks(bn_geom(R, C), chunks, chunk_rows);
+  merge_final_apply(g, (hipStream_t)stream, R, C, bn_planes(chunk_stats, g, C),
+                    BnFinal{1, eps, momentum, running_mean, running_var}, residual_bound, mean, invstd, cmax, cmin,
+                    {x, residual, mean, invstd, gamma, beta, relu, y, y_bound, static_cast<uint2*>(y_hl8), relu_mask});
   return launch_status();
 }
 
@@ -900,28 +932,18 @@ extern "C" int spml_bn_bwd_hl8_f32(const float* dy, const float* y, const unsign
   if (!dy || !x || !mean || !invstd || !gamma || !cmax || !cmin || !d_gamma || !d_beta || R <= 0 || C <= 0 ||
       (dx_hl8 && !dx_bound))
     return SPML_ERR_INVALID_ARG;
-  if ((C & 7) || !bn_ok(dy) || !bn_ok(x) || (y && !bn_ok(y)) || (dx && !bn_ok(dx)) || (dx_hl8 && !bn_ok(dx_hl8)) ||
-      (d_residual && !bn_ok(d_residual)) || !bn_ok(mean))
+  if ((C & 7) || !al16(dy) || !al16(x) || (y && !al16(y)) || (dx && !al16(dx)) || (dx_hl8 && !al16(dx_hl8)) ||
+      (d_residual && !al16(d_residual)) || !al16(mean))
     return SPML_ERR_UNSUPPORTED;
-  if (!ws || ws_bytes < spml_bn_workspace_bytes(R, C)) return SPML_ERR_WORKSPACE;
-  const int chunks = bn_chunks(R, C), cq = bn_cq(C), crows = bn_chunk_rows(R, C), arows = bn_apply_rows(R, C);
-  float* pa = static_cast<float*>(ws);
-  float* pb = pa + (size_t)chunks * C;
-  float* pc = pb + (size_t)chunks * C;
-  float* max_dz = pc + (size_t)chunks * C;              // the fourth quarter of the workspace is free here
-  hipStream_t s = (hipStream_t)stream;
-  const int mask = y ? 1 : (relu_mask ? 2 : 0);
-  SPML_BN_PARTIAL1(mask, dim3(((C >> 2) + cq - 1) / cq, chunks), dim3(256), 0, s, x, dy, y, mean, R, C, cq, crows, pa, pb,
-                   relu_mask, pc, (float*)nullptr, dx_hl8 ? dx_bound : (float*)nullptr);
-  hipLaunchKernelGGL(bn_merge<1>, dim3((C + kMergeCh - 1) / kMergeCh), dim3(kMergeCh * kMergeLanes), 0, s, pa, pb, R,
-                     C, chunks, crows, invstd, d_beta, d_gamma, BnFinal{0, 0.f, 0.f, nullptr, nullptr},
-                     (const float*)pc, (const float*)nullptr, max_dz, (float*)nullptr,
-                     BnBound{dx_hl8 ? dx_bound : nullptr, nullptr, gamma, nullptr, mean, cmax, cmin, (float)(1.0 / (double)R)});
-  if (!dx && !dx_hl8 && !d_residual) return launch_status();
-  const dim3 grid(((C >> 2) + cq - 1) / cq, (unsigned)((R + arows - 1) / arows));
-  SPML_BN_BY_MASK(bn_bwd_apply, mask, grid, dim3(256), 0, s, dy, y, x, R, C, cq, arows, mean, invstd, gamma,
-                  (const float*)d_beta, (const float*)d_gamma, (float)(1.0 / (double)R), (const float*)nullptr, dx,
-                  d_residual, relu_mask, static_cast<uint2*>(dx_hl8), (const float*)dx_bound);
+  const BnGeom g = bn_geom(R, C);
+  if (!ws || ws_bytes < bn_ws_bytes(g, C)) return SPML_ERR_WORKSPACE;
+  const BnPlanes<float> ws4 = bn_planes(static_cast<float*>(ws), g, C);
+  float* max_dz = ws4.d;                       // the fourth quarter of the workspace is free here
+  launch_partial<1>(g, (hipStream_t)stream, R, C, {x, dy, mean, y, relu_mask, dx_hl8 ? dx_bound : nullptr},
+                    ws4.first(3));
+  merge_bound_bwd_apply(g, (hipStream_t)stream, R, C, ws4.first(3), d_beta, d_gamma, max_dz, cmax, cmin,
+                        {dy, y, relu_mask, x, mean, invstd, gamma, d_beta, d_gamma, nullptr, (float)(1.0 / (double)R),
+                         dx, d_residual, static_cast<uint2*>(dx_hl8), dx_bound});
   return launch_status();
 }
 
@@ -935,27 +957,15 @@ extern "C" int spml_bn_bwd_hl8_chunks_f32(const float* dy, const unsigned char* 
                                           float* max_dz, float* dx, void* dx_hl8, float* dx_bound, float* d_residual,
                                           void* stream) {
   if (!dy || !x || !chunk_stats || !mean || !invstd || !gamma || !cmax || !cmin || !d_gamma || !d_beta || !max_dz ||
-      R <= 0 || C <= 0 || chunks <= 0 || chunk_rows <= 0 || (int64_t)chunks * chunk_rows < R ||
-      (int64_t)(chunks - 1) * chunk_rows >= R || (dx_hl8 && !dx_bound))
+      R <= 0 || C <= 0 || !chunks_cover(chunks, chunk_rows, R) || (dx_hl8 && !dx_bound))
     return SPML_ERR_INVALID_ARG;
-  if ((C & 7) || !bn_ok(dy) || !bn_ok(x) || (dx && !bn_ok(dx)) || (dx_hl8 && !bn_ok(dx_hl8)) ||
-      (d_residual && !bn_ok(d_residual)) || !bn_ok(mean))
+  if ((C & 7) || !al16(dy) || !al16(x) || (dx && !al16(dx)) || (dx_hl8 && !al16(dx_hl8)) ||
+      (d_residual && !al16(d_residual)) || !al16(mean))
     return SPML_ERR_UNSUPPORTED;
-  const int cq = bn_cq(C), arows = bn_apply_rows(R, C);
-  const float* pa = chunk_stats;
-  const float* pb = pa + (size_t)chunks * C;
-  const float* pc = pb + (size_t)chunks * C;
-  hipStream_t s = (hipStream_t)stream;
-  const int mask = relu_mask ? 2 : 0;
-  hipLaunchKernelGGL(bn_merge<1>, dim3((C + kMergeCh - 1) / kMergeCh), dim3(kMergeCh * kMergeLanes), 0, s, pa, pb, R,
-                     C, chunks, chunk_rows, invstd, d_beta, d_gamma, BnFinal{0, 0.f, 0.f, nullptr, nullptr}, pc,
-                     (const float*)nullptr, max_dz, (float*)nullptr,
-                     BnBound{dx_hl8 ? dx_bound : nullptr, nullptr, gamma, nullptr, mean, cmax, cmin, (float)(1.0 / (double)R)});
-  if (!dx && !dx_hl8 && !d_residual) return launch_status();
-  const dim3 grid(((C >> 2) + cq - 1) / cq, (unsigned)((R + arows - 1) / arows));
-  SPML_BN_BY_MASK(bn_bwd_apply, mask, grid, dim3(256), 0, s, dy, (const float*)nullptr, x, R, C, cq, arows, mean, invstd,
-                  gamma, (const float*)d_beta, (const float*)d_gamma, (float)(1.0 / (double)R), (const float*)nullptr, dx,
-                  d_residual, relu_mask, static_cast<uint2*>(dx_hl8), (const float*)dx_bound);
+  const BnGeom g = with_chunks(bn_geom(R, C), chunks, chunk_rows);
+  merge_bound_bwd_apply(g, (hipStream_t)stream, R, C, bn_planes(chunk_stats, g, C).first(3), d_beta, d_gamma, max_dz,
+                        cmax, cmin, {dy, nullptr, relu_mask, x, mean, invstd, gamma, d_beta, d_gamma, nullptr,
+                                     (float)(1.0 / (double)R), dx, d_residual, static_cast<uint2*>(dx_hl8), dx_bound});
   return launch_status();
 }
 
@@ -964,16 +974,12 @@ extern "C" int spml_bn_bwd_hl8_chunks_f32(const float* dy, const unsigned char* 
 extern "C" int spml_bn_act_bwd_reduce_ext_chunks_f32(const float* chunk_stats, int chunks, int chunk_rows, int64_t R,
                                                      int C, const float* invstd, float* sum_dz, float* sum_dz_xhat,
                                                      float* max_dz, void* stream) {
-  if (!chunk_stats || !invstd || !sum_dz || !sum_dz_xhat || !max_dz || R <= 0 || C <= 0 || chunks <= 0 ||
-      chunk_rows <= 0 || (int64_t)chunks * chunk_rows < R || (int64_t)(chunks - 1) * chunk_rows >= R)
+  if (!chunk_stats || !invstd || !sum_dz || !sum_dz_xhat || !max_dz || R <= 0 || C <= 0 ||
+      !chunks_cover(chunks, chunk_rows, R))
     return SPML_ERR_INVALID_ARG;
-  const float* pa = chunk_stats;
-  const float* pb = pa + (size_t)chunks * C;
-  const float* pc = pb + (size_t)chunks * C;
-  hipLaunchKernelGGL(bn_merge<1>, dim3((C + kMergeCh - 1) / kMergeCh), dim3(kMergeCh * kMergeLanes), 0,
-                     (hipStream_t)stream, pa, pb, R, C, chunks, chunk_rows, invstd, sum_dz, sum_dz_xhat,
-                     BnFinal{0, 0.f, 0.f, nullptr, nullptr}, pc, (const float*)nullptr, max_dz, (float*)nullptr,
-                     BnBound{});
+  const BnGeom g = with_chunks(BnGeom{}, chunks, chunk_rows);
+  launch_merge<1>(g, (hipStream_t)stream, R, C, bn_planes(chunk_stats, g, C).first(3),
+                  {sum_dz, sum_dz_xhat, invstd, max_dz});
   return launch_status();
 }
 

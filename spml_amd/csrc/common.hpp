@@ -123,6 +123,8 @@ inline int launch_status() {
 }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// 16-byte alignment: what the float4 / 16-byte-unit accesses of the kernels ask of a pointer
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // Launch of a kernel whose dynamic LDS may exceed the 64-KB default: the attribute, then the launch.
 template <typename... Params, typename... Args>

@@ -986,8 +986,6 @@ inline bool use_two_row_groups(int64_t, int, int) {
   return e && e[0] == '2';
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // ---------------------------------------------------------------------------------------
 // routes: which conv_gemm / conv_wgrad instantiation a call launches.  Decided once per call (every environment
 // switch is read then); the entry points, the statistics layout and the path names read the same record.

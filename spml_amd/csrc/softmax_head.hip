@@ -17,8 +17,6 @@
 namespace spml {
 namespace {
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // ---------------------------------------------------------------------------------------
 // x [n][C][hw] fp32 -> hl8 [n*hw][C] of x / |x|_2 over the channels.  A unit row is bounded by 1, so the scale of the
 // split is fixed: S = 2^13, what conv.hip's pow2_scale gives for *bound == 1.0f (the caller hands that bound over).

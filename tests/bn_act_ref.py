@@ -7,7 +7,7 @@ import math
 import torch
 
 # (R, C) -> what the host functions of bn_act.hip make of it; tests/test_bn_act_ref.py recomputes every column from a
-# restatement of bn_cq / bn_chunk_rows / bn_apply_rows, tests/test_bn_act_gpu.py pins `chunks` through the library.
+# restatement of bn_geom (the BnGeom record), tests/test_bn_act_gpu.py pins `chunks` through the library.
 #   R, C, cq, column blocks, row lanes, chunk_rows, chunks, rows of the last chunk, apply_rows, rows of the last tile
 GEOMETRY = (
     (2, 8, 4, 1, 64, 128, 1, 2, 64, 2),             # two of four quads live, R below the row lanes
@@ -28,7 +28,7 @@ OUTLIER_CHANNEL = 37                                # gamma = +1.5 there (make_i
 
 
 def host_geometry(r, c):
-  """bn_cq / bn_chunk_rows / bn_chunks / bn_apply_rows of bn_act.hip restated -> one row of GEOMETRY."""
+  """bn_geom of bn_act.hip (cq, col_blocks, chunk_rows, chunks, apply_rows) restated -> one row of GEOMETRY."""
   q = c >> 2
   cq = 64 if q >= 64 else 32 if q >= 32 else 16 if q >= 16 else 8 if q >= 8 else 4
   col_blocks = (q + cq - 1) // cq

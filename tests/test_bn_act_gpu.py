@@ -564,6 +564,38 @@ def test_hl8_backward_entries_against_float64(r, c, outlier):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize('r,c', FULL_DESTINATIONS)
+def test_backward_calls_without_a_destination(r, c):
+  """The two early returns of the host side: spml_bn_act_bwd_f32 and spml_bn_bwd_hl8_f32 asked for no dx, no hl8 copy
+  and no d_residual stop after the reduction (no apply launch; the hl8 form without the bound reset and publish_bound)
+  and still deliver d_gamma / d_beta, bit-identical to the sums of the reduce entries.  The hl8 wrapper always asks
+  for the hl8 dx, so that call goes to the C ABI."""
+  from ctypes import c_void_p
+  t, case = _case(r, c), _name(r, c)
+  x, dy, gamma, beta = t['x'], t['dy'], t['gamma'], t['beta']
+  f, lib = _ref_fwd(r, c, False, True, True), _lib(r, c, False, True, True)
+  y, _, _, mbytes, saved = _ffi.bn_fwd_hl8(x, r, c, t['res'], t['resb'], gamma, beta, None, None, MOM, EPS, True, True,
+                                           False, True)
+  mean, invstd, cmax, cmin = saved
+  bw = ref.backward(dy, x, f['mean'], f['invstd'], gamma, y > 0)
+  s0, s1 = _ffi.bn_act_bwd_reduce(dy, y, x, mean, invstd)
+  none = _ffi.bn_act_bwd(dy, y, x, mean, invstd, gamma, False, False)          # (dx, dres, d_gamma, d_beta)
+  assert none[0] is None and none[1] is None and _same(none[2:], (s1, s0))
+  _hold('bn_act_bwd (no destination)', case, 'd_beta', _sum_rel(none[3], bw['s0'], bw['abs0']), lib['s0'])
+  _hold('bn_act_bwd (no destination)', case, 'd_gamma', _sum_rel(none[2], bw['s1'], bw['abs1']), lib['s1'])
+  st = _ffi.bn_act_bwd_reduce_ext(dy, None, mbytes, x, r, c, mean, invstd)
+  dgb = torch.full((2, c), float('nan'), device=DEV)
+  ws = _ffi._bn_workspace(r, c, dy.device)
+  dp, null = _ffi._dp, c_void_p(0)
+  _ffi.check(_ffi.lib().spml_bn_bwd_hl8_f32(
+      dp(dy), null, dp(mbytes), dp(x), r, c, dp(mean), dp(invstd), dp(gamma), dp(cmax), dp(cmin), dp(dgb[0]),
+      dp(dgb[1]), null, null, null, null, _ffi.ptr(ws), ws.numel(), _ffi.stream_ptr()), 'spml_bn_bwd_hl8_f32')
+  assert _same((dgb[1], dgb[0]), (st[0], st[1]))
+  _hold('bn_bwd_hl8 (no destination)', case, 'd_beta', _sum_rel(dgb[1], bw['s0'], bw['abs0']), lib['s0'])
+  _hold('bn_bwd_hl8 (no destination)', case, 'd_gamma', _sum_rel(dgb[0], bw['s1'], bw['abs1']), lib['s1'])
+
+
+@pytest.mark.gpu
 def test_finalize_ranks_pools_three_unequal_ranks():
   """bn_finalize_ranks with world = 3 and 50 / 31 / 64 rows of one tensor (the statistics of bn_stats_ext per rank),
   momentum and running statistics, against the float64 statistics of the whole tensor; then one rank's backward apply
