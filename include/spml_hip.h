@@ -51,7 +51,8 @@ const char* spml_status_string(int status);
  *    keep the version: spml_view_votes_*, spml_segsort_nll_batched_*, spml_segment_majority_*, spml_tag_normalize_*,
  *    spml_dense_crf_*, spml_segment_tag_cam_*, spml_conv_hl8_path_name, spml_conv_wgrad_path_name / _splits,
  *    spml_augment_*, spml_image_views_*, spml_label_export_*, spml_score_*, spml_pca_*, spml_summary_panels_u8,
- *    spml_train_summary_workspace_bytes, spml_crf_guide_*, spml_export_scores_bytes, spml_label_export_scored_u8). */
+ *    spml_train_summary_workspace_bytes, spml_crf_guide_*, spml_export_scores_bytes, spml_label_export_scored_u8,
+ *    spml_segsort_nll_path_name). */
 #define SPML_ABI_VERSION 8
 int spml_abi_version(void);
 
@@ -373,8 +374,11 @@ int spml_segment_sum_normalize_bwd_f32(const float* d_protos,
  *   for the backward.
  * backward: given d_nll [P] (upstream gradient per pixel) produces
  *   d_emb [P,D] and d_protos [M,D] (d_protos is ADDED into; zero it first).
- *   Only prototypes [0, m_grad) receive a gradient (m_grad < 0: all M) -- rows of
- *   a detached memory bank appended after the live prototypes are skipped.
+ *   Prototypes [0, m_grad) receive their gradient (m_grad < 0 or > M: all M) -- rows of
+ *   a detached memory bank appended after the live prototypes are skipped.  The
+ *   kernels work on whole tiles of 32 prototypes: a row in [m_grad, ceil32(m_grad))
+ *   receives either nothing or its full gradient (today: the full gradient), rows
+ *   from ceil32(m_grad) on are never touched.
  * ------------------------------------------------------------------------ */
 #define SPML_NLL_LABEL 0
 #define SPML_NLL_TAGSET 1
@@ -402,6 +406,25 @@ int spml_segsort_nll_bwd_f32(const float* emb, const int64_t* own,
                              const float* stats, const float* d_nll,
                              float* d_emb, float* d_protos, int64_t m_grad,
                              void* ws, size_t ws_bytes, void* stream);
+
+/* What spml_segsort_nll_fwd_f32 (backward == 0) or spml_segsort_nll_bwd_f32 launches for these arguments, written
+ * into buf (len bytes, NUL-terminated; SPML_ERR_INVALID_ARG when it does not fit -- 160 bytes always do).  A host
+ * function: no GPU call; it reads the environment switches (SPML_NLL_DE3, SPML_NLL_DP3, SPML_NLL_TCACHE_MB) and the
+ * deterministic mode as a call would, through the predicates the call launches by.  For tests and reports.
+ *   forward   "fwd2<KS,MTB,label|tag> chunks=C"     D <= 80 with SPML_NLL_CODE32 (C chunks of 3072 prototypes);
+ *             "fwd2_plain<...> chunks=C"             the same with SPML_NLL_PLAIN (sums the negatives directly)
+ *             "fwd<KS,1,label|tag,c32|c64>"          everything else (KS: 2, 3, 4, 5, 9, 17, 33 k-steps of 16 channels)
+ *   backward  "de3<..> rows=R + dp3<..> mt=T"       48 < D <= 64 with CODE32 (the pipelined kernels; R grid rows that
+ *                                                    share the prototype chunks, T prototype tiles with a gradient)
+ *             "de3<..> rows=R + dp<4,2,..> chunks=C mt=T"     the same with SPML_NLL_DP3=0
+ *             "de2<KS,DT,..> rows=R + dp<KS,DT,..> chunks=C mt=T"   D <= 48 with CODE32, or SPML_NLL_DE3=0
+ *             "de<KS,DT,..> + dp<KS,DT,..> chunks=C mt=T"     64-bit codes, and 64 < D <= 272
+ *             "wide<..> strips=S launches=1+L mt=T"           272 < D <= 528: per strip of pixel tiles one launch pair
+ *                                                    that keeps the weight tiles and L that read them back
+ *             "... + no dp" where m_grad = 0; " fix64" appended in deterministic mode
+ *   "nothing" for P = 0 (the calls return before their first launch); "unsupported" for what the calls refuse. */
+int spml_segsort_nll_path_name(int64_t P, int64_t M, int D, int mode, int backward,
+                               int64_t m_grad, char* buf, size_t len);
 
 /* A9/A10 over N independent problems in one call
  * replaces: the per-image loop of the image-similarity term, spml/models/predictions/segsort.py:221-241 (one

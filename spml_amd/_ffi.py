@@ -62,6 +62,7 @@ _SIGNATURES = {
                                          _P, _P, _P, c_size_t, _P]),
     'spml_segsort_nll_bwd_f32': (c_int, [_P, _P, _P, c_int64, _P, _P, c_int64, c_int, c_float, c_int,
                                          _P, _P, _P, _P, c_int64, _P, c_size_t, _P]),
+    'spml_segsort_nll_path_name': (c_int, [c_int64, c_int64, c_int, c_int, c_int, c_int64, _P, c_size_t]),
     'spml_segsort_nll_batched_supported': (c_int, [c_int, c_int]),
     'spml_segsort_nll_batched_workspace_bytes': (c_size_t, [c_int, _P, _P, c_int]),
     'spml_segsort_nll_batched_fwd_f32': (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_int,
@@ -596,6 +597,15 @@ def segsort_nll_bwd(emb, own, px_code, protos, pr_code, kappa, mode, stats, d_nl
       ptr(stats, torch.float32), ptr(d_nll, torch.float32), ptr(d_emb), ptr(d_protos),
       int(m_grad), ptr(ws), ws.numel(), stream_ptr()), 'spml_segsort_nll_bwd_f32')
   return d_emb, d_protos
+
+
+def segsort_nll_path_name(p, m, d, mode, backward=False, m_grad=-1):
+  """What segsort_nll_fwd / segsort_nll_bwd launches for these sizes under the current environment and deterministic
+  mode (include/spml_hip.h, spml_segsort_nll_path_name: the library's own predicates, no GPU call)."""
+  buf = ctypes.create_string_buffer(160)
+  check(lib().spml_segsort_nll_path_name(int(p), int(m), int(d), int(mode), 1 if backward else 0, int(m_grad),
+                                         buf, len(buf)), 'spml_segsort_nll_path_name')
+  return buf.value.decode()
 
 
 def segsort_nll_batched_supported(d, mode):

@@ -22,6 +22,7 @@
 // see common.hpp).  Prep kernels convert fp32 rows to fragment-major (hi, lo)
 // f16 arrays once per call; algorithmic flops fwd 2*P*M*D, bwd ~6*P*M*D.
 #include <algorithm>
+#include <cstdio>
 #include <type_traits>
 
 #include "nll_common.hpp"
@@ -316,7 +317,10 @@ __global__ __launch_bounds__(256) void nll_fwd(NllArgs a) {
 //     >> 512 workgroups and short tails; per-chunk partial sums are combined in chunk order by
 //     nll_finalize (deterministic).
 // Two workgroups per CU (12 KB of row codes + 2 x MTB x 2 KS KB of ring each, <= 256 VGPRs).
-template <int KS, int MTB, bool TAG>
+// NEG (SPML_NLL_PLAIN): the first sum takes the prototypes OUTSIDE the positive set.  A PLAIN call needs
+// den = sum_not_same + own and no positive sum; all - same cancels where the positives dwarf the rest (error of den
+// 4.4e-5 at D = 64, kappa = 16 against 3e-6 of an fp32 evaluation, profiles/nll_branch_parity.md).
+template <int KS, int MTB, bool TAG, bool NEG = false>
 __device__ __forceinline__ void nll_fwd2_body(const NllArgs& a) {
   constexpr int TILE = 2 * KS * 1024;            // hi blocks, lo blocks of one prototype tile
   constexpr int SLOT = MTB * TILE;
@@ -424,7 +428,7 @@ __device__ __forceinline__ void nll_fwd2_body(const NllArgs& a) {
           } else {
             if constexpr (LAST) sv = (tile_row(r, 0) < lim) ? sv : 0.f;
             all[nb] += sv;
-            same[nb] += code_match<TAG, int>(pcode[nb], rc[r]) ? sv : 0.f;
+            same[nb] += (code_match<TAG, int>(pcode[nb], rc[r]) != NEG) ? sv : 0.f;
           }
         }
       }
@@ -456,7 +460,7 @@ __device__ __forceinline__ void nll_fwd2_body(const NllArgs& a) {
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb) {
         all[nb] += tsum[nb];
-        same[nb] += code_match<TAG, int>(pcode[nb], code) ? tsum[nb] : 0.f;
+        same[nb] += (code_match<TAG, int>(pcode[nb], code) != NEG) ? tsum[nb] : 0.f;
       }
     }
     if constexpr (GEMM && EPI) {
@@ -553,8 +557,13 @@ template <int KS, int MTB, bool TAG>
 __global__ __launch_bounds__(256, 2) void nll_fwd2(NllArgs a) {
   nll_fwd2_body<KS, MTB, TAG>(a);
 }
+template <int KS, int MTB, bool TAG>
+__global__ __launch_bounds__(256, 2) void nll_fwd2_plain(NllArgs a) {
+  nll_fwd2_body<KS, MTB, TAG, true>(a);
+}
 
-// per pixel: chunk partials (same, all, own) summed in chunk order -> nll, stats (loss.py:61-80)
+// per pixel: chunk partials (same, all, own) summed in chunk order -> nll, stats (loss.py:61-80).
+// plain: the partials are nll_fwd2_plain's, (not same, all, own)
 __device__ __forceinline__ void nll_finalize_body(const float* __restrict__ partial, int chunks,
                                                   int64_t P, int64_t P_pad, int plain,
                                                   float* __restrict__ nll, float* __restrict__ stats) {
@@ -570,7 +579,7 @@ __device__ __forceinline__ void nll_finalize_body(const float* __restrict__ part
   const float pos = same - osim;
   const bool fb = plain || !(pos > 0.f);
   const float num = fb ? osim : pos;
-  const float den = fb ? (all - same) + osim : all - osim;
+  const float den = plain ? same + osim : fb ? (all - same) + osim : all - osim;
   nll[p] = -logf(num / den);
   const float4v st = {num, den, osim, fb ? 1.f : 0.f};
   *reinterpret_cast<float4v*>(stats + (size_t)p * 4) = st;
@@ -1364,6 +1373,41 @@ NllDims nll_bucket_dims(int64_t P, int64_t M, int D) {
   return n;
 }
 
+// The route of a single-problem call: the predicates nll_forward / nll_backward launch by and nll_path_name prints
+// (n: nll_bucket_dims).  Functions of the sizes, the mode and the environment only.
+inline bool nll_c32(int mode) { return (mode & SPML_NLL_CODE32) != 0; }
+// v2 forward (nll_fwd2): narrow embeddings, 32-bit codes
+inline bool route_fwd2(const NllDims& n, int mode) { return n.KS <= 5 && nll_c32(mode); }
+// v2 / v3 embedding gradient (nll_bwd_de2 / nll_bwd_de3); the pipelined kernels take 64 channels
+inline bool route_de2(const NllDims& n, int mode) { return n.KS <= 4 && nll_c32(mode); }
+inline bool route_v3(const NllDims& n, int mode, const NllEnv& env) { return route_de2(n, mode) && n.KS == 4 && env.de3; }
+inline bool route_dp3(const NllDims& n, int mode, const NllEnv& env) { return route_v3(n, mode, env) && env.dp3; }
+// wide embeddings with kept weight tiles (nll_bwd_wide_strips): more channels than the first launch's d-tiles
+inline bool route_wide_strips(const NllDims& n, bool has_tcache) {
+  return n.KS > 17 && has_tcache && 32 * dt_per_launch(n.KS) < n.D;
+}
+// ... strips of pixel tiles a call takes, and launches per strip after the first that read the kept tiles back (7 d-tiles each)
+inline int64_t wide_strips(const NllDims& n, int64_t tcache_mb) {
+  const int64_t strip = tcache_strip_tiles(n, tcache_mb);
+  return strip > 0 ? (n.PT + strip - 1) / strip : 0;
+}
+inline int wide_later_launches(const NllDims& n) {
+  int later = 0;
+  for (int dt0 = dt_per_launch(n.KS); 32 * dt0 < n.D; dt0 += 7) ++later;
+  return later;
+}
+// launches of the round-2 pair outside the strips: one per dt_per_launch d-tiles that hold a channel
+inline int round2_launches(const NllDims& n) {
+  int launches = 0;
+  for (int dt0 = 0; dt0 < n.DT && 32 * dt0 < n.D; dt0 += dt_per_launch(n.KS)) ++launches;
+  return launches;
+}
+// prototype tiles that receive a gradient: whole 32-row tiles up to m_grad (< 0 or > M: all)
+inline int64_t nll_mt_grad(const NllDims& n, int64_t m_grad) {
+  const int64_t mg = m_grad < 0 || m_grad > n.M ? n.M : m_grad;
+  return (mg + 31) / 32;
+}
+
 // The fragment arrays are written here and read by the kernels: the call keeps them as NllArgs does, read-only.
 template <bool RAW>
 void launch_prep_std(const float* x, int64_t R, int D, int KS, float scale, const _Float16* h, const _Float16* l,
@@ -1450,6 +1494,13 @@ __global__ __launch_bounds__(256, 2) void nll_fwd2_batched(NllBatch b) {
   if (!batch_problem(b, blockIdx.z, a)) return;
   if (blockIdx.x >= (a.n.PT + 7) / 8 || blockIdx.y >= fwd2_chunks(a.n)) return;
   nll_fwd2_body<KS, MTB, TAG>(a);
+}
+template <int KS, int MTB, bool TAG>
+__global__ __launch_bounds__(256, 2) void nll_fwd2_plain_batched(NllBatch b) {
+  NllArgs a;
+  if (!batch_problem(b, blockIdx.z, a)) return;
+  if (blockIdx.x >= (a.n.PT + 7) / 8 || blockIdx.y >= fwd2_chunks(a.n)) return;
+  nll_fwd2_body<KS, MTB, TAG, true>(a);
 }
 template <int KS, int DT, bool TAG>
 __global__ __launch_bounds__(256) void nll_bwd_de_batched(NllBatch b) {
@@ -1640,8 +1691,12 @@ int nll_batched(bool backward, const float* emb, const int64_t* own, const int64
       hipLaunchKernelGGL(prep_std_batched<true>, dim3(blocks(PT * KS, 4), 1, z), dim3(256), 0, s, b, 1, 8.0f);
       hipLaunchKernelGGL(prep_std_batched<true>, dim3(blocks(MT * KS, 4), 1, z), dim3(256), 0, s, b, 0,
                          a.kappa_log2e * 0.125f);
-      launch_dyn(tag ? nll_fwd2_batched<KS, 2, true> : nll_fwd2_batched<KS, 2, false>,
-                 dim3(blocks(PT, 8), (unsigned)max_chunks, z), LDS_F, s, b);
+      if (a.mode & SPML_NLL_PLAIN)
+        launch_dyn(tag ? nll_fwd2_plain_batched<KS, 2, true> : nll_fwd2_plain_batched<KS, 2, false>,
+                   dim3(blocks(PT, 8), (unsigned)max_chunks, z), LDS_F, s, b);
+      else
+        launch_dyn(tag ? nll_fwd2_batched<KS, 2, true> : nll_fwd2_batched<KS, 2, false>,
+                   dim3(blocks(PT, 8), (unsigned)max_chunks, z), LDS_F, s, b);
       hipLaunchKernelGGL(nll_finalize_batched, dim3(blocks(max_p, 256), 1, z), dim3(256), 0, s, b);
       continue;
     }
@@ -1707,8 +1762,8 @@ void prep_std_fragments(const NllCall& c) {
 int nll_forward(NllCall& c) {
   NllArgs& a = c.a;
   const NllDims& n = a.n;
-  const bool tag = (a.mode & SPML_NLL_TAGSET) != 0, c32 = (a.mode & SPML_NLL_CODE32) != 0;
-  if (n.KS <= 5 && c32) {              // v2 forward: narrow embeddings, 32-bit codes
+  const bool tag = (a.mode & SPML_NLL_TAGSET) != 0, c32 = nll_c32(a.mode);
+  if (route_fwd2(n, a.mode)) {         // v2 forward: narrow embeddings, 32-bit codes
     prep_std_fragments<true>(c);
     const int64_t chunks = fwd2_chunks(n);
     const dim3 grid((unsigned)((n.PT + 7) / 8), (unsigned)chunks);      // 4 waves x 2 pixel tiles
@@ -1717,7 +1772,10 @@ int nll_forward(NllCall& c) {
       if constexpr (KS <= 5) {
         constexpr int MTB = KS <= 4 ? 4 : 2;
         constexpr int LDS2 = kFwd2TilesPerChunk * 128 + 2 * MTB * 2 * KS * 1024;
-        launch_dyn(tag ? nll_fwd2<KS, MTB, true> : nll_fwd2<KS, MTB, false>, grid, LDS2, c.s, a);
+        if (a.mode & SPML_NLL_PLAIN)
+          launch_dyn(tag ? nll_fwd2_plain<KS, MTB, true> : nll_fwd2_plain<KS, MTB, false>, grid, LDS2, c.s, a);
+        else
+          launch_dyn(tag ? nll_fwd2<KS, MTB, true> : nll_fwd2<KS, MTB, false>, grid, LDS2, c.s, a);
         return SPML_OK;
       } else {
         return SPML_ERR_UNSUPPORTED;
@@ -1780,15 +1838,18 @@ int nll_bwd_wide_strips(NllCall& c) {
   NllArgs& a = c.a;
   const NllDims& n = a.n;
   const int64_t strip = tcache_strip_tiles(n, c.env.tcache_mb), chunks = a.chunks;
-  for (int64_t t0 = 0; t0 < n.PT; t0 += strip) {
+  const int64_t strips = wide_strips(n, c.env.tcache_mb);
+  const int later = wide_later_launches(n);
+  for (int64_t st = 0; st < strips; ++st) {
+    const int64_t t0 = st * strip;
     a.spt0 = t0;
     a.spt1 = t0 + strip < n.PT ? t0 + strip : n.PT;
     const int64_t ch = std::min(chunks, (a.spt1 - a.spt0 + 7) / 8);
     a.chunks = (int)(ch < 1 ? 1 : ch);
     a.dt0 = 0;
     int rc = launch_bwd_pair<KS, DT, 1>(a, c.s);
-    for (int dt0 = DT; rc == SPML_OK && 32 * dt0 < n.D; dt0 += 7) {
-      a.dt0 = dt0;
+    for (int i = 0; rc == SPML_OK && i < later; ++i) {
+      a.dt0 = DT + 7 * i;
       rc = launch_bwd_pair<KS, 7, 2>(a, c.s);
     }
     if (rc != SPML_OK) return rc;
@@ -1803,10 +1864,11 @@ int nll_bwd_round2(NllCall& c) {
   return with_ks(a.n.KS, [&](auto K) -> int {
     constexpr int KS = decltype(K)::value, DT = dt_per_launch(KS);
     if constexpr (KS > 17) {
-      if (a.tcache_de != nullptr && 32 * DT < a.n.D) return nll_bwd_wide_strips(c);
+      if (route_wide_strips(a.n, a.tcache_de != nullptr)) return nll_bwd_wide_strips(c);
     }
-    for (int dt0 = 0; dt0 < a.n.DT && 32 * dt0 < a.n.D; dt0 += DT) {
-      a.dt0 = dt0;
+    const int launches = round2_launches(a.n);
+    for (int i = 0; i < launches; ++i) {
+      a.dt0 = i * DT;
       const int rc = launch_bwd_pair<KS, DT, 0>(a, c.s);
       if (rc != SPML_OK) return rc;
     }
@@ -1866,7 +1928,6 @@ int nll_backward(NllCall& c, int64_t m_grad) {
   NllArgs& a = c.a;
   const NllDims& n = a.n;
   hipStream_t s = c.s;
-  const bool c32 = (a.mode & SPML_NLL_CODE32) != 0;
   float* gscale = reinterpret_cast<float*>(c.ws + c.w.gscale);
   float* rowscale = reinterpret_cast<float*>(c.ws + c.w.rowscale);
   float* own_term = reinterpret_cast<float*>(c.ws + c.w.ownterm);
@@ -1877,8 +1938,7 @@ int nll_backward(NllCall& c, int64_t m_grad) {
   // gscale bounds |g|; kappa is folded into rowscale (kappa * g / gscale stays O(kappa))
   launch_prep_T<false>(c.protos, n.M, n.D, n.DT, nullptr, nullptr, 1.0f, a.pth, a.ptl, s);
   // v2 / v3 paths: narrow embeddings, 32-bit codes; the pipelined kernels (64 channels) prepare their own pixel fragments
-  const bool de2 = n.KS <= 4 && c32;
-  const bool v3 = de2 && n.KS == 4 && c.env.de3, dp3 = v3 && c.env.dp3;
+  const bool de2 = route_de2(n, a.mode), v3 = route_v3(n, a.mode, c.env), dp3 = route_dp3(n, a.mode, c.env);
   if (!dp3) launch_prep_T<false>(c.emb, n.P, n.D, n.DT, rowscale, gscale, 1.0f, a.eth, a.etl, s);
   a.tcache_de = c.w.tde ? reinterpret_cast<float*>(c.ws + c.w.tde) : nullptr;
   a.tcache_dp = c.w.tdp ? reinterpret_cast<float*>(c.ws + c.w.tdp) : nullptr;
@@ -1887,8 +1947,7 @@ int nll_backward(NllCall& c, int64_t m_grad) {
   hipLaunchKernelGGL((a.mode & SPML_NLL_TAGSET) ? coef_kernel<true> : coef_kernel<false>,
                      dim3((unsigned)((n.PT * 32 + 255) / 256)), dim3(256), 0, s, a.stats, a.own, a.px_code, a.pr_code,
                      n.M, n.P, n.PT * 32, const_cast<PixelCoef*>(a.coef));
-  const int64_t mg = m_grad < 0 || m_grad > n.M ? n.M : m_grad;
-  a.mt_grad = (mg + 31) / 32;
+  a.mt_grad = nll_mt_grad(n, m_grad);
   a.chunks = (int)dp_chunks((a.mt_grad + 3) / 4, n.PT);
   a.spt0 = 0;
   a.spt1 = n.PT;
@@ -1940,6 +1999,48 @@ int nll_single(bool backward, const float* emb, const int64_t* own, const int64_
   return backward ? nll_backward(c, m_grad) : nll_forward(c);
 }
 
+// What nll_single launches for these arguments, by the predicates it launches by (no GPU call).  The template
+// arguments are the kernels' own; rows / chunks / strips / mt (prototype tiles with a gradient) are the grid's.
+int nll_path_name(int64_t P, int64_t M, int D, int mode, bool backward, int64_t m_grad, char* buf, size_t len) {
+  const auto put = [&](const char* fmt, auto... v) { return snprintf(buf, len, fmt, v...); };
+  if (P < 0 || M <= 0 || D <= 0 || mode < 0 || mode > (SPML_NLL_TAGSET | SPML_NLL_PLAIN | SPML_NLL_CODE32) ||
+      !ks_bucket((D + 15) / 16))
+    return put("%s", "unsupported");
+  if (P == 0) return put("%s", "nothing");          // nll_single returns before its first launch
+  const NllDims n = nll_bucket_dims(P, M, D);
+  const NllEnv env = nll_env();
+  const char* tag = (mode & SPML_NLL_TAGSET) ? "tag" : "label";
+  if (!backward) {
+    if (route_fwd2(n, mode))
+      return put("fwd2%s<%d,%d,%s> chunks=%lld", (mode & SPML_NLL_PLAIN) ? "_plain" : "", n.KS, n.KS <= 4 ? 4 : 2, tag,
+                 (long long)fwd2_chunks(n));
+    return put("fwd<%d,1,%s,%s>", n.KS, tag, n.KS > 5 && nll_c32(mode) ? "c32" : "c64");
+  }
+  const NllWs w = nll_ws(n, env);
+  const long long mt = nll_mt_grad(n, m_grad), chunks = dp_chunks((mt + 3) / 4, n.PT);
+  const char* det = deterministic_mode() ? " fix64" : "";
+  char de[64], dp[96];
+  const int per = dt_per_launch(n.KS);
+  if (route_de2(n, mode)) {
+    if (route_v3(n, mode, env)) snprintf(de, sizeof de, "de3<%s> rows=%d", tag, bwd2_rows(n));
+    else snprintf(de, sizeof de, "de2<%d,%d,%s> rows=%d", n.KS, (n.KS + 1) / 2, tag, bwd2_rows(n));
+    if (route_dp3(n, mode, env)) {
+      if (mt > 0) snprintf(dp, sizeof dp, "dp3<%s> mt=%lld", tag, mt); else snprintf(dp, sizeof dp, "no dp");
+      return put("%s + %s%s", de, dp, det);
+    }
+  } else if (route_wide_strips(n, w.tde != 0)) {
+    return put("wide<%s> strips=%lld launches=1+%d mt=%lld%s", tag, (long long)wide_strips(n, env.tcache_mb),
+               wide_later_launches(n), mt, det);
+  } else {
+    snprintf(de, sizeof de, "de<%d,%d,%s>", n.KS, per, tag);
+  }
+  const int launches = round2_launches(n);
+  if (mt > 0) snprintf(dp, sizeof dp, "dp<%d,%d,%s> chunks=%lld mt=%lld", n.KS, per, tag, chunks, mt);
+  else snprintf(dp, sizeof dp, "no dp");
+  if (launches != 1) return put("%s + %s launches=%d%s", de, dp, launches, det);
+  return put("%s + %s%s", de, dp, det);
+}
+
 }  // namespace
 }  // namespace spml
 
@@ -1968,6 +2069,13 @@ extern "C" int spml_segsort_nll_bwd_f32(const float* emb, const int64_t* own,
   return nll_single(true, emb, own, px_code, P, protos, pr_code, M, D, kappa, mode, nullptr,
                     const_cast<float*>(stats), d_nll, d_emb, d_protos, m_grad, ws, ws_bytes,
                     (hipStream_t)stream);
+}
+
+extern "C" int spml_segsort_nll_path_name(int64_t P, int64_t M, int D, int mode, int backward, int64_t m_grad,
+                                          char* buf, size_t len) {
+  if (!buf || len == 0) return SPML_ERR_INVALID_ARG;
+  const int need = nll_path_name(P, M, D, mode, backward != 0, m_grad, buf, len);
+  return need >= 0 && (size_t)need < len ? SPML_OK : SPML_ERR_INVALID_ARG;
 }
 
 extern "C" int spml_segsort_nll_batched_supported(int D, int mode) { return batched_supported(D, mode) ? 1 : 0; }

@@ -25,7 +25,8 @@ def test_header_declares_the_hot_path():
   names = declared_symbols()
   for must in ('spml_normalize_concat_loc_f32', 'spml_kmeans_run_f32', 'spml_kmeans_assign_f32',
                'spml_segment_sum_normalize_f32', 'spml_segsort_nll_fwd_f32',
-               'spml_segsort_nll_bwd_f32', 'spml_topk_affinity_f32', 'spml_status_string'):
+               'spml_segsort_nll_bwd_f32', 'spml_segsort_nll_path_name', 'spml_topk_affinity_f32',
+               'spml_status_string'):
     assert must in names
 
 
@@ -50,6 +51,10 @@ def test_ffi_table_matches_header(lib_path):
   assert lib.spml_segsort_nll_workspace_bytes(1000, 100, 64) > 0
   assert lib.spml_topk_workspace_bytes(100, 100, 64, 5) > 0
   assert lib.spml_kmeans_workspace_bytes(-1, 66, 36, 2, 500) == 0
+  # host-only route query of the NLL: the buffer must hold the name
+  assert _ffi.segsort_nll_path_name(1000, 100, 100, 0) == 'fwd<9,1,label,c64>'
+  small = ctypes.create_string_buffer(4)
+  assert lib.spml_segsort_nll_path_name(1000, 100, 100, 0, 0, -1, small, 4) == -1 and small.raw[3:] == b'\0'
 
 
 def test_no_cpu_fallback():
