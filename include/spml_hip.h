@@ -52,7 +52,7 @@ const char* spml_status_string(int status);
  *    spml_dense_crf_*, spml_segment_tag_cam_*, spml_conv_hl8_path_name, spml_conv_wgrad_path_name / _splits,
  *    spml_augment_*, spml_image_views_*, spml_label_export_*, spml_score_*, spml_pca_*, spml_summary_panels_u8,
  *    spml_train_summary_workspace_bytes, spml_crf_guide_*, spml_export_scores_bytes, spml_label_export_scored_u8,
- *    spml_segsort_nll_path_name). */
+ *    spml_segsort_nll_path_name, spml_cam_ingest_*). */
 #define SPML_ABI_VERSION 8
 int spml_abi_version(void);
 
@@ -1434,6 +1434,37 @@ int spml_pca_project_minmax_f32(const float* emb, int N, int C, int H, int W, in
 int spml_summary_panels_u8(const int64_t* semantic, const int64_t* instance, int N, int Hl, int Wl, const float* proj,
                            const float* minmax, int h, int w, const unsigned char* color_map, int pad, int out_h,
                            int out_w, unsigned char* out, void* stream);
+
+/* ------------------------------------------------------------------------
+ * CAM ingest: the class activation maps of a file -> the class maps the random walk takes, one launch
+ * (csrc/cam_ingest.hip)
+ * replaces: pyscripts/inference/pseudo_camrw_crf.py:108-111 (np.zeros((21, h, w)), cam_full_arr[k + 1] = v for the
+ *           entries of the pickled dict, cam_full_arr[0] = np.power(1 - np.max(cam_full_arr[1:], axis=0), ALPHA)) and
+ *           :151-152 (F.interpolate(cam_full_arr, scale_factor=1/8., mode='bilinear')).
+ *
+ * planes: fp32 [K][h][w], device, the K planes the file carries, in any order (NULL allowed for K = 0).  classes: int
+ * [K] ON THE HOST, classes[k] = the dict key of plane k = its class - 1; the entry checks the keys and hands the kernel
+ * a class -> plane table by value, so nothing of `classes` is read after the call returns.  out: fp32
+ * [ncls][h / 8][w / 8], device.  F.interpolate takes the given factor for the source coordinate (8 d + 3.5), so with
+ * taps(a)(y, x) = the mean of a at rows 8 y + 3, 8 y + 4 and columns 8 x + 3, 8 x + 4:
+ *   out[c]  = taps(plane of class c)               for a class c >= 1 the file carries,
+ *   out[c]  = 0                                    for a class it does not carry (written by the kernel: out needs no
+ *                                                  memset and may hold anything on entry),
+ *   out[0]  = taps((1 - m) ^ alpha), m = the maximum over the carried planes at that source pixel, and over an
+ *             implicit 0 exactly when some foreground class is absent (K < ncls - 1) -- with every class present and
+ *             negative activations m is negative and is not clamped; a NaN wins the maximum, as in np.max; ncls == 1
+ *             gives 1.
+ * The [ncls][h][w] array is never formed.  Sums and the power (by multiplication, alpha an integer >= 0, x ^ 0 = 1) run
+ * in fp64 and are rounded to fp32 once: every value is within one rounding of the exact expression on the fp32 inputs.
+ * One launch of ceil(h / 8 * w / 8 / 64) single-wave workgroups, no workspace, no LDS, no atomics: bit-identical from
+ * call to call.
+ * SPML_ERR_UNSUPPORTED, with nothing launched and out untouched: h or w below 8 or above 16384, ncls outside [1, 256],
+ * K outside [0, ncls - 1].  SPML_ERR_INVALID_ARG, the same: a null out (planes or classes with K > 0), planes or out
+ * not 4-byte aligned, alpha < 0, a key outside [0, ncls - 2], a key given twice, out overlapping planes.
+ * spml_cam_ingest_path_name (host only; the shape expression the entry evaluates): "cam_ingest" or "unsupported". */
+const char* spml_cam_ingest_path_name(int K, int h, int w, int ncls);
+int spml_cam_ingest_f32(const float* planes, const int* classes, int K, int h, int w, int ncls, int alpha, float* out,
+                        void* stream);
 
 #ifdef __cplusplus
 }

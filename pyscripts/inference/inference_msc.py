@@ -20,7 +20,19 @@ and writes `semantic_gray/<name>.npy` (uint8).  Without `--semantic_memory_dir` 
 itself: the prototypes of the synthetic images (`full_resolution_prototypes`, what `prototype.py` does) are written with
 `save_image_memory` to `<save_dir>/semantic_prototype` and read back from those files.  One JSON line reports images/s, mIoU and pixel accuracy
 (`pyscripts/benchmark/benchmark_by_mIoU.py`), the number of views and the path taken by the per-view tail.
-`--crf` (off by default) adds the denseCRF tail of `inference_crf_msc.py`, on either kind of `--data_list`: the view mean of the vote maps and the guide image at the file's own size through `spml_amd.inference.dense_crf_refine`; the labels written and scored are the refined ones and the JSON line gains `crf_path`, `crf_share`, `mIoU_before_crf` and `changed_by_crf` (see `run_knn` of spml_amd/inference_cli.py)."""
+`--crf` (off by default) adds the denseCRF tail of `inference_crf_msc.py`, on either kind of `--data_list`: the view mean of the vote maps and the guide image at the file's own size through `spml_amd.inference.dense_crf_refine`; the labels written and scored are the refined ones and the JSON line gains `crf_path`, `crf_share`, `mIoU_before_crf` and `changed_by_crf` (see `run_knn` of spml_amd/inference_cli.py).
+`--pseudo_tags` (off by default) makes the run the kNN pseudo-label step of the image-tag recipe, `pseudo_inference_msc.py`
+(with `--crf`: `pseudo_inference_crf_msc.py`) on either kind of `--data_list`:
+
+  python3 pyscripts/inference/inference_msc.py --snapshot_dir S --cfg_path C.yaml --save_dir OUT --data_dir D \\
+      --data_list L --semantic_memory_dir BANK --kmeans_num_clusters 12,12 --label_divisor 2048 --pseudo_tags [--crf]
+
+eight views (PSEUDO_SCALES, flipped and plain), the image tags from the classes of the file's label map -- the list needs
+its label columns -- and `spml_amd.inference.pseudo_labels_knn_multiscale` (votes normalised per tagged class by their
+maximum over the image, floored at PSEUDO_FLOOR); with `--crf` that normalised map is what the CRF refines.  The JSON line
+gains `normalize_path`.  The instance-weighted IoU of a list is left to `pyscripts/benchmark/benchmark_by_instance.py` on
+the written directory (the list source does not upload the instance plane); on synthetic images `instance_mIoU` is
+reported as `pseudo_inference_msc.py` reports it."""
 import os
 import sys
 
@@ -28,11 +40,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 
 SCALES = [0.5, 0.75, 1, 1.25, 1.5]                                                           # :125
+PSEUDO_SCALES, PSEUDO_FLOOR = [0.5, 1, 1.5, 2], 0.15                     # pseudo_inference_crf_msc.py:135, :260
 
 
 def main(argv=None):
   from spml_amd.inference_cli import run_knn
-  run_knn('Inference for semantic segmentation.', SCALES, True, argv)                          # :123-137
+  run_knn('Inference for semantic segmentation.', SCALES, True, argv,                         # :123-137
+          pseudo_tags=(PSEUDO_SCALES, PSEUDO_FLOOR))
 
 
 if __name__ == '__main__':

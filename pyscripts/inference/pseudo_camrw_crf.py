@@ -17,7 +17,10 @@ mean-field filter of `spml_amd.models.crf.DenseCRF`).  Label maps are
 
 With `--data_list synthetic` and no `--cam_dir` the CAMs come from the synthetic label map (`synthetic_cams`): 0.2 + 0.6 *
 (label == c) for every foreground class the image carries.  A stand-in for the CAM files of another model, like
-`flip_scale_views` for the loader: not parity-pinned."""
+`flip_scale_views` for the loader: not parity-pinned.
+
+This program stays on synthetic images.  The same recipe on image files (`--data_dir D --data_list L --cam_dir CAMS`) is
+`pseudo_softmaxrw.py --cam_dir CAMS --crf`, which forms the class maps in one launch (`spml_cam_ingest_f32`)."""
 import os
 import sys
 

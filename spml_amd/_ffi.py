@@ -201,6 +201,8 @@ _SIGNATURES = {
                                             _P]),
     'spml_summary_panels_u8': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_int, c_int, _P, c_int, c_int, c_int, _P,
                                        _P]),
+    'spml_cam_ingest_path_name': (c_char_p, [c_int, c_int, c_int, c_int]),
+    'spml_cam_ingest_f32': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -2101,4 +2103,45 @@ def summary_panels(semantic, instance, proj, minmax, color_map, out=None):
                                      n, hl, wl, ptr(proj, torch.float32), ptr(minmax, torch.float32), h, w,
                                      ptr(color_map, torch.uint8, allow_none=semantic is None), pad, out_h, out_w,
                                      ptr(out, torch.uint8), stream_ptr()), 'spml_summary_panels_u8')
+  return out
+
+
+# ---------------------------------------------------------------------------
+# CAM ingest (csrc/cam_ingest.hip)
+MAX_CAM_CLASSES = 256                  # the limit of spml_cam_ingest_f32 (include/spml_hip.h)
+
+
+def cam_ingest_path_name(k, h, w, ncls):
+  """'cam_ingest' or 'unsupported' (a host function of the library)."""
+  return lib().spml_cam_ingest_path_name(int(k), int(h), int(w), int(ncls)).decode()
+
+
+def cam_ingest(planes, classes, hw, ncls, alpha, out=None):
+  """One launch: the `K` planes a CAM file carries, fp32 `[K, h, w]` on the device (None or `[0, h, w]` for a file
+  without entries), and `classes`, their `K` dict keys (class - 1) as host integers -> fp32 `[ncls, h // 8, w // 8]`, the
+  background row and the 1/8 bilinear reduction of pseudo_camrw_crf.py:108-111,151-152.  The keys are checked by the
+  library on the host (range, duplicates) before anything is launched."""
+  import ctypes
+  h, w = int(hw[0]), int(hw[1])
+  keys = [int(c) for c in classes]
+  k = len(keys)
+  if planes is None:
+    if k:
+      raise SpmlHipError('cam_ingest: %d classes without planes' % k)
+    device = torch.device('cuda', torch.cuda.current_device())
+  else:
+    if planes.dim() != 3 or tuple(planes.shape) != (k, h, w):
+      raise SpmlHipError('cam_ingest: planes must be fp32 [%d, %d, %d], one per class key' % (k, h, w))
+    device = planes.device
+  oh, ow = h // 8, w // 8
+  if out is None:
+    if oh < 1 or ow < 1 or int(ncls) < 1:
+      raise SpmlHipError('cam_ingest: no output for a %d x %d image and %d classes' % (h, w, int(ncls)))
+    out = torch.empty((int(ncls), oh, ow), dtype=torch.float32, device=device)
+  elif tuple(out.shape) != (int(ncls), oh, ow):
+    raise SpmlHipError('cam_ingest: the output must be fp32 [%d, %d, %d]' % (int(ncls), oh, ow))
+  keys_host = (ctypes.c_int * max(k, 1))(*keys)
+  planes_ptr = ptr(planes, torch.float32, allow_none=True)            # (checked for an empty tensor too)
+  check(lib().spml_cam_ingest_f32(planes_ptr if k else c_void_p(0), keys_host, k, h, w, int(ncls), int(alpha),
+                                  ptr(out, torch.float32), stream_ptr()), 'spml_cam_ingest_f32')
   return out

@@ -4,7 +4,7 @@ import argparse
 from spml_amd.config.default import config, update_config
 
 
-def build_parser(description='', crf_option=False):
+def build_parser(description='', crf_option=False, pseudo_tags_option=False):
   p = argparse.ArgumentParser(description=description)
   p.add_argument('--snapshot_dir', required=True, type=str, help='/path/to/snapshot/dir.')
   p.add_argument('--save_dir', type=str, help='/path/to/save/dir.')
@@ -26,13 +26,17 @@ def build_parser(description='', crf_option=False):
   # `*_crf*` sibling take the sibling's denseCRF tail as an option, off by default
   if crf_option:
     p.add_argument('--crf', action='store_true', help='refine the labels with the dense CRF (the --crf_* options).')
+  # ... and `inference_msc.py` takes the tag-normalised tail of `pseudo_inference_msc.py` the same way
+  if pseudo_tags_option:
+    p.add_argument('--pseudo_tags', action='store_true',
+                   help='pseudo labels of the image-tag recipe: normalise the votes by the tags of the label map.')
   return p
 
 
-def parse_args(description='', argv=None, crf_option=False):
+def parse_args(description='', argv=None, crf_option=False, pseudo_tags_option=False):
   """parse_known_args -> update_config(cfg_path) -> parse_args (parse_args.py:46-53).  `crf_option`: the program takes
-  `--crf`."""
-  parser = build_parser(description, crf_option)
+  `--crf`; `pseudo_tags_option`: it takes `--pseudo_tags`."""
+  parser = build_parser(description, crf_option, pseudo_tags_option)
   args, _ = parser.parse_known_args(argv)
   update_config(args.cfg_path)
   return parser.parse_args(argv)

@@ -752,6 +752,78 @@ def pseudo_labels_softmax_crf(embedding_model, prediction_model, views, image_hw
   return out
 
 
+def _walked_cams_cam(name, embedding_model, views, image_hw, cam_planes, cam_classes, num_classes, alpha, walk_steps,
+                     scale, power):
+  """`pseudo_labels_cam` up to the walked maps, shared with `pseudo_labels_cam_crf`: the argument checks (under the
+  caller's `name`), the embedding and `spml_resample_unit_f32` per view as in `_walked_cams_softmax` (no classifier
+  head), the transition matrix and the walk.  The ingest launch comes first: it needs nothing of the network, and a key
+  out of range or given twice is refused before the views go through it.
+  -> (cam, cam_rw `[ncls, h//8, w//8]`, ingest path)."""
+  h, w = image_hw
+  out_hw = (h // 8, w // 8)
+  if out_hw[0] < 1 or out_hw[1] < 1:
+    raise ValueError(name + ': the image is smaller than 8 x 8')
+  _check_views(name, views)
+  if cam_planes is not None and not cam_planes.is_cuda:
+    raise _ffi.SpmlHipError('the HIP path needs GPU tensors (cam_planes on %s); there is no CPU fallback'
+                            % cam_planes.device)
+  n = out_hw[0] * out_hw[1]
+  device = views[0][0].device
+  nhwc = _is_channels_last(embedding_model)
+  units, b = None, 0
+  with torch.no_grad():
+    cam = _ffi.cam_ingest(cam_planes, cam_classes, (h, w), num_classes, alpha)
+    for part in _group_by_padded_size(views):
+      images = torch.cat([v[0] for v in part], 0) if len(part) > 1 else part[0][0]
+      if nhwc:
+        images = images.contiguous(memory_format=torch.channels_last)
+      embs = embedding_model.generate_embeddings({'image': images}, resize_as_input=True)['embedding'].float()
+      if units is None:
+        units = torch.empty((len(views), embs.shape[1], n), dtype=torch.float32, device=device)
+      for i, (_, crop_hw, flip) in enumerate(part):
+        _ffi.resample_unit(embs[i], crop_hw, flip, out_hw, units, b)
+        b += 1
+    trans = _ffi.affinity_transition(units, scale, power)
+    cam_rw = _walk(trans, cam, walk_steps)
+  return cam, cam_rw, _ffi.cam_ingest_path_name(len(cam_classes), h, w, num_classes)
+
+
+def pseudo_labels_cam(embedding_model, views, image_hw, cam_planes, cam_classes, num_classes, alpha=6, walk_steps=6,
+                      scale=5.0, power=20):
+  """One image of the image-tag recipe's first pseudo-label step (`pyscripts/inference/pseudo_camrw_crf.py:103-170`),
+  before the denseCRF: the class activation maps of another model walked over the pixel affinity of this one.  `views`:
+  list of `(image [1,3,Hp,Wp], (rh, rw), is_flip)` (the program: the flip pair at scale 1); `image_hw`: the un-padded
+  image; `cam_planes`: fp32 `[K,h,w]` device tensor, the planes the image's CAM file carries (None for K = 0);
+  `cam_classes`: their K dict keys (class - 1) as host integers.
+
+  First `spml_cam_ingest_f32` -- the background row and the 1/8 reduction of :108-111 and :151-152 in one launch,
+  without the `[ncls,h,w]` array; a bad key is refused here, before the network runs.  Per view the embedding and
+  `spml_resample_unit_f32` as in `pseudo_labels_softmax` (:139-146; no classifier head).  After the last view:
+  `spml_affinity_transition_f32` (:147-158), the walk's GEMMs (:159-164) and `spml_upsample_argmax_i64` (:167-170).  Returns `cam`, `cam_rw` `[ncls, h//8, w//8]`, `semantic_prediction`
+  `[h,w]` int64 and `cam_path`."""
+  h, w = image_hw
+  cam, cam_rw, path = _walked_cams_cam('pseudo_labels_cam', embedding_model, views, image_hw, cam_planes, cam_classes,
+                                       num_classes, alpha, walk_steps, scale, power)
+  with torch.no_grad():
+    prediction = _ffi.upsample_argmax(cam_rw, h, w)
+  return {'cam': cam, 'cam_rw': cam_rw, 'semantic_prediction': prediction, 'cam_path': path}
+
+
+def pseudo_labels_cam_crf(embedding_model, views, image_hw, cam_planes, cam_classes, num_classes, image_u8, crf, alpha=6,
+                          walk_steps=6, scale=5.0, power=20):
+  """`pseudo_labels_cam` with the denseCRF refinement of `pseudo_camrw_crf.py:166-181`: the same chain up to `cam_rw`,
+  then `random_walk_crf_refine` on `image_u8` (uint8 `[h,w,3]`, `denormalized_uint8` of the un-padded image) with `crf`.
+  Returns `cam`, `cam_rw`, `cam_path`, `semantic_prob`, `semantic_prediction` (the refined labels),
+  `semantic_prediction_before_crf` (equal to `pseudo_labels_cam`'s `semantic_prediction`) and `crf_path`."""
+  if tuple(image_u8.shape[:2]) != tuple(image_hw):
+    raise ValueError('pseudo_labels_cam_crf: image_u8 must be the un-padded image [h,w,3]')
+  cam, cam_rw, path = _walked_cams_cam('pseudo_labels_cam_crf', embedding_model, views, image_hw, cam_planes, cam_classes,
+                                       num_classes, alpha, walk_steps, scale, power)
+  out = {'cam': cam, 'cam_rw': cam_rw, 'cam_path': path}
+  out.update(random_walk_crf_refine(image_u8, cam_rw, crf))
+  return out
+
+
 HIP_SEGMENT_VOTES_PATH = 'hip_segment_votes'
 FRAMEWORK_SEGMENT_VOTES_PATH = 'framework_segment_votes'
 

@@ -11,7 +11,11 @@ lists and takes `--crf`; `X_crf.py` runs the same body with the CRF always on an
 programs reaches image files through `X.py --crf`: the source then adds the CRF's guide image to every
 `SourceImage` (`spml_crf_guide_u8` from the bytes already on the device) and `emit_refined` finishes, scores (after and
 before the CRF) and compares the label maps in one launch (`spml_label_export_scored_u8`).  `pseudo_softmax.py` runs
-`run_pseudo_softmax` too; it has no CRF sibling in the reference and takes no `--crf`."""
+`run_pseudo_softmax` too; it has no CRF sibling in the reference and takes no `--crf`.  The image-tag recipe's two
+pseudo-label steps reach image files the same way: `pseudo_softmaxrw.py --cam_dir` is the CAM walk of
+`pseudo_camrw_crf.py` (the source adds the planes of every image's CAM file to its upload, `run_pseudo_softmax` calls
+`pseudo_labels_cam[_crf]`), `inference_msc.py --pseudo_tags` the kNN pseudo labels of `pseudo_inference[_crf]_msc.py`
+(`run_knn` with that program's scales, the image tags and `pseudo_labels_knn_multiscale`)."""
 import json
 import os
 import time
@@ -48,20 +52,23 @@ def list_dataset(config, args, api_function, need_labels=False):
   return dataset
 
 
-def parse(description, argv, api_function, what='inference', file_lists=None, crf_option=False):
+def parse(description, argv, api_function, what='inference', file_lists=None, crf_option=False, pseudo_tags_option=False):
   """`parse_args`, the reference's `--kmeans_num_clusters` / `--label_divisor` overrides (inference_msc.py:40-41; the
   softmax programs read neither), then the guards, in one order for every program: a file list, a missing `--save_dir`,
   a machine without a GPU.  `file_lists`: None for a program that does not read file lists yet (it refuses one),
-  'images' for one that does, 'labels' for one that also needs the list's label columns.  `crf_option`: the program
-  takes `--crf` (the denseCRF tail of its `*_crf*` sibling).
+  'images' for one that does, 'labels' for one that also needs the list's label columns, or a function of the parsed
+  arguments that gives one of the three (a program whose options decide).  `crf_option`: the program takes `--crf` (the
+  denseCRF tail of its `*_crf*` sibling); `pseudo_tags_option`: it takes `--pseudo_tags`.
   -> (config, args, device), with `device` made the current one."""
   from spml_amd.config.default import config
   from spml_amd.config.parse_args import parse_args
-  args = parse_args(description, argv, crf_option)
+  args = parse_args(description, argv, crf_option, pseudo_tags_option)
   if args.kmeans_num_clusters:
     config.network.kmeans_num_clusters = [int(i) for i in args.kmeans_num_clusters.split(',')]
   if args.label_divisor:
     config.network.label_divisor = args.label_divisor
+  if callable(file_lists):
+    file_lists = file_lists(args)
   if reads_file_list(args):
     if file_lists is None:
       raise SystemExit('file-list data loading (ListDataset) is outside the scope of this repository; '
@@ -216,18 +223,48 @@ class SourceImage(object):
   (the semantic label `[h, w]` on the device, or None).  A source made `with_guide` adds `guide`, the uint8 image
   `[rh, rw, 3]` the denseCRF takes, at the resolution the CRF runs at: the file's own size for the multi-view programs
   (inference_softmax_crf_msc.py:159-164 uses the original image), the un-padded `test.image_size` view for a
-  `single_view` one (inference_crf.py:247-252)."""
+  `single_view` one (inference_crf.py:247-252).  A source made `with_cams` adds `cam_planes` (fp32 `[K,h,w]` on the
+  device, the planes of the image's CAM file, None for a file without entries) and `cam_classes` (their K dict keys,
+  class - 1, as host integers: `spml_cam_ingest_f32` checks them on the host).  `instance`: the instance label `[h, w]`
+  of a synthetic image, None for a file (`ListImageSource` does not upload the instance plane)."""
 
-  def __init__(self, index, name, image_hw, views, label_views, label, guide=None):
+  def __init__(self, index, name, image_hw, views, label_views, label, guide=None, cam_planes=None, cam_classes=None,
+               instance=None):
     self.index, self.name, self.image_hw = index, name, image_hw
     self.views, self.label_views, self.label, self.guide = views, label_views, label, guide
+    self.cam_planes, self.cam_classes, self.instance = cam_planes, cam_classes, instance
+
+
+def read_cam_file(cam_dir, name, image_hw, num_classes):
+  """`<cam_dir>/<name>`, the reference's pickled dict `{class - 1: [h, w]}` (pseudo_camrw_crf.py:106-107)
+  -> (keys int32 `[K]`, the K planes as a list of contiguous fp32 `[h, w]` arrays), in the dict's order; a plane the file
+  holds as contiguous fp32 is the file's own array, so the caller's copy to where the planes go up from is the only one.
+  A file that does not exist, a plane that does not have the image's shape or a key outside `0 .. num_classes - 2` ends
+  the program with a message that names the file."""
+  path = os.path.join(cam_dir, name)
+  if not os.path.isfile(path):
+    raise SystemExit("CAM file '%s' does not exist (--cam_dir holds one pickled {class - 1: [h, w]} dict per image)" % path)
+  cams = np.load(path, allow_pickle=True).item()
+  h, w = image_hw
+  keys, planes = np.empty((len(cams),), np.int32), []
+  for i, (key, value) in enumerate(cams.items()):
+    if not 0 <= int(key) <= num_classes - 2:
+      raise SystemExit("CAM file '%s' has the key %d: outside 0 .. %d (class - 1 of %d classes)"
+                       % (path, int(key), num_classes - 2, num_classes))
+    if tuple(np.shape(value)) != (h, w):
+      raise SystemExit("CAM file '%s': the plane of key %d is %s, the image is %d x %d"
+                       % (path, int(key), ' x '.join(str(s) for s in np.shape(value)), h, w))
+    keys[i] = int(key)
+    planes.append(np.ascontiguousarray(value, dtype=np.float32))
+  return keys, planes
 
 
 class ImageSource(object):
   """Where a program's images come from and where its label maps go: one interface, two implementations, so that a
   program's `main` does not branch.  `scales` / `is_flip`: the views of every image; `single_view`: the program resizes
   to `test.image_size` first (inference_softmax.py:89-94) and its label map goes back to the file's size; `with_labels`:
-  every view comes with its label map (the memory-bank pass); `with_guide`: every image comes with the denseCRF's guide.
+  every view comes with its label map (the memory-bank pass); `with_guide`: every image comes with the denseCRF's guide;
+  `with_cams`: a directory of CAM files, every image comes with the planes and keys of its file (`read_cam_file`).
 
     for_program(...)        the implementation `--data_list` selects
     timed(per_image)        `per_image(SourceImage)` for every image, between two synchronisations -> (done, seconds)
@@ -241,10 +278,11 @@ class ImageSource(object):
     crf_fields()            `mIoU_before_crf` and `changed_by_crf` of the report, after `emit_refined`
     fields()                further fields of the report"""
 
-  def __init__(self, config, args, device, scales, is_flip, single_view=False, with_labels=False, with_guide=False):
+  def __init__(self, config, args, device, scales, is_flip, single_view=False, with_labels=False, with_guide=False,
+               with_cams=None):
     self.config, self.args, self.device = config, args, device
     self.scales, self.is_flip, self.single_view, self.with_labels = list(scales), bool(is_flip), single_view, with_labels
-    self.with_guide = with_guide
+    self.with_guide, self.with_cams = with_guide, with_cams
     self.num_classes, self.crop_size, self.stride, self.size = geometry(config)
     self.counts, self.counts_before, self.changed, self.pixels = None, None, None, 0
 
@@ -278,11 +316,12 @@ class ImageSource(object):
 
 class SyntheticImageSource(ImageSource):
   """`--data_list synthetic` (or none): `synthetic_image` + `flip_scale_views` (+ `label_views` of the densified label),
-  label maps as `.npy` (`save_label_map`)."""
+  label maps as `.npy` (`save_label_map`); `with_cams`: the CAM file of image `index` is `synthetic_%04d.npy`, the name
+  `pseudo_camrw_crf.py` reads."""
 
   def image(self, index):
     from spml_amd import inference
-    image, label, _ = synthetic_image(index, self.size, self.num_classes, self.device)
+    image, label, instance = synthetic_image(index, self.size, self.num_classes, self.device)
     views = inference.flip_scale_views(image, self.scales, self.is_flip, self.crop_size)
     labels = None
     if self.with_labels:
@@ -291,7 +330,12 @@ class SyntheticImageSource(ImageSource):
     guide = None
     if self.with_guide:         # (a single view's padded image holds `image` in its top-left corner: one guide for both)
       guide = inference.denormalized_uint8(image, self.config.network.pixel_means, self.config.network.pixel_stds)
-    return SourceImage(index, 'synthetic_{:04d}'.format(index), (self.size, self.size), views, labels, label, guide)
+    name = 'synthetic_{:04d}'.format(index)
+    planes, keys = None, None
+    if self.with_cams:
+      keys, planes = read_cam_file(self.with_cams, name + '.npy', (self.size, self.size), self.num_classes)
+      planes = torch.from_numpy(np.stack(planes)).to(self.device) if len(keys) else None
+    return SourceImage(index, name, (self.size, self.size), views, labels, label, guide, planes, keys, instance)
 
   def timed(self, per_image):
     return timed_images(lambda index: per_image(self.image(index)))
@@ -336,7 +380,9 @@ class ListImageSource(ImageSource):
   file's own size, one copy brings them into pinned memory and a writer pool saves `semantic_gray/<name>.png` (mode L)
   and `semantic_color/<name>.png` (mode RGB).  `with_guide`: `spml_crf_guide_u8` forms the denseCRF's guide from the
   bytes already on the device, and `emit_refined` finishes, scores (after and before the CRF) and compares in one launch
-  (`spml_label_export_scored_u8`); the counts of the whole list stay in one device tensor."""
+  (`spml_label_export_scored_u8`); the counts of the whole list stay in one device tensor.  `with_cams`: the
+  reader thread also loads `<cam_dir>/<name with .png -> .npy>` (pseudo_camrw_crf.py:97,106) and the fp32 planes go up in
+  the same copy, 16-byte aligned behind the semantic plane."""
 
   AHEAD = 4        # images decoded ahead of the one on the GPU
 
@@ -367,7 +413,11 @@ class ListImageSource(ImageSource):
     rgb, semantic, _ = self.dataset.read(index)
     plan = transforms.plan_views(rgb.shape[0], rgb.shape[1], self.scales, self.is_flip, self.crop_size, self.image_size,
                                  name=self.dataset.image_paths[index])
-    return rgb, semantic, inference.view_records(plan)
+    cams = None
+    if self.with_cams:
+      name = output_name(self.dataset.image_paths[index]).replace('.png', '.npy')
+      cams = read_cam_file(self.with_cams, name, rgb.shape[:2], self.num_classes)
+    return rgb, semantic, inference.view_records(plan), cams
 
   def _stage(self, nbytes):
     slot = self.staging[self.turn]
@@ -380,31 +430,39 @@ class ListImageSource(ImageSource):
     return slot
 
   def image(self, index, decoded):
-    """On the main thread: pack (records, RGB, semantic plane), one copy, one launch."""
+    """On the main thread: pack (records, RGB, semantic plane, CAM planes), one copy, one launch."""
     from spml_amd import inference
-    rgb, semantic, records = decoded
+    rgb, semantic, records, cams = decoded
     h, w = rgb.shape[:2]
     rec_bytes = (records.nbytes + 15) // 16 * 16
     sem_at = rec_bytes + (3 * h * w + 15) // 16 * 16
-    total = sem_at + (h * w if semantic is not None else 0)
+    total = sem_end = sem_at + (h * w if semantic is not None else 0)
+    if cams is not None and len(cams[0]):
+      cam_at = (sem_end + 15) // 16 * 16
+      total = cam_at + 4 * h * w * len(cams[1])
     stage, event = self._stage(total)
     host = stage.numpy()
     host[:records.nbytes] = records.view(np.uint8).reshape(-1)
     host[rec_bytes:rec_bytes + 3 * h * w] = rgb.reshape(-1)
     if semantic is not None:
-      host[sem_at:total] = semantic.reshape(-1)
+      host[sem_at:sem_end] = semantic.reshape(-1)
+    if total > sem_end:
+      for i, plane in enumerate(cams[1]):
+        host[cam_at + 4 * h * w * i:cam_at + 4 * h * w * (i + 1)] = plane.reshape(-1).view(np.uint8)
     packed = torch.empty((total,), dtype=torch.uint8, device=self.device)
     packed.copy_(stage[:total], non_blocking=True)
     event.record()
     rgb_dev = packed[rec_bytes:rec_bytes + 3 * h * w].view(h, w, 3)
-    sem_dev = packed[sem_at:total].view(h, w) if semantic is not None else None
+    sem_dev = packed[sem_at:sem_end].view(h, w) if semantic is not None else None
+    cam_dev = packed[cam_at:total].view(torch.float32).view(-1, h, w) if total > sem_end else None
     views, labels = inference.views_from_records(rgb_dev, records, packed[:records.nbytes], self.mean, self.std,
                                                  sem_dev if self.with_labels else None)
     guide = None
     if self.with_guide:
       guide = inference.crf_guide(rgb_dev, self.config.network.pixel_means, self.config.network.pixel_stds,
                                   views[0][1] if self.single_view else None)
-    return SourceImage(index, output_name(self.dataset.image_paths[index]), (h, w), views, labels, sem_dev, guide)
+    return SourceImage(index, output_name(self.dataset.image_paths[index]), (h, w), views, labels, sem_dev, guide, cam_dev,
+                       None if cams is None else cams[0])
 
   def timed(self, per_image):
     n, done = len(self), 0
@@ -534,22 +592,55 @@ def crf_stage(config, args, crf):
   return CrfStage(config, args) if crf or (crf is None and args.crf) else None
 
 
-def run_pseudo_softmax(description, scales, combine, walk_steps, argv=None, file_lists='labels', crf=False):
+def run_pseudo_softmax(description, scales, combine, walk_steps, argv=None, file_lists='labels', crf=False, cam_alpha=None):
   """`pseudo_softmax.py`, `pseudo_softmaxrw.py` and `pseudo_softmaxrw_crf.py` (`pseudo_softmaxrw_crf.py:33-204` of
   twke18/SPML): every image through `spml_amd.inference.pseudo_labels_softmax`; the programs differ in three constants
   (scales of the image pyramid, how the views' class scores are combined, squarings of the transition matrix) and in
   `crf` (see `crf_stage`).  The label map of an image (synthetic, or the file's own: a data list needs its label columns)
   gives the image tags (:102-106) and the mIoU of the JSON line.  Without the CRF the labels written are those of :176;
   with it every image goes through `pseudo_labels_softmax_crf` on the source's guide image (:172-187) and the
-  refined labels of :187 are written, the labels of :176 scored next to them."""
+  refined labels of :187 are written, the labels of :176 scored next to them.
+
+  `cam_alpha` (the program's ALPHA; `pseudo_softmaxrw.py` alone passes one): with `--cam_dir` the program is the CAM walk
+  of `pseudo_camrw_crf.py:37-198` on either kind of `--data_list` -- the two share the flip pair at scale 1,
+  the affinity, the squarings and the tail, and differ in where the class maps come from.  The embedding network alone is
+  loaded (:76-91), every image comes with the planes of its CAM file (`ImageSource(with_cams=...)`) and goes through
+  `pseudo_labels_cam` / `pseudo_labels_cam_crf`; the reference never uses the label map there (`sem_labs`, :104), so a
+  list needs no label columns and is scored only when it has them; the report carries `cam_dir`, `alpha` and `cam_path`
+  in place of `combine` and `head_path`.  Without `--cam_dir` nothing of this is reached."""
   from spml_amd import inference
   api = 'pseudo_labels_softmax_crf' if crf else 'pseudo_labels_softmax'
+  if cam_alpha is not None:
+    listed = file_lists
+    file_lists = lambda args: 'images' if args.cam_dir else listed
   config, args, device = parse(description, argv, api, file_lists=file_lists, crf_option=crf is None)
+  cam_dir = args.cam_dir if cam_alpha is not None else None
   semantic_dir = output_dir(args, 'semantic_gray')
   stage = crf_stage(config, args, crf)                                                            # :66-73
-  source = ImageSource.for_program(config, args, device, scales, True, api, with_guide=stage is not None)   # :109-125
-  embedding_model, prediction_model, path = load_models(config, args, device, 'softmax_classifier')
+  source = ImageSource.for_program(config, args, device, scales, True, api, with_guide=stage is not None,
+                                   with_cams=cam_dir)                                             # :109-125
+  embedding_model, prediction_model, path = load_models(config, args, device, None if cam_dir else 'softmax_classifier')
+  num_classes = geometry(config)[0]
   out = None
+
+  def one_cam(image):
+    nonlocal out
+    if stage is None:
+      out = inference.pseudo_labels_cam(embedding_model, image.views, image.image_hw, image.cam_planes, image.cam_classes,
+                                        num_classes, alpha=cam_alpha, walk_steps=walk_steps)
+      source.emit(image, out['semantic_prediction'], semantic_dir)
+    else:
+      out = inference.pseudo_labels_cam_crf(embedding_model, image.views, image.image_hw, image.cam_planes,
+                                            image.cam_classes, num_classes, image.guide, stage, alpha=cam_alpha,
+                                            walk_steps=walk_steps)
+      source.emit_refined(image, out['semantic_prediction'], out['semantic_prediction_before_crf'], semantic_dir)
+
+  if cam_dir:
+    done, seconds = source.timed(one_cam)
+    report(done, seconds, **source.scores(), **crf_report(stage, source, seconds), scales=list(scales), is_flip=True,
+           cam_dir=cam_dir, alpha=cam_alpha, walk_steps=walk_steps, cam_path=out['cam_path'], snapshot=path,
+           save_dir=semantic_dir, **source.fields())
+    return
 
   def one(image):
     nonlocal out
@@ -618,18 +709,33 @@ def run_softmax(description, scales, is_flip, argv=None, single_view=False, file
          snapshot=path, save_dir=semantic_dir, **source.fields())
 
 
-def run_knn(description, scales, is_flip, argv=None, single_view=False, file_lists='images', crf=None):
+def run_knn(description, scales, is_flip, argv=None, single_view=False, file_lists='images', crf=None, pseudo_tags=None):
   """The four kNN label-inference programs: `inference.py` / `inference_crf.py` (`single_view`: one view at
   `test.image_size`, inference_crf.py:35-280) and `inference_msc.py` / `inference_crf_msc.py` (the flip pairs of `scales`
   through `predict_knn_multiscale`, inference_crf_msc.py:35-283), against the memory bank of `--semantic_memory_dir`
   (`memory_bank_dir`).  `crf`: see `crf_stage`.  With the CRF a single view goes through the fused
   `predict_knn_full_resolution_crf` (votes gathered inside the CRF's first kernel), the view mean of the
-  votes of a multi-view program through `dense_crf_refine` (:251-260), on the source's guide image."""
+  votes of a multi-view program through `dense_crf_refine` (:251-260), on the source's guide image.
+
+  `pseudo_tags`: `(scales, floor)` in the program that takes `--pseudo_tags` (`inference_msc.py` alone).  With the option
+  the run is the tag recipe's kNN pseudo-label step (`pseudo_inference_crf_msc.py:143-275`) on either kind of
+  `--data_list`: those scales, the tags of the image's label map (a list needs its label columns) and
+  `pseudo_labels_knn_multiscale`; with `--crf` the tag-normalised map is what the CRF stage refines (:265-273).  The
+  report gains `normalize_path` and, on synthetic images, `instance_mIoU` as `pseudo_inference_msc.py` reports it; the
+  instance-weighted IoU of a list is `benchmark_by_instance.py`'s on the written directory."""
   from spml_amd import inference
   api = 'predict_full_resolution' if single_view else 'predict_knn_multiscale'
   if crf and single_view:
     api = 'predict_knn_full_resolution_crf'
-  config, args, device = parse(description, argv, api, file_lists=file_lists, crf_option=crf is None)
+  if pseudo_tags is not None:
+    listed = file_lists
+    file_lists = lambda args: 'labels' if args.pseudo_tags else listed
+  config, args, device = parse(description, argv, api, file_lists=file_lists, crf_option=crf is None,
+                               pseudo_tags_option=pseudo_tags is not None)
+  tagged = pseudo_tags is not None and args.pseudo_tags
+  floor = None
+  if tagged:
+    scales, floor = pseudo_tags
   semantic_dir = output_dir(args, 'semantic_gray')
   embedding_model, prediction_model, path = load_models(config, args, device, 'segsort')
   num_classes, crop_size, stride, _ = geometry(config)
@@ -640,18 +746,30 @@ def run_knn(description, scales, is_flip, argv=None, single_view=False, file_lis
   prototypes, prototype_labels = load_bank(memory_dir, config, device)
   ignore_index = config.dataset.semantic_ignore_index
   out, views = None, []
+  by_instance = None
+  if tagged and not reads_file_list(args):
+    from spml_amd.utils.general import metrics
+    by_instance = metrics.InstanceIoU(num_classes)
 
   def one(image):
     nonlocal out, views
     views = image.views
     if not single_view:
-      out = inference.predict_knn_multiscale(embedding_model, prediction_model, views, image.image_hw, crop_size, stride,
-                                             prototypes, prototype_labels, num_classes)
-      if stage is None:
-        source.emit(image, out['semantic_prediction'], semantic_dir)
+      if tagged:
+        out = inference.pseudo_labels_knn_multiscale(embedding_model, prediction_model, views, image.image_hw, crop_size,
+                                                     stride, prototypes, prototype_labels, num_classes, source.tags(image),
+                                                     floor=floor, return_prob=stage is not None)
       else:
-        refined = stage(image.guide, out['semantic_prob'])
-        source.emit_refined(image, refined['semantic_prediction'], out['semantic_prediction'], semantic_dir)
+        out = inference.predict_knn_multiscale(embedding_model, prediction_model, views, image.image_hw, crop_size, stride,
+                                               prototypes, prototype_labels, num_classes)
+      written = out['semantic_prediction']
+      if stage is None:
+        source.emit(image, written, semantic_dir)
+      else:
+        written = stage(image.guide, out['semantic_prob'])['semantic_prediction']
+        source.emit_refined(image, written, out['semantic_prediction'], semantic_dir)
+      if by_instance is not None:
+        by_instance.update(written, image.label, image.instance.clamp(0, 255))
       return
     padded, valid_hw, _ = views[0]
     if stage is None:
@@ -668,6 +786,10 @@ def run_knn(description, scales, is_flip, argv=None, single_view=False, file_lis
   more = {} if single_view else {'views': len(views), 'combine_path': out['combine_path']}
   if single_view and stage is not None:
     more['votes_path'] = out['votes_path']
+  if tagged:
+    more['normalize_path'] = out['normalize_path']
+  if by_instance is not None:
+    more['instance_mIoU'] = round(by_instance.result()['mean_iou'], 4)
   report(done, seconds, **source.scores(), **more, **crf_report(stage, source, seconds),
          memory_prototypes=int(prototypes.shape[0]), snapshot=path, semantic_memory_dir=memory_dir, save_dir=semantic_dir,
          **source.fields())
