@@ -5,6 +5,7 @@ below passes raw `data_ptr()`s and `torch.cuda.current_stream().cuda_stream` to
 the C-ABI.  There is no CPU fallback: if the library is missing or a tensor is
 not on a GPU the call raises."""
 import ctypes
+import functools
 import os
 import threading
 from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void_p
@@ -977,19 +978,22 @@ def _ptr_any(t, allow_none=False):
   return c_void_p(t.data_ptr())
 
 
+def _stream_workspace(cache, need, device):
+  """Scratch of at least `need` bytes, cached per (device, current stream): reuse is stream-ordered (every call
+  consumes its scratch before the next one on the same stream overwrites it), and two streams never share a buffer."""
+  key = (device.index, torch.cuda.current_stream().cuda_stream)
+  ws = cache.get(key)
+  if ws is None or ws.numel() < need:
+    ws = cache[key] = workspace(need, device)
+  return ws
+
+
 _bn_ws = {}
 
 
 def _bn_workspace(r, c, device):
-  """Cached scratch for the batch-norm partial sums (stream-ordered reuse: every call consumes its
-  partials before the next one on the same stream overwrites them)."""
-  need = lib().spml_bn_workspace_bytes(r, c)
-  key = (device.index, torch.cuda.current_stream().cuda_stream)
-  ws = _bn_ws.get(key)
-  if ws is None or ws.numel() < need:
-    ws = workspace(need, device)
-    _bn_ws[key] = ws
-  return ws
+  """Cached scratch for the batch-norm partial sums."""
+  return _stream_workspace(_bn_ws, lib().spml_bn_workspace_bytes(r, c), device)
 
 
 def bn_act_fwd(x, residual, gamma, beta, running_mean, running_var, momentum, eps, relu):
@@ -1104,20 +1108,25 @@ def hl8_weight(w):
   return fwd, Hl8(tr, fwd.bound, cin, taps * cout)
 
 
+@functools.lru_cache(maxsize=None)         # (a pure function of the three numbers, asked per unit and forward)
 def conv_hl8_supported(k, n, taps):
   return bool(lib().spml_conv_hl8_supported(int(k), int(n), int(taps)))
 
 
-def conv_hl8(a, b, n_img, h, w, taps, dilation=1, addend=None, addend_mask=None):
-  """out [n_img, N, h, w] (channels-last fp32) = conv(a, b): a Hl8 [n_img*h*w, K], b Hl8 [N, taps*K]."""
+def _conv_operands(who, a, b, n_img, h, w, taps):
+  """Head of the conv_hl8* wrappers (`who`): a Hl8 [n_img*h*w, K], b Hl8 [N, taps*K] -> (K, N, the output
+  [n_img, N, h, w] channels-last fp32, the four operand pointers a, a_bound, b, b_bound)."""
   k, n = a.channels, b.rows
   if a.rows != n_img * h * w or b.channels != taps * k:
-    raise SpmlHipError('conv_hl8: operand shapes do not match')
-  out = torch.empty((n_img, n, h, w), dtype=torch.float32, device=a.data.device,
-                    memory_format=torch.channels_last)
-  check(lib().spml_conv_hl8_f32(ptr(a.data), c_void_p(a.bound.data_ptr()), ptr(b.data),
-                                c_void_p(b.bound.data_ptr()), _ptr_any(addend, True), _dp(addend_mask), _ptr_any(out),
-                                n_img, h, w,
+    raise SpmlHipError('%s: operand shapes do not match' % who)
+  out = torch.empty((n_img, n, h, w), dtype=torch.float32, device=a.data.device, memory_format=torch.channels_last)
+  return k, n, out, (ptr(a.data), c_void_p(a.bound.data_ptr()), ptr(b.data), c_void_p(b.bound.data_ptr()))
+
+
+def conv_hl8(a, b, n_img, h, w, taps, dilation=1, addend=None, addend_mask=None):
+  """out [n_img, N, h, w] (channels-last fp32) = conv(a, b): a Hl8 [n_img*h*w, K], b Hl8 [N, taps*K]."""
+  k, n, out, operands = _conv_operands('conv_hl8', a, b, n_img, h, w, taps)
+  check(lib().spml_conv_hl8_f32(*operands, _ptr_any(addend, True), _dp(addend_mask), _ptr_any(out), n_img, h, w,
                                 k, n, taps, dilation, stream_ptr()), 'spml_conv_hl8_f32')
   return out
 
@@ -1133,21 +1142,15 @@ class ChunkStats(object):
 def conv_hl8_stats(a, b, n_img, h, w, taps, dilation=1):
   """conv_hl8 whose epilogue also leaves the chunk statistics of the output -> (out, ChunkStats), or
   (out, None) where the launch has no per-tile column owner (narrow outputs).  SPML_CONV_BN_STATS=0: never."""
-  import ctypes
-  k, n = a.channels, b.rows
   chunks, rows = ctypes.c_int(0), ctypes.c_int(0)
   if os.environ.get('SPML_CONV_BN_STATS') == '0' or lib().spml_conv_hl8_stats_layout(
-      n_img, h, w, k, n, taps, ctypes.byref(chunks), ctypes.byref(rows)) != 0:
+      n_img, h, w, a.channels, b.rows, taps, ctypes.byref(chunks), ctypes.byref(rows)) != 0:
     return conv_hl8(a, b, n_img, h, w, taps, dilation), None
-  if a.rows != n_img * h * w or b.channels != taps * k:
-    raise SpmlHipError('conv_hl8_stats: operand shapes do not match')
-  dev = a.data.device
-  out = torch.empty((n_img, n, h, w), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
-  st = torch.empty((4, chunks.value, n), dtype=torch.float32, device=dev)
-  bound = _f32(1, dev)
-  check(lib().spml_conv_hl8_stats_f32(ptr(a.data), c_void_p(a.bound.data_ptr()), ptr(b.data),
-                                      c_void_p(b.bound.data_ptr()), _ptr_any(out), _dp(st), _dp(bound), n_img, h, w,
-                                      k, n, taps, dilation, stream_ptr()), 'spml_conv_hl8_stats_f32')
+  k, n, out, operands = _conv_operands('conv_hl8_stats', a, b, n_img, h, w, taps)
+  st = torch.empty((4, chunks.value, n), dtype=torch.float32, device=out.device)
+  bound = _f32(1, out.device)
+  check(lib().spml_conv_hl8_stats_f32(*operands, _ptr_any(out), _dp(st), _dp(bound), n_img, h, w, k, n, taps,
+                                      dilation, stream_ptr()), 'spml_conv_hl8_stats_f32')
   return out, ChunkStats(st, chunks.value, rows.value, bound)
 
 
@@ -1157,32 +1160,26 @@ def conv_hl8_bwd_stats(a, b, n_img, h, w, taps, dilation, bn_x, relu_mask, bn_me
   where the launch has no per-tile column owner (narrow outputs) or there is no mask.  SPML_CONV_BN_BWD_STATS=0:
   never.  addend (+ addend_mask): added to the result as conv_hl8 does, before the sums are taken (a unit's last data
   gradient in front of the bn3 of the unit below); launches with the chunked accumulation take the plain route."""
-  import ctypes
   k, n = a.channels, b.rows
   chunks, rows = ctypes.c_int(0), ctypes.c_int(0)
   if relu_mask is None or os.environ.get('SPML_CONV_BN_BWD_STATS') == '0' or lib().spml_conv_hl8_bwd_stats_layout(
       n_img, h, w, k, n, taps, ctypes.byref(chunks), ctypes.byref(rows)) != 0 or \
       (addend is not None and 'chunk' in conv_hl8_path_name('bwd_stats', n_img, h, w, k, n, taps)):
     return conv_hl8(a, b, n_img, h, w, taps, dilation, addend, addend_mask), None
-  if a.rows != n_img * h * w or b.channels != taps * k or bn_x.numel() != a.rows * n or \
-      relu_mask.numel() != a.rows * (n // 4) or bn_mean.numel() != n or \
+  if bn_x.numel() != a.rows * n or relu_mask.numel() != a.rows * (n // 4) or bn_mean.numel() != n or \
       (addend is not None and addend.numel() != a.rows * n) or (addend is None and addend_mask is not None) or \
       (addend_mask is not None and addend_mask.numel() != a.rows * (n // 4)):
     raise SpmlHipError('conv_hl8_bwd_stats: operand shapes do not match')
-  dev = a.data.device
-  out = torch.empty((n_img, n, h, w), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
-  st = torch.empty((3, chunks.value, n), dtype=torch.float32, device=dev)
-  bound = _f32(1, dev)
+  k, n, out, operands = _conv_operands('conv_hl8_bwd_stats', a, b, n_img, h, w, taps)
+  st = torch.empty((3, chunks.value, n), dtype=torch.float32, device=out.device)
+  bound = _f32(1, out.device)
+  args = operands + (_ptr_any(out), _ptr_any(bn_x), _dp(relu_mask), _dp(bn_mean), _dp(st), _dp(bound), n_img, h, w,
+                     k, n, taps, dilation)
   if addend is None:
-    check(lib().spml_conv_hl8_bwd_stats_f32(ptr(a.data), c_void_p(a.bound.data_ptr()), ptr(b.data),
-                                            c_void_p(b.bound.data_ptr()), _ptr_any(out), _ptr_any(bn_x), _dp(relu_mask),
-                                            _dp(bn_mean), _dp(st), _dp(bound), n_img, h, w, k, n, taps, dilation,
-                                            stream_ptr()), 'spml_conv_hl8_bwd_stats_f32')
+    check(lib().spml_conv_hl8_bwd_stats_f32(*args, stream_ptr()), 'spml_conv_hl8_bwd_stats_f32')
   else:
-    check(lib().spml_conv_hl8_bwd_stats_addend_f32(
-        ptr(a.data), c_void_p(a.bound.data_ptr()), ptr(b.data), c_void_p(b.bound.data_ptr()), _ptr_any(out),
-        _ptr_any(bn_x), _dp(relu_mask), _dp(bn_mean), _dp(st), _dp(bound), n_img, h, w, k, n, taps, dilation,
-        _ptr_any(addend), _dp(addend_mask), stream_ptr()), 'spml_conv_hl8_bwd_stats_addend_f32')
+    check(lib().spml_conv_hl8_bwd_stats_addend_f32(*args, _ptr_any(addend), _dp(addend_mask), stream_ptr()),
+          'spml_conv_hl8_bwd_stats_addend_f32')
   return out, ChunkStats(st, chunks.value, rows.value, bound)
 
 
@@ -1209,6 +1206,7 @@ def conv_wgrad_splits(n_img, h, w, k, n, taps_or_branches, pyramid=False):
                                       int(bool(pyramid)))
 
 
+@functools.lru_cache(maxsize=None)
 def conv_wgrad_hl8_supported(k, n, taps):
   return bool(lib().spml_conv_wgrad_hl8_supported(int(k), int(n), int(taps)))
 
@@ -1221,12 +1219,7 @@ def conv_wgrad_hl8(dy, x, n_img, h, w, taps, dilation=1):
   n, k = dy.channels, x.channels
   if dy.rows != n_img * h * w or x.rows != dy.rows:
     raise SpmlHipError('conv_wgrad_hl8: operand shapes do not match')
-  need = lib().spml_conv_wgrad_workspace_bytes(n_img, h, w, k, n, taps)
-  key = (dy.data.device.index, torch.cuda.current_stream().cuda_stream)
-  ws = _wgrad_ws.get(key)
-  if ws is None or ws.numel() < need:
-    ws = workspace(need, dy.data.device)
-    _wgrad_ws[key] = ws
+  ws = _stream_workspace(_wgrad_ws, lib().spml_conv_wgrad_workspace_bytes(n_img, h, w, k, n, taps), dy.data.device)
   side = 3 if taps == 9 else 1
   dw = torch.empty((n, k, side, side), dtype=torch.float32, device=dy.data.device,
                    memory_format=torch.channels_last)
@@ -1250,11 +1243,7 @@ def conv_wgrad_pyramid_hl8(dy, x, n_img, h, w, dilations):
   need = lib().spml_conv_wgrad_pyramid_workspace_bytes(n_img, h, w, k, n, nb)
   if need == 0:
     raise SpmlHipError('conv_wgrad_pyramid_hl8: unsupported shape (K %d, N %d, %d branches)' % (k, n, nb))
-  key = (dy.data.device.index, torch.cuda.current_stream().cuda_stream)
-  ws = _wgrad_ws.get(key)
-  if ws is None or ws.numel() < need:
-    ws = workspace(need, dy.data.device)
-    _wgrad_ws[key] = ws
+  ws = _stream_workspace(_wgrad_ws, need, dy.data.device)
   dw = torch.empty((nb, n, 3, 3, k), dtype=torch.float32, device=dy.data.device)
   dil = (ctypes.c_int * nb)(*[int(d) for d in dilations])
   check(lib().spml_conv_wgrad_pyramid_hl8_f32(ptr(dy.data), c_void_p(dy.bound.data_ptr()), ptr(x.data),
@@ -1379,13 +1368,13 @@ def bn_fwd_hl8(x, rows, channels, residual, residual_bound, gamma, beta, running
         _dp(residual_bound), rows, channels, ptr(gamma, torch.float32), ptr(beta, torch.float32), _dp(running_mean),
         _dp(running_var), float(momentum), float(eps), int(bool(relu)), _ptr_any(y, True), _dp(yh), _dp(bound),
         _dp(mask), _dp(st[0]), _dp(st[1]), _dp(st[2]), _dp(st[3]), stream_ptr()), 'spml_bn_fwd_hl8_chunks_f32')
-    return y, (Hl8(yh, bound, rows, channels) if want_hl8 else None), bound, mask, (st[0], st[1], st[2], st[3])
-  ws = _bn_workspace(rows, channels, x.device)
-  check(lib().spml_bn_fwd_hl8_f32(
-      _ptr_any(x), _ptr_any(residual, True), _dp(residual_bound), rows, channels, ptr(gamma, torch.float32),
-      ptr(beta, torch.float32), _dp(running_mean), _dp(running_var), float(momentum), float(eps), int(bool(relu)),
-      _ptr_any(y, True), _dp(yh), _dp(bound), _dp(mask), _dp(st[0]), _dp(st[1]), _dp(st[2]), _dp(st[3]), ptr(ws),
-      ws.numel(), stream_ptr()), 'spml_bn_fwd_hl8_f32')
+  else:
+    ws = _bn_workspace(rows, channels, x.device)
+    check(lib().spml_bn_fwd_hl8_f32(
+        _ptr_any(x), _ptr_any(residual, True), _dp(residual_bound), rows, channels, ptr(gamma, torch.float32),
+        ptr(beta, torch.float32), _dp(running_mean), _dp(running_var), float(momentum), float(eps), int(bool(relu)),
+        _ptr_any(y, True), _dp(yh), _dp(bound), _dp(mask), _dp(st[0]), _dp(st[1]), _dp(st[2]), _dp(st[3]), ptr(ws),
+        ws.numel(), stream_ptr()), 'spml_bn_fwd_hl8_f32')
   return y, (Hl8(yh, bound, rows, channels) if want_hl8 else None), bound, mask, (st[0], st[1], st[2], st[3])
 
 
@@ -1403,14 +1392,14 @@ def bn_bwd_hl8(dy, relu_mask, x, rows, channels, saved, gamma, want_dres=False, 
         rows, channels, _dp(mean), _dp(invstd), ptr(gamma, torch.float32), _dp(cmax), _dp(cmin), _dp(dgb[0]),
         _dp(dgb[1]), _dp(dgb[2]), c_void_p(0), _dp(dxh), _dp(bound), _ptr_any(dres, True), stream_ptr()),
           'spml_bn_bwd_hl8_chunks_f32')
-    return Hl8(dxh, bound, rows, channels), dres, dgb[0], dgb[1]
-  bound = _f32(1, dy.device)
-  dgb = torch.empty((2, channels), dtype=torch.float32, device=dy.device)
-  ws = _bn_workspace(rows, channels, dy.device)
-  check(lib().spml_bn_bwd_hl8_f32(
-      _ptr_any(dy), c_void_p(0), _dp(relu_mask), _ptr_any(x), rows, channels, _dp(mean), _dp(invstd),
-      ptr(gamma, torch.float32), _dp(cmax), _dp(cmin), _dp(dgb[0]), _dp(dgb[1]), c_void_p(0), _dp(dxh), _dp(bound),
-      _ptr_any(dres, True), ptr(ws), ws.numel(), stream_ptr()), 'spml_bn_bwd_hl8_f32')
+  else:
+    bound = _f32(1, dy.device)
+    dgb = torch.empty((2, channels), dtype=torch.float32, device=dy.device)
+    ws = _bn_workspace(rows, channels, dy.device)
+    check(lib().spml_bn_bwd_hl8_f32(
+        _ptr_any(dy), c_void_p(0), _dp(relu_mask), _ptr_any(x), rows, channels, _dp(mean), _dp(invstd),
+        ptr(gamma, torch.float32), _dp(cmax), _dp(cmin), _dp(dgb[0]), _dp(dgb[1]), c_void_p(0), _dp(dxh), _dp(bound),
+        _ptr_any(dres, True), ptr(ws), ws.numel(), stream_ptr()), 'spml_bn_bwd_hl8_f32')
   return Hl8(dxh, bound, rows, channels), dres, dgb[0], dgb[1]
 
 
@@ -1430,7 +1419,6 @@ def conv_hl8_pyramid_dgrad(dy, weights, dilations, n_img, h, w):
     check(lib().spml_hl8_weight_transposed_into_f32(_ptr_any(wt), cout, 9, cin, _dp(bound), ptr(b), 9 * groups, 9 * g,
                                                     stream_ptr()), 'spml_hl8_weight_transposed_into_f32')
   out = torch.empty((n_img, cin, h, w), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
-  import ctypes
   dil = (ctypes.c_int * 4)(*([int(d) for d in dilations] + [1] * (4 - groups)))
   check(lib().spml_conv_hl8_pyramid_f32(ptr(dy.data), _dp(dy.bound), ptr(b), _dp(bound), c_void_p(0), c_void_p(0),
                                         _ptr_any(out), n_img, h, w, cout, cin, groups, dil, stream_ptr()),
@@ -1441,7 +1429,6 @@ def conv_hl8_pyramid_dgrad(dy, weights, dilations, n_img, h, w):
 def conv_hl8_pyramid_forward(x, weights, biases, dilations, n_img, h, w):
   """sum_g conv2d(x, weights[g], biases[g], dilation = padding = dilations[g]) for 3x3 weights
   [Cout, Cin, 3, 3] in one launch (x: Hl8 [R, Cin]) -> fp32 [n_img, Cout, h, w]."""
-  import ctypes
   groups = len(weights)
   cout, cin = weights[0].shape[0], weights[0].shape[1]
   dev = x.data.device
@@ -1472,7 +1459,6 @@ def conv_hl8_pyramid_forward_gemm(x, weights, biases, dilations, n_img, h, w):
   with 9 * branches * Cout columns (z[r][tap * Cout + n] = x[r] . w_tap[n]: x is streamed once per 256 columns
   instead of once per tap) + `spml_conv_tap_gather_f32`, which adds every output pixel's taps from their shifted
   rows of z in a fixed order."""
-  import ctypes
   groups = len(weights)
   cout, cin = weights[0].shape[0], weights[0].shape[1]
   dev = x.data.device
@@ -1506,7 +1492,6 @@ def conv_hl8_pyramid_forward_gemm(x, weights, biases, dilations, n_img, h, w):
 def hl8_weight_set(weights):
   """[(forward operand, data-gradient operand)] of up to four conv weights [Cout, Cin, kh, kw] in two
   launches (one unit's weights); every weight has its own bound / scale."""
-  import ctypes
   n = len(weights)
   dev = weights[0].device
   wl = [wt.detach().contiguous(memory_format=torch.channels_last) for wt in weights]
@@ -1528,15 +1513,11 @@ def hl8_weight_set(weights):
 
 def conv_hl8_affine(a, b, bias, n_img, h, w, taps, dilation=1, addend=None, relu=True, want_hl8=True):
   """Inference: act(conv(a, b) + bias [+ addend]) -> (out fp32 channels-last, Hl8 of it or None)."""
-  k, n = a.channels, b.rows
-  if a.rows != n_img * h * w or b.channels != taps * k:
-    raise SpmlHipError('conv_hl8_affine: operand shapes do not match')
-  dev = a.data.device
-  out = torch.empty((n_img, n, h, w), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
-  bound = _f32(1, dev) if want_hl8 else None
-  check(lib().spml_conv_hl8_affine_f32(ptr(a.data), _dp(a.bound), ptr(b.data), _dp(b.bound), ptr(bias, torch.float32),
-                                       _ptr_any(addend, True), int(bool(relu)), _ptr_any(out), _dp(bound), n_img, h, w,
-                                       k, n, taps, dilation, stream_ptr()), 'spml_conv_hl8_affine_f32')
+  k, n, out, operands = _conv_operands('conv_hl8_affine', a, b, n_img, h, w, taps)
+  bound = _f32(1, out.device) if want_hl8 else None
+  check(lib().spml_conv_hl8_affine_f32(*operands, ptr(bias, torch.float32), _ptr_any(addend, True), int(bool(relu)),
+                                       _ptr_any(out), _dp(bound), n_img, h, w, k, n, taps, dilation, stream_ptr()),
+        'spml_conv_hl8_affine_f32')
   return out, (hl8_from_f32(out, bound=bound) if want_hl8 else None)
 
 

@@ -1275,22 +1275,29 @@ extern "C" int spml_conv_hl8_supported(int K, int N, int taps) {
   return (taps == 1 || taps == 9) && K > 0 && (K & 15) == 0 && N > 0 && (N & 63) == 0;
 }
 
+// The fields every entry point fills alike: the operands with their bounds, the output and the geometry.
+static ConvArgs conv_args(const void* a, const float* a_bound, const void* b, const float* b_bound, float* out,
+                          int n_img, int H, int W, int K, int N, int taps, int dil) {
+  ConvArgs c{};
+  c.a = static_cast<const uint4*>(a);
+  c.b = static_cast<const uint4*>(b);
+  c.a_bound = a_bound;
+  c.b_bound = b_bound;
+  c.out = out;
+  c.R = (int64_t)n_img * H * W;
+  c.H = H; c.W = W; c.K = K; c.N = N; c.taps = taps; c.dil = dil;
+  return c;
+}
+
 extern "C" int spml_conv_hl8_f32(const void* a, const float* a_bound, const void* b, const float* b_bound,
                                  const float* addend, const unsigned char* addend_mask, float* out, int n_img,
                                  int H, int W, int K, int N, int taps, int dilation, void* stream) {
   if (!a || !b || !out || n_img <= 0 || H <= 0 || W <= 0 || dilation < 1) return SPML_ERR_INVALID_ARG;
   if (!spml_conv_hl8_supported(K, N, taps) || !al16(a) || !al16(b) || !al16(out) || (addend && !al16(addend)))
     return SPML_ERR_UNSUPPORTED;
-  ConvArgs c{};
-  c.a = static_cast<const uint4*>(a);
-  c.b = static_cast<const uint4*>(b);
-  c.a_bound = a_bound;
-  c.b_bound = b_bound;
+  ConvArgs c = conv_args(a, a_bound, b, b_bound, out, n_img, H, W, K, N, taps, dilation);
   c.addend = addend;
   c.addend_mask = addend ? addend_mask : nullptr;
-  c.out = out;
-  c.R = (int64_t)n_img * H * W;
-  c.H = H; c.W = W; c.K = K; c.N = N; c.taps = taps; c.dil = dilation;
   hipStream_t s = (hipStream_t)stream;
   // long reductions (K * taps >= 4096: the 3x3 convolutions of res5): the accumulation chain is cut every
   // 1024 k, so that its rounding error stays at the level of the fp32 library's split-K kernels
@@ -1324,16 +1331,9 @@ extern "C" int spml_conv_hl8_stats_f32(const void* a, const float* a_bound, cons
   if (spml_conv_hl8_stats_layout(n_img, H, W, K, N, taps, &chunks, &rows) != SPML_OK || !al16(a) || !al16(b) ||
       !al16(out))
     return SPML_ERR_UNSUPPORTED;
-  ConvArgs c{};
-  c.a = static_cast<const uint4*>(a);
-  c.b = static_cast<const uint4*>(b);
-  c.a_bound = a_bound;
-  c.b_bound = b_bound;
-  c.out = out;
+  ConvArgs c = conv_args(a, a_bound, b, b_bound, out, n_img, H, W, K, N, taps, dilation);
   c.stats = chunk_stats;
   c.stats_zero = zero_me;
-  c.R = (int64_t)n_img * H * W;
-  c.H = H; c.W = W; c.K = K; c.N = N; c.taps = taps; c.dil = dilation;
   hipStream_t s = (hipStream_t)stream;
   const ConvRoute r = conv_route(kEntryStats, c.R, K, N, taps, 1, false);
   if (r.tile_rows != rows) return SPML_ERR_UNSUPPORTED;       // (a switch changed between the two reads)
@@ -1347,34 +1347,39 @@ extern "C" int spml_conv_hl8_bwd_stats_layout(int n_img, int H, int W, int K, in
   return spml_conv_hl8_stats_layout(n_img, H, W, K, N, taps, chunks, chunk_rows);
 }
 
-extern "C" int spml_conv_hl8_bwd_stats_f32(const void* a, const float* a_bound, const void* b, const float* b_bound,
-                                           float* out, const float* bn_x, const unsigned char* relu_mask,
-                                           const float* bn_mean, float* chunk_stats, float* zero_me, int n_img, int H,
-                                           int W, int K, int N, int taps, int dilation, void* stream) {
-  if (!a || !b || !out || !bn_x || !relu_mask || !bn_mean || !chunk_stats || n_img <= 0 || H <= 0 || W <= 0 ||
-      dilation < 1)
+// Body of both bwd_stats entry points.  with_addend: the addend is required, has to be aligned, goes into the launch
+// with its mask, and launches with the chunked accumulation are refused.
+static int conv_bwd_stats(const void* a, const float* a_bound, const void* b, const float* b_bound, float* out,
+                          const float* bn_x, const unsigned char* relu_mask, const float* bn_mean, float* chunk_stats,
+                          float* zero_me, int n_img, int H, int W, int K, int N, int taps, int dilation,
+                          bool with_addend, const float* addend, const unsigned char* addend_mask, void* stream) {
+  if (!a || !b || !out || !bn_x || !relu_mask || !bn_mean || !chunk_stats || (with_addend && !addend) || n_img <= 0 ||
+      H <= 0 || W <= 0 || dilation < 1)
     return SPML_ERR_INVALID_ARG;
   int chunks = 0, rows = 0;
   if (spml_conv_hl8_bwd_stats_layout(n_img, H, W, K, N, taps, &chunks, &rows) != SPML_OK || !al16(a) || !al16(b) ||
-      !al16(out) || !al16(bn_x))
+      !al16(out) || !al16(bn_x) || (with_addend && !al16(addend)))
     return SPML_ERR_UNSUPPORTED;
-  ConvArgs c{};
-  c.a = static_cast<const uint4*>(a);
-  c.b = static_cast<const uint4*>(b);
-  c.a_bound = a_bound;
-  c.b_bound = b_bound;
-  c.out = out;
+  ConvArgs c = conv_args(a, a_bound, b, b_bound, out, n_img, H, W, K, N, taps, dilation);
+  c.addend = addend;
+  c.addend_mask = addend_mask;
   c.bstat_x = bn_x;
   c.bstat_mask = relu_mask;
   c.bstat_mean = bn_mean;
   c.bstats = chunk_stats;
   c.stats_zero = zero_me;
-  c.R = (int64_t)n_img * H * W;
-  c.H = H; c.W = W; c.K = K; c.N = N; c.taps = taps; c.dil = dilation;
-  hipStream_t s = (hipStream_t)stream;
   const ConvRoute r = conv_route(kEntryBwdStats, c.R, K, N, taps, 1, false);
-  if (r.tile_rows != rows) return SPML_ERR_UNSUPPORTED;       // (a switch changed between the two reads)
-  return launch_route(r, c, s);
+  // (other rows: a switch changed between the two reads)
+  if (r.tile_rows != rows || (with_addend && r.chunk)) return SPML_ERR_UNSUPPORTED;
+  return launch_route(r, c, (hipStream_t)stream);
+}
+
+extern "C" int spml_conv_hl8_bwd_stats_f32(const void* a, const float* a_bound, const void* b, const float* b_bound,
+                                           float* out, const float* bn_x, const unsigned char* relu_mask,
+                                           const float* bn_mean, float* chunk_stats, float* zero_me, int n_img, int H,
+                                           int W, int K, int N, int taps, int dilation, void* stream) {
+  return conv_bwd_stats(a, a_bound, b, b_bound, out, bn_x, relu_mask, bn_mean, chunk_stats, zero_me, n_img, H, W, K, N,
+                        taps, dilation, false, nullptr, nullptr, stream);
 }
 
 // ... with an addend (optionally gated by its own ReLU mask bytes), as spml_conv_hl8_f32 applies it: the last data
@@ -1385,32 +1390,8 @@ extern "C" int spml_conv_hl8_bwd_stats_addend_f32(const void* a, const float* a_
                                                   float* chunk_stats, float* zero_me, int n_img, int H, int W, int K,
                                                   int N, int taps, int dilation, const float* addend,
                                                   const unsigned char* addend_mask, void* stream) {
-  if (!a || !b || !out || !bn_x || !relu_mask || !bn_mean || !chunk_stats || !addend || n_img <= 0 || H <= 0 ||
-      W <= 0 || dilation < 1)
-    return SPML_ERR_INVALID_ARG;
-  int chunks = 0, rows = 0;
-  if (spml_conv_hl8_bwd_stats_layout(n_img, H, W, K, N, taps, &chunks, &rows) != SPML_OK || !al16(a) || !al16(b) ||
-      !al16(out) || !al16(bn_x) || !al16(addend))
-    return SPML_ERR_UNSUPPORTED;
-  ConvArgs c{};
-  c.a = static_cast<const uint4*>(a);
-  c.b = static_cast<const uint4*>(b);
-  c.a_bound = a_bound;
-  c.b_bound = b_bound;
-  c.addend = addend;
-  c.addend_mask = addend_mask;
-  c.out = out;
-  c.bstat_x = bn_x;
-  c.bstat_mask = relu_mask;
-  c.bstat_mean = bn_mean;
-  c.bstats = chunk_stats;
-  c.stats_zero = zero_me;
-  c.R = (int64_t)n_img * H * W;
-  c.H = H; c.W = W; c.K = K; c.N = N; c.taps = taps; c.dil = dilation;
-  hipStream_t s = (hipStream_t)stream;
-  const ConvRoute r = conv_route(kEntryBwdStats, c.R, K, N, taps, 1, false);
-  if (r.tile_rows != rows || r.chunk) return SPML_ERR_UNSUPPORTED;
-  return launch_route(r, c, s);
+  return conv_bwd_stats(a, a_bound, b, b_bound, out, bn_x, relu_mask, bn_mean, chunk_stats, zero_me, n_img, H, W, K, N,
+                        taps, dilation, true, addend, addend_mask, stream);
 }
 
 extern "C" int spml_conv_hl8_affine_f32(const void* a, const float* a_bound, const void* b, const float* b_bound,
@@ -1420,18 +1401,11 @@ extern "C" int spml_conv_hl8_affine_f32(const void* a, const float* a_bound, con
   if (!a || !b || !out || n_img <= 0 || H <= 0 || W <= 0 || dilation < 1) return SPML_ERR_INVALID_ARG;
   if (!spml_conv_hl8_supported(K, N, taps) || !al16(a) || !al16(b) || !al16(out) || (addend && !al16(addend)))
     return SPML_ERR_UNSUPPORTED;
-  ConvArgs c{};
-  c.a = static_cast<const uint4*>(a);
-  c.b = static_cast<const uint4*>(b);
-  c.a_bound = a_bound;
-  c.b_bound = b_bound;
+  ConvArgs c = conv_args(a, a_bound, b, b_bound, out, n_img, H, W, K, N, taps, dilation);
   c.bias = bias;
   c.addend = addend;
   c.relu = relu;
-  c.out = out;
   c.out_bound = out_bound;
-  c.R = (int64_t)n_img * H * W;
-  c.H = H; c.W = W; c.K = K; c.N = N; c.taps = taps; c.dil = dilation;
   hipStream_t s = (hipStream_t)stream;
   if (out_bound && hipMemsetAsync(out_bound, 0, sizeof(float), s) != hipSuccess) return SPML_ERR_LAUNCH;
   return launch_route(conv_route(kEntryAffine, c.R, K, N, taps, 1, addend != nullptr), c, s);
@@ -1444,16 +1418,9 @@ extern "C" int spml_conv_hl8_pyramid_f32(const void* a, const float* a_bound, co
     return SPML_ERR_INVALID_ARG;
   if (!spml_conv_hl8_supported(K, N, 9) || !al16(a) || !al16(b) || !al16(out) || (addend && !al16(addend)))
     return SPML_ERR_UNSUPPORTED;
-  ConvArgs c{};
-  c.a = static_cast<const uint4*>(a);
-  c.b = static_cast<const uint4*>(b);
-  c.a_bound = a_bound;
-  c.b_bound = b_bound;
+  ConvArgs c = conv_args(a, a_bound, b, b_bound, out, n_img, H, W, K, N, 9 * groups, dilations[0]);
   c.bias = bias;
   c.addend = addend;
-  c.out = out;
-  c.R = (int64_t)n_img * H * W;
-  c.H = H; c.W = W; c.K = K; c.N = N; c.taps = 9 * groups; c.dil = dilations[0];
   for (int g = 0; g < 4; ++g) {
     c.dils[g] = dilations[g < groups ? g : 0];
     if (c.dils[g] < 1) return SPML_ERR_INVALID_ARG;

@@ -15,7 +15,12 @@ branch is accumulated in the epilogue of conv1's data gradient.  One autograd no
 SyncBatchNorm: per-rank statistics are combined between the statistics pass and the apply pass
 (all_gather / all_reduce of [C]-sized vectors), as in `ops._BatchNormAct`.
 """
+import collections
+import inspect
 import os
+import types
+import weakref
+from itertools import islice
 
 import torch
 import torch.distributed as dist
@@ -30,11 +35,21 @@ def _group_of(bn):
   return None
 
 
-def available(block, x, allow_forward_only=True):
-  """Training-mode, channels-last fp32 GPU input, stride 1, channel counts the kernels tile."""
+def _conv_tiles(conv, need_backward):
+  """Stride-1, ungrouped, unbiased 1x1 / 9-tap convolution whose channel counts the forward kernel tiles -- and,
+  need_backward, the data- and weight-gradient kernels.  (The padding tests differ and stay with the callers.)"""
+  cin, cout, taps = conv.in_channels, conv.out_channels, conv.kernel_size[0] * conv.kernel_size[1]
+  return (conv.stride == (1, 1) and conv.groups == 1 and conv.bias is None and taps in (1, 9) and
+          _ffi.conv_hl8_supported(cin, cout, taps) and (not need_backward or (
+              _ffi.conv_hl8_supported(cout, cin, taps) and _ffi.conv_wgrad_hl8_supported(cin, cout, taps))))
+
+
+def available(block, x, allow_forward_only=True, training=True):
+  """Channels-last fp32 GPU input, stride 1, channel counts the kernels tile; the block in training mode (or,
+  training=False, in eval mode: `eval_available`)."""
   if os.environ.get('SPML_NO_MC_CONV') == '1' or not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
     return False
-  if not block.training or block.stride != 1 or not x.is_contiguous(memory_format=torch.channels_last):
+  if block.training != training or block.stride != 1 or not x.is_contiguous(memory_format=torch.channels_last):
     return False
   convs = [block.conv1, block.conv2, block.conv3] + ([block.downsample[0]] if block.downsample is not None else [])
   # units with 128-multiple channel counts only (res3) run the 128-wide tiles; SPML_MC_NARROW_UNITS=0 keeps
@@ -51,29 +66,14 @@ def available(block, x, allow_forward_only=True):
       p.requires_grad for m in convs + bns for p in m.parameters())))
   if forward_only and any(c.out_channels & 127 for c in convs) and os.environ.get('SPML_MC_FROZEN_UNITS') != '1':
     return False
-  for c in convs:
-    taps = c.kernel_size[0] * c.kernel_size[1]
-    if c.stride != (1, 1) or c.groups != 1 or c.bias is not None or taps not in (1, 9):
-      return False
-    if taps == 9 and (c.padding != c.dilation or c.dilation[0] != c.dilation[1]):
-      return False
-    if not _ffi.conv_hl8_supported(c.in_channels, c.out_channels, taps):
-      return False
-    if not forward_only and not (_ffi.conv_hl8_supported(c.out_channels, c.in_channels, taps) and
-                                 _ffi.conv_wgrad_hl8_supported(c.in_channels, c.out_channels, taps)):
-      return False
-  return all(b.affine and b.track_running_stats and b.momentum is not None for b in bns)
+  return (all((c.kernel_size == (1, 1) or (c.padding == c.dilation and c.dilation[0] == c.dilation[1])) and
+              _conv_tiles(c, not forward_only) for c in convs) and
+          all(b.affine and b.track_running_stats and b.momentum is not None for b in bns))
 
 
 def eval_available(block, x):
   """Inference (eval mode, no autograd): same shape conditions as the training path."""
-  if block.training or torch.is_grad_enabled():
-    return False
-  block.training = True                  # reuse the shape / layout checks of the training path
-  try:
-    return available(block, x, allow_forward_only=False)
-  finally:
-    block.training = False
+  return not torch.is_grad_enabled() and available(block, x, allow_forward_only=False, training=False)
 
 
 def _touch(bn):
@@ -83,16 +83,13 @@ def _touch(bn):
     torch.autograd.graph.increment_version((bn.running_mean, bn.running_var))
 
 
-import weakref
-
 _folded = weakref.WeakKeyDictionary()       # conv module -> (version key, folded weights, bias); dies with the module
 
 
 def _fold(conv, bn):
   """Batch norm in eval mode folded into the convolution: weight * (gamma * invstd)[co] in both hl8
   layouts + bias = beta - mean * gamma * invstd; cached per module (weakly: not carried by deepcopy / torch.save of
-  the model) until a parameter or statistic
-  changes (version counters; every in-library update of the statistics goes through `_touch`)."""
+  the model) until a parameter or statistic changes (version counters; in-library updates go through `_touch`)."""
   ver = tuple(t._version for t in (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)) + \
       (conv.weight.data_ptr(), bn.running_mean.data_ptr(), bn.eps)
   hit = _folded.get(conv)
@@ -145,31 +142,25 @@ class _Bn(object):
     group = _group_of(bn)
     world = dist.get_world_size(group) if group is not None else 1
     self.count, self.group, self.world, self.relu = rows * world, group, world, relu
-    if world == 1:                       # everything inside the library: three launches
-      if bn.num_batches_tracked is not None:
-        if counters is not None:
-          counters.append(bn.num_batches_tracked)
-        else:
-          bn.num_batches_tracked.add_(1)
-      self.y, self.yh, self.bound, self.mask, self.saved = _ffi.bn_fwd_hl8(
-          a, rows, channels, residual, residual_bound, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-          bn.momentum, bn.eps, relu, want_f32, want_hl8, relu, chunk_stats=chunk_stats)
-      _touch(bn)
-      return
     # SyncBatchNorm: (count, mean, M2) of the ranks are gathered, pooled and finalised in one launch;
     # the channel extremes stay local (they only have to bound this rank's tensor)
-    if gathered is None:
+    if world > 1 and gathered is None:
       st = _ffi.bn_stats_ext(a, rows, channels, chunk_stats=chunk_stats)
       allst = torch.empty((world * 3, channels), dtype=st.dtype, device=st.device)
       dist.all_gather_into_tensor(allst, st[:3], group=group)       # one contiguous [world, 3, C] block
-      allst = allst.view(world, 3, channels)
-    else:
-      allst, st = gathered
+      gathered = allst.view(world, 3, channels), st
     if bn.num_batches_tracked is not None:
       if counters is not None:
         counters.append(bn.num_batches_tracked)
       else:
         bn.num_batches_tracked.add_(1)
+    if world == 1:                       # everything inside the library: three launches
+      self.y, self.yh, self.bound, self.mask, self.saved = _ffi.bn_fwd_hl8(
+          a, rows, channels, residual, residual_bound, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+          bn.momentum, bn.eps, relu, want_f32, want_hl8, relu, chunk_stats=chunk_stats)
+      _touch(bn)
+      return
+    allst, st = gathered
     # (the pooled row count stays on the device: the ranks' counts may differ, batchnorm.py:124-145)
     mean, invstd, self.count = _ffi.bn_finalize_ranks(allst, bn.eps, bn.momentum, bn.running_mean, bn.running_var)
     _touch(bn)
@@ -180,24 +171,31 @@ class _Bn(object):
     self.saved = (mean, invstd, cmax, cmin)
 
 
-def _bn_backward(dy, a, rows, channels, gamma, saved, count, group, world, mask, want_dres=False,
-                 want_dx_f32=False, chunk_stats=None):
-  """-> (dx fp32 | None, dx hl8, d_residual | None, d_gamma, d_beta)
+class _BnRecord(collections.namedtuple(
+    '_BnRecord', 'a gamma mean invstd cmax cmin mask count group world rows channels')):
+  """What the backward of one batch norm reads: its input a (fp32 [rows, channels]), gamma, the four saved statistics,
+  the ReLU mask bytes (None: no ReLU), and the row count (a device float where the ranks' counts were pooled) / process
+  group / world size of the statistics."""
+  __slots__ = ()
+  saved = property(lambda self: (self.mean, self.invstd, self.cmax, self.cmin))
+
+
+def _bn_backward(dy, bn, want_dres=False, want_dx_f32=False, chunk_stats=None):
+  """-> (dx fp32 | None, dx hl8, d_residual | None, d_gamma, d_beta) of the batch norm of record `bn`
   chunk_stats: the chunk sums the data gradient that produced dy left (`_ffi.conv_hl8_bwd_stats`): the reduction
   pass over dy and a is replaced by their merge."""
-  if world == 1:
-    dxh, dres, d_gamma, d_beta = _ffi.bn_bwd_hl8(dy, mask, a, rows, channels, saved, gamma, want_dres=want_dres,
-                                                 chunk_stats=chunk_stats)
+  if bn.world == 1:
+    dxh, dres, d_gamma, d_beta = _ffi.bn_bwd_hl8(dy, bn.mask, bn.a, bn.rows, bn.channels, bn.saved, bn.gamma,
+                                                 want_dres=want_dres, chunk_stats=chunk_stats)
     return None, dxh, dres, d_gamma, d_beta
-  mean, invstd, cmax, cmin = saved
-  st = _ffi.bn_act_bwd_reduce_ext(dy, None, mask, a, rows, channels, mean, invstd,
+  st = _ffi.bn_act_bwd_reduce_ext(dy, None, bn.mask, bn.a, bn.rows, bn.channels, bn.mean, bn.invstd,
                                   chunk_stats=chunk_stats)                           # (sum dz, sum dz*xhat, max|dz|)
   local = st[:2].clone()                           # local sums: DDP averages parameter gradients
   d_beta, d_gamma = local[0], local[1]
-  dist.all_reduce(st[:2], group=group)
-  dx, dxh, dres = _ffi.bn_act_bwd_apply_hl8(dy, None, mask, a, rows, channels, mean, invstd, gamma, st[0], st[1],
-                                            st[2], cmax, cmin, count, want_dx_f32=want_dx_f32, want_dx_hl8=True,
-                                            want_dres=want_dres)
+  dist.all_reduce(st[:2], group=bn.group)
+  dx, dxh, dres = _ffi.bn_act_bwd_apply_hl8(dy, None, bn.mask, bn.a, bn.rows, bn.channels, bn.mean, bn.invstd,
+                                            bn.gamma, st[0], st[1], st[2], bn.cmax, bn.cmin, bn.count,
+                                            want_dx_f32=want_dx_f32, want_dx_hl8=True, want_dres=want_dres)
   return dx, dxh, dres, d_gamma, d_beta
 
 
@@ -218,24 +216,24 @@ def sync_pair(bn_a, a_a, chunk_a, bn_b, a_b, chunk_b, rows, channels):
   return (allst[:, :, :channels].contiguous(), st_a), (allst[:, :, channels:].contiguous(), st_b)
 
 
-def _bn_backward_pair(d_out, mask, a3, gamma3, saved3, ad, gammad, savedd, rows, channels, count, group):
-  """Backward of a unit's third batch norm (+ identity, ReLU) and of its downsample batch norm, synchronised: both
-  see dz = d_out * mask (the downsample branch IS the residual), so both (sum dz, sum dz x-hat) pairs are reduced
-  before ONE all_reduce of [2, 2 C], and the gradient of the residual branch is never materialised.
-  -> (da3 hl8, dad hl8, d_gamma3, d_beta3, d_gammad, d_betad)"""
-  mean3, invstd3, cmax3, cmin3 = saved3
-  meand, invstdd, cmaxd, cmind = savedd
-  st3 = _ffi.bn_act_bwd_reduce_ext(d_out, None, mask, a3, rows, channels, mean3, invstd3)
-  std = _ffi.bn_act_bwd_reduce_ext(d_out, None, mask, ad, rows, channels, meand, invstdd)
+def _bn_backward_pair(d_out, bn3, bnd):
+  """Backward of a unit's third batch norm (+ identity, ReLU) and of its downsample batch norm (records bn3, bnd),
+  synchronised: both see dz = d_out * mask3 (the downsample branch IS the residual), so both (sum dz, sum dz x-hat)
+  pairs are reduced before ONE all_reduce of [2, 2 C], and the gradient of the residual branch is never materialised.
+  -> what `_bn_backward` returns, for bn3 and for bnd (no fp32 dx, no d_residual)"""
+  mask, rows, c = bn3.mask, bn3.rows, bn3.channels
+  st3 = _ffi.bn_act_bwd_reduce_ext(d_out, None, mask, bn3.a, rows, c, bn3.mean, bn3.invstd)
+  std = _ffi.bn_act_bwd_reduce_ext(d_out, None, mask, bnd.a, rows, c, bnd.mean, bnd.invstd)
   both = torch.cat([st3[:2], std[:2]], dim=1)                  # [2, 2 C]
   local = both.clone()                                        # local sums: DDP averages parameter gradients
-  dist.all_reduce(both, group=group)
-  c = channels
-  _, da3, _ = _ffi.bn_act_bwd_apply_hl8(d_out, None, mask, a3, rows, c, mean3, invstd3, gamma3, both[0, :c].contiguous(),
-                                        both[1, :c].contiguous(), st3[2], cmax3, cmin3, count)
-  _, dad, _ = _ffi.bn_act_bwd_apply_hl8(d_out, None, mask, ad, rows, c, meand, invstdd, gammad, both[0, c:].contiguous(),
-                                        both[1, c:].contiguous(), std[2], cmaxd, cmind, count)
-  return da3, dad, local[1, :c], local[0, :c], local[1, c:], local[0, c:]
+  dist.all_reduce(both, group=bn3.group)
+  _, da3, _ = _ffi.bn_act_bwd_apply_hl8(d_out, None, mask, bn3.a, rows, c, bn3.mean, bn3.invstd, bn3.gamma,
+                                        both[0, :c].contiguous(), both[1, :c].contiguous(), st3[2], bn3.cmax,
+                                        bn3.cmin, bn3.count)
+  _, dad, _ = _ffi.bn_act_bwd_apply_hl8(d_out, None, mask, bnd.a, rows, c, bnd.mean, bnd.invstd, bnd.gamma,
+                                        both[0, c:].contiguous(), both[1, c:].contiguous(), std[2], bnd.cmax,
+                                        bnd.cmin, bn3.count)
+  return (None, da3, None, local[1, :c], local[0, :c]), (None, dad, None, local[1, c:], local[0, c:])
 
 
 _side_streams = BoundedCache(16)      # one HIP stream per device, created once (a device resource, not call state)
@@ -300,143 +298,150 @@ class _Handover(object):
     return stats
 
 
+def _save_named(ctx, **entries):
+  """`ctx.save_for_backward` under names; `_saved_named` is the mirror.  An entry is a tensor, None, a tuple of
+  tensors, an Hl8 (saved as its two tensors, (rows, channels) kept in the layout) or a _BnRecord (its seven tensors --
+  six where there is no mask --, the rest of it kept in the layout).  Only tensors are saved, in the order given."""
+  layout, tensors = [], []
+  for name, v in entries.items():
+    kind = type(v)
+    if kind is _ffi.Hl8:
+      make, parts, rest = kind, (v.data, v.bound), (v.rows, v.channels)
+    elif kind is _BnRecord:
+      k = 6 if v.mask is None else 7       # (its tensors lead the record; a None mask stays in the layout)
+      make, parts, rest = kind, v[:k], v[k:]
+    elif kind is tuple:
+      make, parts, rest = (lambda *p: p), v, ()
+    else:
+      make, parts, rest = (lambda p=None: p), (() if v is None else (v,)), ()
+    layout.append((name, make, len(parts), rest))
+    tensors += parts
+  ctx.saved_layout = layout
+  ctx.save_for_backward(*tensors)
+
+
+def _saved_named(ctx):
+  it = iter(ctx.saved_tensors)
+  return types.SimpleNamespace(**{name: make(*islice(it, k), *rest) for name, make, k, rest in ctx.saved_layout})
+
+
+def _forward_stage(xh, wf, geom, taps, dil, bn, gamma, conv_out=None, **bn_args):
+  """conv(xh, wf) -> batch norm `bn` (+ residual, ReLU: bn_args as for `_Bn`) -> (_Bn, its _BnRecord).  Where the
+  tiling allows it (256-column tiles) the convolution's epilogue leaves the chunk statistics and the batch norm does
+  not read the tensor for them.  conv_out: (a, chunk statistics) of a convolution the caller has already launched."""
+  n, h, w = geom
+  a, st = conv_out or _ffi.conv_hl8_stats(xh, wf, n, h, w, taps, dil)
+  nb = _Bn(bn, a, n * h * w, wf.rows, chunk_stats=st, **bn_args)
+  return nb, _BnRecord(a, gamma, *nb.saved, nb.mask, nb.count, nb.group, nb.world, n * h * w, wf.rows)
+
+
+def _backward_stage(side, dy, bn, xh, geom, taps, dil, dgrad, done=None, **bn_args):
+  """Backward of one conv -> bn stage: batch-norm backward of record `bn` (bn_args as for `_bn_backward`; done: its
+  result where the caller has run it) -> weight gradient against the stage's input xh on the side stream -> the data
+  gradient `dgrad(da)` (None: none) -> (what dgrad returned, d_residual | None, dw, d_gamma, d_beta); da is dropped."""
+  _, da, dres, dg, db = done or _bn_backward(dy, bn, **bn_args)
+  dw = _wgrad(side, da, xh, *geom, taps, dil)
+  return (dgrad(da) if dgrad is not None else None), dres, dw, dg, db
+
+
 class _Unit(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, block, x, xh_data, xh_bound, w1, g1, b1, w2, g2, b2, w3, g3, b3, wd, gd, bd, hand_out=None,
-              hand_in=None, *p_bn3):
-    # hand_out: this unit's _Handover (filled here); hand_in + p_bn3 (its three tensors): the one of the unit that
-    # produced x, if any
+              hand_in=None, below_a3=None, below_mask3=None, below_mean3=None):
+    # hand_out: this unit's _Handover (filled here); hand_in + below_* (its three tensors, the bn3 operands of the unit
+    # that produced x), if any
     n, cin, h, w = x.shape
-    rows = n * h * w
-    dil = block.conv2.dilation[0]
-    width, cout = w1.shape[0], w3.shape[0]
-    xh = _ffi.Hl8(xh_data, xh_bound, rows, cin) if xh_data is not None else _ffi.hl8_from_f32(x)
-    wset = _ffi.hl8_weight_set([w1, w2, w3] + ([wd] if wd is not None else []))
-    (w1f, w1t), (w2f, w2t), (w3f, w3t) = wset[:3]
-    # every convolution feeds a batch norm: where the tiling allows it (256-column tiles) the convolution's
-    # epilogue leaves the chunk statistics and the batch norm does not read the tensor for them
-    conv = _ffi.conv_hl8_stats
-    a1, s1 = conv(xh, w1f, n, h, w, 1)
+    geom, dil = (n, h, w), block.conv2.dilation[0]
+    xh = _ffi.Hl8(xh_data, xh_bound, n * h * w, cin) if xh_data is not None else _ffi.hl8_from_f32(x)
+    (w1f, w1t), (w2f, w2t), (w3f, w3t), *wds = _ffi.hl8_weight_set([w1, w2, w3] + ([wd] if wd is not None else []))
     counters = []
-    n1 = _Bn(block.bn1, a1, rows, width, chunk_stats=s1, counters=counters)
-    a2, s2 = conv(n1.yh, w2f, n, h, w, 9, dil)
-    n2 = _Bn(block.bn2, a2, rows, width, chunk_stats=s2, counters=counters)
-    a3, s3 = conv(n2.yh, w3f, n, h, w, 1)
-    nd = ad = wdt = None
-    ex3 = None                             # (exchanged statistics of bn3, if it shares the exchange)
+    n1, bn1 = _forward_stage(xh, w1f, geom, 1, 1, block.bn1, g1, counters=counters)
+    n2, bn2 = _forward_stage(n1.yh, w2f, geom, 9, dil, block.bn2, g2, counters=counters)
+    out3 = _ffi.conv_hl8_stats(n2.yh, w3f, n, h, w, 1)
+    nd = wdt = bnd = ex3 = None            # (ex3: exchanged statistics of bn3, if it shares the exchange)
     if wd is not None:
-      wdf, wdt = wset[3]
-      ad, sd = conv(xh, wdf, n, h, w, 1)
+      (wdf, wdt), = wds
+      outd = _ffi.conv_hl8_stats(xh, wdf, n, h, w, 1)
       # the statistics of the third convolution and of the downsample convolution are independent: one exchange
-      ex3, exd = sync_pair(block.bn3, a3, s3, block.downsample[1], ad, sd, rows, cout)
-      nd = _Bn(block.downsample[1], ad, rows, cout, relu=False, want_f32=True, want_hl8=False, chunk_stats=sd,
-               counters=counters, gathered=exd)
-      residual, res_bound = nd.y, nd.bound
-    else:
-      residual, res_bound = x, xh.bound
-    n3 = _Bn(block.bn3, a3, rows, cout, residual=residual, residual_bound=res_bound, want_f32=True, chunk_stats=s3,
-             counters=counters, gathered=ex3)
+      ex3, exd = sync_pair(block.bn3, *out3, block.downsample[1], *outd, n * h * w, w3f.rows)
+      nd, bnd = _forward_stage(xh, wdf, geom, 1, 1, block.downsample[1], gd, conv_out=outd, relu=False, want_f32=True,
+                               want_hl8=False, counters=counters, gathered=exd)
+    residual, res_bound = (x, xh.bound) if nd is None else (nd.y, nd.bound)
+    n3, bn3 = _forward_stage(n2.yh, w3f, geom, 1, 1, block.bn3, g3, conv_out=out3, residual=residual,
+                             residual_bound=res_bound, want_f32=True, counters=counters, gathered=ex3)
     bump_counters(counters)
-    ctx.block, ctx.geom = block, (n, cin, h, w, dil, width, cout)
-    ctx.bn_meta = [(m.count, m.group, m.world) for m in (n1, n2, n3)] + \
-        ([(nd.count, nd.group, nd.world)] if nd is not None else [])
-    tensors = [xh.data, xh.bound, a1, n1.yh.data, n1.yh.bound, a2, n2.yh.data, n2.yh.bound, a3, n3.mask,
-               n1.mask, n2.mask,
-               w1t.data, w1t.bound, w2t.data, w2t.bound, w3t.data, w3t.bound, g1, g2, g3]
-    tensors += list(n1.saved) + list(n2.saved) + list(n3.saved)
-    if nd is not None:
-      tensors += [ad, wdt.data, wdt.bound, gd] + list(nd.saved)
-    ctx.hand_in = ctx.hand_out = None
-    if hand_in is not None and len(p_bn3) == 3 and p_bn3[0] is not None and n3.world == 1 and \
-        tuple(p_bn3[0].shape) == tuple(x.shape):
-      ctx.hand_in = hand_in
-      tensors += list(p_bn3)
+    ctx.block, ctx.geom, ctx.has_downsample = block, (n, h, w, dil), wd is not None
+    ctx.hand_in = ctx.hand_out = below_bn3 = None
+    if hand_in is not None and below_a3 is not None and n3.world == 1 and tuple(below_a3.shape) == tuple(x.shape):
+      ctx.hand_in, below_bn3 = hand_in, (below_a3, below_mask3, below_mean3)
     if hand_out is not None and n3.world == 1 and n3.mask is not None:
-      hand_out.bn3 = (a3, n3.mask, n3.saved[0])
-      ctx.hand_out = hand_out
-    ctx.save_for_backward(*tensors)
+      ctx.hand_out, hand_out.bn3 = hand_out, (bn3.a, bn3.mask, bn3.mean)
+    _save_named(ctx, xh=xh, y1h=n1.yh, y2h=n2.yh, w1t=w1t, w2t=w2t, w3t=w3t, wdt=wdt, bn1=bn1, bn2=bn2, bn3=bn3,
+                bnd=bnd, below_bn3=below_bn3)
     ctx.mark_non_differentiable(n3.yh.data, n3.yh.bound)
     ctx.set_materialize_grads(False)       # no zero-filled 0.3-0.5 GB "gradients" for the hl8 side outputs
     return n3.y, n3.yh.data, n3.yh.bound
 
   @staticmethod
   def backward(ctx, d_out, _unused_data, _unused_bound):
+    g = dict.fromkeys(_UNIT_GRADS)         # one gradient per forward argument, filled by name
     if d_out is None:
-      return (None,) * 21
-    t = ctx.saved_tensors
+      return tuple(g.values())
+    s = _saved_named(ctx)
     # the chunk sums of bn3's backward, if the unit above left them with this very d_out (checked before any copy);
     # the forward references have served
-    handed = None
+    handed = ctx.hand_out.take(d_out) if ctx.hand_out is not None else None
     if ctx.hand_out is not None:
-      handed = ctx.hand_out.take(d_out)
       ctx.hand_out.bn3 = None
-    p_bn3 = None                           # bn3 of the unit below: what this unit's dx feeds
-    if ctx.hand_in is not None:
-      p_bn3, t = t[-3:], t[:-3]
-    n, cin, h, w, dil, width, cout = ctx.geom
-    rows = n * h * w
-    (xh_d, xh_b, a1, y1_d, y1_b, a2, y2_d, y2_b, a3, m3, m1, m2, w1t_d, w1t_b, w2t_d, w2t_b, w3t_d, w3t_b, g1, g2,
-     g3) = t[:21]
-    s1, s2, s3 = t[21:25], t[25:29], t[29:33]
-    has_ds = len(t) > 33
-    H = _ffi.Hl8
-    xh, y1h, y2h = H(xh_d, xh_b, rows, cin), H(y1_d, y1_b, rows, width), H(y2_d, y2_b, rows, width)
-    w1t, w2t, w3t = H(w1t_d, w1t_b, cin, width), H(w2t_d, w2t_b, width, 9 * width), H(w3t_d, w3t_b, width, cout)
+    n, h, w, dil = ctx.geom
+    geom, has_ds = (n, h, w), ctx.has_downsample
     if not d_out.is_contiguous(memory_format=torch.channels_last):
       d_out = d_out.contiguous(memory_format=torch.channels_last)
-    need_x = ctx.needs_input_grad[1]
-    m = ctx.bn_meta
+    need_x = ctx.needs_input_grad[_UNIT_GRADS.index('x')]
+    side = _side_stream(d_out.device)
     # bn3 (+ identity, relu)
     # the residual branch's gradient d_out * mask3 is only materialised for the downsample branch; the
     # plain identity takes it in the epilogue of conv1's data gradient (masked addend)
-    dwd = dgd = dbd = dad = None
-    pair = has_ds and m[2][2] > 1 and m[3][1] is m[2][1]      # synchronised: both reductions before ONE all_reduce
-    if pair:
-      da3, dad, dg3, db3, dgd, dbd = _bn_backward_pair(d_out, m3, a3, g3, s3, t[33], t[36], t[37:41], rows, cout,
-                                                       m[2][0], m[2][1])
-      dres = None
-    else:
-      _, da3, dres, dg3, db3 = _bn_backward(d_out, a3, rows, cout, g3, s3, m[2][0], m[2][1], m[2][2], m3,
-                                            want_dres=has_ds, chunk_stats=handed)
-    side = _side_stream(d_out.device)
-    dw3 = _wgrad(side, da3, y2h, n, h, w, 1)
+    done3 = doned = None
+    if has_ds and s.bn3.world > 1 and s.bnd.group is s.bn3.group:     # synchronised: both reductions, ONE all_reduce
+      done3, doned = _bn_backward_pair(d_out, s.bn3, s.bnd)
     # dy2 / dy1 are the dy of bn2 / bn1: where the tiling allows it (256-column tiles) the data gradient's epilogue
     # leaves the chunk sums of that batch norm's backward and the reduction pass over (dy, a, mask) is not run
-    dy2, c2 = _ffi.conv_hl8_bwd_stats(da3, w3t, n, h, w, 1, 1, a2, m2, s2[0])
-    del da3
-    _, da2, _, dg2, db2 = _bn_backward(dy2, a2, rows, width, g2, s2, m[1][0], m[1][1], m[1][2], m2, chunk_stats=c2)
-    dw2 = _wgrad(side, da2, y1h, n, h, w, 9, dil)
-    dy1, c1 = _ffi.conv_hl8_bwd_stats(da2, w2t, n, h, w, 9, dil, a1, m1, s1[0])
-    del da2, dy2
-    _, da1, _, dg1, db1 = _bn_backward(dy1, a1, rows, width, g1, s1, m[0][0], m[0][1], m[0][2], m1, chunk_stats=c1)
-    dw1 = _wgrad(side, da1, xh, n, h, w, 1)
-    dx = None
+    stats = _ffi.conv_hl8_bwd_stats
+    dgrad = lambda wt, taps, dil, bn: lambda da: stats(da, wt, n, h, w, taps, dil, bn.a, bn.mask, bn.mean)
+    (dy2, c2), dres, g['w3'], g['g3'], g['b3'] = _backward_stage(
+        side, d_out, s.bn3, s.y2h, geom, 1, 1, dgrad(s.w3t, 1, 1, s.bn2), done=done3, want_dres=has_ds,
+        chunk_stats=handed)
+    del done3                              # (da3, as the stages release their da on return)
+    (dy1, c1), _, g['w2'], g['g2'], g['b2'] = _backward_stage(
+        side, dy2, s.bn2, s.y1h, geom, 9, dil, dgrad(s.w2t, 9, dil, s.bn1), chunk_stats=c2)
+    del dy2
     # the last data gradient (conv1's + the masked d_out of the identity branch; with a downsample branch the second
     # launch, which adds the first one's result unmasked) is the d_out of the unit below: its epilogue leaves the chunk
     # sums of that unit's bn3 backward (dz = dx * mask3 of that unit), which then skips its reduction pass over
     # (d_out, a3, mask3)
-    if p_bn3 is not None and need_x and handover_mode():
-      last = lambda dy, wt, **kw: _ffi.conv_hl8_bwd_stats(dy, wt, n, h, w, 1, 1, p_bn3[0], p_bn3[1], p_bn3[2], **kw)
+    if s.below_bn3 is not None and need_x and handover_mode():
+      last = lambda dy, wt, **kw: _ffi.conv_hl8_bwd_stats(dy, wt, n, h, w, 1, 1, *s.below_bn3, **kw)
     else:
       last = lambda dy, wt, **kw: (_ffi.conv_hl8(dy, wt, n, h, w, 1, **kw), None)
-    cx = None
-    if has_ds:
-      ad, wdt_d, wdt_b, gd = t[33:37]
-      sd = t[37:41]
-      if not pair:
-        _, dad, _, dgd, dbd = _bn_backward(dres, ad, rows, cout, gd, sd, m[3][0], m[3][1], m[3][2], None)
-      dwd = _wgrad(side, dad, xh, n, h, w, 1)
-      if need_x:
-        dx = _ffi.conv_hl8(da1, w1t, n, h, w, 1)
-        dx, cx = last(dad, H(wdt_d, wdt_b, cin, cout), addend=dx)
-    elif need_x:
-      dx, cx = last(da1, w1t, addend=d_out, addend_mask=m3)
+    if has_ds:        # conv1's data gradient waits for the downsample branch's weight gradient: stage 1 hands da1 out
+      da1, _, g['w1'], g['g1'], g['b1'] = _backward_stage(side, dy1, s.bn1, s.xh, geom, 1, 1, lambda da: da,
+                                                          chunk_stats=c1)
+      dgrad_x = lambda dad: last(dad, s.wdt, addend=_ffi.conv_hl8(da1, s.w1t, n, h, w, 1))
+      dxc, _, g['wd'], g['gd'], g['bd'] = _backward_stage(side, dres, s.bnd, s.xh, geom, 1, 1,
+                                                          dgrad_x if need_x else None, done=doned)
+    else:
+      dgrad_x = lambda da1: last(da1, s.w1t, addend=d_out, addend_mask=s.bn3.mask)
+      dxc, _, g['w1'], g['g1'], g['b1'] = _backward_stage(side, dy1, s.bn1, s.xh, geom, 1, 1,
+                                                          dgrad_x if need_x else None, chunk_stats=c1)
+    g['x'], cx = dxc or (None, None)
     if cx is not None:
-      ctx.hand_in.put(dx, cx)
+      ctx.hand_in.put(g['x'], cx)
     if side is not None:
       torch.cuda.current_stream().wait_stream(side)      # the weight gradients are consumed on this stream
-    return (None, dx, None, None, dw1, dg1, db1, dw2, dg2, db2, dw3, dg3, db3, dwd, dgd, dbd) + (None,) * 5
+    return tuple(g.values())
+
 
 
 class _ConvBnAct(torch.autograd.Function):
@@ -446,36 +451,34 @@ class _ConvBnAct(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, conv, bn, x, weight, gamma, beta):
-    n, cin, h, w = x.shape
-    rows, cout = n * h * w, weight.shape[0]
+    n, _, h, w = x.shape
     taps, dil = weight.shape[2] * weight.shape[3], conv.dilation[0]
     xh = getattr(x, '_spml_hl8', None) or _ffi.hl8_from_f32(x)
     (wf, wt), = _ffi.hl8_weight_set([weight])
-    a, st = _ffi.conv_hl8_stats(xh, wf, n, h, w, taps, dil)
-    nb = _Bn(bn, a, rows, cout, relu=True, want_f32=True, want_hl8=False, chunk_stats=st)
-    ctx.geom = (n, cin, h, w, taps, dil, cout)
-    ctx.bn_meta = (nb.count, nb.group, nb.world)
-    ctx.save_for_backward(xh.data, xh.bound, a, nb.mask, wt.data, wt.bound, gamma, *nb.saved)
+    nb, rec = _forward_stage(xh, wf, (n, h, w), taps, dil, bn, gamma, relu=True, want_f32=True, want_hl8=False)
+    ctx.geom = (n, h, w, taps, dil)
+    _save_named(ctx, xh=xh, wt=wt, bn=rec)
     return nb.y
 
   @staticmethod
   def backward(ctx, dy):
-    n, cin, h, w, taps, dil, cout = ctx.geom
-    rows = n * h * w
-    xh_d, xh_b, a, mask, wt_d, wt_b, gamma = ctx.saved_tensors[:7]
-    saved = ctx.saved_tensors[7:11]
+    g = dict.fromkeys(_CONV_BN_ACT_GRADS)
+    n, h, w, taps, dil = ctx.geom
+    s = _saved_named(ctx)
     if not dy.is_contiguous(memory_format=torch.channels_last):
       dy = dy.contiguous(memory_format=torch.channels_last)
-    count, group, world = ctx.bn_meta
-    _, da, _, dg, db = _bn_backward(dy, a, rows, cout, gamma, saved, count, group, world, mask)
     side = _side_stream(dy.device)
-    dw = _wgrad(side, da, _ffi.Hl8(xh_d, xh_b, rows, cin), n, h, w, taps, dil)
-    dx = None
-    if ctx.needs_input_grad[2]:
-      dx = _ffi.conv_hl8(da, _ffi.Hl8(wt_d, wt_b, cin, taps * cout), n, h, w, taps, dil)
+    dgrad = lambda da: _ffi.conv_hl8(da, s.wt, n, h, w, taps, dil)
+    g['x'], _, g['weight'], g['gamma'], g['beta'] = _backward_stage(
+        side, dy, s.bn, s.xh, (n, h, w), taps, dil,
+        dgrad if ctx.needs_input_grad[_CONV_BN_ACT_GRADS.index('x')] else None)
     if side is not None:
       torch.cuda.current_stream().wait_stream(side)
-    return None, None, dx, dw, dg, db
+    return tuple(g.values())
+
+
+# one gradient per argument of forward (all but ctx), in this order
+_UNIT_GRADS, _CONV_BN_ACT_GRADS = (tuple(inspect.signature(f.forward).parameters)[1:] for f in (_Unit, _ConvBnAct))
 
 
 def conv_bn_act_available(conv, bn, x):
@@ -486,13 +489,9 @@ def conv_bn_act_available(conv, bn, x):
   if not (bn.training and torch.is_grad_enabled() and x.is_contiguous(memory_format=torch.channels_last)):
     return False
   k = conv.kernel_size
-  taps = k[0] * k[1]
-  cin, cout = conv.in_channels, conv.out_channels
-  return (conv.bias is None and conv.groups == 1 and conv.stride == (1, 1) and k in ((1, 1), (3, 3)) and
-          conv.dilation[0] == conv.dilation[1] and conv.padding == tuple(d * (k[0] // 2) for d in conv.dilation) and
-          bn.affine and bn.track_running_stats and
-          _ffi.conv_hl8_supported(cin, cout, taps) and _ffi.conv_hl8_supported(cout, cin, taps) and
-          _ffi.conv_wgrad_hl8_supported(cin, cout, taps))
+  return (k in ((1, 1), (3, 3)) and conv.dilation[0] == conv.dilation[1] and
+          conv.padding == tuple(d * (k[0] // 2) for d in conv.dilation) and bn.affine and bn.track_running_stats and
+          _conv_tiles(conv, True))
 
 
 def conv_bn_act(conv, bn, x):
@@ -504,8 +503,8 @@ def bottleneck_forward(block, x):
   copy (attribute `_spml_hl8`) for the next unit."""
   xh = getattr(x, '_spml_hl8', None)
   ds = block.downsample
-  hand_in = getattr(x, '_spml_handover', None) if torch.is_grad_enabled() and handover_mode() else None
-  hand_out = _Handover() if torch.is_grad_enabled() and handover_mode() else None
+  hand = torch.is_grad_enabled() and handover_mode()
+  hand_in, hand_out = (getattr(x, '_spml_handover', None), _Handover()) if hand else (None, None)
   out, oh, ob = _Unit.apply(
       block, x, None if xh is None else xh.data, None if xh is None else xh.bound,
       block.conv1.weight, block.bn1.weight, block.bn1.bias, block.conv2.weight, block.bn2.weight, block.bn2.bias,

@@ -1,5 +1,6 @@
 """Host-side dispatch of the matrix-core bottleneck units (no GPU): which units qualify, and that
 everything else stays on the framework ops."""
+import pytest
 import torch
 
 from spml_amd import _ffi, mc_bottleneck
@@ -53,3 +54,138 @@ def test_aspp_fused_data_gradient_needs_gpu_channels_last_and_bare_branches():
   assert x.grad is not None and out.shape == (1, 64, 9, 9)
   with_bn = ASPP(256, 64, bn=True, relu=True)
   assert with_bn(torch.randn(2, 256, 9, 9)).shape == (2, 64, 9, 9)
+
+
+# ---------------------------------------------------------------------------
+# the three predicates of spml_amd/mc_bottleneck.py, as a table.  They only read attributes of the input, so a stand-in
+# for a channels-last fp32 GPU tensor reaches every branch without a GPU.
+class _GpuInput(object):
+  is_cuda, dtype = True, torch.float32
+
+  def __init__(self, requires_grad=True, channels_last=True):
+    self.requires_grad, self.channels_last = requires_grad, channels_last
+
+  def dim(self):
+    return 4
+
+  def is_contiguous(self, memory_format=torch.contiguous_format):
+    return self.channels_last == (memory_format is torch.channels_last)
+
+
+def _unit(inplanes, planes, downsample=False, stride=1):
+  from spml_amd.models.backbones.resnet import _bn
+  ds = torch.nn.Sequential(torch.nn.Conv2d(inplanes, planes * 4, 1, bias=False), _bn(planes * 4)) if downsample else None
+  return Bottleneck(inplanes, planes, stride, dilation=2, downsample=ds)
+
+
+def _frozen(blk):
+  for p in blk.parameters():
+    p.requires_grad_(False)
+  return blk
+
+
+def _with(blk, **replace):
+  for name, module in replace.items():
+    setattr(blk, name, module)
+  return blk
+
+
+_C, _B = torch.nn.Conv2d, torch.nn.BatchNorm2d
+TRAIN, EVAL, NEITHER = 'train', 'eval', 'neither'
+# name -> (unit, input, environment, which path takes it).  'train': `available` in training mode (autograd on or
+# off), nothing else; 'eval': additionally `eval_available` in eval mode without autograd.  `available` is False in eval
+# mode and `eval_available` is False in training mode or with autograd on, for every row.
+UNIT_TABLE = {
+    'res4': (lambda: _unit(1024, 256), {}, {}, EVAL),
+    'res4 with downsample': (lambda: _unit(512, 256, True), {}, {}, EVAL),
+    'res3': (lambda: _unit(512, 128), {}, {}, EVAL),
+    'res2': (lambda: _unit(256, 64), {}, {}, NEITHER),
+    'switched off': (lambda: _unit(1024, 256), {}, {'SPML_NO_MC_CONV': '1'}, NEITHER),
+    'NCHW input': (lambda: _unit(1024, 256), {'channels_last': False}, {}, NEITHER),
+    'stride 2': (lambda: _unit(1024, 256, stride=2), {}, {}, NEITHER),
+    'res3, narrow units off': (lambda: _unit(512, 128), {}, {'SPML_MC_NARROW_UNITS': '0'}, NEITHER),
+    'res4, narrow units off': (lambda: _unit(1024, 256), {}, {'SPML_MC_NARROW_UNITS': '0'}, EVAL),
+    'frozen res2': (lambda: _frozen(_unit(256, 64)), {'requires_grad': False}, {}, NEITHER),
+    'frozen res2, opted in': (lambda: _frozen(_unit(256, 64)), {'requires_grad': False},
+                              {'SPML_MC_FROZEN_UNITS': '1'}, TRAIN),
+    'frozen res4': (lambda: _frozen(_unit(1024, 256)), {'requires_grad': False}, {}, EVAL),
+    'dilation != padding': (lambda: _with(_unit(1024, 256), conv2=_C(256, 256, 3, padding=1, dilation=2, bias=False)),
+                            {}, {}, NEITHER),
+    'anisotropic dilation': (lambda: _with(_unit(1024, 256),
+                                           conv2=_C(256, 256, 3, padding=(2, 3), dilation=(2, 3), bias=False)),
+                             {}, {}, NEITHER),
+    'biased convolution': (lambda: _with(_unit(1024, 256), conv1=_C(1024, 256, 1, bias=True)), {}, {}, NEITHER),
+    'grouped convolution': (lambda: _with(_unit(1024, 256), conv3=_C(256, 1024, 1, groups=2, bias=False)), {}, {},
+                            NEITHER),
+    '5x5 convolution': (lambda: _with(_unit(1024, 256), conv2=_C(256, 256, 5, padding=4, dilation=2, bias=False)), {},
+                        {}, NEITHER),
+    'momentum=None': (lambda: _with(_unit(1024, 256), bn2=_B(256, momentum=None)), {}, {}, NEITHER),
+    'no affine': (lambda: _with(_unit(1024, 256), bn3=_B(1024, affine=False)), {}, {}, NEITHER),
+    'no running statistics': (lambda: _with(_unit(1024, 256), bn1=_B(256, track_running_stats=False)), {}, {}, NEITHER),
+    'padded 1x1 (the unit does not look)': (lambda: _with(_unit(1024, 256), conv1=_C(1024, 256, 1, padding=1, bias=False)),
+                                            {}, {}, EVAL),
+    '1000 input channels': (lambda: _unit(1000, 256), {}, {}, NEITHER),
+}
+
+
+@pytest.mark.parametrize('name', sorted(UNIT_TABLE))
+def test_unit_predicates(name, monkeypatch):
+  make, x_kw, env, path = UNIT_TABLE[name]
+  for switch in ('SPML_NO_MC_CONV', 'SPML_MC_NARROW_UNITS', 'SPML_MC_FROZEN_UNITS'):
+    monkeypatch.delenv(switch, raising=False)
+  for k, v in env.items():
+    monkeypatch.setenv(k, v)
+  blk, x = make(), _GpuInput(**x_kw)
+  for training in (True, False):
+    blk.train(training)
+    for grad in (True, False):
+      with torch.set_grad_enabled(grad):
+        got = (mc_bottleneck.available(blk, x), mc_bottleneck.eval_available(blk, x))
+      want = (training and path != NEITHER, not training and not grad and path == EVAL)
+      assert got == want, (training, grad)
+      assert blk.training == training
+
+
+CONV_TABLE = {
+    'pyramid head 3x3': (lambda: (_C(4096, 512, 3, padding=12, dilation=12, bias=False), _B(512)), {}, {}, True),
+    '1x1': (lambda: (_C(512, 256, 1, bias=False), _B(256)), {}, {}, True),
+    'input without gradient': (lambda: (_C(512, 256, 1, bias=False), _B(256)), {'requires_grad': False}, {}, True),
+    'switched off': (lambda: (_C(512, 256, 1, bias=False), _B(256)), {}, {'SPML_NO_MC_CONV': '1'}, False),
+    'narrow units off (units only)': (lambda: (_C(512, 128, 1, bias=False), _B(128)), {}, {'SPML_MC_NARROW_UNITS': '0'},
+                                      True),
+    'NCHW input': (lambda: (_C(512, 256, 1, bias=False), _B(256)), {'channels_last': False}, {}, False),
+    'dilation != padding': (lambda: (_C(512, 256, 3, padding=1, dilation=2, bias=False), _B(256)), {}, {}, False),
+    'anisotropic dilation': (lambda: (_C(512, 256, 3, padding=(2, 3), dilation=(2, 3), bias=False), _B(256)), {}, {},
+                             False),
+    'padded 1x1': (lambda: (_C(512, 256, 1, padding=1, bias=False), _B(256)), {}, {}, False),
+    'biased convolution': (lambda: (_C(512, 256, 1, bias=True), _B(256)), {}, {}, False),
+    'stride 2': (lambda: (_C(512, 256, 1, stride=2, bias=False), _B(256)), {}, {}, False),
+    'momentum=None (not asked for here)': (lambda: (_C(512, 256, 1, bias=False), _B(256, momentum=None)), {}, {}, True),
+    'no affine': (lambda: (_C(512, 256, 1, bias=False), _B(256, affine=False)), {}, {}, False),
+    '64 input channels, 3x3': (lambda: (_C(64, 256, 3, padding=1, bias=False), _B(256)), {}, {}, False),
+}
+
+
+@pytest.mark.parametrize('name', sorted(CONV_TABLE))
+def test_conv_bn_act_predicate(name, monkeypatch):
+  make, x_kw, env, want = CONV_TABLE[name]
+  monkeypatch.delenv('SPML_NO_MC_CONV', raising=False)
+  for k, v in env.items():
+    monkeypatch.setenv(k, v)
+  (conv, bn), x = make(), _GpuInput(**x_kw)
+  for training in (True, False):
+    bn.train(training)
+    for grad in (True, False):
+      with torch.set_grad_enabled(grad):
+        assert mc_bottleneck.conv_bn_act_available(conv, bn, x) == (want and training and grad), (training, grad)
+
+
+def test_eval_available_does_not_write_the_training_flag():
+  class ReadOnly(Bottleneck):
+    training = property(lambda self: False, lambda self, value: pytest.fail('eval_available wrote block.training'))
+
+  blk = _unit(1024, 256).eval()
+  blk.__class__ = ReadOnly
+  with torch.no_grad():
+    assert mc_bottleneck.eval_available(blk, _GpuInput())
+    assert not mc_bottleneck.eval_available(blk, _GpuInput(channels_last=False))
