@@ -1,6 +1,7 @@
 """Atrous spatial pyramid head of DeepLab-v2 (`spml/models/heads/spp.py:8-43`):
 four dilated 3x3 branches (6/12/18/24) whose outputs are SUMMED."""
 import os
+import typing
 
 import torch
 import torch.nn as nn
@@ -11,47 +12,69 @@ from spml_amd._cache import BoundedCache
 from spml_amd.nn.batchnorm import BatchNorm2d
 
 
+class AsppRoute(typing.NamedTuple):
+  """How `_DilatedSum` runs one head (`_aspp_route`); the data gradient is the 36-tap launch on every route."""
+  forward: str       # 'gemm-gather' | 'taps36' | 'library'
+  wgrad: str         # 'per-branch' | 'pyramid' | 'library'
+  keep_xh: bool      # the backward pass needs the input's hl8 copy (the own weight-gradient kernels read it)
+
+
+def _aspp_route(cin, cout, branches, dilations):
+  """The route of a head of `branches` dilated 3x3 convolutions cin -> cout, from its shape and the three switches
+  that nothing else reads.
+  Wide heads (256-multiple output channels, e.g. the 512-d embedding of BASELINE config 5): the 36-tap launch
+  forward, one matrix-core weight-gradient call per branch; they ask no switch.
+  Narrow heads (64 output channels): forward = one 1x1 convolution with 36 x 64 columns + a gather of every pixel's
+  taps (x is streamed 9 times instead of 36; SPML_ASPP_FWD_GEMM=0: the 36-tap launch on 64-column tiles with one
+  workgroup per (256-pixel tile, dilation group) and taps that only see padding skipped, 3.9 ms against 4.9 ms for the
+  four library calls + three additions, tools/bench_conv.py --narrow; SPML_ASPP_FWD_MC=0 keeps the library); weight
+  gradients = ONE launch whose 256-column tiles are four taps x 64 channels (`spml_conv_wgrad_pyramid_hl8_f32`;
+  SPML_ASPP_WGRAD_MC=0 keeps the four library calls).  The two one-launch narrow kernels take dilations 1 .. 255."""
+  from spml_amd import _ffi
+  own_fwd = _ffi.conv_hl8_supported(cin, cout, 9)
+  if own_fwd and _ffi.conv_wgrad_hl8_supported(cin, cout, 9):          # wide
+    return AsppRoute('taps36', 'per-branch', True)
+  small_dilations = all(1 <= d <= 255 for d in dilations)
+  forward = 'library'
+  if own_fwd and os.environ.get('SPML_ASPP_FWD_MC') != '0':
+    gemm = (os.environ.get('SPML_ASPP_FWD_GEMM') != '0' and small_dilations and
+            _ffi.conv_hl8_pyramid_forward_gemm_supported(cin, cout, branches))
+    forward = 'gemm-gather' if gemm else 'taps36'
+  pyramid = (_ffi.conv_wgrad_pyramid_hl8_supported(cin, cout, branches) and small_dilations and
+             os.environ.get('SPML_ASPP_WGRAD_MC') != '0')
+  return AsppRoute(forward, 'pyramid' if pyramid else 'library', pyramid)
+
+
+def aspp_path_name(route):
+  """'fwd=gemm-gather wgrad=pyramid', ...: a pure function of the route."""
+  return 'fwd=%s wgrad=%s' % (route.forward, route.wgrad)
+
+
 class _DilatedSum(torch.autograd.Function):
   """sum_i conv2d(x, w_i, b_i, dilation = padding = d_i) for 3x3 weights, on the matrix-core kernels.  The data
   gradient -- four convolutions of the SAME output gradient, summed -- is one 36-tap launch
   (`spml_conv_hl8_pyramid_f32`) instead of four library calls and three additions over the 2048-channel tensor.
-  Narrow heads (64 output channels): forward = one 1x1 convolution with 36 x 64 columns + a gather of every
-  pixel's taps (`spml_conv_tap_gather_f32`), weight gradients = one launch on tiles of four taps x 64 channels
-  (`spml_conv_wgrad_pyramid_hl8_f32`).  Wide heads (256-multiple channels): the 36-tap launch forward, one
-  weight-gradient call per branch."""
+  Forward and weight gradients: as `_aspp_route` says."""
 
   @staticmethod
   def forward(ctx, x, dilations, *params):
     from spml_amd import _ffi
     ws, bs = params[0::2], params[1::2]
-    cout, cin = ws[0].shape[0], ws[0].shape[1]
     n, _, h, w = x.shape
-    # wide heads (256-multiple output channels, e.g. the 512-d embedding of BASELINE config 5): forward and
-    # weight gradients on the matrix-core kernels too.  The 64-channel head: forward on the 36-tap kernel with
-    # one workgroup per (256-pixel tile, dilation group) and taps that only see padding skipped (3.9 ms against
-    # 4.9 ms for the four library calls + three additions, tools/bench_conv.py --narrow; SPML_ASPP_FWD_MC=0
-    # keeps the library); its weight gradients are ONE launch whose 256-column tiles are four taps x 64 channels
-    # (`spml_conv_wgrad_pyramid_hl8_f32`; SPML_ASPP_WGRAD_MC=0 keeps the four library calls)
-    ctx.wide = _ffi.conv_hl8_supported(cin, cout, 9) and _ffi.conv_wgrad_hl8_supported(cin, cout, 9)
-    fwd_mc = ctx.wide or (_ffi.conv_hl8_supported(cin, cout, 9) and os.environ.get('SPML_ASPP_FWD_MC') != '0')
-    ctx.narrow_wgrad = (not ctx.wide and _ffi.conv_wgrad_pyramid_hl8_supported(cin, cout, len(ws)) and
-                        all(1 <= d <= 255 for d in dilations) and os.environ.get('SPML_ASPP_WGRAD_MC') != '0')
-    ctx.xh = None
-    if fwd_mc or ctx.narrow_wgrad:
+    route = _aspp_route(ws[0].shape[1], ws[0].shape[0], len(ws), dilations)
+    xh = None
+    if route.forward != 'library' or route.keep_xh:
       xh = getattr(x, '_spml_hl8', None) or _ffi.hl8_from_f32(x)
-      ctx.xh = xh if (ctx.wide or ctx.narrow_wgrad) else None
-    if fwd_mc and not ctx.wide and os.environ.get('SPML_ASPP_FWD_GEMM') != '0' and \
-        _ffi.conv_hl8_pyramid_forward_gemm_supported(cin, cout, len(ws)) and all(1 <= d <= 255 for d in dilations):
-      # narrow head: one 1x1 convolution with 36 x 64 columns + a gather of every pixel's taps (x is streamed 9
-      # times instead of 36; SPML_ASPP_FWD_GEMM=0: the 36-tap launch on 64-column tiles)
+    if route.forward == 'gemm-gather':
       out = _ffi.conv_hl8_pyramid_forward_gemm(xh, ws, bs, dilations, n, h, w)
-    elif fwd_mc:
+    elif route.forward == 'taps36':
       out = _ffi.conv_hl8_pyramid_forward(xh, ws, bs, dilations, n, h, w)
     else:
       out = None
       for wt, b, d in zip(ws, bs, dilations):
         y = F.conv2d(x, wt, b, 1, d, d)
         out = y if out is None else out.add_(y)
+    ctx.route, ctx.xh = route, (xh if route.keep_xh else None)
     ctx.dilations = dilations
     ctx.save_for_backward(x, *ws)
     ctx.has_bias = [b is not None for b in bs]
@@ -63,20 +86,21 @@ class _DilatedSum(torch.autograd.Function):
     x, ws = ctx.saved_tensors[0], ctx.saved_tensors[1:]
     dy = dy.contiguous(memory_format=torch.channels_last)
     n, _, h, w = x.shape
-    grads = []
+    wgrad = ctx.route.wgrad
     any_w = any(ctx.needs_input_grad[2 + 2 * i] for i in range(len(ws)))
-    own = ctx.wide or ctx.narrow_wgrad
-    dyh = _ffi.hl8_from_f32(dy) if (ctx.needs_input_grad[0] or (own and any_w)) else None
-    db_all = dy.sum(dim=(0, 2, 3)) if own and any(ctx.has_bias) else None
-    dws = _ffi.conv_wgrad_pyramid_hl8(dyh, ctx.xh, n, h, w, ctx.dilations) if ctx.narrow_wgrad and any_w else None
+    dyh = _ffi.hl8_from_f32(dy) if (ctx.needs_input_grad[0] or (wgrad != 'library' and any_w)) else None
+    db_all = dy.sum(dim=(0, 2, 3)) if wgrad != 'library' and any(ctx.has_bias) else None
+    dws = _ffi.conv_wgrad_pyramid_hl8(dyh, ctx.xh, n, h, w, ctx.dilations) if wgrad == 'pyramid' and any_w else None
+    grads = []
     for i, (wt, d) in enumerate(zip(ws, ctx.dilations)):
       need_w, need_b = ctx.needs_input_grad[2 + 2 * i], ctx.has_bias[i] and ctx.needs_input_grad[3 + 2 * i]
       dw = db = None
-      if own:
-        if need_w:
-          dw = dws[i] if ctx.narrow_wgrad else _ffi.conv_wgrad_hl8(dyh, ctx.xh, n, h, w, 9, d)
-        if need_b:
-          db = db_all
+      if wgrad == 'per-branch':
+        dw = _ffi.conv_wgrad_hl8(dyh, ctx.xh, n, h, w, 9, d) if need_w else None
+        db = db_all if need_b else None
+      elif wgrad == 'pyramid':
+        dw = dws[i] if need_w else None
+        db = db_all if need_b else None
       elif need_w or need_b:
         _, dw, db = torch.ops.aten.convolution_backward(
             dy, x, wt, [wt.shape[0]] if ctx.has_bias[i] else None, [1, 1], [d, d], [d, d], False, [0, 0], 1,
@@ -89,7 +113,9 @@ class _DilatedSum(torch.autograd.Function):
 
 
 def _dilated_sum_available(x, convs):
-  if os.environ.get('SPML_NO_MC_CONV') == '1' or os.environ.get('SPML_NO_ASPP_DGRAD') == '1' or not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
+  if os.environ.get('SPML_NO_MC_CONV') == '1' or os.environ.get('SPML_NO_ASPP_DGRAD') == '1':
+    return False
+  if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
     return False
   from spml_amd import _ffi
   if not x.is_contiguous(memory_format=torch.channels_last):
@@ -219,13 +245,11 @@ class PSPP(nn.Module):
       # the four adaptive average pools as ONE plain GEMM over the channels-last map (the framework's NHWC
       # adaptive pool kernel runs at 130 GB/s: 14 ms per step at 8 x 2048 x 97 x 97, a third of it per level)
       feats = [branch[1:](p) for branch, p in zip(branches, _pyramid_pool(x, [b[0].output_size for b in branches]))]
-    else:
-      feats = [branch(x) for branch in branches]
-    if _pyramid_pool_available(x, branches):
       # ... and back up as plain GEMMs too: the framework's bilinear backward scatter-adds 154 MB of output
       # gradient into a b x b map with atomics (1.1 ms per branch at 8 x 512 x 97 x 97)
       pooled = [_upsample_gemm(f, size) for f in feats]
     else:
+      feats = [branch(x) for branch in branches]
       pooled = [F.interpolate(f, size=size, mode='bilinear') for f in feats]
     cat = torch.cat([x] + pooled, dim=1)
     from spml_amd import mc_bottleneck

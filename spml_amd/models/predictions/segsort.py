@@ -2,7 +2,9 @@
 assembles the pixel-to-segment contrastive losses (semantic annotation,
 semantic co-occurrence, low-level image similarity) on the gfx950 NLL kernels
 and predicts by nearest-neighbour retrieval."""
+import contextlib
 import os
+import typing
 
 import torch
 import torch.nn as nn
@@ -40,6 +42,85 @@ def _nonzero_pair(mask_a, mask_b, extra=None):
     src = torch.arange(mask.shape[0], device=mask.device)
     out.append(src.new_empty((n + 1,)).scatter_(0, dst, src)[:n])
   return (out[0], out[1], tail) if extra is not None else out
+
+
+class _ImagePairs(typing.NamedTuple):
+  """Dense ids of the (image, cluster, over-segmentation id) pairs of a batch, image-major."""
+  sizes: list                 # pixels of every image that has any (host)
+  off: torch.Tensor           # 0-d: over-segmentation ids are < off; a pair's id is its key % off
+  uniq: torch.Tensor          # [P] the distinct keys in ascending order, padded with INT64_MAX
+  pair: torch.Tensor          # [P] every pixel's dense pair id
+  last_dev: torch.Tensor      # [images] the last pair id of every image (on the device: one host read away)
+  img_of_px: torch.Tensor     # [P] index of the pixel's image among the present ones
+
+
+def _image_pairs(datas):
+  """Pixels are image-major: every image is one contiguous slice (sizes known on the host from the clustering,
+  `cluster_image_sizes`).  The reference re-indexes (over-segmentation id, cluster) pairs per image
+  (prepare_prototype_labels, segsort.py:228-240); here ONE dense re-indexing over (image, cluster, id) does it for all
+  images, and one host read (of `last_dev`, left to the caller) returns every image's last id."""
+  clu = datas['cluster_index']
+  ins = datas['cluster_instance_label']
+  bat = datas['cluster_batch_index']
+  sizes = datas.get('cluster_image_sizes', None)
+  if sizes is None:
+    sizes = torch.unique_consecutive(bat, return_counts=True)[1].tolist()
+  sizes = [int(v) for v in sizes if int(v) > 0]
+  img_of_px = torch.zeros_like(bat)
+  if int(clu.shape[0]) > 1:
+    img_of_px[1:] = torch.cumsum(bat[1:] != bat[:-1], 0)
+  off = ins.max() + 1
+  stride = (clu.max() + 1) * off                       # keys of image b lie in [b * stride, (b + 1) * stride)
+  uniq, pair = segsort_common._unique_inverse((img_of_px * (clu.max() + 1) + clu) * off + ins,
+                                              with_uniq=False, padded=True)
+  # distinct pairs of the images up to and including b = position of (b + 1) * stride among the sorted keys
+  bounds = torch.arange(1, len(sizes) + 1, device=uniq.device) * stride
+  return _ImagePairs(sizes, off, uniq, pair, torch.searchsorted(uniq, bounds) - 1, img_of_px)
+
+
+def _pair_labels(pairs, last):
+  """-> (the over-segmentation id of every pair [pairs], the number of pairs of every image (host)), from the
+  images' last pair ids on the host."""
+  counts = [end + 1 - (last[i - 1] + 1 if i else 0) for i, end in enumerate(last)]
+  return pairs.uniq[:last[-1] + 1] % pairs.off, counts
+
+
+class ImgSimRoute(typing.NamedTuple):
+  """How the image-similarity term of one call is evaluated (`_img_sim_route`)."""
+  shared_protos: bool         # the prototypes of all images from one segment sum (otherwise one call per image)
+  batched: bool               # one batched NLL call for all images (otherwise one call per image)
+  streams: int                # side streams the per-image calls are spread over (0: the current stream)
+  record_stream: bool         # tell the caching allocator which side stream reads what
+
+
+def _img_sim_route(on_gpu, contiguous, covered, env=None):
+  """The route of the image-similarity term, from plain values -- the embedding is on the GPU; the images' pixels are
+  one contiguous run (sum of the image sizes == rows of the embedding); the batched kernels cover the loss
+  (`batched_supported`) -- and the four switches, which nothing else in this file reads:
+    SPML_IMG_SIM_BATCHED_PROTOS=0  prototypes from one call per image
+    SPML_IMG_SIM_BATCHED=0         the per-image loop instead of the batched NLL kernels
+    SPML_IMG_SIM_STREAMS=n         the per-image loop on n side streams (default 4; <= 1: none); set at all, it asks
+                                   for the loop
+    SPML_IMG_SIM_RECORD_STREAM=0   no record_stream calls for what the side streams read
+  Launches nothing."""
+  env = os.environ if env is None else env
+  shared = env.get('SPML_IMG_SIM_BATCHED_PROTOS') != '0' and contiguous
+  batched = (shared and on_gpu and env.get('SPML_IMG_SIM_BATCHED') != '0' and
+             'SPML_IMG_SIM_STREAMS' not in env and covered)
+  streams = 0
+  if on_gpu and not batched:
+    streams = int(env.get('SPML_IMG_SIM_STREAMS', '4'))
+    streams = streams if streams > 1 else 0
+  return ImgSimRoute(bool(shared), bool(batched), streams,
+                     streams > 0 and env.get('SPML_IMG_SIM_RECORD_STREAM') != '0')
+
+
+def img_sim_path_name(route):
+  """'batched', 'looped/shared-protos/streams=4', 'looped/per-image-protos/streams=0', ...: a pure function of the
+  route (no record of the last call is kept)."""
+  if route.batched:
+    return 'batched'
+  return 'looped/%s/streams=%d' % ('shared-protos' if route.shared_protos else 'per-image-protos', route.streams)
 
 
 class Segsort(nn.Module):
@@ -133,154 +214,129 @@ class Segsort(nn.Module):
     img_sets, p_sets = segsort_loss.pack_tag_set_pair(targets['semantic_tag'][:, 1:nc], p_tags)
     return img_sets[bat], p_sets
 
-  def _contrastive_losses(self, datas, targets):
-    """The three contrastive terms + retrieval accuracy (segsort.py:127-243)."""
-    sem_ann = sem_occ = img_sim = acc = None
+  def _semantic_terms(self, datas, targets, pairs):
+    """The semantic annotation and co-occurrence terms + retrieval accuracy (segsort.py:127-218) -> (sem_ann, sem_occ,
+    acc, last): `last` is `pairs.last_dev` on the host, which travels with the one host read of this part (None
+    without `pairs` or when neither term is on)."""
+    sem_ann = sem_occ = acc = last = None
+    if self.sem_ann_loss is None and self.sem_occ_loss is None:
+      return sem_ann, sem_occ, acc, last
     nc = self.num_classes
+    clu = datas['cluster_index']
+    emb = datas['cluster_embedding']
+    sem = datas['cluster_semantic_label']
+    bat = datas['cluster_batch_index']
+    protos = targets['prototype']
+    live = protos.shape[0]          # prototypes that carry a gradient (memory bank is detached)
+    p_sem = targets['prototype_semantic_label']
+    p_bat = targets['prototype_batch_index']
 
-    # per-image term, device part first: its one host read (every image's last pair id) travels
-    # with the sizes the semantic terms need -- 3 host synchronisations per training step in all
-    sim = None
-    if self.img_sim_loss is not None:
-      clu = datas['cluster_index']
-      ins = datas['cluster_instance_label']
-      bat = datas['cluster_batch_index']
-      # pixels are image-major: every image is one contiguous slice (sizes known on the host from the
-      # clustering, `cluster_image_sizes`).  The reference re-indexes (over-segmentation id, cluster)
-      # pairs per image (prepare_prototype_labels, segsort.py:228-240); here ONE dense re-indexing over
-      # (image, cluster, id) does it for all images, and one host read returns every image's last id
-      sizes = datas.get('cluster_image_sizes', None)
-      if sizes is None:
-        sizes = torch.unique_consecutive(bat, return_counts=True)[1].tolist()
-      sizes = [int(v) for v in sizes if int(v) > 0]
-      n_img, total = len(sizes), int(clu.shape[0])
-      img_of_px = torch.zeros_like(bat)                    # index of the pixel's image among the present ones
-      if total > 1:
-        img_of_px[1:] = torch.cumsum(bat[1:] != bat[:-1], 0)
-      off = ins.max() + 1
-      stride = (clu.max() + 1) * off                       # keys of image b lie in [b * stride, (b + 1) * stride)
-      uniq, pair = segsort_common._unique_inverse((img_of_px * (clu.max() + 1) + clu) * off + ins,
-                                                  with_uniq=False, padded=True)
-      # distinct pairs of the images up to and including b = position of (b + 1) * stride among the sorted keys
-      bounds = torch.arange(1, n_img + 1, device=uniq.device) * stride
-      sim = (sizes, off, uniq, pair, torch.searchsorted(uniq, bounds) - 1, img_of_px)
-    last = None
+    mem_p = targets.get('memory_prototype', [])
+    mem_sem = targets.get('memory_prototype_semantic_label', [])
+    mem_bat = targets.get('memory_prototype_batch_index', [])
+    use_memory = self._memory_bank_ready(targets)        # memory bank (segsort.py:162-183)
+    if use_memory:
+      protos = torch.cat([protos] + list(mem_p), dim=0)
+      p_sem = torch.cat([p_sem] + list(mem_sem), dim=0)
+      p_bat = torch.cat([p_bat] + list(mem_bat), dim=0)
+    px_sets, p_sets = self._occurrence_sets(targets, use_memory, clu, bat, p_sem, p_bat)
 
-    if self.sem_ann_loss is not None or self.sem_occ_loss is not None:
-      clu = datas['cluster_index']
-      emb = datas['cluster_embedding']
-      sem = datas['cluster_semantic_label']
-      bat = datas['cluster_batch_index']
-      protos = targets['prototype']
-      live = protos.shape[0]          # prototypes that carry a gradient (memory bank is detached)
-      p_sem = targets['prototype_semantic_label']
-      p_bat = targets['prototype_batch_index']
+    # labelled pixels / prototypes and the index remap (segsort.py:185-195):
+    # the i-th labelled prototype gets id i
+    labelled = p_sem < nc
+    if pairs is not None:
+      px, pr, last = _nonzero_pair(sem < nc, labelled, extra=pairs.last_dev)   # (one host sync for all of it)
+    else:
+      px, pr = _nonzero_pair(sem < nc, labelled)         # (one host sync for both sizes)
+    remap = torch.cumsum(labelled, 0) - 1
+    remap = torch.where(labelled, remap, torch.full_like(remap, pr.shape[0]))
+    new_clu = remap[clu]
 
-      mem_p = targets.get('memory_prototype', [])
-      mem_sem = targets.get('memory_prototype_semantic_label', [])
-      mem_bat = targets.get('memory_prototype_batch_index', [])
-      use_memory = self._memory_bank_ready(targets)        # memory bank (segsort.py:162-183)
-      if use_memory:
-        protos = torch.cat([protos] + list(mem_p), dim=0)
-        p_sem = torch.cat([p_sem] + list(mem_sem), dim=0)
-        p_bat = torch.cat([p_bat] + list(mem_bat), dim=0)
-      px_sets, p_sets = self._occurrence_sets(targets, use_memory, clu, bat, p_sem, p_bat)
+    if self.sem_ann_loss is not None:
+      sem_ann = self.sem_ann_loss(emb[px], sem[px], new_clu[px], protos[pr], p_sem[pr],
+                                  codes32=True)          # class ids
+      sem_ann = sem_ann * self.sem_ann_loss_weight
+    if self.sem_occ_loss is not None:
+      sem_occ = self.sem_occ_loss(emb, px_sets, clu, protos, p_sets,
+                                  prototype_grad_rows=live, codes32=self.num_classes <= 32)
+      sem_occ = sem_occ * self.sem_occ_loss_weight
+    acc = parallel.sharded_retrieval_accuracy(segsort_eval.top_k_ranking, protos, p_sem, 5)
+    return sem_ann, sem_occ, acc, last
 
-      # labelled pixels / prototypes and the index remap (segsort.py:185-195):
-      # the i-th labelled prototype gets id i
-      labelled = p_sem < nc
-      if sim is not None:
-        px, pr, last = _nonzero_pair(sem < nc, labelled, extra=sim[4])   # (one host sync for all of it)
-      else:
-        px, pr = _nonzero_pair(sem < nc, labelled)         # (one host sync for both sizes)
-      remap = torch.cumsum(labelled, 0) - 1
-      remap = torch.where(labelled, remap, torch.full_like(remap, pr.shape[0]))
-      new_clu = remap[clu]
+  def _img_sim_batched(self, route, emb, ins, pairs, last):
+    """ALL images' terms from one forward and one backward call of the library (the image is the grid's z coordinate
+    of every kernel: ops.segsort_nll_batched) instead of 16 x ~17 launches on side streams.  `pairs.pair` is the
+    own-prototype index into the concatenated prototypes as it stands."""
+    assert route.batched and route.shared_protos
+    pair_lab, counts = _pair_labels(pairs, last)
+    protos_all = segsort_common.calculate_prototypes_from_labels(emb, pairs.pair, last[-1] + 1)
+    nll_all = self.img_sim_loss.batched_nll(emb, ins, pairs.pair, pairs.sizes, protos_all, pair_lab, counts)
+    # sum_i mean(nll_i) / n_img: every pixel divided by its image's pixel count, one sum (the divisions in
+    # the order of the looped form, so that the upstream gradient of a pixel has the same bits).  The counts
+    # are formed on the device from the pixels' image index (sums of ones: exact in fp32, whatever their
+    # order): no host-to-device copy, which from pageable memory would make the host wait for the stream
+    n_px = torch.zeros(len(pairs.sizes), dtype=nll_all.dtype, device=emb.device)
+    n_px.index_add_(0, pairs.img_of_px, torch.ones_like(nll_all))
+    return (nll_all / n_px[pairs.img_of_px]).sum() / len(pairs.sizes) * self.img_sim_loss_weight
 
-      if self.sem_ann_loss is not None:
-        sem_ann = self.sem_ann_loss(emb[px], sem[px], new_clu[px], protos[pr], p_sem[pr],
-                                    codes32=True)          # class ids
-        sem_ann = sem_ann * self.sem_ann_loss_weight
-      if self.sem_occ_loss is not None:
-        sem_occ = self.sem_occ_loss(emb, px_sets, clu, protos, p_sets,
-                                    prototype_grad_rows=live, codes32=self.num_classes <= 32)
-        sem_occ = sem_occ * self.sem_occ_loss_weight
-      acc = parallel.sharded_retrieval_accuracy(segsort_eval.top_k_ranking, protos, p_sem, 5)
-
-    if sim is not None:
-      sizes, off, uniq, pair, last_dev, img_of_px = sim
-      emb = datas[self.img_sim_embedding_key]
-      ins = datas['cluster_instance_label']
-      if last is None:
-        last = last_dev.tolist()                           # (no semantic term to share the read with)
-      last = [int(v) for v in last]
-      pair_lab = uniq[:last[-1] + 1] % off                 # over-segmentation id of every pair
-      terms, lo, first = [], 0, 0
+  def _img_sim_looped(self, route, emb, ins, pairs, last):
+    """One NLL call per image.  The images' terms are independent and each is a handful of launch-latency-bound
+    kernels (16 900 pixels x ~150 prototypes: 340 us of GPU time per image, forward + backward, on a chip it cannot
+    fill): they are spread over `route.streams` side streams (the backward of an op runs on its forward's stream)."""
+    pair_lab, counts = _pair_labels(pairs, last)
+    pr_all = e_all = None
+    if route.shared_protos:
       # the prototypes of ALL images from one segment sum over the dense pair ids (a pair belongs to one image; a
-      # prototype is normalised on its own), split per image: 1 launch forward + 1 backward instead of 16 + 16
-      # (SPML_IMG_SIM_BATCHED_PROTOS=0: one call per image); the pixel rows are split the same way (one concatenation
-      # in the backward pass instead of 16 zero-filled [P, D] gradients that are then added up)
-      pr_all = e_all = nll_all = None
-      if os.environ.get('SPML_IMG_SIM_BATCHED_PROTOS') != '0' and sum(sizes) == int(emb.shape[0]):
-        counts = [end + 1 - (last[i - 1] + 1 if i else 0) for i, end in enumerate(last)]
-        protos_all = segsort_common.calculate_prototypes_from_labels(emb, pair, last[-1] + 1)
-        # ALL images' terms from one forward and one backward call of the library (the image is the grid's z
-        # coordinate of every kernel: ops.segsort_nll_batched) instead of 16 x ~17 launches on side streams;
-        # SPML_IMG_SIM_BATCHED=0, an explicit SPML_IMG_SIM_STREAMS, or a shape the batched kernels do not cover:
-        # the loop below.  `pair` is the own-prototype index into the concatenated prototypes as it stands.
-        nll_all = self.img_sim_loss.batched_nll(emb, ins, pair, sizes, protos_all, pair_lab, counts) \
-            if (emb.is_cuda and os.environ.get('SPML_IMG_SIM_BATCHED') != '0' and
-                'SPML_IMG_SIM_STREAMS' not in os.environ) else None
-        if nll_all is None:
-          pr_all = torch.split(protos_all, counts)
-          e_all = torch.split(emb, sizes)
-      if nll_all is not None:
-        # sum_i mean(nll_i) / n_img: every pixel divided by its image's pixel count, one sum (the divisions in
-        # the order of the looped form, so that the upstream gradient of a pixel has the same bits).  The counts
-        # are formed on the device from the pixels' image index (sums of ones: exact in fp32, whatever their
-        # order): no host-to-device copy, which from pageable memory would make the host wait for the stream
-        n_px = torch.zeros(len(sizes), dtype=torch.float32, device=emb.device)
-        n_px.index_add_(0, img_of_px, torch.ones_like(nll_all))
-        img_sim = (nll_all / n_px[img_of_px]).sum() / len(sizes) * self.img_sim_loss_weight
-      else:
-        # the images' terms are independent and each is a handful of launch-latency-bound kernels (16 900 pixels x ~150
-        # prototypes: 340 us of GPU time per image, forward + backward, on a chip it cannot fill): they are spread over
-        # SPML_IMG_SIM_STREAMS side streams (default 4; the backward of an op runs on its forward's stream)
-        streams = _side_streams(emb.device, int(os.environ.get('SPML_IMG_SIM_STREAMS', '4'))) if emb.is_cuda else []
-        cur = torch.cuda.current_stream(emb.device) if streams else None
-        for st in streams:
-          st.wait_stream(cur)
-        for i, (n_px, end) in enumerate(zip(sizes, last)):
-          lab, c_abs, first_i = ins[lo:lo + n_px], pair[lo:lo + n_px], first        # (views: no launch)
-          e = e_all[i] if e_all is not None else emb[lo:lo + n_px]
-          p_lab = pair_lab[first:end + 1]
-          lo, first = lo + n_px, end + 1
-          if streams:
-            side = streams[i % len(streams)]
-            # (allocated on the current stream, consumed on the side stream -- forward and, through the saved tensors,
-            # backward: tell the caching allocator, so that a block freed host-side while a side-stream kernel still
-            # reads it is not handed out again early; ADVICE r5)
-            if os.environ.get('SPML_IMG_SIM_RECORD_STREAM') != '0':
-              for t_ in (e, lab, c_abs, p_lab) + ((pr_all[i],) if pr_all is not None else ()):
-                t_.record_stream(side)
-            with torch.cuda.stream(side):
-              c = c_abs - first_i                                # (on the side stream: everything it reads was
-              #                                                    produced before the streams were forked)
-              pr_img = pr_all[i] if pr_all is not None else \
-                  segsort_common.calculate_prototypes_from_labels(e, c, p_lab.shape[0])
-              term = self.img_sim_loss(e, lab, c, pr_img, p_lab, codes32=True)   # over-segmentation ids
-              term.record_stream(cur)
-            terms.append(term)
-            continue
-          c = c_abs - first_i
-          pr_img = pr_all[i] if pr_all is not None else \
-              segsort_common.calculate_prototypes_from_labels(e, c, p_lab.shape[0])
-          terms.append(self.img_sim_loss(e, lab, c, pr_img, p_lab, codes32=True))   # over-segmentation ids
-        for st in streams:
-          cur.wait_stream(st)
-        img_sim = sum(terms) / len(terms) * self.img_sim_loss_weight
+      # prototype is normalised on its own), split per image: 1 launch forward + 1 backward instead of 16 + 16; the
+      # pixel rows are split the same way (one concatenation in the backward pass instead of 16 zero-filled [P, D]
+      # gradients that are then added up)
+      pr_all = torch.split(segsort_common.calculate_prototypes_from_labels(emb, pairs.pair, last[-1] + 1), counts)
+      e_all = torch.split(emb, pairs.sizes)
+    streams = _side_streams(emb.device, route.streams)
+    cur = torch.cuda.current_stream(emb.device) if streams else None
+    for st in streams:
+      st.wait_stream(cur)
+    terms, lo, first = [], 0, 0
+    for i, (n_px, end) in enumerate(zip(pairs.sizes, last)):
+      lab, c_abs = ins[lo:lo + n_px], pairs.pair[lo:lo + n_px]                      # (views: no launch)
+      e = e_all[i] if e_all is not None else emb[lo:lo + n_px]
+      p_lab = pair_lab[first:end + 1]
+      side = streams[i % len(streams)] if streams else None
+      # (allocated on the current stream, consumed on the side stream -- forward and, through the saved tensors,
+      # backward: tell the caching allocator, so that a block freed host-side while a side-stream kernel still
+      # reads it is not handed out again early; ADVICE r5)
+      if side is not None and route.record_stream:
+        for t_ in (e, lab, c_abs, p_lab) + ((pr_all[i],) if pr_all is not None else ()):
+          t_.record_stream(side)
+      with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+        c = c_abs - first           # (on the side stream: everything it reads was produced before the streams were forked)
+        pr_img = pr_all[i] if pr_all is not None else \
+            segsort_common.calculate_prototypes_from_labels(e, c, p_lab.shape[0])
+        term = self.img_sim_loss(e, lab, c, pr_img, p_lab, codes32=True)            # over-segmentation ids
+        if side is not None:
+          term.record_stream(cur)
+      terms.append(term)
+      lo, first = lo + n_px, end + 1
+    for st in streams:
+      cur.wait_stream(st)
+    return sum(terms) / len(terms) * self.img_sim_loss_weight
 
-    return sem_ann, sem_occ, img_sim, acc
+  def _contrastive_losses(self, datas, targets):
+    """The three contrastive terms + retrieval accuracy (segsort.py:127-243).  The per-image term's device part comes
+    first: its one host read (every image's last pair id) travels with the sizes the semantic terms need -- 3 host
+    synchronisations per training step in all."""
+    pairs = _image_pairs(datas) if self.img_sim_loss is not None else None
+    sem_ann, sem_occ, acc, last = self._semantic_terms(datas, targets, pairs)
+    if pairs is None:
+      return sem_ann, sem_occ, None, acc
+    emb = datas[self.img_sim_embedding_key]
+    ins = datas['cluster_instance_label']
+    if last is None:
+      last = pairs.last_dev.tolist()                       # (no semantic term to share the read with)
+    route = _img_sim_route(emb.is_cuda, sum(pairs.sizes) == int(emb.shape[0]),
+                           self.img_sim_loss.batched_supported(emb, ins))
+    run = self._img_sim_batched if route.batched else self._img_sim_looped
+    return sem_ann, sem_occ, run(route, emb, ins, pairs, [int(v) for v in last]), acc
 
   def feature_affinity_loss(self, datas, targets):
     """Set-SegSort over nearest-neighbour propagated tags

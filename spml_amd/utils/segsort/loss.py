@@ -111,18 +111,21 @@ class _NcaLoss(_Loss):
 
   _batched_mode = None
 
+  def batched_supported(self, embeddings, semantic_labels):
+    """True when `batched_nll` covers this loss, its reduction and these shapes on the batched kernels (otherwise the
+    caller evaluates the problems one by one)."""
+    base = type(self)._batched_mode
+    if base is None or self.reduction != 'mean' or embeddings.dim() != 2 or semantic_labels.dim() != 1:
+      return False
+    return ops.segsort_nll_batched_supported(embeddings.shape[-1], _mode(self.group_mode, base, True))
+
   def batched_nll(self, embeddings, semantic_labels, instance_labels, pixel_counts, prototypes,
                   prototype_semantic_labels, prototype_counts):
     """Per-pixel NLL `[sum P]` of independent problems laid out one after the other (problem i: `pixel_counts[i]`
     consecutive pixels against `prototype_counts[i]` consecutive prototypes; `instance_labels` index the concatenated
-    prototypes; integer labels that fit in 32 bits) from one call of the batched kernels, or None when this loss, the
-    reduction or the shape is not one they cover (the caller then evaluates the problems one by one)."""
-    base = type(self)._batched_mode
-    if base is None or self.reduction != 'mean' or embeddings.dim() != 2 or semantic_labels.dim() != 1:
-      return None
-    mode = _mode(self.group_mode, base, True)
-    if not ops.segsort_nll_batched_supported(embeddings.shape[-1], mode):
-      return None
+    prototypes; integer labels that fit in 32 bits) from one call of the batched kernels.  For what
+    `batched_supported` accepts."""
+    mode = _mode(self.group_mode, type(self)._batched_mode, True)
     return ops.segsort_nll_batched(embeddings, instance_labels, semantic_labels, pixel_counts, prototypes,
                                    prototype_semantic_labels, prototype_counts, self.concentration, mode)
 

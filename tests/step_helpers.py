@@ -63,6 +63,45 @@ def count_calls(module, name, counter):
     setattr(module, name, real)
 
 
+def loss_head(dev):
+  """The loss head of a training step at batch 4, crop 257 (a 66 x 66 embedding map, 64-d, 6 x 6 clusters): -> step(),
+  which runs embedding map -> K1 + k-means -> prototypes -> the three contrastive terms on the same inputs every time
+  and returns (the predictor's outputs, the embedding map that needs the gradient, the cluster index of k-means)."""
+  import types
+  from oracle import spml_oracle as O
+  from spml_amd import synth
+  from spml_amd.models.embeddings.resnet_deeplab import ResnetDeeplab
+  from spml_amd.models.predictions.segsort import segsort
+  from spml_amd.train import voc12_scribble_config
+  import spml_amd.models.utils as model_utils
+  cfg = voc12_scribble_config(batch_size=4, crop=257, embedding_dim=64, kmeans=6)
+  pred = segsort(cfg).to(dev)
+  _, targets = synth.make_batch(4, 257, seed=11)
+  g = torch.Generator().manual_seed(7)
+  emb0 = torch.randn(4, 64, 66, 66, generator=g)
+  yy = torch.linspace(-1, 1, 66).view(1, 1, 66, 1)
+  emb0 = (0.3 * emb0 + torch.randn(1, 64, 1, 1, generator=g) * yy).to(dev)
+  sem = O.resize_labels(targets['semantic_label'], (66, 66)).to(dev)
+  ins = O.resize_labels(targets['instance_label'], (66, 66)).to(dev)
+  clusterer = types.SimpleNamespace(label_divisor=2048, semantic_ignore_index=255, kmeans_num_clusters=[6, 6],
+                                    kmeans_iterations=10)
+
+  def step():
+    emb = emb0.clone().requires_grad_(True)
+    datas = ResnetDeeplab.generate_clusters(clusterer, emb, sem, ins)
+    ci = datas['cluster_index']
+    protos = model_utils.local_prototypes(datas['cluster_embedding'], datas['cluster_embedding_with_loc'], ci,
+                                          datas['cluster_batch_index'], datas['cluster_semantic_label'],
+                                          datas['cluster_instance_label'])
+    t = {'prototype': protos[0], 'prototype_with_loc': protos[1], 'prototype_semantic_label': protos[2],
+         'prototype_instance_label': protos[3], 'prototype_batch_index': protos[4],
+         'semantic_tag': targets['semantic_tag'].to(dev)}
+    datas['cluster_index'] = protos[5]
+    t['prototype_semantic_tag'] = t['semantic_tag'][t['prototype_batch_index']]
+    return pred(datas, t), emb, ci
+  return step
+
+
 def to_gpu(datas, targets, channels_last):
   d = {k: v.cuda() for k, v in datas.items()}
   if channels_last:

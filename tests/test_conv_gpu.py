@@ -275,6 +275,49 @@ def test_narrow_aspp_forward_on_64_column_tiles(monkeypatch):
   _within(_rel(y_mc, y64), _rel(y_lib, y64), FLOOR, 'narrow aspp forward mc', 2.0)
 
 
+def test_narrow_aspp_forward_routes_through_the_module(monkeypatch):
+  """The 64-channel head through the module: the default forward (1x1 GEMM + tap gather) and SPML_ASPP_FWD_GEMM=0
+  (the 36-tap launch) carry the path names of their routes, really run another kernel each, and both lie within
+  FLOOR of the fp64 sum of the branches; forward-only calls leave the own kernels under SPML_ASPP_EVAL_MC=0."""
+  import copy
+  from spml_amd.models.heads import spp
+  for switch in ('SPML_NO_MC_CONV', 'SPML_NO_ASPP_DGRAD', 'SPML_ASPP_FWD_MC', 'SPML_ASPP_FWD_GEMM',
+                 'SPML_ASPP_WGRAD_MC', 'SPML_ASPP_EVAL_MC'):
+    monkeypatch.delenv(switch, raising=False)
+  torch.manual_seed(SEED + 13)
+  head = spp.ASPP(256, 64, bn=False, relu=False).to(DEV).to(memory_format=torch.channels_last)
+  convs = [b[0] for b in (head.aspp_1, head.aspp_2, head.aspp_3, head.aspp_4)]
+  x = _nhwc(torch.randn(2, 256, 29, 33, device=DEV).clamp_min(0)).requires_grad_(True)
+  y64 = copy.deepcopy(head).double()(x.detach().double())
+  ran = []
+  for name in ('conv_hl8_pyramid_forward_gemm', 'conv_hl8_pyramid_forward'):
+    monkeypatch.setattr(_ffi, name, lambda *a, _real=getattr(_ffi, name), _name=name: (ran.append(_name), _real(*a))[1])
+
+  def route_name():
+    return spp.aspp_path_name(spp._aspp_route(256, 64, 4, (6, 12, 18, 24)))
+
+  assert route_name() == 'fwd=gemm-gather wgrad=pyramid'
+  y_gemm = head(x).detach()
+  monkeypatch.setenv('SPML_ASPP_FWD_GEMM', '0')
+  assert route_name() == 'fwd=taps36 wgrad=pyramid'
+  y_taps = head(x).detach()
+  assert ran == ['conv_hl8_pyramid_forward_gemm', 'conv_hl8_pyramid_forward']
+  assert not torch.equal(y_taps, y_gemm)                   # (a different kernel really ran)
+  monkeypatch.setenv('SPML_NO_MC_CONV', '1')
+  y_lib = head(x).detach()
+  monkeypatch.delenv('SPML_NO_MC_CONV')
+  assert len(ran) == 2
+  e_lib = _rel(y_lib, y64)
+  _within(_rel(y_gemm, y64), e_lib, FLOOR, 'narrow aspp module forward gemm-gather', 2.0)
+  _within(_rel(y_taps, y64), e_lib, FLOOR, 'narrow aspp module forward taps36', 2.0)
+  with torch.no_grad():
+    assert not _ffi.deterministic() and spp._dilated_sum_available(x, convs)
+    monkeypatch.setenv('SPML_ASPP_EVAL_MC', '0')
+    assert not spp._dilated_sum_available(x, convs)
+    assert head(x).shape == y_lib.shape and len(ran) == 2  # (the library's forward)
+  assert spp._dilated_sum_available(x, convs)              # (with autograd on the switch is not asked)
+
+
 @pytest.mark.parametrize('n,cin,h,w,dils', [(2, 256, 33, 29, (6, 12, 18, 24)),        # the head's four branches
                                             (1, 512, 17, 19, (1, 2, 3)),              # 27 taps: a padded last group
                                             (3, 256, 9, 11, (2, 5)),                  # dilation beyond the map's edge

@@ -189,22 +189,8 @@ def test_loss_head_of_a_training_step_is_bit_reproducible(deterministic, monkeyp
   """Embedding map -> K1 + k-means -> prototypes -> the three contrastive terms, forward and backward, twice on the
   same inputs: the losses and d loss / d embedding are bit-identical (everything in between is this library's) --
   whatever the number of side streams the per-image terms are spread over."""
-  from spml_amd.models.predictions.segsort import segsort
-  from spml_amd.train import voc12_scribble_config
-  import spml_amd.models.utils as model_utils
-  cfg = voc12_scribble_config(batch_size=4, crop=257, embedding_dim=64, kmeans=6)
-  pred = segsort(cfg).to(DEV)
-  _, targets = synth.make_batch(4, 257, seed=11)
-  g = torch.Generator().manual_seed(7)
-  emb0 = torch.randn(4, 64, 66, 66, generator=g)
-  yy = torch.linspace(-1, 1, 66).view(1, 1, 66, 1)
-  emb0 = (0.3 * emb0 + torch.randn(1, 64, 1, 1, generator=g) * yy).to(DEV)
-  sem = O.resize_labels(targets['semantic_label'], (66, 66)).to(DEV)
-  ins = O.resize_labels(targets['instance_label'], (66, 66)).to(DEV)
-  from spml_amd.models.embeddings.resnet_deeplab import ResnetDeeplab
-  import types
-  clusterer = types.SimpleNamespace(label_divisor=2048, semantic_ignore_index=255, kmeans_num_clusters=[6, 6],
-                                    kmeans_iterations=10)
+  from step_helpers import loss_head
+  step = loss_head(DEV)
   results = []
   # (ADVICE r5: the per-image similarity terms run on side streams whose inputs live on the current stream's pool:
   # twelve repetitions with one, four and eight side streams, with allocator churn in between -- a block recycled
@@ -213,18 +199,7 @@ def test_loss_head_of_a_training_step_is_bit_reproducible(deterministic, monkeyp
     monkeypatch.setenv('SPML_IMG_SIM_STREAMS', n_streams)
     junk = [torch.empty((1 << 20) * (1 + (rep + i) % 5), device=DEV) for i in range(6)]     # churn: blocks of 4 .. 20 MB
     del junk
-    emb = emb0.clone().requires_grad_(True)
-    datas = ResnetDeeplab.generate_clusters(clusterer, emb, sem, ins)
-    ci = datas['cluster_index']
-    protos = model_utils.local_prototypes(datas['cluster_embedding'], datas['cluster_embedding_with_loc'], ci,
-                                          datas['cluster_batch_index'], datas['cluster_semantic_label'],
-                                          datas['cluster_instance_label'])
-    t = {'prototype': protos[0], 'prototype_with_loc': protos[1], 'prototype_semantic_label': protos[2],
-         'prototype_instance_label': protos[3], 'prototype_batch_index': protos[4],
-         'semantic_tag': targets['semantic_tag'].to(DEV)}
-    datas['cluster_index'] = protos[5]
-    t['prototype_semantic_tag'] = t['semantic_tag'][t['prototype_batch_index']]
-    out = pred(datas, t)
+    out, emb, ci = step()
     loss = out['sem_ann_loss'] + out['sem_occ_loss'] + out['img_sim_loss']
     loss.backward()
     results.append((loss.detach().clone(), emb.grad.clone(), ci.clone()))

@@ -189,3 +189,101 @@ def test_eval_available_does_not_write_the_training_flag():
   with torch.no_grad():
     assert mc_bottleneck.eval_available(blk, _GpuInput())
     assert not mc_bottleneck.eval_available(blk, _GpuInput(channels_last=False))
+
+
+# ---------------------------------------------------------------------------
+# the route of the image-similarity term (spml_amd/models/predictions/segsort.py): (on the GPU, the images' pixels one
+# contiguous run, the batched kernels cover the loss, environment) -> (shared prototypes, batched, side streams,
+# record_stream calls) and the path name
+IMG_SIM_TABLE = [
+    ((True, True, True, {}), (True, True, 0, False), 'batched'),
+    ((True, True, False, {}), (True, False, 4, True), 'looped/shared-protos/streams=4'),
+    ((True, False, True, {}), (False, False, 4, True), 'looped/per-image-protos/streams=4'),
+    ((False, True, True, {}), (True, False, 0, False), 'looped/shared-protos/streams=0'),
+    ((False, False, True, {}), (False, False, 0, False), 'looped/per-image-protos/streams=0'),
+    ((True, True, True, {'SPML_IMG_SIM_BATCHED': '0'}), (True, False, 4, True), 'looped/shared-protos/streams=4'),
+    ((True, True, True, {'SPML_IMG_SIM_BATCHED': '1'}), (True, True, 0, False), 'batched'),
+    ((True, True, True, {'SPML_IMG_SIM_BATCHED_PROTOS': '0'}), (False, False, 4, True),
+     'looped/per-image-protos/streams=4'),
+    ((False, True, True, {'SPML_IMG_SIM_BATCHED_PROTOS': '0'}), (False, False, 0, False),
+     'looped/per-image-protos/streams=0'),
+    ((True, True, True, {'SPML_IMG_SIM_STREAMS': '4'}), (True, False, 4, True), 'looped/shared-protos/streams=4'),
+    ((True, True, True, {'SPML_IMG_SIM_STREAMS': '1'}), (True, False, 0, False), 'looped/shared-protos/streams=0'),
+    ((True, True, True, {'SPML_IMG_SIM_STREAMS': '0'}), (True, False, 0, False), 'looped/shared-protos/streams=0'),
+    ((True, True, True, {'SPML_IMG_SIM_STREAMS': '8'}), (True, False, 8, True), 'looped/shared-protos/streams=8'),
+    ((False, True, True, {'SPML_IMG_SIM_STREAMS': '8'}), (True, False, 0, False), 'looped/shared-protos/streams=0'),
+    ((True, True, True, {'SPML_IMG_SIM_RECORD_STREAM': '0'}), (True, True, 0, False), 'batched'),
+    ((True, True, True, {'SPML_IMG_SIM_BATCHED': '0', 'SPML_IMG_SIM_RECORD_STREAM': '0'}), (True, False, 4, False),
+     'looped/shared-protos/streams=4'),
+    ((True, True, True, {'SPML_IMG_SIM_STREAMS': '8', 'SPML_IMG_SIM_RECORD_STREAM': '0'}), (True, False, 8, False),
+     'looped/shared-protos/streams=8'),
+    ((True, True, True, {'SPML_IMG_SIM_BATCHED_PROTOS': '0', 'SPML_IMG_SIM_BATCHED': '0', 'SPML_IMG_SIM_STREAMS': '0',
+                         'SPML_IMG_SIM_RECORD_STREAM': '0'}), (False, False, 0, False),
+     'looped/per-image-protos/streams=0'),
+]
+
+
+@pytest.mark.parametrize('row', range(len(IMG_SIM_TABLE)))
+def test_img_sim_route(row, monkeypatch):
+  from spml_amd.models.predictions import segsort as head
+  (on_gpu, contiguous, covered, env), want, name = IMG_SIM_TABLE[row]
+  for switch in ('SPML_IMG_SIM_BATCHED_PROTOS', 'SPML_IMG_SIM_BATCHED', 'SPML_IMG_SIM_STREAMS',
+                 'SPML_IMG_SIM_RECORD_STREAM'):
+    monkeypatch.delenv(switch, raising=False)
+  for k, v in env.items():
+    monkeypatch.setenv(k, v)
+  route = head._img_sim_route(on_gpu, contiguous, covered)
+  assert tuple(route) == want
+  assert (route.shared_protos, route.batched, route.streams, route.record_stream) == want
+  assert head.img_sim_path_name(route) == name
+  assert head._img_sim_route(on_gpu, contiguous, covered, env=env) == route      # (the environment handed in)
+
+
+def _aspp_flags_before_the_routes_had_names(cin, cout, branches, dilations):
+  """The expressions `_DilatedSum.forward` evaluated in line before `_aspp_route`, word for word -> (wide, fwd_mc,
+  narrow_wgrad, keeps the hl8 copy, gemm forward)."""
+  import os
+  wide = _ffi.conv_hl8_supported(cin, cout, 9) and _ffi.conv_wgrad_hl8_supported(cin, cout, 9)
+  fwd_mc = wide or (_ffi.conv_hl8_supported(cin, cout, 9) and os.environ.get('SPML_ASPP_FWD_MC') != '0')
+  narrow_wgrad = (not wide and _ffi.conv_wgrad_pyramid_hl8_supported(cin, cout, branches) and
+                  all(1 <= d <= 255 for d in dilations) and os.environ.get('SPML_ASPP_WGRAD_MC') != '0')
+  gemm = bool(fwd_mc and not wide and os.environ.get('SPML_ASPP_FWD_GEMM') != '0' and
+              _ffi.conv_hl8_pyramid_forward_gemm_supported(cin, cout, branches) and
+              all(1 <= d <= 255 for d in dilations))
+  return wide, fwd_mc, narrow_wgrad, wide or narrow_wgrad, gemm
+
+
+_D4 = (6, 12, 18, 24)
+# (cin, cout, dilations, environment) -> (forward, weight gradients, keeps the hl8 copy), path name
+ASPP_TABLE = [
+    ((256, 64, _D4, {}), ('gemm-gather', 'pyramid', True), 'fwd=gemm-gather wgrad=pyramid'),
+    ((2048, 64, _D4, {}), ('gemm-gather', 'pyramid', True), 'fwd=gemm-gather wgrad=pyramid'),
+    ((256, 256, _D4, {}), ('taps36', 'per-branch', True), 'fwd=taps36 wgrad=per-branch'),
+    ((256, 64, (6, 12, 18, 300), {}), ('taps36', 'library', False), 'fwd=taps36 wgrad=library'),
+    ((256, 256, (6, 12, 18, 300), {}), ('taps36', 'per-branch', True), 'fwd=taps36 wgrad=per-branch'),
+    ((256, 64, _D4, {'SPML_ASPP_FWD_GEMM': '0'}), ('taps36', 'pyramid', True), 'fwd=taps36 wgrad=pyramid'),
+    ((256, 64, _D4, {'SPML_ASPP_FWD_MC': '0'}), ('library', 'pyramid', True), 'fwd=library wgrad=pyramid'),
+    ((256, 64, _D4, {'SPML_ASPP_WGRAD_MC': '0'}), ('gemm-gather', 'library', False), 'fwd=gemm-gather wgrad=library'),
+    ((2048, 64, _D4, {'SPML_ASPP_FWD_MC': '0', 'SPML_ASPP_WGRAD_MC': '0'}), ('library', 'library', False),
+     'fwd=library wgrad=library'),
+    ((256, 256, _D4, {'SPML_ASPP_FWD_MC': '0', 'SPML_ASPP_FWD_GEMM': '0', 'SPML_ASPP_WGRAD_MC': '0'}),
+     ('taps36', 'per-branch', True), 'fwd=taps36 wgrad=per-branch'),
+    ((256, 32, _D4, {}), ('library', 'library', False), 'fwd=library wgrad=library'),      # no 32-column tiles
+]
+
+
+@pytest.mark.parametrize('row', range(len(ASPP_TABLE)))
+def test_aspp_route(row, monkeypatch):
+  from spml_amd.models.heads import spp
+  (cin, cout, dilations, env), want, name = ASPP_TABLE[row]
+  for switch in ('SPML_ASPP_FWD_MC', 'SPML_ASPP_FWD_GEMM', 'SPML_ASPP_WGRAD_MC'):
+    monkeypatch.delenv(switch, raising=False)
+  for k, v in env.items():
+    monkeypatch.setenv(k, v)
+  route = spp._aspp_route(cin, cout, 4, dilations)
+  assert (route.forward, route.wgrad, route.keep_xh) == want
+  assert spp.aspp_path_name(route) == name
+  wide, fwd_mc, narrow_wgrad, keeps, gemm = _aspp_flags_before_the_routes_had_names(cin, cout, 4, dilations)
+  assert route.forward == ('gemm-gather' if gemm else 'taps36' if fwd_mc else 'library')
+  assert route.wgrad == ('per-branch' if wide else 'pyramid' if narrow_wgrad else 'library')
+  assert route.keep_xh == keeps

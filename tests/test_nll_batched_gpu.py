@@ -283,46 +283,26 @@ class ffi_deterministic:
     ffi().set_deterministic(self.before)
 
 
-def _loss_head(monkeypatch, batched):
-  """The loss head of tests/test_determinism_gpu.py (batch 4, crop 257), no SPML_IMG_SIM_STREAMS set."""
-  import types
-  from spml_amd import synth
-  from spml_amd.models.embeddings.resnet_deeplab import ResnetDeeplab
-  from spml_amd.models.predictions.segsort import segsort
-  from spml_amd.train import voc12_scribble_config
-  import spml_amd.models.utils as model_utils
-  monkeypatch.delenv('SPML_IMG_SIM_STREAMS', raising=False)
-  if batched:
-    monkeypatch.delenv('SPML_IMG_SIM_BATCHED', raising=False)
-  else:
+IMG_SIM_SWITCHES = ('SPML_IMG_SIM_BATCHED_PROTOS', 'SPML_IMG_SIM_BATCHED', 'SPML_IMG_SIM_STREAMS',
+                    'SPML_IMG_SIM_RECORD_STREAM')
+
+
+def _loss_head(monkeypatch, batched, env=None):
+  """The loss head of tests/step_helpers.py (batch 4, crop 257), no SPML_IMG_SIM_STREAMS set; `env`: further
+  SPML_IMG_SIM_* switches."""
+  from step_helpers import loss_head
+  for switch in IMG_SIM_SWITCHES:
+    monkeypatch.delenv(switch, raising=False)
+  if not batched:
     monkeypatch.setenv('SPML_IMG_SIM_BATCHED', '0')
-  cfg = voc12_scribble_config(batch_size=4, crop=257, embedding_dim=64, kmeans=6)
-  pred = segsort(cfg).to(DEV)
-  _, targets = synth.make_batch(4, 257, seed=11)
-  g = torch.Generator().manual_seed(7)
-  emb0 = torch.randn(4, 64, 66, 66, generator=g)
-  yy = torch.linspace(-1, 1, 66).view(1, 1, 66, 1)
-  emb0 = (0.3 * emb0 + torch.randn(1, 64, 1, 1, generator=g) * yy).to(DEV)
-  sem = O.resize_labels(targets['semantic_label'], (66, 66)).to(DEV)
-  ins = O.resize_labels(targets['instance_label'], (66, 66)).to(DEV)
-  clusterer = types.SimpleNamespace(label_divisor=2048, semantic_ignore_index=255, kmeans_num_clusters=[6, 6],
-                                    kmeans_iterations=10)
-  emb = emb0.clone().requires_grad_(True)
-  datas = ResnetDeeplab.generate_clusters(clusterer, emb, sem, ins)
-  ci = datas['cluster_index']
-  protos = model_utils.local_prototypes(datas['cluster_embedding'], datas['cluster_embedding_with_loc'], ci,
-                                        datas['cluster_batch_index'], datas['cluster_semantic_label'],
-                                        datas['cluster_instance_label'])
-  t = {'prototype': protos[0], 'prototype_with_loc': protos[1], 'prototype_semantic_label': protos[2],
-       'prototype_instance_label': protos[3], 'prototype_batch_index': protos[4],
-       'semantic_tag': targets['semantic_tag'].to(DEV)}
-  datas['cluster_index'] = protos[5]
-  t['prototype_semantic_tag'] = t['semantic_tag'][t['prototype_batch_index']]
+  for k, v in (env or {}).items():
+    monkeypatch.setenv(k, v)
+  step = loss_head(DEV)
   calls = []
   from spml_amd import _ffi
   real = _ffi.segsort_nll_batched_fwd
   monkeypatch.setattr(_ffi, 'segsort_nll_batched_fwd', lambda *a, **k: (calls.append(len(a[3])), real(*a, **k))[1])
-  out = pred(datas, t)
+  out, emb, _ = step()
   loss = out['sem_ann_loss'] + out['sem_occ_loss'] + out['img_sim_loss']
   loss.backward()
   torch.cuda.synchronize()
@@ -342,3 +322,19 @@ def test_call_site_batched_against_looped(deterministic, monkeypatch):
   assert torch.equal(grad, loop_grad), (grad - loop_grad).abs().max().item()
   loss2, grad2, _ = _loss_head(monkeypatch, batched=True)
   assert torch.equal(loss2, loss) and torch.equal(grad2, grad)
+
+
+@pytest.mark.parametrize('env', [{'SPML_IMG_SIM_BATCHED_PROTOS': '0'}, {'SPML_IMG_SIM_RECORD_STREAM': '0'}],
+                         ids=['per-image-protos', 'no-record-stream'])
+def test_call_site_looped_routes_against_the_default_loop(deterministic, monkeypatch, env):
+  """Case 8, the other two looped routes against the default loop (SPML_IMG_SIM_BATCHED=0), in deterministic mode: the
+  loss and d loss / d embedding are bit-identical.  Prototypes per image instead of from one call: the segment sums
+  are 64-bit fixed point with one constant scale (csrc/segsum.hip), so a sum over one image's pixels has the same bits
+  whichever launch forms it.  No record_stream calls: they move no data."""
+  loop_loss, loop_grad, loop_calls = _loss_head(monkeypatch, batched=False)
+  loss, grad, calls = _loss_head(monkeypatch, batched=False, env=env)
+  assert loop_calls == [] and calls == []
+  print('img_sim default loop %.9g %s %.9g, max |d grad| %.3e' % (loop_loss.item(), env, loss.item(),
+                                                                  (grad - loop_grad).abs().max().item()))
+  assert torch.equal(loss, loop_loss), (loss.item(), loop_loss.item())
+  assert torch.equal(grad, loop_grad), (grad - loop_grad).abs().max().item()
