@@ -29,6 +29,25 @@ def _is_channels_last(embedding_model):
       first.is_contiguous(memory_format=torch.channels_last) and not first.is_contiguous()
 
 
+def _require_gpu(*tensors, what=None):
+  """The device check of every entry point: each of `tensors` is on the GPU, or the one error of the HIP path.  `what`
+  names the offender in front of its device ('a view on', 'got'); without it the message is the dense CRF's, which
+  names neither."""
+  for tensor in tensors:
+    if not (torch.is_tensor(tensor) and tensor.is_cuda):
+      why = 'the dense CRF has no CPU fallback)' if what is None else '%s %s); there is no CPU fallback' % (what, tensor.device)
+      raise _ffi.SpmlHipError('the HIP path needs GPU tensors (' + why)
+
+
+def _eighth_size(name, image_hw):
+  """-> `(h // 8, w // 8)`, the size the random walk runs at; `name` is the caller's, for the error of an image that has
+  none."""
+  out_hw = (image_hw[0] // 8, image_hw[1] // 8)
+  if out_hw[0] < 1 or out_hw[1] < 1:
+    raise ValueError(name + ': the image is smaller than 8 x 8')
+  return out_hw
+
+
 def _check_views(who, views, also=None):
   """What every multi-view routine asks of `views`: at least one, each one image `[1,3,Hp,Wp]`, each on the GPU.  `who`
   names the caller in the errors; `also(i)` is the caller's own check of view `i`, run before that view's device check."""
@@ -39,8 +58,7 @@ def _check_views(who, views, also=None):
       raise ValueError('%s expects views of one image [1,3,Hp,Wp]' % who)
     if also is not None:
       also(i)
-    if not image.is_cuda:
-      raise _ffi.SpmlHipError('the HIP path needs GPU tensors (a view on %s); there is no CPU fallback' % image.device)
+    _require_gpu(image, what='a view on')
 
 
 def _group_by_padded_size(views):
@@ -433,9 +451,7 @@ def pseudo_labels_knn_multiscale(embedding_model, prediction_model, views, image
   `combine_path`, `normalize_path`, and per view `cluster_index` and `segment_topk` as `predict_knn_multiscale`."""
   if not views:
     raise ValueError('pseudo_labels_knn_multiscale needs at least one view')
-  if not label_tags.is_cuda:
-    raise _ffi.SpmlHipError('the HIP path needs GPU tensors (label_tags on %s); there is no CPU fallback'
-                            % label_tags.device)
+  _require_gpu(label_tags, what='label_tags on')
   if label_tags.dim() != 1 or label_tags.shape[0] != int(num_classes):
     raise ValueError('pseudo_labels_knn_multiscale expects one tag per class')
   acc, combine_path, cluster_index, segment_topk = _knn_view_votes_sum(
@@ -568,8 +584,7 @@ def device_views(rgb_u8, scales, is_flip, crop_size, pixel_means, pixel_stds, im
   `semantic_label` (uint8 `[h,w]` on the device) -> `(views, label views)`: the label of every view `[rh, rw]` int64
   (cv2.INTER_NEAREST, mirrored with its view), the `label_views` of `multiscale_prototypes`.  No CPU path."""
   from spml_amd.data import transforms
-  if not rgb_u8.is_cuda:
-    raise _ffi.SpmlHipError('the HIP path needs GPU tensors (got %s); there is no CPU fallback' % rgb_u8.device)
+  _require_gpu(rgb_u8, what='got')
   if rgb_u8.dim() != 3 or rgb_u8.shape[2] != 3 or rgb_u8.dtype != torch.uint8:
     raise ValueError('device_views expects one decoded image, uint8 [h,w,3]')
   records = view_records(transforms.plan_views(rgb_u8.shape[0], rgb_u8.shape[1], scales, is_flip, crop_size, image_size))
@@ -596,8 +611,7 @@ def crf_guide(rgb_u8, pixel_means, pixel_stds, out_hw=None):
   file's own size, the multi-view programs; the un-padded `test.image_size` view for the single-view ones,
   `inference_crf.py:247-252`).  Not the bytes themselves: the reference rebuilds the image from the normalised fp32
   input and that round trip lowers some (byte, channel) pairs by one.  No CPU path."""
-  if not rgb_u8.is_cuda:
-    raise _ffi.SpmlHipError('the HIP path needs GPU tensors (got %s); there is no CPU fallback' % rgb_u8.device)
+  _require_gpu(rgb_u8, what='got')
   if rgb_u8.dim() != 3 or rgb_u8.shape[2] != 3 or rgb_u8.dtype != torch.uint8:
     raise ValueError('crf_guide expects one decoded image, uint8 [h,w,3]')
   mean, std = _normalisation(rgb_u8.device, pixel_means, pixel_stds)
@@ -613,13 +627,39 @@ def export_scored_label_map(refined, before, valid_hw, out_hw, color_map, truth,
   the device, accumulated INTO over the images of a list (a fresh zero tensor when None): `scores[:-1].view(2, 3, -1)`
   are the `iou_stats` tables after and before the CRF, `scores[-1]` the changed pixels.
   -> `(gray, rgb, scores)`."""
-  if not refined.is_cuda:
-    raise _ffi.SpmlHipError('the HIP path needs GPU tensors (got %s); there is no CPU fallback' % refined.device)
+  _require_gpu(refined, what='got')
   with torch.no_grad():
     if scores is None:
       scores = torch.zeros((2 * 3 * int(num_classes) + 1,), dtype=torch.int64, device=refined.device)
     gray, rgb = _ffi.label_export_scored(refined, before, valid_hw, out_hw, color_map, truth, num_classes, scores, out)
   return gray, rgb, scores
+
+
+def _embedded_views(embedding_model, views):
+  """The view loop of the random-walk functions (pseudo_softmaxrw_crf.py:116-128 = pseudo_camrw_crf.py:139-142): the
+  whole padded image of every view through `generate_embeddings(..., resize_as_input=True)`, consecutive views of one
+  padded size in one call, in the memory format of the model.  Yields `(b, embedding [1,C,Hp,Wp] fp32, crop_hw, flip)`
+  per view, `b` counting the views in call order; the caller holds `torch.no_grad()`."""
+  nhwc = _is_channels_last(embedding_model)
+  b = 0
+  for part in _group_by_padded_size(views):
+    images = torch.cat([v[0] for v in part], 0) if len(part) > 1 else part[0][0]
+    if nhwc:
+      images = images.contiguous(memory_format=torch.channels_last)
+    embs = embedding_model.generate_embeddings({'image': images}, resize_as_input=True)['embedding'].float()
+    for i, (_, crop_hw, flip) in enumerate(part):
+      yield b, embs[i:i + 1], crop_hw, flip
+      b += 1
+
+
+def _walk_tail(cam_rw, image_hw, refine=None):
+  """Where the four random-walk functions end: the walked maps `[ncls, h//8, w//8]` up-sampled to `image_hw` and their
+  arg-max (`spml_upsample_argmax_i64`, pseudo_softmaxrw_crf.py:172-176) -> `semantic_prediction`; with `refine` =
+  `(image_u8, crf)` the fused up-sampling + denseCRF of `random_walk_crf_refine` instead -> its fields."""
+  if refine is not None:
+    return random_walk_crf_refine(refine[0], cam_rw, refine[1])
+  with torch.no_grad():
+    return {'semantic_prediction': _ffi.upsample_argmax(cam_rw, image_hw[0], image_hw[1])}
 
 
 def _walked_cams_softmax(name, embedding_model, prediction_model, views, image_hw, label_tags, combine, walk_steps,
@@ -629,34 +669,24 @@ def _walked_cams_softmax(name, embedding_model, prediction_model, views, image_h
   -> (cam, cam_rw `[ncls, h//8, w//8]`, head path, transition before the squarings)."""
   if combine not in _ffi.COMBINE_MODES:
     raise ValueError("combine must be 'prob_mean' or 'logit_mean'")
-  if views and not label_tags.is_cuda:                # (an empty list is reported first, by _check_views)
-    raise _ffi.SpmlHipError('the HIP path needs GPU tensors (label_tags on %s); there is no CPU fallback'
-                            % label_tags.device)
+  if views:                                           # (an empty list is reported first, by _check_views)
+    _require_gpu(label_tags, what='label_tags on')
   _check_views(name, views)
-  h, w = image_hw
-  out_hw = (h // 8, w // 8)
-  if out_hw[0] < 1 or out_hw[1] < 1:
-    raise ValueError(name + ': the image is smaller than 8 x 8')
+  out_hw = _eighth_size(name, image_hw)
   n = out_hw[0] * out_hw[1]
   device = views[0][0].device
   ncls = prediction_model.num_classes
-  nhwc = _is_channels_last(embedding_model)
   prediction_model.prepare_inference()          # once per image, as in predict_softmax_full_resolution
-  units, acc, path, b = None, torch.zeros((ncls, n), dtype=torch.float32, device=device), None, 0
+  units, canvas, acc, path = None, None, torch.zeros((ncls, n), dtype=torch.float32, device=device), None
   with torch.no_grad():
-    for part in _group_by_padded_size(views):
-      images = torch.cat([v[0] for v in part], 0) if len(part) > 1 else part[0][0]
-      if nhwc:
-        images = images.contiguous(memory_format=torch.channels_last)
-      embs = embedding_model.generate_embeddings({'image': images}, resize_as_input=True)['embedding'].float()
-      canvas = torch.empty((1, ncls) + tuple(embs.shape[-2:]), dtype=torch.float32, device=device)
+    for b, emb, crop_hw, flip in _embedded_views(embedding_model, views):
       if units is None:
-        units = torch.empty((len(views), embs.shape[1], n), dtype=torch.float32, device=device)
-      for i, (_, crop_hw, flip) in enumerate(part):
-        path = prediction_model.accumulate_logits(embs[i:i + 1], canvas.zero_(), 0, 0)
-        _ffi.resample_unit(embs[i], crop_hw, flip, out_hw, units, b)
-        _ffi.resample_classes_accumulate(canvas[0], crop_hw, flip, out_hw, acc, combine)
-        b += 1
+        units = torch.empty((len(views), emb.shape[1], n), dtype=torch.float32, device=device)
+      if canvas is None or canvas.shape[-2:] != emb.shape[-2:]:             # (one canvas per group of one padded size)
+        canvas = torch.empty((1, ncls) + tuple(emb.shape[-2:]), dtype=torch.float32, device=device)
+      path = prediction_model.accumulate_logits(emb, canvas.zero_(), 0, 0)
+      _ffi.resample_unit(emb[0], crop_hw, flip, out_hw, units, b)
+      _ffi.resample_classes_accumulate(canvas[0], crop_hw, flip, out_hw, acc, combine)
     trans = _ffi.affinity_transition(units, scale, power)
     cam = _ffi.cam_finalize(acc, len(views), label_tags, combine, background_threshold).view(ncls, *out_hw)
     cam_rw = _walk(trans, cam, walk_steps)
@@ -678,13 +708,10 @@ def pseudo_labels_softmax(embedding_model, prediction_model, views, image_hw, la
   last view: `spml_affinity_transition_f32`, `spml_cam_finalize_f32`, the walk's GEMMs, `spml_upsample_argmax_i64`.
   Returns `cam`, `cam_rw` `[ncls, h//8, w//8]`, `semantic_prediction` `[h,w]` int64, `head_path`, and `transition`
   `[n,n]` (before the squarings) only with `return_transition`."""
-  h, w = image_hw
   cam, cam_rw, path, trans = _walked_cams_softmax('pseudo_labels_softmax', embedding_model, prediction_model, views,
                                                   image_hw, label_tags, combine, walk_steps, background_threshold,
                                                   scale, power)
-  with torch.no_grad():
-    prediction = _ffi.upsample_argmax(cam_rw, h, w)
-  out = {'cam': cam, 'cam_rw': cam_rw, 'semantic_prediction': prediction, 'head_path': path}
+  out = dict({'cam': cam, 'cam_rw': cam_rw}, **_walk_tail(cam_rw, image_hw), head_path=path)
   if return_transition:
     out['transition'] = trans
   return out
@@ -745,8 +772,7 @@ def pseudo_labels_softmax_crf(embedding_model, prediction_model, views, image_hw
   cam, cam_rw, path, trans = _walked_cams_softmax('pseudo_labels_softmax_crf', embedding_model, prediction_model, views,
                                                   image_hw, label_tags, combine, walk_steps, background_threshold,
                                                   scale, power)
-  out = {'cam': cam, 'cam_rw': cam_rw, 'head_path': path}
-  out.update(random_walk_crf_refine(image_u8, cam_rw, crf))
+  out = dict({'cam': cam, 'cam_rw': cam_rw, 'head_path': path}, **_walk_tail(cam_rw, image_hw, (image_u8, crf)))
   if return_transition:
     out['transition'] = trans
   return out
@@ -760,29 +786,18 @@ def _walked_cams_cam(name, embedding_model, views, image_hw, cam_planes, cam_cla
   out of range or given twice is refused before the views go through it.
   -> (cam, cam_rw `[ncls, h//8, w//8]`, ingest path)."""
   h, w = image_hw
-  out_hw = (h // 8, w // 8)
-  if out_hw[0] < 1 or out_hw[1] < 1:
-    raise ValueError(name + ': the image is smaller than 8 x 8')
+  out_hw = _eighth_size(name, image_hw)
   _check_views(name, views)
-  if cam_planes is not None and not cam_planes.is_cuda:
-    raise _ffi.SpmlHipError('the HIP path needs GPU tensors (cam_planes on %s); there is no CPU fallback'
-                            % cam_planes.device)
+  if cam_planes is not None:
+    _require_gpu(cam_planes, what='cam_planes on')
   n = out_hw[0] * out_hw[1]
-  device = views[0][0].device
-  nhwc = _is_channels_last(embedding_model)
-  units, b = None, 0
+  units = None
   with torch.no_grad():
     cam = _ffi.cam_ingest(cam_planes, cam_classes, (h, w), num_classes, alpha)
-    for part in _group_by_padded_size(views):
-      images = torch.cat([v[0] for v in part], 0) if len(part) > 1 else part[0][0]
-      if nhwc:
-        images = images.contiguous(memory_format=torch.channels_last)
-      embs = embedding_model.generate_embeddings({'image': images}, resize_as_input=True)['embedding'].float()
+    for b, emb, crop_hw, flip in _embedded_views(embedding_model, views):
       if units is None:
-        units = torch.empty((len(views), embs.shape[1], n), dtype=torch.float32, device=device)
-      for i, (_, crop_hw, flip) in enumerate(part):
-        _ffi.resample_unit(embs[i], crop_hw, flip, out_hw, units, b)
-        b += 1
+        units = torch.empty((len(views), emb.shape[1], n), dtype=torch.float32, device=views[0][0].device)
+      _ffi.resample_unit(emb[0], crop_hw, flip, out_hw, units, b)
     trans = _ffi.affinity_transition(units, scale, power)
     cam_rw = _walk(trans, cam, walk_steps)
   return cam, cam_rw, _ffi.cam_ingest_path_name(len(cam_classes), h, w, num_classes)
@@ -801,12 +816,9 @@ def pseudo_labels_cam(embedding_model, views, image_hw, cam_planes, cam_classes,
   `spml_resample_unit_f32` as in `pseudo_labels_softmax` (:139-146; no classifier head).  After the last view:
   `spml_affinity_transition_f32` (:147-158), the walk's GEMMs (:159-164) and `spml_upsample_argmax_i64` (:167-170).  Returns `cam`, `cam_rw` `[ncls, h//8, w//8]`, `semantic_prediction`
   `[h,w]` int64 and `cam_path`."""
-  h, w = image_hw
   cam, cam_rw, path = _walked_cams_cam('pseudo_labels_cam', embedding_model, views, image_hw, cam_planes, cam_classes,
                                        num_classes, alpha, walk_steps, scale, power)
-  with torch.no_grad():
-    prediction = _ffi.upsample_argmax(cam_rw, h, w)
-  return {'cam': cam, 'cam_rw': cam_rw, 'semantic_prediction': prediction, 'cam_path': path}
+  return dict({'cam': cam, 'cam_rw': cam_rw}, **_walk_tail(cam_rw, image_hw), cam_path=path)
 
 
 def pseudo_labels_cam_crf(embedding_model, views, image_hw, cam_planes, cam_classes, num_classes, image_u8, crf, alpha=6,
@@ -819,9 +831,7 @@ def pseudo_labels_cam_crf(embedding_model, views, image_hw, cam_planes, cam_clas
     raise ValueError('pseudo_labels_cam_crf: image_u8 must be the un-padded image [h,w,3]')
   cam, cam_rw, path = _walked_cams_cam('pseudo_labels_cam_crf', embedding_model, views, image_hw, cam_planes, cam_classes,
                                        num_classes, alpha, walk_steps, scale, power)
-  out = {'cam': cam, 'cam_rw': cam_rw, 'cam_path': path}
-  out.update(random_walk_crf_refine(image_u8, cam_rw, crf))
-  return out
+  return dict({'cam': cam, 'cam_rw': cam_rw, 'cam_path': path}, **_walk_tail(cam_rw, image_hw, (image_u8, crf)))
 
 
 HIP_SEGMENT_VOTES_PATH = 'hip_segment_votes'
@@ -852,8 +862,7 @@ def knn_votes_crf_refine(image_u8, cluster_index, segment_topk, num_classes, crf
   `semantic_prob` `[ncls,h,w]` (the refined marginals), `semantic_prediction` `[h,w]` int64 (their arg-max),
   `semantic_prediction_before_crf` `[h,w]` int64 (the arg-max of the votes, lowest class on ties), `crf_path` and
   `votes_path`."""
-  if not all(torch.is_tensor(t) and t.is_cuda for t in (image_u8, cluster_index, segment_topk)):
-    raise _ffi.SpmlHipError('the HIP path needs GPU tensors (the dense CRF has no CPU fallback)')
+  _require_gpu(image_u8, cluster_index, segment_topk)
   h, w = int(image_u8.shape[0]), int(image_u8.shape[1])
   ncls = int(num_classes)
   if segment_topk.shape[0] <= _ffi.MAX_DENSE_CRF_VOTE_SEGMENTS:
@@ -969,9 +978,7 @@ def densepose_segment_cam(clustered, label_tags, half_hw, out_hw, num_classes, l
   and what the new stage was fed: `nn_index`, `nn_value` `[N]`, `proto_label` `[S]`, `cluster_index` `[N]` (the
   re-indexed segment ids) and `num_segments`."""
   ncls = int(num_classes)
-  if not label_tags.is_cuda:
-    raise _ffi.SpmlHipError('the HIP path needs GPU tensors (label_tags on %s); there is no CPU fallback'
-                            % label_tags.device)
+  _require_gpu(label_tags, what='label_tags on')
   if label_tags.dim() != 1 or label_tags.shape[0] != ncls:
     raise ValueError('densepose_segment_cam expects one tag per class')
   sem, embs = clustered['cluster_semantic_label'], clustered['cluster_embedding']
@@ -1025,12 +1032,10 @@ def pseudo_labels_densepose_crf(embedding_model, image, valid_hw, semantic_label
   if tuple(image_u8.shape[:2]) != (h, w) or tuple(semantic_label.shape) != (h, w) or \
       tuple(instance_label.shape) != (h, w):
     raise ValueError(name + ': image_u8 must be the un-padded image [h,w,3] and the labels [h,w]')
-  if h < 8 or w < 8:
-    raise ValueError(name + ': the image is smaller than 8 x 8')
-  if not image.is_cuda:
-    raise _ffi.SpmlHipError('the HIP path needs GPU tensors (the image on %s); there is no CPU fallback' % image.device)
+  out_hw = _eighth_size(name, valid_hw)
+  _require_gpu(image, what='the image on')
   pad_h, pad_w = image.shape[-2:]
-  half_hw, out_hw = (h // 2, w // 2), (h // 8, w // 8)
+  half_hw = (h // 2, w // 2)
   ncls = int(embedding_model.num_classes)
   ignore = int(embedding_model.semantic_ignore_index)
   with torch.no_grad():

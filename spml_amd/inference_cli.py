@@ -16,6 +16,7 @@ pseudo-label steps reach image files the same way: `pseudo_softmaxrw
 `pseudo_camrw_crf.py` (the source adds the planes of every image's CAM file to its upload, `run_pseudo_softmax` calls
 `pseudo_labels_cam[_crf]`), `inference_msc.py --pseudo_tags` the kNN pseudo labels of `pseudo_inference[_crf]_msc.py`
 (`run_knn` with that program's scales, the image tags and `pseudo_labels_knn_multiscale`)."""
+import collections
 import json
 import os
 import time
@@ -268,6 +269,9 @@ class ImageSource(object):
 
     for_program(...)        the implementation `--data_list` selects
     timed(per_image)        `per_image(SourceImage)` for every image, between two synchronisations -> (done, seconds)
+    write(image, out, directory)
+                            the label writer of the programs: `emit` of a per-image result, `emit_refined` of one that
+                            carries the labels before the denseCRF
     emit(image, prediction, directory)
                             scores the label map `[h, w]` against the image's label and writes it
     emit_refined(image, refined, before, directory)
@@ -296,6 +300,15 @@ class ImageSource(object):
     """The image tags of the pseudo-label programs (pseudo_softmaxrw_crf.py:102-106)."""
     from spml_amd import inference
     return inference.label_tags_from_map(image.label, self.num_classes)
+
+  def write(self, image, out, directory):
+    """`out`: what a `spml_amd.inference` function returned for `image` (or `refined_by` made of it).  Its
+    `semantic_prediction` is written; where it holds `semantic_prediction_before_crf` the run has a denseCRF stage."""
+    before = out.get('semantic_prediction_before_crf')
+    if before is None:
+      self.emit(image, out['semantic_prediction'], directory)
+    else:
+      self.emit_refined(image, out['semantic_prediction'], before, directory)
 
   def score(self, prediction, label):
     from spml_amd.utils.general import metrics
@@ -372,6 +385,25 @@ def write_label_pngs(gray_path, color_path, gray, color):
     Image.fromarray(array, mode=mode).save(path)
 
 
+UploadLayout = collections.namedtuple('UploadLayout', 'records_end rgb_at sem_at sem_end cam_at total')
+
+
+def upload_layout(records_nbytes, h, w, has_semantic, num_cam_planes):
+  """Where the parts of an image's one upload lie, in bytes: the view records `[0, records_end)`, the RGB bytes from
+  `rgb_at`, the semantic plane `[sem_at, sem_end)` (empty without one) and the fp32 CAM planes from `cam_at` (None
+  without planes) to `total`.  Every part starts on a multiple of 16: the kernels read the records and the image with
+  wide loads and the planes as fp32."""
+  def aligned(nbytes):
+    return (nbytes + 15) // 16 * 16
+  rgb_at = aligned(records_nbytes)
+  sem_at = rgb_at + aligned(3 * h * w)
+  sem_end = sem_at + (h * w if has_semantic else 0)
+  if not num_cam_planes:
+    return UploadLayout(records_nbytes, rgb_at, sem_at, sem_end, None, sem_end)
+  cam_at = aligned(sem_end)
+  return UploadLayout(records_nbytes, rgb_at, sem_at, sem_end, cam_at, cam_at + 4 * h * w * num_cam_planes)
+
+
 class ListImageSource(ImageSource):
   """`--data_dir D --data_list L`: the files of `ListDataset(training=False)`, decoded ahead on a thread pool (threads,
   never processes: a forked child of a process that holds the GPU is not safe); the raw bytes and the view records go
@@ -434,28 +466,23 @@ class ListImageSource(ImageSource):
     from spml_amd import inference
     rgb, semantic, records, cams = decoded
     h, w = rgb.shape[:2]
-    rec_bytes = (records.nbytes + 15) // 16 * 16
-    sem_at = rec_bytes + (3 * h * w + 15) // 16 * 16
-    total = sem_end = sem_at + (h * w if semantic is not None else 0)
-    if cams is not None and len(cams[0]):
-      cam_at = (sem_end + 15) // 16 * 16
-      total = cam_at + 4 * h * w * len(cams[1])
-    stage, event = self._stage(total)
+    at = upload_layout(records.nbytes, h, w, semantic is not None, 0 if cams is None else len(cams[1]))
+    stage, event = self._stage(at.total)
     host = stage.numpy()
-    host[:records.nbytes] = records.view(np.uint8).reshape(-1)
-    host[rec_bytes:rec_bytes + 3 * h * w] = rgb.reshape(-1)
+    host[:at.records_end] = records.view(np.uint8).reshape(-1)
+    host[at.rgb_at:at.rgb_at + 3 * h * w] = rgb.reshape(-1)
     if semantic is not None:
-      host[sem_at:sem_end] = semantic.reshape(-1)
-    if total > sem_end:
+      host[at.sem_at:at.sem_end] = semantic.reshape(-1)
+    if at.cam_at is not None:
       for i, plane in enumerate(cams[1]):
-        host[cam_at + 4 * h * w * i:cam_at + 4 * h * w * (i + 1)] = plane.reshape(-1).view(np.uint8)
-    packed = torch.empty((total,), dtype=torch.uint8, device=self.device)
-    packed.copy_(stage[:total], non_blocking=True)
+        host[at.cam_at + 4 * h * w * i:at.cam_at + 4 * h * w * (i + 1)] = plane.reshape(-1).view(np.uint8)
+    packed = torch.empty((at.total,), dtype=torch.uint8, device=self.device)
+    packed.copy_(stage[:at.total], non_blocking=True)
     event.record()
-    rgb_dev = packed[rec_bytes:rec_bytes + 3 * h * w].view(h, w, 3)
-    sem_dev = packed[sem_at:sem_end].view(h, w) if semantic is not None else None
-    cam_dev = packed[cam_at:total].view(torch.float32).view(-1, h, w) if total > sem_end else None
-    views, labels = inference.views_from_records(rgb_dev, records, packed[:records.nbytes], self.mean, self.std,
+    rgb_dev = packed[at.rgb_at:at.rgb_at + 3 * h * w].view(h, w, 3)
+    sem_dev = packed[at.sem_at:at.sem_end].view(h, w) if semantic is not None else None
+    cam_dev = packed[at.cam_at:at.total].view(torch.float32).view(-1, h, w) if at.cam_at is not None else None
+    views, labels = inference.views_from_records(rgb_dev, records, packed[:at.records_end], self.mean, self.std,
                                                  sem_dev if self.with_labels else None)
     guide = None
     if self.with_guide:
@@ -485,13 +512,19 @@ class ListImageSource(ImageSource):
     torch.cuda.synchronize()
     return done, time.time() - t0
 
+  def _label_bytes(self, image):
+    """The bytes of an image's two label files on the device -> (`[gray | colour]` uint8 `[4 * h * w]`, gray `[h, w]`,
+    colour `[h, w, 3]`: views of it the export kernels write into)."""
+    h, w = image.image_hw
+    out = torch.empty((4 * h * w,), dtype=torch.uint8, device=self.device)
+    return out, out[:h * w].view(h, w), out[h * w:].view(h, w, 3)
+
   def emit(self, image, prediction, directory):
     """`prediction` `[rh, rw]` (the un-padded view of a single-view program, else the file's size) -> the file's size
     (INTER_NEAREST; the identity where the sizes agree), scored there, written by the writer pool."""
     from spml_amd import inference
     h, w = image.image_hw
-    out = torch.empty((4 * h * w,), dtype=torch.uint8, device=self.device)
-    gray, color = out[:h * w].view(h, w), out[h * w:].view(h, w, 3)
+    out, gray, color = self._label_bytes(image)
     inference.export_label_map(prediction.contiguous(), tuple(prediction.shape), (h, w), self.color_map, out=(gray, color))
     if image.label is not None:
       self.score(gray, image.label)
@@ -503,8 +536,7 @@ class ListImageSource(ImageSource):
     from spml_amd import inference
     h, w = image.image_hw
     n = self.num_classes
-    out = torch.empty((4 * h * w,), dtype=torch.uint8, device=self.device)
-    gray, color = out[:h * w].view(h, w), out[h * w:].view(h, w, 3)
+    out, gray, color = self._label_bytes(image)
     if self.changed is None:
       self.crf_scores = torch.zeros((2 * 3 * n + 1,), dtype=torch.int64, device=self.device)
       self.changed = self.crf_scores[-1]
@@ -555,6 +587,42 @@ def memory_bank_dir(embedding_model, config, args, device):
   return build_synthetic_bank(embedding_model, config, args, device)
 
 
+def run_loop(source, per_image):
+  """The one timed loop of the programs: `per_image(SourceImage)` -> that image's result dict, for every image of
+  `source` (`source.timed`).  -> (images done, seconds, the last image's result, the last image's views): what the
+  report reads after the loop."""
+  last = {'out': None, 'views': []}
+
+  def one(image):
+    last.update(out=per_image(image), views=image.views)
+
+  done, seconds = source.timed(one)
+  return done, seconds, last['out'], last['views']
+
+
+def route_fields(out, views=None, constants=(), paths=(), instance_iou=None):
+  """The fields of a report that depend on the route chosen before the loop, in the report's order: `views` (their
+  number; None for a single-view route), the route's `constants` (name, value pairs), the `paths` its function names in
+  its result -- read off `out`, the last image's -- and the instance-weighted IoU where the route kept one."""
+  fields = {} if views is None else {'views': len(views)}
+  fields.update(constants)
+  fields.update((key, out[key]) for key in paths)
+  if instance_iou is not None:
+    fields['instance_mIoU'] = round(instance_iou.result()['mean_iou'], 4)
+  return fields
+
+
+def refined_by(stage, image, out, prob):
+  """The result `out` of a label-inference function with the denseCRF stage behind it: `prob(out)`, the class
+  probabilities `[ncls, h, w]` the reference hands to its CRF, through `stage` on the image's guide; the refined labels
+  take the place of `semantic_prediction` and the function's own become `semantic_prediction_before_crf`.  Without a
+  stage `out` as it is."""
+  if stage is None:
+    return out
+  refined = stage(image.guide, prob(out))
+  return dict(out, semantic_prediction=refined['semantic_prediction'], semantic_prediction_before_crf=out['semantic_prediction'])
+
+
 def run_prototypes(description, scales, argv=None, single_view=False):
   """`prototype.py` and `prototype_msc.py` (`prototype_msc.py:34-207` of twke18/SPML): every image through
   `spml_amd.inference.multiscale_prototypes`; the programs differ in the scales of the image pyramid (`[1]` against
@@ -570,18 +638,17 @@ def run_prototypes(description, scales, argv=None, single_view=False):
   embedding_model, _, path = load_models(config, args, device, None)                              # :69-79
   _, crop_size, stride, _ = geometry(config)
   ignore_index = config.dataset.semantic_ignore_index
-  per_image, out, views = [], None, []
+  per_image = []
 
   def one(image):
-    nonlocal out, views
-    views = image.views
-    out = inference.multiscale_prototypes(embedding_model, views, image.label_views, crop_size, stride, ignore_index,
+    out = inference.multiscale_prototypes(embedding_model, image.views, image.label_views, crop_size, stride, ignore_index,
                                           NUM_LABEL_VALUES)
     inference.save_image_memory(os.path.join(prototype_dir, source.bank_name(image)), out['prototype'],
                                 out['prototype_label'])                                           # :200-207
     per_image.append(int(out['prototype'].shape[0]))
+    return out
 
-  done, seconds = source.timed(one)
+  done, seconds, out, views = run_loop(source, one)
   report(done, seconds, prototypes_per_image=per_image, views=len(views), scales=list(scales),
          majority_path=out['majority_path'], snapshot=path, save_dir=prototype_dir, **source.fields())
 
@@ -621,43 +688,40 @@ def run_pseudo_softmax(description, scales, combine, walk_steps, argv=None, file
                                    with_cams=cam_dir)                                             # :109-125
   embedding_model, prediction_model, path = load_models(config, args, device, None if cam_dir else 'softmax_classifier')
   num_classes = geometry(config)[0]
-  out = None
 
-  def one_cam(image):
-    nonlocal out
-    if stage is None:
-      out = inference.pseudo_labels_cam(embedding_model, image.views, image.image_hw, image.cam_planes, image.cam_classes,
-                                        num_classes, alpha=cam_alpha, walk_steps=walk_steps)
-      source.emit(image, out['semantic_prediction'], semantic_dir)
-    else:
-      out = inference.pseudo_labels_cam_crf(embedding_model, image.views, image.image_hw, image.cam_planes,
-                                            image.cam_classes, num_classes, image.guide, stage, alpha=cam_alpha,
-                                            walk_steps=walk_steps)
-      source.emit_refined(image, out['semantic_prediction'], out['semantic_prediction_before_crf'], semantic_dir)
+  def softmax_walk(image):                                                                        # :126-176
+    return inference.pseudo_labels_softmax(embedding_model, prediction_model, image.views, image.image_hw,
+                                           source.tags(image), combine=combine, walk_steps=walk_steps)
+
+  def softmax_walk_crf(image):                                                                    # :126-187
+    return inference.pseudo_labels_softmax_crf(embedding_model, prediction_model, image.views, image.image_hw,
+                                               source.tags(image), image.guide, stage, combine=combine,
+                                               walk_steps=walk_steps)
+
+  def cam_walk(image):
+    return inference.pseudo_labels_cam(embedding_model, image.views, image.image_hw, image.cam_planes, image.cam_classes,
+                                       num_classes, alpha=cam_alpha, walk_steps=walk_steps)
+
+  def cam_walk_crf(image):
+    return inference.pseudo_labels_cam_crf(embedding_model, image.views, image.image_hw, image.cam_planes,
+                                           image.cam_classes, num_classes, image.guide, stage, alpha=cam_alpha,
+                                           walk_steps=walk_steps)
 
   if cam_dir:
-    done, seconds = source.timed(one_cam)
-    report(done, seconds, **source.scores(), **crf_report(stage, source, seconds), scales=list(scales), is_flip=True,
-           cam_dir=cam_dir, alpha=cam_alpha, walk_steps=walk_steps, cam_path=out['cam_path'], snapshot=path,
-           save_dir=semantic_dir, **source.fields())
-    return
+    labels = cam_walk if stage is None else cam_walk_crf
+    route = dict(constants=(('cam_dir', cam_dir), ('alpha', cam_alpha), ('walk_steps', walk_steps)), paths=('cam_path',))
+  else:
+    labels = softmax_walk if stage is None else softmax_walk_crf
+    route = dict(constants=(('combine', combine), ('walk_steps', walk_steps)), paths=('head_path',))
 
   def one(image):
-    nonlocal out
-    if stage is None:
-      out = inference.pseudo_labels_softmax(embedding_model, prediction_model, image.views, image.image_hw,
-                                            source.tags(image), combine=combine, walk_steps=walk_steps)
-      source.emit(image, out['semantic_prediction'], semantic_dir)
-    else:
-      out = inference.pseudo_labels_softmax_crf(embedding_model, prediction_model, image.views, image.image_hw,
-                                                source.tags(image), image.guide, stage, combine=combine,
-                                                walk_steps=walk_steps)                            # :126-187
-      source.emit_refined(image, out['semantic_prediction'], out['semantic_prediction_before_crf'], semantic_dir)
+    out = labels(image)
+    source.write(image, out, semantic_dir)
+    return out
 
-  done, seconds = source.timed(one)
+  done, seconds, out, _ = run_loop(source, one)
   report(done, seconds, **source.scores(), **crf_report(stage, source, seconds), scales=list(scales), is_flip=True,
-         combine=combine, walk_steps=walk_steps, head_path=out['head_path'], snapshot=path, save_dir=semantic_dir,
-         **source.fields())
+         **route_fields(out, **route), snapshot=path, save_dir=semantic_dir, **source.fields())
 
 
 def crf_report(stage, source, seconds):
@@ -683,30 +747,28 @@ def run_softmax(description, scales, is_flip, argv=None, single_view=False, file
   stage = crf_stage(config, args, crf)
   source = ImageSource.for_program(config, args, device, scales, is_flip, api, single_view=single_view,
                                    with_guide=stage is not None)
-  out, views = None, []
+
+  def one_view(image):
+    padded, (h, w), _ = image.views[0]
+    out = inference.predict_softmax_full_resolution(embedding_model, prediction_model, padded, (h, w), crop_size, stride)
+    return refined_by(stage, image, out, lambda out: torch.softmax(out['semantic_logit'], dim=1)[0, :, :h, :w].contiguous())
+
+  def all_views(image):
+    out = inference.predict_softmax_multiscale(embedding_model, prediction_model, image.views, image.image_hw, crop_size,
+                                               stride)
+    return refined_by(stage, image, out,
+                      lambda out: out['semantic_prob'] / torch.full((), float(len(image.views)), device=device))
+
+  predict, paths = (one_view, ('head_path',)) if single_view else (all_views, ('combine_path', 'head_path'))
 
   def one(image):
-    nonlocal out, views
-    views = image.views
-    if single_view:
-      padded, (h, w), _ = views[0]
-      out = inference.predict_softmax_full_resolution(embedding_model, prediction_model, padded, (h, w), crop_size, stride)
-    else:
-      out = inference.predict_softmax_multiscale(embedding_model, prediction_model, views, image.image_hw, crop_size, stride)
-    if stage is None:
-      source.emit(image, out['semantic_prediction'], semantic_dir)
-      return
-    if single_view:
-      prob = torch.softmax(out['semantic_logit'], dim=1)[0, :, :h, :w].contiguous()
-    else:
-      prob = out['semantic_prob'] / torch.full((), float(len(views)), device=device)
-    refined = stage(image.guide, prob)
-    source.emit_refined(image, refined['semantic_prediction'], out['semantic_prediction'], semantic_dir)
+    out = predict(image)
+    source.write(image, out, semantic_dir)
+    return out
 
-  done, seconds = source.timed(one)
-  more = {} if single_view else {'views': len(views), 'combine_path': out['combine_path']}
-  report(done, seconds, **source.scores(), **more, head_path=out['head_path'], **crf_report(stage, source, seconds),
-         snapshot=path, save_dir=semantic_dir, **source.fields())
+  done, seconds, out, views = run_loop(source, one)
+  report(done, seconds, **source.scores(), **route_fields(out, None if single_view else views, paths=paths),
+         **crf_report(stage, source, seconds), snapshot=path, save_dir=semantic_dir, **source.fields())
 
 
 def run_knn(description, scales, is_flip, argv=None, single_view=False, file_lists='images', crf=None, pseudo_tags=None):
@@ -745,54 +807,52 @@ def run_knn(description, scales, is_flip, argv=None, single_view=False, file_lis
   memory_dir = memory_bank_dir(embedding_model, config, args, device)
   prototypes, prototype_labels = load_bank(memory_dir, config, device)
   ignore_index = config.dataset.semantic_ignore_index
-  out, views = None, []
   by_instance = None
   if tagged and not reads_file_list(args):
     from spml_amd.utils.general import metrics
     by_instance = metrics.InstanceIoU(num_classes)
+  models, windows, bank = (embedding_model, prediction_model), (crop_size, stride), (prototypes, prototype_labels)
+
+  def one_view(image):
+    padded, valid_hw, _ = image.views[0]
+    return inference.predict_full_resolution(*models, padded, valid_hw, *windows, *bank, ignore_index)
+
+  def one_view_crf(image):
+    padded, valid_hw, _ = image.views[0]
+    return inference.predict_knn_full_resolution_crf(*models, padded, valid_hw, *windows, *bank, num_classes, image.guide,
+                                                     stage, ignore_index)
+
+  def view_votes(image):
+    return inference.predict_knn_multiscale(*models, image.views, image.image_hw, *windows, *bank, num_classes)
+
+  def tagged_view_votes(image):
+    return inference.pseudo_labels_knn_multiscale(*models, image.views, image.image_hw, *windows, *bank, num_classes,
+                                                  source.tags(image), floor=floor, return_prob=stage is not None)
+
+  votes = tagged_view_votes if tagged else view_votes
+
+  def all_views(image):
+    return refined_by(stage, image, votes(image), lambda out: out['semantic_prob'])
+
+  if not single_view:
+    predict, paths = all_views, ('combine_path', 'normalize_path') if tagged else ('combine_path',)
+  elif stage is None:
+    predict, paths = one_view, ()
+  else:
+    predict, paths = one_view_crf, ('votes_path',)
 
   def one(image):
-    nonlocal out, views
-    views = image.views
-    if not single_view:
-      if tagged:
-        out = inference.pseudo_labels_knn_multiscale(embedding_model, prediction_model, views, image.image_hw, crop_size,
-                                                     stride, prototypes, prototype_labels, num_classes, source.tags(image),
-                                                     floor=floor, return_prob=stage is not None)
-      else:
-        out = inference.predict_knn_multiscale(embedding_model, prediction_model, views, image.image_hw, crop_size, stride,
-                                               prototypes, prototype_labels, num_classes)
-      written = out['semantic_prediction']
-      if stage is None:
-        source.emit(image, written, semantic_dir)
-      else:
-        written = stage(image.guide, out['semantic_prob'])['semantic_prediction']
-        source.emit_refined(image, written, out['semantic_prediction'], semantic_dir)
-      if by_instance is not None:
-        by_instance.update(written, image.label, image.instance.clamp(0, 255))
-      return
-    padded, valid_hw, _ = views[0]
-    if stage is None:
-      out = inference.predict_full_resolution(embedding_model, prediction_model, padded, valid_hw, crop_size, stride,
-                                              prototypes, prototype_labels, ignore_index)
-      source.emit(image, out['semantic_prediction'], semantic_dir)
-    else:
-      out = inference.predict_knn_full_resolution_crf(embedding_model, prediction_model, padded, valid_hw, crop_size,
-                                                      stride, prototypes, prototype_labels, num_classes, image.guide,
-                                                      stage, ignore_index)
-      source.emit_refined(image, out['semantic_prediction'], out['semantic_prediction_before_crf'], semantic_dir)
+    out = predict(image)
+    source.write(image, out, semantic_dir)
+    if by_instance is not None:
+      by_instance.update(out['semantic_prediction'], image.label, image.instance.clamp(0, 255))
+    return out
 
-  done, seconds = source.timed(one)
-  more = {} if single_view else {'views': len(views), 'combine_path': out['combine_path']}
-  if single_view and stage is not None:
-    more['votes_path'] = out['votes_path']
-  if tagged:
-    more['normalize_path'] = out['normalize_path']
-  if by_instance is not None:
-    more['instance_mIoU'] = round(by_instance.result()['mean_iou'], 4)
-  report(done, seconds, **source.scores(), **more, **crf_report(stage, source, seconds),
-         memory_prototypes=int(prototypes.shape[0]), snapshot=path, semantic_memory_dir=memory_dir, save_dir=semantic_dir,
-         **source.fields())
+  done, seconds, out, views = run_loop(source, one)
+  report(done, seconds, **source.scores(),
+         **route_fields(out, None if single_view else views, paths=paths, instance_iou=by_instance),
+         **crf_report(stage, source, seconds), memory_prototypes=int(prototypes.shape[0]), snapshot=path,
+         semantic_memory_dir=memory_dir, save_dir=semantic_dir, **source.fields())
 
 
 class CrfStage(object):
@@ -814,11 +874,7 @@ class CrfStage(object):
 
   def __call__(self, image_u8, prob):
     from spml_amd import inference
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    out = inference.dense_crf_refine(image_u8, prob, self.crf)
-    end.record()
-    self.events.append((start, end))
+    out = self._timed(inference.dense_crf_refine, image_u8, prob, self.crf)
     self.path = out['crf_path']
     return out
 
@@ -827,14 +883,10 @@ class CrfStage(object):
     up-sampled inside the CRF's first kernel) between the same device events.  With this method and `path_name` the stage
     stands in for its `DenseCRF` as the `crf` of `inference.random_walk_crf_refine` and `pseudo_labels_softmax_crf`, so
     the events enclose the CRF alone and not the network and the walk in front of it."""
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    out = self.crf.refine_upsampled(image_u8, lowres)
-    end.record()
-    self.events.append((start, end))
-    return out
+    return self._timed(self.crf.refine_upsampled, image_u8, lowres)
 
   def _timed(self, call, *args):
+    """`call(*args)` between two device events of the stage: the one place they are recorded."""
     start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     start.record()
     out = call(*args)
